@@ -10,10 +10,16 @@ One step = zero-grad + forward + backward (+ gradient all-reduce over RCCL when 
 the reference's probabilities.  Weak scaling: 256 molecules per rank; InfoNCE negatives are global.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
+  python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
   python bench.py --gpus N ...        (no WORLD_SIZE in the environment: starts the N ranks itself, before touching the GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement):
+Prints ONE JSON line on rank 0: `value` (molecules/s) and `ms_per_step` of the --steps timed steps after --warmup untimed ones.
+A plain run does only that.  --dump-outputs DIR then writes what the last timed step returned (logits, the four losses) and a
+seeded sample of the weights that step updated as DIR/<name>.npy (float32), rank 0's.  --full adds the rest of the record:
+  workloads     the other workloads timed in the same process (mixed lengths in both layouts, the reference's batch size of 32,
+                the other precision mode, the loader-fed step);
   roofline      the kernel family that takes the most GPU time of the step (the GEMMs: bound "mfma"), timed live with HIP
                 events on the launch streams;
   rooflines     the same for every hot kernel family (pair attention fwd/bwd, the fused pair-distance kernel fwd/bwd that
@@ -60,7 +66,9 @@ def cpu_baseline(atoms, tokens, sample_B=32, iters=3, scaling_B=8):
     `iters` timed steps after one warm-up at sample_B molecules, plus one timed step at scaling_B to show how the rate
     depends on the sample size (small GEMMs under-use many cores)."""
     from oracle import mmdti_oracle as O
-    torch.set_num_threads(max(1, min(os.cpu_count() or 1, 64)))
+    # (an OMP_NUM_THREADS in the environment is the share of the host this process has: os.cpu_count() counts the whole host)
+    omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    torch.set_num_threads(int(omp) if omp.isdigit() and int(omp) > 0 else max(1, min(os.cpu_count() or 1, 64)))
     cfg = O.ModelCfg(task="classification", output_dim=2)
     P = {k: v.requires_grad_() for k, v in O.init_params(cfg, seed=1).items()}
 
@@ -352,6 +360,29 @@ def pipeline_workload(tuner, model, args, dev, world, rank, barrier):
             "layout": model.last_layout}
 
 
+PARAM_SAMPLE = 1 << 20          # updated weights written by --dump-outputs: 4 MB of the ~300 MB of fp32 weights
+
+
+def step_outputs(out, model, sample=PARAM_SAMPLE, seed=0):
+    """What one training step hands its caller, as host float32 arrays: the StepOutput tensors (logits and the four losses) and
+    `params_sample`, the weights the step's optimizer update left, at `sample` positions drawn with a fixed seed from every
+    parameter of `model` flattened in named_parameters() order (the same positions in every run of the same model)."""
+    import numpy as np
+    arrays = {name: getattr(out, name) for name in ("logits", "loss", "task_loss", "infonce_loss", "ct_loss")}
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters()])
+        idx = torch.randint(flat.numel(), (min(sample, flat.numel()),), generator=torch.Generator().manual_seed(seed)).sort().values
+        arrays["params_sample"] = flat[idx.to(flat.device)]
+    return {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in arrays.items() if v is not None}
+
+
+def dump_outputs(arrays, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -365,9 +396,15 @@ def main():
     ap.add_argument("--no-rooflines", action="store_true", help="skip the extra (untimed) steps that time every kernel family")
     ap.add_argument("--graph", action="store_true", help="replay the step from one captured HIP graph (FineTuner.graphed_step; single GPU)")
     ap.add_argument("--ragged", action="store_true", help="molecules of mixed length padded to the batch maximum (not the headline workload)")
-    ap.add_argument("--no-ragged-workload", action="store_true", help="skip the second (mixed-length) workload record of the default run")
+    ap.add_argument("--no-ragged-workload", action="store_true", help="skip the second (mixed-length) workload record of the --full run")
     ap.add_argument("--no-pipeline-workload", action="store_true", help="skip the fresh-batch-every-step workload record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the other workloads, the per-family rooflines and the CPU baseline (the --no-* switches "
+                         "above leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
 
@@ -411,9 +448,10 @@ def main():
     for _ in range(args.warmup):
         out = step(batch, label, epoch=0)
     barrier()
-    # inside the timed region only the two pair-attention kernels are event-timed (30 launches per step); everything else is
-    # timed in extra steps afterwards so that ~1 000 event pairs per step do not perturb `value`
-    ops.kernel_timer.enable(("pair_attn_bwd", "pair_attn_fwd"))
+    # --full: inside the timed region only the two pair-attention kernels are event-timed (30 launches per step); everything else
+    # is timed in extra steps afterwards so that ~1 000 event pairs per step do not perturb `value`
+    if args.full:
+        ops.kernel_timer.enable(("pair_attn_bwd", "pair_attn_fwd"))
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step(batch, label, epoch=0)
@@ -427,6 +465,8 @@ def main():
         dt = float(t)
     losses = {"loss": float(out.loss), "task": float(out.task_loss), "infonce": float(out.infonce_loss), "ct": float(out.ct_loss)}
     headline_layout = model.last_layout
+    if args.dump_outputs and rank == 0:          # (before --full's extra steps move the weights on)
+        dump_outputs(step_outputs(out, model), args.dump_outputs)
 
     # Second workload, timed in the same process (not the headline): SURVEY 8d's C-main length distribution -- atoms ~ N(48, 20^2)
     # clamped to [8, 128], SMILES 0.8 x atoms, padded to the batch maximum as the reference collates.  Timed on the layout the DEFAULT
@@ -435,7 +475,7 @@ def main():
     # default wherever no dropout is live).
     workloads = {}
     sr_default = model.strict_reference
-    if not args.ragged and not args.no_ragged_workload:
+    if args.full and not args.ragged and not args.no_ragged_workload:
         rb, rl = resident(4321 + rank, True)
         rec = {}
         for tag, strict in (("default", sr_default), ("packed", False)):
@@ -503,7 +543,7 @@ def main():
 
     # Fourth record: the headline batch with bf16 operands everywhere (MMDTI_FWD_FP16=0, the round-1..3 default) -- faster by the
     # in-kernel conversions of the fp16 mode, and outside the north star's 1e-3 on embeddings (4.6e-3): the A/B of the precision choice
-    if not args.ragged and not args.no_ragged_workload:
+    if args.full and not args.ragged and not args.no_ragged_workload:
         was16 = ops.FWD_F16
         ops.set_forward_fp16(not was16)
         try:
@@ -533,14 +573,14 @@ def main():
             tuner.step(batch, label, epoch=0)
     # (N = 1 only: the loader's worker processes are per rank -- four more processes on every GPU of a node say nothing the one-GPU
     #  record does not, and the scaling runs stay what they measure)
-    if not args.ragged and not args.no_ragged_workload and not args.no_pipeline_workload and not args.graph and world == 1:
+    if args.full and not args.ragged and not args.no_ragged_workload and not args.no_pipeline_workload and not args.graph and world == 1:
         workloads["pipeline"] = pipeline_workload(tuner, model, args, dev, world, rank, barrier)
 
     # every kernel family in two extra modes (every rank runs them: the step holds collectives):
     #   "overlapped": streams as in the timed region (a launch's event time includes sharing the chip with the other tower);
     #   "alone"     : towers back to back on one stream, every stream-level overlap off -- each launch has the chip to itself.
     fam = {}
-    extra = 0 if args.no_rooflines else 2
+    extra = 2 if args.full and not args.no_rooflines else 0
     if extra:
         from mmdti_hip import functional as Fn
         was = (model.overlap_towers, model.infonce_on_side_stream, model.cross_modal_module.two_streams, Fn.DEFER_WGRAD_LAYERS)
@@ -590,7 +630,7 @@ def main():
                 roofline["step_hbm_frac_of_peak"] = round(step_bytes / (dt / args.steps) / (HBM_PEAK_GBS * 1e9), 4)
                 roofline["step_hbm_source"] = src
         cpu = None
-        if not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: the other ranks of a multi-GPU run would sit in a collective for a minute)
+        if args.full and not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: the other ranks of a multi-GPU run would sit in a collective for a minute)
             cpu = cpu_baseline(args.atoms, args.tokens, args.cpu_sample)
         mols = args.batch * world * args.steps
         shape = "mixed lengths padded to the batch maximum" if args.ragged else "all at max length"

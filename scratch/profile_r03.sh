@@ -7,7 +7,7 @@ mkdir -p $O
 rm -rf $O/prof_stats $O/prof_fetch $O/prof_write $O/prof_rdreq $O/prof_rdreq2
 rocprofv3 -L > $O/counters_all.txt 2>&1
 grep -oE "TCC_EA0_RDREQ[A-Za-z0-9_]*|TCC_EA0_RD[A-Za-z0-9_]*|TCP_TCC_READ_REQ[A-Za-z0-9_]*|TCC_REQ[A-Za-z0-9_]*|TCC_READ[A-Za-z0-9_]*" $O/counters_all.txt | sort -u > $O/counters_rd.txt
-rocprofv3 --output-format csv --kernel-trace --stats -d $O/prof_stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/prof_stats.log 2>&1 || { tail -20 $O/prof_stats.log; exit 1; }
+rocprofv3 --output-format csv --kernel-trace --stats -d $O/prof_stats -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $O/prof_stats.log 2>&1 || { tail -20 $O/prof_stats.log; exit 1; }
 echo stats done
 rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $O/prof_fetch -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-rooflines --no-ragged-workload > $O/prof_fetch.log 2>&1 || { tail -20 $O/prof_fetch.log; exit 1; }
 echo fetch done
