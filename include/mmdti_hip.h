@@ -571,6 +571,28 @@ int mmdti_step_state_advance(mmdti_stream_t stream, float* state, unsigned long 
  * 0 (the initial value) leaves the generators exactly as the by-value seeds define them. */
 int mmdti_seed_salt_pull(mmdti_stream_t stream, const unsigned long long* salt);
 
+/* ---- skipping optimizer steps on non-finite gradients (GradScaler.step, tasks/trainer.py:268-282) ---- */
+/* The reproducible mmdti_sumsq_f32 pass (same workgroup count, so out[0] is the same to the bit) that also counts the elements of g
+ * that are inf or NaN (exponent bits all ones): out[0] += sum of squares (zero first), out[1] = non-finite count (as fp32).
+ * ws: ws_floats >= 2, 4096 used at most (per-workgroup partials | per-workgroup counts).
+ * guard (nullable): the device guard state, fp32 {steps taken t, steps skipped, this step's skip flag, 1-beta1^t, sqrt(1-beta2^t)}
+ * (zero-initialised).  When given, the pass decides the step after its fixed-order fold, on the device: a non-finite count sets the
+ * flag, out[2] = 1 and counts a skip; otherwise the flag clears, out[2] = 0, t advances and the bias corrections of the new t are
+ * taken from bias_table (pairs for t = 1 .. table_steps, mmdti_adam_bias_table; the caller keeps table_steps >= every t it enqueues)
+ * or, if bias_table is null, computed on the device as mmdti_step_state_advance does. */
+int mmdti_sumsq_check_f32(mmdti_stream_t stream, const float* g, long long n, float* out, float* ws, int ws_floats, float* guard,
+                          const float* bias_table, int table_steps, float beta1, float beta2);
+/* mmdti_adam_step under the guard of mmdti_sumsq_check_f32: when the guard's flag is set nothing is read or written (p, m, v and both
+ * shadows keep their values); otherwise the same update, with the bias corrections read from the guard (lr: by value, or from
+ * step_state_dev when given).  With the flag clear it reproduces mmdti_adam_step to the bit for the same t and the same source of
+ * bias corrections (bias_table: the by-value step; no table: the step state). */
+int mmdti_adam_step_guarded(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev,
+                            const float* step_state_dev, void* p_f16 /* nullable */, const float* guard);
+/* HOST function: table_host[2(t-1)], [2(t-1)+1] = 1-beta1^t, sqrt(1-beta2^t) for t = 1 .. steps, exactly as mmdti_adam_step computes
+ * them from its by-value step. */
+int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host);
+
 /* ---- hardware probes used by the test-suite ------------------------------------------------- */
 /* out[64*4] <- what ds_read_b64_tr_b16 returns to each lane for an LDS image holding element index == value */
 int mmdti_probe_tr_read(mmdti_stream_t stream, int row_stride_elems, unsigned short* out);

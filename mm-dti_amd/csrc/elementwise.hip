@@ -480,33 +480,99 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 // sumsq_fold_kernel -- the gradient norm, and with it the clip coefficient of every Adam step, is the same to the bit from run to run
 // (the atomic form above differs in the last bit, and a training trajectory with it).
 constexpr int SUMSQ_WGS = 2048;
-__global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict__ g, long long n, float* __restrict__ part) {
+// CHECK: the same pass also counts the non-finite gradient elements (the found-inf test of GradScaler.unscale_) -- one per-workgroup count
+// next to each partial.  Inf / NaN is told by the exponent bits, which no fast-math flag can fold away (a `x != x` test can vanish).  The
+// float arithmetic is the same statement sequence in both instantiations: the sum is the same to the bit with or without the check.
+__device__ __forceinline__ unsigned nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+template <bool CHECK>
+__global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict__ g, long long n, float* __restrict__ part,
+                                                         unsigned* __restrict__ cnt) {
   const long long n4 = n >> 2;
   const float4* g4 = reinterpret_cast<const float4*>(g);
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  unsigned c = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     const float4 v = g4[i];
     a.x += v.x * v.x; a.y += v.y * v.y; a.z += v.z * v.z; a.w += v.w * v.w;
+    if constexpr (CHECK) c += nonfinite(v.x) + nonfinite(v.y) + nonfinite(v.z) + nonfinite(v.w);
   }
   float s = (a.x + a.y) + (a.z + a.w);
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s += v * v; }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const float v = g[(n4 << 2) + threadIdx.x];
+    s += v * v;
+    if constexpr (CHECK) c += nonfinite(v);
+  }
   s = wave_sum(s);
   __shared__ float red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  if constexpr (CHECK) {
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    __shared__ unsigned cred[4];
+    if ((threadIdx.x & 63) == 0) cred[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[blockIdx.x] = cred[0] + cred[1] + cred[2] + cred[3];
+  } else {
+    __syncthreads();
+  }
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-__global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict__ part, int np, float* __restrict__ out) {
+// Adam's bias corrections for step t: 1 - beta1^t and sqrt(1 - beta2^t) -- ONE device expression for the step state and the guard
+__device__ __forceinline__ void adam_bias_dev(float b1, float b2, float t, float* bc1, float* bc2_sqrt) {
+  *bc1 = 1.f - powf(b1, t);
+  *bc2_sqrt = sqrtf(1.f - powf(b2, t));
+}
+// Non-finite guard state (device, fp32): NF_T = optimizer steps actually taken, NF_SKIPPED = steps skipped, NF_FLAG = this step is
+// skipped (1) or not (0), NF_BC1 / NF_BC2 = the bias corrections 1-beta1^t, sqrt(1-beta2^t) of the taken step t.
+enum { NF_T = 0, NF_SKIPPED = 1, NF_FLAG = 2, NF_BC1 = 3, NF_BC2 = 4 };
+// CHECK: out[1] = the non-finite count; with a guard, out[2] = this step's skip flag and the guard advances (one thread, after the
+// fold): a clean step takes t+1 and its bias corrections -- from bias_table[2(t-1) ..] (host powf, what mmdti_adam_step computes
+// by value) or, without a table, from the device expression of step_state_advance_kernel.
+template <bool CHECK>
+__global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict__ part, int np, float* __restrict__ out,
+                                                         const unsigned* __restrict__ cnt, float* __restrict__ guard,
+                                                         const float* __restrict__ bias_table, int table_steps, float b1, float b2) {
   __shared__ float red[256];
   float s = 0.f;
   for (int i = threadIdx.x; i < np; i += 256) s += part[i];
   red[threadIdx.x] = s;
+  __shared__ unsigned cred[CHECK ? 256 : 1];
+  if constexpr (CHECK) {
+    unsigned c = 0;
+    for (int i = threadIdx.x; i < np; i += 256) c += cnt[i];
+    cred[threadIdx.x] = c;
+  }
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    if (threadIdx.x < w) {
+      red[threadIdx.x] += red[threadIdx.x + w];
+      if constexpr (CHECK) cred[threadIdx.x] += cred[threadIdx.x + w];
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) *out += red[0];
+  if (threadIdx.x == 0) {
+    *out += red[0];
+    if constexpr (CHECK) {
+      out[1] = (float)cred[0];
+      if (guard) {
+        const bool skip = cred[0] != 0;
+        out[2] = skip ? 1.f : 0.f;
+        guard[NF_FLAG] = skip ? 1.f : 0.f;
+        if (skip) {
+          guard[NF_SKIPPED] += 1.f;
+        } else {
+          const float t = guard[NF_T] + 1.f;
+          guard[NF_T] = t;
+          if (bias_table) {
+            const int i = min((int)t, table_steps) - 1;      // (the host sizes the table to every step it has enqueued)
+            guard[NF_BC1] = bias_table[2 * i];
+            guard[NF_BC2] = bias_table[2 * i + 1];
+          } else {
+            adam_bias_dev(b1, b2, t, &guard[NF_BC1], &guard[NF_BC2]);
+          }
+        }
+      }
+    }
+  }
 }
 
 // Step state kept on the device so that a whole training step can be replayed from a captured HIP graph (host-side
@@ -520,8 +586,7 @@ __global__ void step_state_advance_kernel(float* __restrict__ st, unsigned long 
   const float t = (float)(k + 1);
   st[0] = t;
   st[1] = base_lr * lam;
-  st[2] = 1.f - powf(b1, t);
-  st[3] = sqrtf(1.f - powf(b2, t));
+  adam_bias_dev(b1, b2, t, &st[2], &st[3]);
   unsigned long long x = *salt + 0x9E3779B97F4A7C15ull;       // splitmix64: a fresh, well-mixed word per step
   unsigned long long z = x;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -530,15 +595,26 @@ __global__ void step_state_advance_kernel(float* __restrict__ st, unsigned long 
   salt[1] = z ^ (z >> 31);
 }
 
+// GUARD: the non-finite guard of sumsq_fold_kernel<true> decides -- a skipped step leaves before anything is read or written,
+// a taken one uses the guard's bias corrections (of the steps actually taken).  The unguarded instantiation is the plain Adam pass.
+template <bool GUARD>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, bf16_t* __restrict__ pb, bf16_t* __restrict__ ph, long long n, float lr, float b1,
                                                    float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                   const float* __restrict__ gscale, const float* __restrict__ state) {
+                                                   const float* __restrict__ gscale, const float* __restrict__ state,
+                                                   const float* __restrict__ guard) {
+  if constexpr (GUARD) {
+    if (guard[NF_FLAG] != 0.f) return;
+  }
   const float gs = gscale ? *gscale : 1.0f;
   if (state) {               // device-resident schedule (graph replay): this step's rate and bias corrections
     lr = state[1];
     bc1 = state[2];
     bc2_sqrt = state[3];
+  }
+  if constexpr (GUARD) {
+    bc1 = guard[NF_BC1];
+    bc2_sqrt = guard[NF_BC2];
   }
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     float gi = g[i] * gs;
@@ -576,6 +652,13 @@ using namespace mmdti;
 
 extern "C" const char* mmdti_last_error(void) { return g_err; }
 extern "C" int mmdti_abi_version(void) { return 1; }
+
+// Adam's bias corrections of step t as mmdti_adam_step computes them by value (host powf): also what mmdti_adam_bias_table lists,
+// so that a guarded eager step reproduces the unguarded one to the bit
+static void adam_bias_host(float beta1, float beta2, int step, float* bc1, float* bc2_sqrt) {
+  *bc1 = 1.f - powf(beta1, (float)step);
+  *bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
+}
 
 #define DROP_SETUP(name)                                                                  \
   MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, name ": dropout p out of range");          \
@@ -793,8 +876,9 @@ extern "C" int mmdti_sumsq_f32(mmdti_stream_t stream, const float* g, long long 
   MMDTI_REQUIRE(g && out && n > 0, "sumsq_f32: bad arguments");
   if (ws && ws_floats >= 1 && aligned16(g)) {
     const int wgs = (int)min((long long)min(ws_floats, SUMSQ_WGS), (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(sumsq_part_kernel, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g, n, ws);
-    hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, wgs, out);
+    hipLaunchKernelGGL(sumsq_part_kernel<false>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g, n, ws, nullptr);
+    hipLaunchKernelGGL(sumsq_fold_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, wgs, out, nullptr, nullptr, nullptr, 0,
+                       0.f, 0.f);
   } else {
     hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, g, n, out);
   }
@@ -806,11 +890,43 @@ extern "C" int mmdti_adam_step(mmdti_stream_t stream, float* p, const float* g, 
                                long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                int step, const float* grad_scale_dev, const float* step_state_dev, void* p_f16) {
   MMDTI_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_state_dev), "adam_step: bad arguments");
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev, step_state_dev);
+  float bc1, bc2s;
+  adam_bias_host(beta1, beta2, step, &bc1, &bc2s);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev, step_state_dev, nullptr);
   MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_sumsq_check_f32(mmdti_stream_t stream, const float* g, long long n, float* out, float* ws, int ws_floats, float* guard,
+                                     const float* bias_table, int table_steps, float beta1, float beta2) {
+  MMDTI_REQUIRE(g && out && ws && n > 0 && ws_floats >= 2, "sumsq_check_f32: bad arguments");
+  MMDTI_REQUIRE(aligned16(g), "sumsq_check_f32: 16-byte alignment required");
+  MMDTI_REQUIRE(!bias_table || table_steps >= 1, "sumsq_check_f32: empty bias-correction table");
+  // the workgroup count of mmdti_sumsq_f32 with ws_floats / 2 partials: the same partials, so the same sum to the bit
+  const int wgs = (int)min((long long)min(ws_floats / 2, SUMSQ_WGS), (n / 4 + 255) / 256 + 1);
+  unsigned* cnt = reinterpret_cast<unsigned*>(ws + wgs);
+  hipLaunchKernelGGL(sumsq_part_kernel<true>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g, n, ws, cnt);
+  hipLaunchKernelGGL(sumsq_fold_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, wgs, out, cnt, guard, bias_table,
+                     table_steps, beta1, beta2);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_adam_step_guarded(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev,
+                                       const float* step_state_dev, void* p_f16, const float* guard) {
+  MMDTI_REQUIRE(p && g && m && v && n > 0 && guard, "adam_step_guarded: bad arguments");
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale_dev, step_state_dev,
+                     guard);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host) {
+  MMDTI_REQUIRE(table_host && steps >= 1, "adam_bias_table: bad arguments");
+  for (int t = 1; t <= steps; ++t) adam_bias_host(beta1, beta2, t, &table_host[2 * (t - 1)], &table_host[2 * (t - 1) + 1]);
   return MMDTI_OK;
 }
 

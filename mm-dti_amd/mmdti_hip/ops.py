@@ -1036,6 +1036,40 @@ def adam_step(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, gra
                           float(beta2), float(eps), float(weight_decay), int(step), _p(grad_scale), _p(step_state), _p(p_f16))
 
 
+def sumsq_check(g, out, ws, guard=None, bias_table=None, beta1=0.9, beta2=0.999):
+    """out[0] += sum of squares of g -- the same to the bit as sumsq(g, out, ws[:len(ws) // 2]) -- and out[1] = the number of
+    inf / NaN elements of g.  ws: fp32 scratch, up to 4096 values.  guard (fp32 [>= 5], zero-initialised): the device state of
+    the non-finite step guard -- the pass then decides this step (out[2] = skip flag) and advances the guard; its bias corrections
+    come from bias_table (adam_bias_table) or, if None, from the device expression of step_state_advance."""
+    _chk(g, F32, "sumsq_check.g"); _chk(out, F32, "sumsq_check.out"); _chk(ws, F32, "sumsq_check.ws")
+    assert out.numel() >= (3 if guard is not None else 2), "sumsq_check: out holds {sum, count[, flag]}"
+    if guard is not None:
+        _chk(guard, F32, "sumsq_check.guard")
+        assert guard.numel() >= 5
+    if bias_table is not None:
+        _chk(bias_table, F32, "sumsq_check.bias_table")
+    lib().mmdti_sumsq_check_f32(_stream(), g.data_ptr(), g.numel(), out.data_ptr(), ws.data_ptr(), ws.numel(), _p(guard), _p(bias_table),
+                                0 if bias_table is None else bias_table.numel() // 2, float(beta1), float(beta2))
+    return out
+
+
+def adam_step_guarded(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, guard, grad_scale=None, step_state=None, p_f16=None):
+    """adam_step under the guard that sumsq_check advanced: nothing is written when the guard's flag is set; the bias corrections are
+    the guard's (lr: by value, or the step state's)."""
+    _chk(guard, F32, "adam_step_guarded.guard")
+    lib().mmdti_adam_step_guarded(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), p.numel(), float(lr),
+                                  float(beta1), float(beta2), float(eps), float(weight_decay), _p(grad_scale), _p(step_state), _p(p_f16),
+                                  guard.data_ptr())
+
+
+def adam_bias_table(beta1, beta2, steps, device):
+    """fp32 [steps, 2] device table of (1-beta1^t, sqrt(1-beta2^t)) for t = 1 .. steps, computed on the host exactly as adam_step does
+    from its by-value step; enqueued from pinned memory (no synchronisation)."""
+    host = torch.empty(steps, 2, dtype=F32, pin_memory=True)
+    lib().mmdti_adam_bias_table(float(beta1), float(beta2), int(steps), host.data_ptr())
+    return host.to(device, non_blocking=True)
+
+
 def step_state_advance(state, salt, base_lr, warmup, total, beta1=0.9, beta2=0.999):
     """state [4] fp32, salt [2] int64 (device): advance the optimizer-step counter, this step's learning rate / bias
     corrections and the dropout salt, then publish the salt to every kernel library."""

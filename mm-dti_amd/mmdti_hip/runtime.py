@@ -131,27 +131,65 @@ class ParamArena:
         # (bf16 shadow, fp32 data, fp32 gradient, forward-GEMM shadow: fp16 in the fp16 forward-operand mode, else the bf16 one)
         return self.shadow[o0:o].view(shape), self.data[o0:o].view(shape), self.grad[o0:o].view(shape), (w16 if w16 is not None else self.shadow[o0:o].view(shape))
 
-    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_norm: Optional[float] = None, step_state=None):
+    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, max_norm: Optional[float] = None, step_state=None, guard=None):
         """torch.optim.Adam semantics (tasks/trainer.py:160) + optional global-norm clipping (:274), one fused pass.
-        step_state: device-resident schedule (ops.step_state_advance) -- lr and the step count then live on the device."""
+        step_state: device-resident schedule (ops.step_state_advance) -- lr and the step count then live on the device.
+        guard: device state of the non-finite step guard (new_nonfinite_guard) -- GradScaler.step's skip (:280): one pass over the
+        gradients counts inf / NaN elements (fused with the clipping norm) and, if there is any, the Adam pass writes nothing.  The
+        bias corrections then follow the guard's count of steps actually taken (a table of the host's values indexed by it, or the
+        step state's device expression), never the host's step_count, which cannot know about a skip without a synchronisation.
+        -> (grad_norm, skipped): the pre-clip global norm (None when neither clipping nor the guard computed it) and this step's
+        skip flag as a device scalar (None without a guard)."""
         if self.adam_m is None:
             self.adam_m = torch.zeros_like(self.data)
             self.adam_v = torch.zeros_like(self.data)
         self.step_count += 1
-        scale = None
-        if max_norm is not None:
+        scale = norm = skipped = None
+        if guard is not None:
+            table = None
+            if step_state is None:
+                table = self._bias_table(betas)
+            buf = torch.zeros(3 + 4096, device=self.data.device, dtype=torch.float32)    # {sum, count, flag} | partials | counts
+            ops.sumsq_check(self.grad, buf[:3], buf[3:], guard, table, betas[0], betas[1])
+            ss, skipped = buf[:1], buf[2:3]
+        elif max_norm is not None:
             buf = torch.zeros(1 + 2048, device=self.data.device, dtype=torch.float32)      # the sum | per-workgroup partials (fixed-order fold)
             ss = buf[:1]
             ops.sumsq(self.grad, ss, buf[1:])
+        if guard is not None or max_norm is not None:
+            norm = ss.sqrt()
+        if max_norm is not None:
             # clip_grad_norm_: coef = max_norm / (norm + 1e-6), clamped to 1 (tiny scalar math; stays on device, no sync)
-            scale = torch.clamp(max_norm / (ss.sqrt() + 1e-6), max=1.0)
+            scale = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
         # (the Adam pass writes BOTH 16-bit shadows -- bf16 for the backward GEMMs, fp16 for the forward ones -- through raw pointers:
         #  a captured graph's replays keep them fresh too; the fp16 one exists once a forward GEMM has asked for it)
-        ops.adam_step(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, weight_decay,
-                      self.step_count, scale, step_state, p_f16=self.shadow16 if self._epoch16 == self._epoch else None)
+        p_f16 = self.shadow16 if self._epoch16 == self._epoch else None
+        if guard is None:
+            ops.adam_step(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, weight_decay,
+                          self.step_count, scale, step_state, p_f16=p_f16)
+        else:
+            ops.adam_step_guarded(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, weight_decay,
+                                  guard, scale, step_state, p_f16=p_f16)
         self._epoch += 1
         if self.shadow16 is not None and self._epoch16 == self._epoch - 1:
             self._epoch16 = self._epoch
+        return norm, skipped
+
+    def _bias_table(self, betas):
+        """Device table of the host's bias corrections for t = 1 .. >= step_count (the guard's t never exceeds the steps enqueued):
+        rebuilt, at twice the length, when the step count outgrows it -- enqueued, no synchronisation."""
+        tab = getattr(self, "_bias_tab", None)
+        if tab is None or tab[0] != tuple(betas) or tab[1].shape[0] < self.step_count:
+            steps = max(1024, 2 * self.step_count)
+            tab = (tuple(betas), ops.adam_bias_table(betas[0], betas[1], steps, self.data.device))
+            self._bias_tab = tab
+        return tab[1]
+
+
+def new_nonfinite_guard(device) -> torch.Tensor:
+    """Device state of the non-finite step guard (ops.sumsq_check): fp32 {optimizer steps taken, steps skipped, this step's skip
+    flag, 1-beta1^t, sqrt(1-beta2^t)} (+ padding), all zero."""
+    return torch.zeros(8, device=device, dtype=torch.float32)
 
 
 class _ShadowCache:

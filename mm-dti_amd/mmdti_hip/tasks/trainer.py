@@ -10,6 +10,8 @@ reproduced, with the reference's own run frozen in tests/golden/g10_trainer_*.np
   * Adam(lr, eps=1e-6), HF linear warm-up/decay over ``len(loader) * epochs`` steps, warm-up ``int(steps*warmup_ratio)``;
   * ``loss = alpha*task + beta*infonce + beta*ct`` in the four call forms selected by return_infonce_loss/return_ct_loss;
   * gradient clipping at ``max_norm`` only in the AMP branch (``use_amp``), none otherwise (:270-281);
+  * in the AMP branch also the GradScaler's skip of an optimizer step whose gradients hold an inf / NaN (:280; the schedule still
+    advances, :282) -- ``skip_nonfinite`` (default: ``use_amp``); the epoch's skipped steps go to ``history`` and the epoch log;
   * the per-epoch FDS pass over the re-shuffled training loader in train mode under no_grad (:288-306);
   * validation each epoch, first metric decides; best checkpoint ``{'model_state_dict': ...}`` written to
     ``dump_dir/model_{fold}.pth`` (rank 0 only under data parallelism), early stopping with ``patience``, reload of the
@@ -184,6 +186,8 @@ class Trainer(object):
         self.max_norm = params.get('max_norm', 1.0)
         self.cuda = params.get('use_cuda', False)
         self.amp = params.get('use_amp', False)
+        # the skip-on-inf/NaN half of the reference's GradScaler (use_amp, :268-282): on exactly where the reference has a scaler
+        self.skip_nonfinite = bool(params.get('skip_nonfinite', self.amp))
         self.device = torch.device("cuda" if torch.cuda.is_available() and self.cuda else "cpu")
         self.scaler = None          # bf16 MFMA compute with fp32 master weights: no loss scaling (the reference: fp16 + GradScaler)
         self.alpha = params.get('alpha', 1)
@@ -312,7 +316,7 @@ class Trainer(object):
         num_training_steps = len(train_dataloader) * self.max_epochs
         engine = FineTuner(model, self.task, learning_rate=self.learning_rate, adam_eps=1e-6, warmup_ratio=0.0,
                            total_steps=num_training_steps, alpha=self.alpha, beta=self.beta,
-                           max_norm=self.max_norm if self.amp else None, distributed=self.distributed)
+                           max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite)
         engine.warmup = int(num_training_steps * self.warmup_ratio)
         self._engine = engine
         task_loss = None if _is_builtin_loss(loss_func, self.task) else loss_func
@@ -327,21 +331,26 @@ class Trainer(object):
             for net_input, net_target in self.device_batches(train_dataloader, feature_name):
                 out = engine.step(net_input, net_target, epoch=epoch, use_weight=use_weight, return_infonce_loss=return_infonce_loss,
                                   return_ct_loss=return_ct_loss, loss_func=task_loss)
-                logged.append(torch.stack([out.loss, out.task_loss,
-                                           out.infonce_loss if out.infonce_loss is not None else out.loss.new_zeros(()),
-                                           out.ct_loss if out.ct_loss is not None else out.loss.new_zeros(())]))
+                row = [out.loss, out.task_loss, out.infonce_loss if out.infonce_loss is not None else out.loss.new_zeros(()),
+                       out.ct_loss if out.ct_loss is not None else out.loss.new_zeros(())]
+                if out.skipped is not None:
+                    row.append(out.skipped.reshape(()))          # (the guard's skip flag rides on the same read)
+                logged.append(torch.stack(row))
             steps = torch.stack(logged).cpu().numpy() if logged else np.zeros((0, 4))        # the epoch's ONE device->host sync
+            skipped = int(steps[:, 4].sum()) if steps.shape[1] > 4 else 0
+            steps = steps[:, :4]
             if self.fds and epoch >= model.fds_cfg.start_update:
                 engine.fds_epoch_pass((self.decorate_batch(b, feature_name) for b in train_dataloader), epoch)
             y_preds, val_loss, metric_score = self.predict(model, valid_dataset, loss_func, activation_fn, dump_dir, fold, target_scaler,
                                                            epoch, load_model=False, feature_name=feature_name, return_infonce_loss=False)
             total_val_loss = float(np.mean(val_loss))
             _metric, _score = next(iter(metric_score.items()))
-            self.history.append(dict(epoch=epoch, steps=steps, val_loss=total_val_loss, metric=_metric, score=_score))
+            self.history.append(dict(epoch=epoch, steps=steps, val_loss=total_val_loss, metric=_metric, score=_score, skipped=skipped))
             if steps.size:
                 logger.info('Epoch [{}/{}] train_loss: {:.4f}, train_m_loss: {:.4f}, train_infonce_loss: {:.4f}, train_ct_loss: {:.4f}, '
                             'val_loss: {:.4f}, val_{}: {:.4f}, {:.1f}s'.format(epoch + 1, self.max_epochs, *steps.mean(0), total_val_loss,
-                                                                                _metric, _score, time.time() - start_time))
+                                                                                _metric, _score, time.time() - start_time)
+                            + (', skipped steps: {}'.format(skipped) if self.skip_nonfinite else ''))
             is_early_stop, min_val_loss, wait, max_score = self._early_stop_choice(
                 wait, total_val_loss, min_val_loss, metric_score, max_score, model, dump_dir, fold, self.patience, epoch)
             if is_early_stop:

@@ -9,7 +9,9 @@ AMP branch :274), same per-epoch FDS statistics pass (:288-306).  What changes i
     clip + Adam + shadow refresh are each ONE pass over contiguous HBM;
   * no host synchronisation inside the step: the four logged scalars stay on the device (``StepOutput``) and are
     fetched by the caller when it wants them (the reference does four ``float(t.data)`` syncs per step, :195-197,238);
-  * optional data parallelism (``parallel.py``): global InfoNCE negatives + bucketed gradient all-reduce over RCCL.
+  * optional data parallelism (``parallel.py``): global InfoNCE negatives + bucketed gradient all-reduce over RCCL;
+  * ``skip_nonfinite``: the other half of the reference's GradScaler (:268-282) -- an optimizer step whose gradients hold an inf or
+    NaN is skipped (parameters and Adam state untouched, the schedule advances), decided on the device.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import torch
 
 from .functional import CELossFn, MSELossFn, BCELogitsLossFn
 from .parallel import ArenaReducer, GlobalNegatives, gather_features
-from .runtime import ParamArena, add_grad_ready_hook, remove_grad_ready_hook, dropout_state
+from .runtime import ParamArena, add_grad_ready_hook, remove_grad_ready_hook, dropout_state, new_nonfinite_guard
 
 
 @dataclass
@@ -31,6 +33,8 @@ class StepOutput:
     infonce_loss: Optional[torch.Tensor]    # the GLOBAL InfoNCE value (under DDP: sum of the ranks' shares)
     ct_loss: Optional[torch.Tensor]
     logits: torch.Tensor
+    skipped: Optional[torch.Tensor] = None     # skip_nonfinite: 1.0 if this step's optimizer update was skipped (non-finite gradient)
+    grad_norm: Optional[torch.Tensor] = None   # pre-clip global gradient norm (what clip_grad_norm_ returns), when the step computed it
 
 
 def linear_warmup_lr(base_lr: float, step: int, warmup: int, total: int) -> float:
@@ -55,13 +59,20 @@ def _qkv_groups(model):
 
 class FineTuner:
     def __init__(self, model, task: str, learning_rate=1e-4, adam_eps=1e-6, warmup_ratio=0.03, total_steps=1000, alpha=1.0, beta=0.1,
-                 max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20):
+                 max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False):
+        """skip_nonfinite: GradScaler.step's guard (tasks/trainer.py:268-282) -- a step whose gradient arena holds any inf / NaN element
+        leaves the parameters, both Adam moments, Adam's step count and the 16-bit shadows as they were, while the learning-rate
+        schedule advances.  The decision is taken on the device (no host synchronisation, captured inside graphed_step) from the
+        all-reduced gradients under data parallelism, so every rank takes the same one."""
         self.model, self.task = model, task
         self.lr, self.eps, self.alpha, self.beta, self.max_norm = learning_rate, adam_eps, alpha, beta, max_norm
         self.total_steps = total_steps
         self.warmup = int(total_steps * warmup_ratio)
         self.sched_step = 0
         self.arena = ParamArena(model.parameters(), adjacent=_qkv_groups(model))
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.last_optimizer_outputs = (None, None)       # (skipped, grad_norm) of the latest optimizer_step
+        self.guard = new_nonfinite_guard(self.arena.data.device) if self.skip_nonfinite else None
         self._graphs, self._state, self._salt, self._salted = {}, None, None, False
         self.world = 1
         self.reducer = None
@@ -143,9 +154,24 @@ class FineTuner:
         return StepOutput(loss.detach(), tl.detach(), infonce_global, None if ct is None else ct.detach(), logits.detach())
 
     def optimizer_step(self):
+        """Clip + Adam with this step's learning rate; the schedule advances (also on a step the guard skips).
+        -> (skipped, grad_norm) device scalars, each None when this engine does not compute it (see StepOutput).  They are also kept
+        as ``last_optimizer_outputs``, which is where step() reads them: callers may wrap this method and drop its return value."""
         lr = linear_warmup_lr(self.lr, self.sched_step, self.warmup, self.total_steps)
-        self.arena.adam_step(lr, eps=self.eps, max_norm=self.max_norm)
+        norm, skipped = self.arena.adam_step(lr, eps=self.eps, max_norm=self.max_norm, guard=self.guard)
         self.sched_step += 1
+        self.last_optimizer_outputs = (skipped, norm)
+        return skipped, norm
+
+    @property
+    def optimizer_steps(self) -> Optional[torch.Tensor]:
+        """skip_nonfinite: optimizer updates actually applied (Adam's step count), a device scalar (fp32); None without the guard."""
+        return None if self.guard is None else self.guard[0]
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """skip_nonfinite: optimizer steps skipped for a non-finite gradient, a device scalar (fp32); None without the guard."""
+        return None if self.guard is None else self.guard[1]
 
     # ------------------------------------------------------------------ the whole step as ONE HIP graph
     def graphed_step(self, net_input: dict, net_target: torch.Tensor, epoch: int = 0, use_weight: bool = False, **kw) -> StepOutput:
@@ -187,7 +213,7 @@ class FineTuner:
         from . import ops
         ops.step_state_advance(self._state, self._salt, self.lr, self.warmup, self.total_steps)
         out = self.forward_backward(net_input, net_target, epoch, use_weight, **kw)
-        self.arena.adam_step(0.0, eps=self.eps, max_norm=self.max_norm, step_state=self._state)
+        out.grad_norm, out.skipped = self.arena.adam_step(0.0, eps=self.eps, max_norm=self.max_norm, step_state=self._state, guard=self.guard)
         self.arena.step_count -= 1                   # (the host-side counter is advanced by graphed_step, once per replay)
         return out
 
@@ -207,7 +233,7 @@ class FineTuner:
         # warm-up on a side stream (lazy stream / buffer creation must not happen inside the capture), with a throw-away copy of
         # the state this step mutates
         saved = (self.arena.data.clone(), self.arena.adam_m.clone(), self.arena.adam_v.clone(), self._state.clone(), self._salt.clone(),
-                 self.arena.step_count)
+                 self.arena.step_count, None if self.guard is None else self.guard.clone())
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -217,6 +243,8 @@ class FineTuner:
         self.arena.data.copy_(saved[0]); self.arena.adam_m.copy_(saved[1]); self.arena.adam_v.copy_(saved[2])
         self._state.copy_(saved[3]); self._salt.copy_(saved[4])
         self.arena.step_count = saved[5]
+        if self.guard is not None:
+            self.guard.copy_(saved[6])
         self.arena.refresh_shadow()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -232,7 +260,9 @@ class FineTuner:
             ops.seed_salt_reset(sync=False)
             self._salted = False
         out = self.forward_backward(net_input, net_target, epoch, use_weight, **kw)
+        self.last_optimizer_outputs = (None, None)
         self.optimizer_step()
+        out.skipped, out.grad_norm = self.last_optimizer_outputs
         return out
 
     # ------------------------------------------------------------------ tasks/trainer.py:288-306
