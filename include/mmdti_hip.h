@@ -201,7 +201,8 @@ int mmdti_bert_layer_bwd(mmdti_stream_t stream, int Mq, int B, int L, int heads,
  * closers, intermediate + GELU), and the backward UP TO the weight gradients (ten launches; ds1 / ds2: the gradients of the two inputs).
  * The backward's five bf16 activation gradients (dzb, du, dyb, dq, dkv) are the caller's: they are the A operands of the layer's weight
  * gradients, which the caller launches (mmdti_linear_dw_grouped takes one token-row count per launch, this layer has two).
- * ws of the backward: da [Mq,D] | dctx [Mq,D] (bf16) | dz [Mq,D] f32 | the attention backward's row term. */
+ * ws of the backward: da [Mq,D] | dctx [Mq,D] (bf16) | dz [Mq,D] f32 | the attention backward's row term.
+ * ds2 may be null (s2 needs no gradient, e.g. a frozen tower 2): its GEMM is then not launched; dkv is still written. */
 int mmdti_bert_cross_layer_fwd(mmdti_stream_t stream, int Mq, int Mk, int B, int Lq, int Lk, int heads, int D, int F, float scale,
                                float p_hid, float p_att, unsigned long long seed, unsigned int site_att, unsigned int site_o,
                                unsigned int site_f, const float* s1_32, const void* s1_16, const void* s2_16, const float* key_add,
@@ -589,6 +590,14 @@ int mmdti_sumsq_check_f32(mmdti_stream_t stream, const float* g, long long n, fl
 int mmdti_adam_step_guarded(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
                             float lr, float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev,
                             const float* step_state_dev, void* p_f16 /* nullable */, const float* guard);
+/* mmdti_adam_step (guard null) or mmdti_adam_step_guarded (guard given; step ignored) that leaves alone every element i with
+ * skip[i / 8] != 0: p, m, v and both shadows keep their bits (parameters frozen after the arena was built, the reference's
+ * requires_grad = False: torch.optim.Adam skips a parameter whose grad is None).  skip: one byte per 8 elements, (n + 7) / 8 bytes;
+ * the arena's parameters start at multiples of 8 elements.  The other elements get exactly the unmasked update. */
+int mmdti_adam_step_masked(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev,
+                           const float* step_state_dev, void* p_f16 /* nullable */, const float* guard /* nullable */,
+                           const unsigned char* skip);
 /* HOST function: table_host[2(t-1)], [2(t-1)+1] = 1-beta1^t, sqrt(1-beta2^t) for t = 1 .. steps, exactly as mmdti_adam_step computes
  * them from its by-value step. */
 int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host);

@@ -597,12 +597,14 @@ __global__ void step_state_advance_kernel(float* __restrict__ st, unsigned long 
 
 // GUARD: the non-finite guard of sumsq_fold_kernel<true> decides -- a skipped step leaves before anything is read or written,
 // a taken one uses the guard's bias corrections (of the steps actually taken).  The unguarded instantiation is the plain Adam pass.
-template <bool GUARD>
+// MASK: skip[i / 8] != 0 leaves element i alone (p, m, v and both shadows): parameters frozen after the arena was built.  Arena
+// offsets are multiples of 8, so a group of 8 elements never straddles two parameters.  Only mmdti_adam_step_masked instantiates it.
+template <bool GUARD, bool MASK = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, bf16_t* __restrict__ pb, bf16_t* __restrict__ ph, long long n, float lr, float b1,
                                                    float b2, float eps, float wd, float bc1, float bc2_sqrt,
                                                    const float* __restrict__ gscale, const float* __restrict__ state,
-                                                   const float* __restrict__ guard) {
+                                                   const float* __restrict__ guard, const unsigned char* __restrict__ skip = nullptr) {
   if constexpr (GUARD) {
     if (guard[NF_FLAG] != 0.f) return;
   }
@@ -617,6 +619,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     bc2_sqrt = guard[NF_BC2];
   }
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    if constexpr (MASK) {
+      if (skip[i >> 3]) continue;
+    }
     float gi = g[i] * gs;
     float pi = p[i];
     if (wd != 0.f) gi += wd * pi;
@@ -920,6 +925,26 @@ extern "C" int mmdti_adam_step_guarded(mmdti_stream_t stream, float* p, const fl
   hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale_dev, step_state_dev,
                      guard);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_adam_step_masked(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                      const float* grad_scale_dev, const float* step_state_dev, void* p_f16, const float* guard,
+                                      const unsigned char* skip) {
+  MMDTI_REQUIRE(p && g && m && v && n > 0 && skip && (guard || step >= 1 || step_state_dev), "adam_step_masked: bad arguments");
+  if (guard) {
+    hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale_dev, step_state_dev,
+                       guard, skip);
+  } else {
+    float bc1, bc2s;
+    adam_bias_host(beta1, beta2, step, &bc1, &bc2s);
+    hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev, step_state_dev,
+                       nullptr, skip);
+  }
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

@@ -210,7 +210,7 @@ extern "C" int mmdti_bert_cross_layer_bwd(mmdti_stream_t stream, int Mq, int Mk,
                                           float* db_o, float* db_o2, float* dg_ln1, float* dbt_ln1, float* dg_ln2, float* dbt_ln2, void* dzb,
                                           void* du, void* dyb, void* dq, void* dkv, void* ws, long long ws_bytes) {
   MMDTI_REQUIRE(Mq > 0 && Mk > 0 && D > 0 && F > 0 && heads > 0 && D % heads == 0, "bert_cross_layer_bwd: bad shape");
-  MMDTI_REQUIRE(dout && ds1 && ds2 && q && kv && stats && y && am && ar && u_aux && z && zm && zr && w_q && w_kv && w_o && w_i && w_o2 && g_ln1 && g_ln2 && dzb &&
+  MMDTI_REQUIRE(dout && ds1 && q && kv && stats && y && am && ar && u_aux && z && zm && zr && w_q && w_kv && w_o && w_i && w_o2 && g_ln1 && g_ln2 && dzb &&
                     du && dyb && dq && dkv && ws, "bert_cross_layer_bwd: null argument");
   const int hd = D / heads;
   const long long MD = (long long)Mq * D;
@@ -240,6 +240,7 @@ extern "C" int mmdti_bert_cross_layer_bwd(mmdti_stream_t stream, int Mq, int Mk,
   if (int e = mmdti_gemm_bf16(stream, dq, w_q, ds1, Mq, D, D, D, D, D, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 1.f, 1.f, nullptr, nullptr, D, MMDTI_ACT_NONE, nullptr,
                               nullptr, D, MMDTI_DT_F32, 0.f, 0ull, 0u, nullptr, nullptr, nullptr, 0))
     return e;
+  if (!ds2) return MMDTI_OK;          // (s2 needs no gradient)
   return mmdti_gemm_bf16(stream, dkv, w_kv, ds2, Mk, D, 2 * D, 2 * D, D, D, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 1.f, 0.f, nullptr, nullptr, D, MMDTI_ACT_NONE, nullptr,
                          nullptr, D, MMDTI_DT_F32, 0.f, 0ull, 0u, nullptr, nullptr, nullptr, 0);
 }

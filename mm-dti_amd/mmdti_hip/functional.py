@@ -12,6 +12,7 @@ stream / LayerNorm statistics / softmax / pair-bias chain S fp32, q|k|v and atte
 from __future__ import annotations
 
 import os
+import weakref
 
 import math
 from types import SimpleNamespace
@@ -22,6 +23,7 @@ import torch
 from . import ops
 from .ops import BF16, F32
 from .runtime import fused_views, wbf16, wfwd, gbuf, dropout_state, notify_grads_ready
+from .freeze import layer_trainable, plan_tower, trainable_flags
 
 
 # ------------------------------------------------------------------------------------------------- helpers
@@ -120,6 +122,14 @@ def _wgrad_stream():
     return _wgrad_stream_obj
 
 
+def _kept(L, li, plan):
+    """What the forward keeps of layer li for the backward: everything, or -- below the lowest layer the backward reaches
+    (freeze.plan_tower) -- only the dropout site numbers (the layer above reads the site of the one under it)."""
+    if li >= plan.lowest:
+        return L
+    return SimpleNamespace(site_f=getattr(L, "site_f", None))
+
+
 class _Sites:
     """Dropout site numbering inside one forward call."""
 
@@ -146,10 +156,12 @@ class PairEncoderFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, emb, bias, padding_mask, mod, training, key_tiles=None, pack=None, aux_grads=False):
+    def forward(ctx, emb, bias, padding_mask, mod, training, key_tiles=None, pack=None, aux_grads=False, anchor=None):
         """aux_grads: S_last and x_pre are differentiable outputs (the reference's auxiliary returns -- attn, delta_pair_repr, x_norm,
         delta_pair_repr_norm, models/transformers.py:141-181 -- are functions of them); fp32 pair planes only.  MM_Model discards those
-        returns (mm_model.py:559), so the hot path leaves it off and autograd never materialises a gradient for them."""
+        returns (mm_model.py:559), so the hot path leaves it off and autograd never materialises a gradient for them.
+        anchor: freeze.grad_anchor(mod.parameters()) -- the backward runs when a parameter of the tower trains even if neither emb nor
+        bias needs a gradient (frozen embedding and pair-bias front end); no gradient is returned for it."""
         if pack is not None:
             B, N, D = pack.B, pack.S, emb.shape[-1]
             if emb.dim() != 2 or emb.shape[0] != pack.M:
@@ -181,8 +193,14 @@ class PairEncoderFn(torch.autograd.Function):
         sites = _Sites()
         st = SimpleNamespace(B=B, N=N, D=D, H=H, ld=ld, M=M, seed=seed, p_emb=p_emb, p_res=p_res, p_att=p_att, layers=[], kt=key_tiles, slot=slot,
                              row_off=row_off, packed=pack is not None)
-        keep = any(ctx.needs_input_grad)      # inference (torch.no_grad / frozen inputs): nothing is kept for a backward --
+        keep = any(ctx.needs_input_grad)      # inference (torch.no_grad / frozen tower and inputs): nothing is kept for a backward --
                                               # the 15 per-layer logit tensors are freed as the stack advances
+        if keep:
+            # the backward follows the trainable set (freeze.plan_tower): it stops at the lowest layer that trains unless the embedding
+            # LayerNorm or emb needs the stream gradient; the pair-gradient chain leaves layer 0 only when the bias needs a gradient
+            eln = mod.emb_layer_norm
+            st.plan = plan_tower(layer_trainable(mod.layers), ctx.needs_input_grad[0] or eln.weight.requires_grad or eln.bias.requires_grad,
+                                 ctx.needs_input_grad[1])
         emb = emb.contiguous()
         st.emb = emb
         st.pad = padding_mask
@@ -230,7 +248,7 @@ class PairEncoderFn(torch.autograd.Function):
                 elif nl is not None:
                     out, st.f_mean, st.f_rstd = ln_out, mn, rn
                 if keep:
-                    st.layers.append(L)
+                    st.layers.append(_kept(L, li, st.plan))
                 continue
             L.qkv = ops.linear_fwd(L.h1, wfwd(att.in_proj.weight), att.in_proj.bias)
             L.site_att = sites.next()
@@ -256,7 +274,7 @@ class PairEncoderFn(torch.autograd.Function):
             else:
                 x = ops.linear_fwd(L.a, wfwd(layer.fc2.weight), layer.fc2.bias, residual=L.x1, out_dtype=F32, drop_p=p_res, seed=seed, site=L.site_f)
             if keep:
-                st.layers.append(L)
+                st.layers.append(_kept(L, li, st.plan))
         st.x_last = x
         if out is None:
             if mod.final_layer_norm is not None:
@@ -315,20 +333,28 @@ class PairEncoderFn(torch.autograd.Function):
         # (holding weight gradients back for the end pays where the pair-bias backward has work to hide -- large batches; at a few
         #  thousand rows every launch is latency-bound and the held layers would only miss the sequenced path below)
         n_defer = DEFER_WGRAD_LAYERS if (dout.is_cuda and M >= 8192) else 0
-        seq_ok, seq_ws = _unimol_seq_workspace(st, mod) if (LAYER_SEQ and dout.is_cuda and st.layers) else (False, None)
+        plan = st.plan
+        full = [all(p.requires_grad for p in l.parameters()) for l in mod.layers] if st.layers else []
+        seq_ok, seq_ws = (_unimol_seq_workspace(st, mod, full[plan.lowest:]) if (LAYER_SEQ and dout.is_cuda and st.layers and plan.lowest < len(st.layers))
+                          else (False, None))
         for li, layer, L in zip(range(len(st.layers) - 1, -1, -1), reversed(mod.layers), reversed(st.layers)):
+            if li < plan.lowest:                         # nothing at or under this layer trains: the backward stops above it
+                L.__dict__.clear()
+                continue
             att, ln1, ln2 = layer.self_attn, layer.self_attn_layer_norm, layer.final_layer_norm
             hold = li < n_defer                          # this layer's weight gradients wait for the end (see _launch_deferred_wgrads)
             pending = []                                 # the layer's four weight gradients leave as ONE grouped launch
+            lowest = not plan.needs_dx(li)               # the lowest layer that runs, with nothing under it that reads its dx
 
             def _wgrad(*args, **kw):
                 pending.append((args, kw))
-            if seq_ok and dx16 is not None and not hold:
+            if seq_ok and dx16 is not None and not hold and full[li]:
+                # (a frozen layer, or one with some frozen parameters, takes the op-by-op path below: its gradient kernels drop out)
                 g_zero = G is None
                 if g_zero:
                     G = (torch.empty if st.kt is None else torch.zeros)(L.s.shape, device=L.s.device, dtype=ops.pair_grad_dtype(L.s))
                 dx, dx16 = _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, seq_ws,
-                                                 None if li == 0 else (below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)))
+                                                 None if (li == 0 or lowest) else (below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)))
                 L.__dict__.clear()
                 notify_grads_ready(layer.parameters())
                 continue
@@ -350,8 +376,15 @@ class PairEncoderFn(torch.autograd.Function):
                 G = (torch.empty if st.kt is None else torch.zeros)(L.s.shape, device=L.s.device, dtype=ops.pair_grad_dtype(L.s))
             dqkv = ops.pair_attn_bwd(L.qkv, L.s, do, G, B, N, H, ld, scale, g_zero, st.p_att, seed, L.site_att, key_tiles=st.kt, row_off=st.row_off)
             _wgrad(dqkv, L.h1, att.in_proj.weight, att.in_proj.bias)
-            dh1 = ops.linear_bwd_input(dqkv, wbf16(att.in_proj.weight))
-            if li > 0:
+            if lowest and not (ln1.weight.requires_grad or ln1.bias.requires_grad):
+                dh1 = None                               # (no dX product: nothing reads it)
+            else:
+                dh1 = ops.linear_bwd_input(dqkv, wbf16(att.in_proj.weight))
+            if dh1 is None:
+                dx, dx16 = None, None
+            elif lowest:
+                dx, dx16 = ops.layernorm_bwd(dh1, L.x, ln1.weight, L.m1, L.r1, gbuf(ln1.weight), gbuf(ln1.bias), dres=dx), None
+            elif li > 0:
                 dx, dx16 = ops.layernorm_bwd(dh1, L.x, ln1.weight, L.m1, L.r1, gbuf(ln1.weight), gbuf(ln1.bias), dres=dx,
                                              bf16_copy=(st.p_res, below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)))
             else:
@@ -365,17 +398,25 @@ class PairEncoderFn(torch.autograd.Function):
             if not hold:
                 notify_grads_ready(layer.parameters())
         eln = mod.emb_layer_norm
-        demb = ops.layernorm_bwd(dx, st.emb.view(M, D), eln.weight, st.emb_mean, st.emb_rstd, gbuf(eln.weight), gbuf(eln.bias),
-                                 row_zero=None if st.pad is None else st.pad.reshape(-1), drop_p=st.p_emb, seed=seed, site=st.site_emb)
+        demb = None
+        if plan.below:
+            demb = ops.layernorm_bwd(dx, st.emb.view(M, D), eln.weight, st.emb_mean, st.emb_rstd, gbuf(eln.weight), gbuf(eln.bias),
+                                     row_zero=None if st.pad is None else st.pad.reshape(-1), drop_p=st.p_emb, seed=seed, site=st.site_emb)
+            if not ctx.needs_input_grad[0]:
+                demb = None
         notify_grads_ready(list(eln.parameters()) + ([] if mod.final_layer_norm is None else list(mod.final_layer_norm.parameters())))
-        if G is None:
+        if not ctx.needs_input_grad[1]:
+            G = None                                                                 # (the pair bias does not train)
+        elif G is None:
             G = torch.zeros_like(st.bias0)
-        if st.slot is not None:
+        if G is not None and st.slot is not None:
             st.slot.g = G                                                            # -> PairBiasFn.backward (see forward)
             G = torch.zeros((), device=G.device, dtype=torch.float16).expand(G.shape)
         _launch_deferred_wgrads(deferred, deferred_layers)
         _join_stream_after_backward()
-        return (demb if st.packed else demb.view(B, N, D)), G, None, None, None, None, None, None
+        if demb is not None and not st.packed:
+            demb = demb.view(B, N, D)
+        return demb, G, None, None, None, None, None, None, None
 
 
 # ---- all layers of the tower behind one library call per direction (csrc/layers.hip: mmdti_unimol_stack_fwd / _bwd).  At the
@@ -409,7 +450,9 @@ def _unimol_stack_tables(mod, M):
     if arena is None or not ops.GROUPED_DW or M < ops.GROUPED_DW_MIN_ROWS:
         return None
     cache = arena.__dict__.setdefault("_stack_tables", {})
-    key = (id(mod), ops.FWD_F16)
+    # (a weak reference: an id is recycled once the module dies; the flags: a parameter frozen after the first step must not be written
+    #  through the raw gradient table -- the stack calls take every parameter of every layer as trainable)
+    key = (weakref.ref(mod), ops.FWD_F16, trainable_flags(q for l in layers for q in l.parameters()))
     T = cache.get(key)
     if T is None:
         D, F = l0.fc1.weight.shape[1], l0.fc1.weight.shape[0]
@@ -569,15 +612,16 @@ def _unimol_layer_fwd_seq(st, layer, L, s_prev, key_pad, key_tiles, rag_store, r
     return x_out, ln_out, mn, rn
 
 
-def _unimol_seq_workspace(st, mod):
-    """-> (usable, workspace) for mmdti_unimol_layer_bwd: the variant the library sequences is the hot one -- every parameter trainable, dimensions the grouped weight-gradient kernels take, no per-launch event
-    timing requested.  The workspace holds one layer's temporaries and is shared by all layers of this backward."""
+def _unimol_seq_workspace(st, mod, full):
+    """-> (usable, workspace) for mmdti_unimol_layer_bwd: the variant the library sequences is the hot one -- every parameter of the layer
+    trainable (full: per running layer), dimensions the grouped weight-gradient kernels take, no per-launch event timing requested.  The
+    workspace holds one layer's temporaries and is shared by all layers of this backward."""
     lay = mod.layers[0]
     D, F, M = st.D, lay.fc1.weight.shape[0], st.M
-    L0 = st.layers[0]
+    L0 = st.layers[st.plan.lowest]
     ok = ((L0.h1.dtype != torch.float16 or L0.s.dtype == torch.float16)      # (fp16 operands: the sequencer covers the compact pair planes)
           and not ops.kernel_timer.names and ops.GROUPED_DW and D % 256 == 0 and F % 256 == 0 and M >= ops.GROUPED_DW_MIN_ROWS
-          and all(p.requires_grad for p in mod.parameters()))
+          and any(full))
     if not ok:
         return False, None
     tiles = (D // 256) * (F // 256) * 2 + (D // 256) ** 2 * 4
@@ -619,6 +663,8 @@ class PairBiasFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, dist, edge_type, gbf, proj, ld, key_tiles_host=None, rows_host=None):
+        # anchor: freeze.grad_anchor over gbf and proj (None when both are frozen): autograd reaches the backward whenever one of
+        # them trains, whichever one it is
         # key_tiles_host ([B] ints on the HOST, ragged batches): real key tiles per molecule -- the fused compact path then
         # neither produces the bias of the all-padding key tiles nor visits them in the backward (PairEncoderFn skips them too)
         B, N, _ = dist.shape
@@ -822,8 +868,10 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
     return L, out32, out16
 
 
-def _bert_layer_bwd(st, L, dout, seed):
-    """-> (ds1 fp32 [B*Lq,D], ds2 fp32 [B*Lk,D] or None when self_attn (then ds1 holds the sum))."""
+def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
+    """-> (ds1 fp32 [B*Lq,D], ds2 fp32 [B*Lk,D] or None when self_attn (then ds1 holds the sum)).  want: (ds1, ds2) are needed -- an
+    input gradient nobody reads is returned as None and its dX products are skipped where the path launches them itself (the
+    self-attention sequencers compute ds1 inside their one call)."""
     B, Lq, Lk, D = st.B, st.Lq, st.Lk, st.D
     Mq, Mk, vl = st.Mq, st.Mk, st.vl
     W, heads, ld = L.W, L.heads, L.ld
@@ -832,7 +880,7 @@ def _bert_layer_bwd(st, L, dout, seed):
                                                                                                         W.ln2_w, W.ln2_b)):
         return _bert_layer_bwd_seq(st, L, dout, seed), None
     if getattr(L, "seq", False) == "cross" and not ops.kernel_timer.names and all(gbuf(p) is not None for p in (W.o_b, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b)):
-        return _bert_cross_layer_bwd_seq(st, L, dout, seed)
+        return _bert_cross_layer_bwd_seq(st, L, dout, seed, want)
     pend, raw = [], []                     # the layer's weight gradients leave as one grouped launch (see _lin_bwd_params_many)
     dz, dzb = ops.layernorm_bwd(dout, L.z, W.ln2_w, L.zm, L.zr, gbuf(W.ln2_w), gbuf(W.ln2_b), bf16_copy=(L.p_hid, L.site_f, gbuf(W.o2_b)))
     pend.append(((dzb, L.i, W.o2_w, W.o2_b), dict(bias_done=True)))
@@ -855,14 +903,16 @@ def _bert_layer_bwd(st, L, dout, seed):
         dq, dk, dv = ops.attn_bwd(L.q, L.k, L.v, L.key_add, dctx, L.stats, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), L.p_att, seed, L.site_att,
                                   out=outv, vl=vl)
         raw.append((dqkv, L.s1_16 if L.self_attn else L.s2_16, L.fw[2], L.fb[2].view(-1), None))
-        ds1 = dy
+        ds1 = dy if want[0] else None
         if L.self_attn:
-            ops.gemm(dqkv, L.fw[0], M=Mq, N=D, K=3 * D, lda=3 * D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+            if want[0]:
+                ops.gemm(dqkv, L.fw[0], M=Mq, N=D, K=3 * D, lda=3 * D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
             _lin_bwd_params_many(pend, raw)
             return ds1, None
         pend.append(((dq, L.s1_16, W.q_w, W.q_b), {}))
-        ops.gemm(dq, wbf16(W.q_w), M=Mq, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
-        ds2 = ops.gemm(dqkv, L.fw[0], M=Mk, N=D, K=2 * D, lda=2 * D, ldb=D, transB=True, out_dtype=F32)
+        if want[0]:
+            ops.gemm(dq, wbf16(W.q_w), M=Mq, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+        ds2 = ops.gemm(dqkv, L.fw[0], M=Mk, N=D, K=2 * D, lda=2 * D, ldb=D, transB=True, out_dtype=F32) if want[1] else None
         _lin_bwd_params_many(pend, raw)
         return ds1, ds2
     if L.fused:
@@ -887,11 +937,15 @@ def _bert_layer_bwd(st, L, dout, seed):
     pend.append(((dv, L.s2_16, W.v_w, W.v_b), {}))
     _lin_bwd_params_many(pend, raw)
     # ds1 = dy (residual) + dq.Wq ; ds2 = dk.Wk + dv.Wv     (fp32, accumulated by the GEMM's beta=1 epilogue)
-    ds1 = dy
-    ops.gemm(dq, wbf16(W.q_w), M=Mq, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+    ds1 = dy if want[0] else None
+    if want[0]:
+        ops.gemm(dq, wbf16(W.q_w), M=Mq, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
     if L.self_attn:
-        ops.gemm(dk, wbf16(W.k_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
-        ops.gemm(dv, wbf16(W.v_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+        if want[0]:
+            ops.gemm(dk, wbf16(W.k_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+            ops.gemm(dv, wbf16(W.v_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+        return ds1, None
+    if not want[1]:
         return ds1, None
     ds2 = ops.gemm(dk, wbf16(W.k_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out_dtype=F32)
     ops.gemm(dv, wbf16(W.v_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds2, ldc=D, beta=1.0)
@@ -926,7 +980,7 @@ def _bert_cross_layer_fwd_seq(st, L, s1_32, s1_16, s2_16, key_add, W, heads, p_h
     return L, out32, out16
 
 
-def _bert_cross_layer_bwd_seq(st, L, dout, seed):
+def _bert_cross_layer_bwd_seq(st, L, dout, seed, want=(True, True)):
     """_bert_layer_bwd of a layer that went through _bert_cross_layer_fwd_seq: its ten launches up to the weight gradients as ONE library
     call, then the weight gradients exactly as the op-by-op path launches them -> (ds1, ds2) fp32."""
     B, Lq, Lk, D, Mq, Mk, vl = st.B, st.Lq, st.Lk, st.D, st.Mq, st.Mk, st.vl
@@ -935,7 +989,7 @@ def _bert_cross_layer_bwd_seq(st, L, dout, seed):
     dev = dout.device
     dout = dout.contiguous()
     e = torch.empty
-    ds1, ds2 = e(Mq, D, device=dev, dtype=F32), e(Mk, D, device=dev, dtype=F32)
+    ds1, ds2 = e(Mq, D, device=dev, dtype=F32), (e(Mk, D, device=dev, dtype=F32) if want[1] else None)   # (ds2 null: not launched)
     dzb, du, dyb = e(Mq, D, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=BF16), e(Mq, D, device=dev, dtype=BF16)
     dq, dqkv = e(Mq, D, device=dev, dtype=BF16), torch.empty_like(L.qkv)
     nrow = heads * Mq if vl is not None else B * heads * Lq
@@ -943,7 +997,7 @@ def _bert_cross_layer_bwd_seq(st, L, dout, seed):
     p = ops._p
     ops.lib().mmdti_bert_cross_layer_bwd(
         ops._stream(), Mq, Mk, B, Lq, Lk, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(L.p_hid), float(L.p_att), int(seed), int(L.site_att),
-        int(L.site_o), int(L.site_f), dout.data_ptr(), ds1.data_ptr(), ds2.data_ptr(), p(L.key_add), *(ops._NO_VARLEN if vl is None else vl.args()),
+        int(L.site_o), int(L.site_f), dout.data_ptr(), ds1.data_ptr(), p(ds2), p(L.key_add), *(ops._NO_VARLEN if vl is None else vl.args()),
         L.q.data_ptr(), L.qkv.data_ptr(), L.stats.data_ptr(), L.y.data_ptr(), L.am.data_ptr(), L.ar.data_ptr(), L.u.data_ptr(), ops.ACT_GELU_DX,
         L.z.data_ptr(), L.zm.data_ptr(), L.zr.data_ptr(), wbf16(W.q_w).data_ptr(), L.fw[0].data_ptr(), wbf16(W.o_w).data_ptr(), wbf16(W.i_w).data_ptr(),
         wbf16(W.o2_w).data_ptr(), W.ln1_w.data_ptr(), W.ln2_w.data_ptr(), gbuf(W.o_b).data_ptr(), gbuf(W.o2_b).data_ptr(), gbuf(W.ln1_w).data_ptr(),
@@ -953,7 +1007,7 @@ def _bert_cross_layer_bwd_seq(st, L, dout, seed):
     pend = [((dzb, L.i, W.o2_w, W.o2_b), dict(bias_done=True)), ((du, L.a16, W.i_w, W.i_b), {}), ((dyb, L.ctx, W.o_w, W.o_b), dict(bias_done=True)),
             ((dq, L.s1_16, W.q_w, W.q_b), {})]
     _lin_bwd_params_many(pend, [(dqkv, L.s2_16, L.fw[2], L.fb[2].view(-1), None)])
-    return ds1, ds2
+    return (ds1 if want[0] else None), ds2
 
 
 def _bert_layer_fwd_seq(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites):
@@ -1021,7 +1075,7 @@ def _bert_stack_tables(mod, st):
     if (arena is None or not ops.GROUPED_DW or st.Mq < ops.GROUPED_DW_MIN_ROWS or D % heads or not ops.attn_eligible(st.Lq, st.Lk, D // heads, D)):
         return None
     cache = arena.__dict__.setdefault("_stack_tables", {})
-    key = (id(mod), ops.FWD_F16, "bert")
+    key = (weakref.ref(mod), ops.FWD_F16, "bert", trainable_flags(q for l in layers for q in l.parameters()))
     T = cache.get(key)
     if T is None:
         ok = D % 256 == 0 and F % 256 == 0
@@ -1143,7 +1197,9 @@ class RobertaEncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, input_ids, attention_mask, mod, training, pack=None):
-        """pack (packing.PackedRows over the right-padded input_ids): the tower runs on the packed rows -- every sequence's real
+        """anchor: freeze.grad_anchor(mod.parameters()), None when the whole tower is frozen (it then runs forward only and keeps
+        nothing).
+        pack (packing.PackedRows over the right-padded input_ids): the tower runs on the packed rows -- every sequence's real
         tokens plus ONE representative pad row (pad word embedding + position padding_idx: all masked slots are that row) -- and
         returns [pack.M, D]; masked keys are left out of the attention instead of being added finfo.min (probability 0 either way)."""
         B, Lq = input_ids.shape
@@ -1162,7 +1218,10 @@ class RobertaEncoderFn(torch.autograd.Function):
         e = ops.embedding_fwd3(ids, mod.word, pos, mod.position, mod.token_type)      # word + position + token type 0, one pass
         zeros = None
         st = SimpleNamespace(B=B, Lq=Lq, Lk=Lq if vl is None else vl.Lk, D=D, seed=seed, ids=ids, pos=pos, zeros=zeros, e=e, layers=[], p_hid=p_hid, Mq=Mq, Mk=Mq, vl=vl)
-        keep = any(ctx.needs_input_grad)      # inference: no per-layer activations are kept
+        keep = any(ctx.needs_input_grad)      # inference (or a frozen tower): no per-layer activations are kept
+        if keep:
+            # the backward stops at the lowest layer that trains unless the embeddings train (freeze.plan_tower)
+            st.plan = plan_tower(layer_trainable(mod.layers), any(p.requires_grad for p in mod.embeddings.parameters()))
         st.site_emb = sites.next()
         x32, x16, st.em, st.er = ops.layernorm_fwd(e.view(Mq, D), mod.emb_ln_w, mod.emb_ln_b, cfg.ln_eps, want_f32=True, want_bf16=True,
                                                    drop_p=p_hid, seed=seed, site=st.site_emb)
@@ -1173,10 +1232,10 @@ class RobertaEncoderFn(torch.autograd.Function):
                                              and not ops.kernel_timer.names) else None)
         if T is not None:
             x32 = _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites)
-        for layer in (mod.layers if T is None else ()):
+        for li, layer in enumerate(mod.layers if T is None else ()):
             L, x32, x16 = _bert_layer_fwd(st, x32, x16, x16, key_add, bert_weights(layer), cfg.heads, p_hid, p_att, cfg.ln_eps, seed, sites, True)
             if keep:
-                st.layers.append(L)
+                st.layers.append(_kept(L, li, st.plan))
         if keep:
             ctx.st, ctx.mod = st, mod
         return x32.view(B, Lq, D) if vl is None else x32
@@ -1193,10 +1252,17 @@ class RobertaEncoderFn(torch.autograd.Function):
             dx = _bert_stack_bwd(st, dx)
             notify_grads_ready(st.stack.T.params)
             st.stack = None
-        for layer, L in zip(reversed(list(mod.layers)), reversed(st.layers)):
-            dx, _ = _bert_layer_bwd(st, L, dx, st.seed)
+        plan = st.plan
+        for li, layer, L in zip(range(len(st.layers) - 1, -1, -1), reversed(list(mod.layers)), reversed(st.layers)):
+            if li < plan.lowest:                 # nothing at or under this layer trains
+                L.__dict__.clear()
+                continue
+            dx, _ = _bert_layer_bwd(st, L, dx, st.seed, (plan.needs_dx(li), False))
             L.__dict__.clear()
             notify_grads_ready(layer.parameters())
+        if not plan.below:                       # frozen embeddings: no LayerNorm backward, no embedding-gradient kernels
+            _join_stream_after_backward()
+            return None, None, None, None, None, None
         de = ops.layernorm_bwd(dx, st.e.view(st.Mq, D), mod.emb_ln_w, st.em, st.er, gbuf(mod.emb_ln_w), gbuf(mod.emb_ln_b),
                                drop_p=st.p_hid, seed=st.seed, site=st.site_emb)
         cfg = mod.cfg
@@ -1216,8 +1282,10 @@ class CrossLayerFn(torch.autograd.Function):
     """One BertCrossEncoder layer (mm_module.py:663-677, :615-626): s1 attends to s2 under an additive key mask."""
 
     @staticmethod
-    def forward(ctx, s1, s2, key_add, layer, cfg, training, packs=None):
-        """packs = (PackedRows of s1, PackedRows of s2): s1 [M1, D] / s2 [M2, D] are packed rows, key_add is None -- the keys of a
+    def forward(ctx, s1, s2, key_add, layer, cfg, training, packs=None, anchor=None):
+        """anchor: freeze.grad_anchor(layer.parameters()) -- the backward runs when the layer trains even if neither input needs a
+        gradient.
+        packs = (PackedRows of s1, PackedRows of s2): s1 [M1, D] / s2 [M2, D] are packed rows, key_add is None -- the keys of a
         sequence are the REAL rows of s2 (the reference adds -10000 to padded keys, mm_model.py:392-393: probability exactly 0)."""
         seed = dropout_state.next_seed()
         sites = _Sites()
@@ -1244,10 +1312,12 @@ class CrossLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         st, L = ctx.st, ctx.L
-        ds1, ds2 = _bert_layer_bwd(st, L, dout.contiguous().view(st.Mq, st.D), st.seed)
+        want = ctx.needs_input_grad[:2]          # (a frozen tower feeding s1 / s2: its input gradient is not computed)
+        ds1, ds2 = _bert_layer_bwd(st, L, dout.contiguous().view(st.Mq, st.D), st.seed, want)
         L.__dict__.clear()
         notify_grads_ready(ctx.layer.parameters())
-        return ds1.view(ctx.shapes[0]), ds2.view(ctx.shapes[1]), None, None, None, None, None
+        return (None if ds1 is None else ds1.view(ctx.shapes[0]), None if ds2 is None else ds2.view(ctx.shapes[1]), None, None, None, None, None,
+                None)
 
 
 class DropoutFn(torch.autograd.Function):
@@ -1281,8 +1351,9 @@ class InfoNCEFn(torch.autograd.Function):
     returned is this rank's share of the global loss (the sum over ranks equals the single-process loss)."""
 
     @staticmethod
-    def forward(ctx, query, positive, mod, training, gather, reduce_scatter, row0, packs=None):
-        """packs = (PackedRows of query, PackedRows of positive): [M, D] packed rows; the unmasked mean over the padded positions
+    def forward(ctx, query, positive, mod, training, gather, reduce_scatter, row0, packs=None, anchor=None):
+        """anchor: freeze.grad_anchor(mod.parameters()) -- the backward runs when the head trains even if neither input needs a gradient.
+        packs = (PackedRows of query, PackedRows of positive): [M, D] packed rows; the unmasked mean over the padded positions
         (infonce.py:32-33) weights each representative pad row by the number of padded positions it stands for."""
         if packs is not None:
             B, D = packs[0].B, query.shape[-1]
@@ -1393,8 +1464,9 @@ class InfoNCEFn(torch.autograd.Function):
         dxp = proj_bwd(st.Lp, dboth[:, d:], mod.info_proj_positive, st.Np, 0.0, 2, ctx.needs_input_grad[1], None if pk is None else pk[1])
         notify_grads_ready(mod.parameters())
         if pk is not None:
-            return dxq, dxp, None, None, None, None, None, None
-        return (None if dxq is None else dxq.view(B, st.Nq, st.D), None if dxp is None else dxp.view(B, st.Np, st.D), None, None, None, None, None, None)
+            return dxq, dxp, None, None, None, None, None, None, None
+        return (None if dxq is None else dxq.view(B, st.Nq, st.D), None if dxp is None else dxp.view(B, st.Np, st.D), None, None, None, None, None, None,
+                None)
 
 
 class InfoNCELossFn(torch.autograd.Function):

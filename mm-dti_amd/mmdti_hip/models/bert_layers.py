@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from ..unicore_compat import LayerNorm
 from ..functional import RobertaEncoderFn, CrossLayerFn
+from ..freeze import grad_anchor
 
 
 class _SelfAttnParams(nn.Module):
@@ -71,7 +72,8 @@ class BertCrossEncoder(nn.Module):
             key_add = None
         outs = []
         for layer in self.layer:
-            s1_hidden_states = CrossLayerFn.apply(s1_hidden_states.float(), s2_hidden_states.float(), key_add, layer, self.cfg, self.training, packs)
+            s1_hidden_states = CrossLayerFn.apply(s1_hidden_states.float(), s2_hidden_states.float(), key_add, layer, self.cfg, self.training, packs,
+                                                  grad_anchor(layer.parameters()))
             if output_all_encoded_layers:
                 outs.append(s1_hidden_states)
         if not output_all_encoded_layers:
@@ -147,7 +149,7 @@ class RobertaTower(nn.Module):
             attention_mask = torch.ones_like(input_ids)
         if input_ids.shape[1] + self.cfg.pad_idx + 1 > self.cfg.max_pos:
             raise ValueError(f"sequence length {input_ids.shape[1]} exceeds max_position_embeddings {self.cfg.max_pos}")
-        out = RobertaEncoderFn.apply(self.word, input_ids, attention_mask, self, self.training, pack)
+        out = RobertaEncoderFn.apply(grad_anchor(self.parameters()), input_ids, attention_mask, self, self.training, pack)
         return (out,)
 
     @classmethod

@@ -11,6 +11,7 @@ star nevertheless lists it as replaced, so this module offers the same two class
 State-dict keys equal the corresponding sub-trees of ``MM_Model`` (``embed_tokens``, ``encoder``, ``gbf``, ``gbf_proj`` /
 ``bert``), so tower weights can be moved between the fused model and the stand-alone encoders.
 """
+import itertools
 import os
 
 import torch
@@ -18,6 +19,7 @@ import torch.nn as nn
 
 from ..unicore_compat import Dictionary, init_bert_params
 from ..functional import PairBiasFn, EmbeddingFn
+from ..freeze import grad_anchor
 from .. import ops
 from .transformers import TransformerEncoderWithPair
 from .bert_layers import RobertaTower
@@ -72,7 +74,7 @@ class UnimolEncoder(nn.Module):
         padding_mask = src_tokens.eq(self.padding_idx)
         x = EmbeddingFn.apply(self.embed_tokens.weight, src_tokens, self.padding_idx)
         N = src_distance.shape[-1]
-        bias = PairBiasFn.apply(self.gbf.means.weight, src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N))
+        bias = PairBiasFn.apply(grad_anchor(itertools.chain(self.gbf.parameters(), self.gbf_proj.parameters())), src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N))
         encoder_rep, _, _ = self.encoder.encode(x, bias, padding_mask)
         return encoder_rep
 

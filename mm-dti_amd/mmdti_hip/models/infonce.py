@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from ..functional import InfoNCEFn, InfoNCELossFn
+from ..freeze import grad_anchor
 
 
 class InfoNCE(nn.Module):
@@ -41,7 +42,8 @@ class InfoNCE(nn.Module):
         if packs is not None:
             if negative_keys is not None or self.reduction != 'mean' or query.dim() != 2 or positive_key.dim() != 2 or packs[0].B != packs[1].B:
                 raise ValueError('packed rows: <query> / <positive_key> must be [rows, dim] with one packing each, implicit negatives.')
-            return InfoNCEFn.apply(query.float(), positive_key.float(), self, self.training, self._gather, self._reduce_scatter, self._row0, packs)
+            return InfoNCEFn.apply(query.float(), positive_key.float(), self, self.training, self._gather, self._reduce_scatter, self._row0, packs,
+                                   grad_anchor(self.parameters()))
         if negative_keys is not None:
             raise ValueError("explicit negative_keys are unreachable in the reference (infonce.py:98 raises); not supported")
         if self.reduction != 'mean':
@@ -52,7 +54,8 @@ class InfoNCE(nn.Module):
             raise ValueError('<query> and <positive_key> must be [batch, seq, dim] token representations.')
         if len(query) != len(positive_key):
             raise ValueError('<query> and <positive_key> must must have the same number of samples.')
-        return InfoNCEFn.apply(query.float(), positive_key.float(), self, self.training, self._gather, self._reduce_scatter, self._row0)
+        return InfoNCEFn.apply(query.float(), positive_key.float(), self, self.training, self._gather, self._reduce_scatter, self._row0, None,
+                               grad_anchor(self.parameters()))
 
 
 def info_nce(query, positive_key, negative_keys=None, temperature=0.1, reduction='mean', negative_mode='unpaired'):

@@ -20,6 +20,7 @@ Differences by design, all opt-in or inert for the reference's own usage:
 from __future__ import annotations
 
 import argparse
+import itertools
 import os
 from types import SimpleNamespace
 
@@ -29,6 +30,7 @@ import torch.nn as nn
 from ..unicore_compat import Dictionary, init_bert_params, get_activation_fn
 from ..functional import PairBiasFn, PairCompactFn, EmbeddingFn, DropoutFn, MaskedPoolFn, LinearF32Fn
 from .. import ops
+from ..freeze import grad_anchor
 from ..collate import right_pad, collate_batch
 from ..packing import PackedRows
 
@@ -322,7 +324,7 @@ class MM_Model(nn.Module):
         """mm_model.py:553-556 fused: -> the pair bias ([B,H,N,ld] fp32, or the tiled pair layout on the hot path).  key_tiles_host
         (ragged batches): [B] real key tiles per molecule, on the HOST; rows_host (packed token rows): [B] query rows per molecule."""
         N = src_distance.shape[-1]
-        return PairBiasFn.apply(self.gbf.means.weight, src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N), key_tiles_host,
+        return PairBiasFn.apply(grad_anchor(itertools.chain(self.gbf.parameters(), self.gbf_proj.parameters())), src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N), key_tiles_host,
                                 rows_host)
 
     def _packings(self, src_tokens, input_ids, atom_counts, token_counts, token_pad_id, packable):

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from ..unicore_compat import TransformerEncoderLayer, LayerNorm
 from ..functional import PairEncoderFn
+from ..freeze import grad_anchor
 
 
 class TransformerEncoderWithPair(nn.Module):
@@ -69,7 +70,7 @@ class TransformerEncoderWithPair(nn.Module):
         attention kernels skip the all-padding key tiles past it (ragged batches).
         pack (packing.PackedRows, with key_tiles): emb / padding_mask / x are packed rows [pack.M, ...] -- real tokens plus one
         representative pad row per molecule (see packing.py)."""
-        return PairEncoderFn.apply(emb, pair_bias, padding_mask, self, self.training, key_tiles, pack)
+        return PairEncoderFn.apply(emb, pair_bias, padding_mask, self, self.training, key_tiles, pack, False, grad_anchor(self.parameters()))
 
     def forward(
         self,
@@ -90,7 +91,8 @@ class TransformerEncoderWithPair(nn.Module):
             # the reference merges the key-padding mask into the CALLER's tensor in place (:122-135)
             pad = padding_mask.unsqueeze(1).unsqueeze(2).to(torch.bool)
             bias.masked_fill_(pad, float("-inf"))
-        x, s_last, x_pre = PairEncoderFn.apply(emb.float(), bias.float(), padding_mask, self, self.training, None, None, True)
+        x, s_last, x_pre = PairEncoderFn.apply(emb.float(), bias.float(), padding_mask, self, self.training, None, None, True,
+                                               grad_anchor(self.parameters()))
         token_mask = 1.0 - padding_mask.float() if padding_mask is not None else torch.ones(bsz, seq_len, device=emb.device)
         delta = s_last - bias.float()                  # (-inf - -inf at padded keys: filled next, as :163-164 does)
         if pad is not None:

@@ -1062,6 +1062,18 @@ def adam_step_guarded(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, g
                                   guard.data_ptr())
 
 
+def adam_step_masked(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, skip, guard=None, grad_scale=None, step_state=None,
+                     p_f16=None):
+    """adam_step (guard None) or adam_step_guarded (guard given) that leaves every element i with skip[i // 8] != 0 untouched: value, both
+    moments and both 16-bit shadows keep their bits (parameters frozen after the arena was built).  skip: uint8 device tensor."""
+    assert skip.dtype == torch.uint8 and skip.is_contiguous() and skip.numel() >= (p.numel() + 7) // 8, "adam_step_masked.skip"
+    if guard is not None:
+        _chk(guard, F32, "adam_step_masked.guard")
+    lib().mmdti_adam_step_masked(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), p.numel(), float(lr),
+                                 float(beta1), float(beta2), float(eps), float(weight_decay), int(step), _p(grad_scale), _p(step_state),
+                                 _p(p_f16), _p(guard), skip.data_ptr())
+
+
 def adam_bias_table(beta1, beta2, steps, device):
     """fp32 [steps, 2] device table of (1-beta1^t, sqrt(1-beta2^t)) for t = 1 .. steps, computed on the host exactly as adam_step does
     from its by-value step; enqueued from pinned memory (no synchronisation)."""

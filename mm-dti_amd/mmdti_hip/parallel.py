@@ -167,6 +167,17 @@ class ArenaReducer:
                 self._launch(*self.buckets[b], events=self._events[b])
                 self.overlapped += 1
 
+    def set_trainable(self, flags):
+        """flags: requires_grad per arena parameter (arena.params order).  A parameter frozen after construction never reports -- the
+        backward stops above it or drops its gradient kernels -- so buckets stop waiting for it: its slots stay zero."""
+        self._need = [set() for _ in self.buckets]
+        for p, f in zip(getattr(self.arena, "params", ()), flags):
+            if not f:
+                continue
+            lo, hi = self._range[id(p)]
+            for b in range(lo // self.per, (hi - 1) // self.per + 1):
+                self._need[b].add(id(p))
+
     def unreported(self):
         """ids of parameters that did not report during the last backward, per bucket (diagnostic / tests)."""
         return [need - have for need, have in zip(self._need, self._have)]

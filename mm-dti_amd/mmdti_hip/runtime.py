@@ -64,6 +64,25 @@ class ParamArena:
         self.adam_m: Optional[torch.Tensor] = None
         self.adam_v: Optional[torch.Tensor] = None
         self.step_count = 0
+        # parameters frozen after the arena was built (requires_grad cleared): their elements are skipped by the Adam pass
+        self.skip_mask: Optional[torch.Tensor] = None
+        self._flags = (True,) * len(self.params)
+
+    def sync_trainable(self) -> bool:
+        """Re-read requires_grad of the arena's parameters; rebuild the Adam skip mask when it changed.  -> True on a change.  (A
+        parameter frozen after construction keeps its slots: it gets no gradient and the masked Adam pass leaves it, and its moments,
+        alone -- torch.optim.Adam skips a parameter whose grad is None.)"""
+        flags = tuple(p.requires_grad for p in self.params)
+        if flags == self._flags:
+            return False
+        from .freeze import arena_skip_mask
+        self._flags = flags
+        m = arena_skip_mask(flags, [self.offsets[id(p)] for p in self.params], [p.numel() for p in self.params], self.numel, _ALIGN)
+        self.skip_mask = None if m is None else m.to(self.data.device)
+        for p, f in zip(self.params, flags):
+            if not f:
+                p.grad = None
+        return True
 
     def refresh_shadow(self):
         """Re-cast the whole fp32 arena into the bf16 shadow the GEMMs read."""
@@ -86,6 +105,9 @@ class ParamArena:
     def zero_grad(self):
         self.grad.zero_()
         for p in self.params:          # re-bind in case an optimizer dropped the views (set_to_none)
+            if not p.requires_grad:    # (frozen after construction: no gradient, as after the reference's zero_grad)
+                p.grad = None
+                continue
             if p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * self.offsets[id(p)]:
                 o, n = self.offsets[id(p)], p.numel()
                 p.grad = self.grad[o:o + n].view(p.shape)
@@ -164,7 +186,10 @@ class ParamArena:
         # (the Adam pass writes BOTH 16-bit shadows -- bf16 for the backward GEMMs, fp16 for the forward ones -- through raw pointers:
         #  a captured graph's replays keep them fresh too; the fp16 one exists once a forward GEMM has asked for it)
         p_f16 = self.shadow16 if self._epoch16 == self._epoch else None
-        if guard is None:
+        if self.skip_mask is not None:
+            ops.adam_step_masked(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, weight_decay,
+                                 self.step_count, self.skip_mask, guard, scale, step_state, p_f16=p_f16)
+        elif guard is None:
             ops.adam_step(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, weight_decay,
                           self.step_count, scale, step_state, p_f16=p_f16)
         else:

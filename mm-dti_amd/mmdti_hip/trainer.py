@@ -15,6 +15,7 @@ AMP branch :274), same per-epoch FDS statistics pass (:288-306).  What changes i
 """
 from __future__ import annotations
 
+import logging
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -24,6 +25,8 @@ import torch
 from .functional import CELossFn, MSELossFn, BCELogitsLossFn
 from .parallel import ArenaReducer, GlobalNegatives, gather_features
 from .runtime import ParamArena, add_grad_ready_hook, remove_grad_ready_hook, dropout_state, new_nonfinite_guard
+
+logger = logging.getLogger(__name__)
 
 
 @dataclass
@@ -69,7 +72,11 @@ class FineTuner:
         self.total_steps = total_steps
         self.warmup = int(total_steps * warmup_ratio)
         self.sched_step = 0
+        # the trainable set is what requires_grad says NOW (the reference's Adam(filter(lambda p: p.requires_grad, ...)), :160): frozen
+        # parameters (freeze_layers) stay out of the arena and never change
         self.arena = ParamArena(model.parameters(), adjacent=_qkv_groups(model))
+        self._outside = [p for p in model.parameters() if id(p) not in self.arena.offsets]
+        self._warned_unfrozen = False
         self.skip_nonfinite = bool(skip_nonfinite)
         self.last_optimizer_outputs = (None, None)       # (skipped, grad_norm) of the latest optimizer_step
         self.guard = new_nonfinite_guard(self.arena.data.device) if self.skip_nonfinite else None
@@ -106,6 +113,19 @@ class FineTuner:
             self.task_loss = None
 
     # ------------------------------------------------------------------
+    def _sync_trainable(self):
+        """Follow requires_grad changes made after construction: a parameter frozen since gets no gradient, no update and no moment
+        change from the next step on (masked Adam pass; captured graphs are re-captured); one unfrozen since is not in the optimizer
+        -- as in the reference, where it is not in Adam's parameter list -- and is never updated (one warning)."""
+        if self.arena.sync_trainable():
+            self._graphs.clear()
+            if self.reducer is not None:
+                self.reducer.set_trainable(self.arena._flags)
+        if not self._warned_unfrozen and self._outside and any(p.requires_grad for p in self._outside):
+            self._warned_unfrozen = True
+            logger.warning("FineTuner: a parameter that was frozen when the engine was built now requires grad; it is not in the "
+                           "optimizer and will not be updated (build a new FineTuner to train it)")
+
     def _bind_global_negatives(self, b_loc: int):
         if self.negs.active and self._b_loc != b_loc:
             self.model.infonce.set_global_negatives(self.negs.gather, self.negs.reduce_scatter, self.negs.row0(b_loc))
@@ -117,6 +137,8 @@ class FineTuner:
         select the reference's four call forms (tasks/trainer.py:184-212); ``loss_func`` replaces the built-in task-loss
         kernel with any callable on (logits, target)."""
         model = self.model
+        if not torch.cuda.is_current_stream_capturing():
+            self._sync_trainable()
         self.arena.zero_grad()
         if self.reducer is not None:
             self._bind_global_negatives(net_target.shape[0])
@@ -188,6 +210,7 @@ class FineTuner:
         # a replay with another batch of the same padded shape would run with the captured batch's lengths.  The graph therefore
         # runs the padded layout: correct for any batch of the shape.
         from .collate import HOST_FIELDS
+        self._sync_trainable()          # (before the graph look-up: a change of the trainable set drops the captured graphs)
         net_input = {k: v for k, v in net_input.items() if k not in HOST_FIELDS}
         key = (epoch >= getattr(getattr(self.model, "fds_cfg", None), "start_smooth", 1 << 30), bool(use_weight), tuple(sorted(kw.items())),
                tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(net_input.items())), tuple(net_target.shape), net_target.dtype)
