@@ -11,6 +11,7 @@ stream / LayerNorm statistics / softmax / pair-bias chain S fp32, q|k|v and atte
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import weakref
 
@@ -20,7 +21,7 @@ from typing import List, Optional
 
 import torch
 
-from . import ops
+from . import ops, paths
 from .ops import BF16, F32
 from .runtime import fused_views, wbf16, wfwd, gbuf, dropout_state, notify_grads_ready
 from .freeze import layer_trainable, plan_tower, trainable_flags
@@ -67,6 +68,7 @@ def _lin_bwd_params_many(calls, raw_items=()):
 
 # one C call per layer backward where the library has a sequencer for the variant at hand (csrc/layers.hip): the launch order,
 # kernels and arguments of the op-by-op path below, minus ~140 us of Python per layer -- what paces a step of 16-32 molecules
+# (which path a layer takes -- this call, the stack call further down, or op by op -- is decided in paths.py)
 LAYER_SEQ = os.environ.get("MMDTI_LAYER_SEQ", "1") != "0"
 POOL_THEN_PROJECT = os.environ.get("MMDTI_INFONCE_POOL_FIRST", "1") != "0"      # InfoNCE head: pool the GELU outputs, then project
 
@@ -120,6 +122,17 @@ def _wgrad_stream():
     if _wgrad_stream_obj is None:
         _wgrad_stream_obj = torch.cuda.Stream()
     return _wgrad_stream_obj
+
+
+def _switches():
+    """The switch values of this moment, for the decisions of paths.py (read per call: tests and bench.py flip them between steps)."""
+    return paths.Switches(LAYER_SEQ, STACK_SEQ, STACK_MAX_ROWS, ops.GROUPED_DW, ops.GROUPED_DW_MIN_ROWS, ops.FWD_F16, bool(ops.kernel_timer.names))
+
+
+def _pair_grad_chain(s, key_tiles):
+    """The pair-gradient chain G for logits `s`: fp32, or bf16 under MMDTI_PAIR_G_BF16; zeroed for ragged batches, whose skipped key
+    tiles are never written."""
+    return (torch.empty if key_tiles is None else torch.zeros)(s.shape, device=s.device, dtype=ops.pair_grad_dtype(s))
 
 
 def _kept(L, li, plan):
@@ -218,13 +231,15 @@ class PairEncoderFn(torch.autograd.Function):
         nlayers = len(mod.layers)
         nxt = None
         out = None
-        # (fp16 forward operands: the library's sequence covers the compact pair planes -- the only layout with fp16 q | k | v kernels)
-        seq = LAYER_SEQ and emb.is_cuda and (compact or not ops.FWD_F16) and not ops.kernel_timer.names and D == H * 8
+        sw = _switches()
+        path = paths.unimol_layer_fwd(sw, emb.is_cuda, compact, D, H)
+        seq = path == paths.LAYER
         kp0 = ops._u8(padding_mask) if seq else None
         # small batches: ALL layers from one library call (see _unimol_stack_fwd); the per-layer loop below then has nothing left to do
         st.stack = None
-        T = (_unimol_stack_tables(mod, M) if (seq and keep and STACK_SEQ and nlayers and M < STACK_MAX_ROWS and not aux_grads
-                                                and mod.final_layer_norm is not None) else None)
+        T = None
+        if paths.unimol_tower_fwd(sw, path, keep, nlayers, M, aux_grads, mod.final_layer_norm is not None) == paths.STACK:
+            T = _stack_tables(_unimol_stack_desc, mod, M, sw)
         if T is not None:
             x, out, s_prev = _unimol_stack_fwd(st, T, mod, x, s_prev, kp0, key_tiles, pack is None, row_off, scale, sites, tiled)
         for li, layer in enumerate(mod.layers if T is None else ()):
@@ -335,8 +350,7 @@ class PairEncoderFn(torch.autograd.Function):
         n_defer = DEFER_WGRAD_LAYERS if (dout.is_cuda and M >= 8192) else 0
         plan = st.plan
         full = [all(p.requires_grad for p in l.parameters()) for l in mod.layers] if st.layers else []
-        seq_ok, seq_ws = (_unimol_seq_workspace(st, mod, full[plan.lowest:]) if (LAYER_SEQ and dout.is_cuda and st.layers and plan.lowest < len(st.layers))
-                          else (False, None))
+        seq_path, seq_ws = _unimol_seq_workspace(st, mod, full, dout.is_cuda)
         for li, layer, L in zip(range(len(st.layers) - 1, -1, -1), reversed(mod.layers), reversed(st.layers)):
             if li < plan.lowest:                         # nothing at or under this layer trains: the backward stops above it
                 L.__dict__.clear()
@@ -348,11 +362,10 @@ class PairEncoderFn(torch.autograd.Function):
 
             def _wgrad(*args, **kw):
                 pending.append((args, kw))
-            if seq_ok and dx16 is not None and not hold and full[li]:
-                # (a frozen layer, or one with some frozen parameters, takes the op-by-op path below: its gradient kernels drop out)
+            if paths.unimol_layer_bwd(seq_path, dx16 is not None, hold, full[li]) == paths.LAYER:
                 g_zero = G is None
                 if g_zero:
-                    G = (torch.empty if st.kt is None else torch.zeros)(L.s.shape, device=L.s.device, dtype=ops.pair_grad_dtype(L.s))
+                    G = _pair_grad_chain(L.s, st.kt)
                 dx, dx16 = _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, seq_ws,
                                                  None if (li == 0 or lowest) else (below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)))
                 L.__dict__.clear()
@@ -372,8 +385,7 @@ class PairEncoderFn(torch.autograd.Function):
             do = ops.linear_bwd_input(dy1, wbf16(att.out_proj.weight))
             g_zero = G is None
             if g_zero:
-                # (fp32, or bf16 under MMDTI_PAIR_G_BF16; skipped key tiles of G are never written)
-                G = (torch.empty if st.kt is None else torch.zeros)(L.s.shape, device=L.s.device, dtype=ops.pair_grad_dtype(L.s))
+                G = _pair_grad_chain(L.s, st.kt)
             dqkv = ops.pair_attn_bwd(L.qkv, L.s, do, G, B, N, H, ld, scale, g_zero, st.p_att, seed, L.site_att, key_tiles=st.kt, row_off=st.row_off)
             _wgrad(dqkv, L.h1, att.in_proj.weight, att.in_proj.bias)
             if lowest and not (ln1.weight.requires_grad or ln1.bias.requires_grad):
@@ -382,13 +394,11 @@ class PairEncoderFn(torch.autograd.Function):
                 dh1 = ops.linear_bwd_input(dqkv, wbf16(att.in_proj.weight))
             if dh1 is None:
                 dx, dx16 = None, None
-            elif lowest:
+            elif lowest or li == 0:                      # (no layer under this one reads a bf16 copy)
                 dx, dx16 = ops.layernorm_bwd(dh1, L.x, ln1.weight, L.m1, L.r1, gbuf(ln1.weight), gbuf(ln1.bias), dres=dx), None
-            elif li > 0:
+            else:
                 dx, dx16 = ops.layernorm_bwd(dh1, L.x, ln1.weight, L.m1, L.r1, gbuf(ln1.weight), gbuf(ln1.bias), dres=dx,
                                              bf16_copy=(st.p_res, below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)))
-            else:
-                dx, dx16 = ops.layernorm_bwd(dh1, L.x, ln1.weight, L.m1, L.r1, gbuf(ln1.weight), gbuf(ln1.bias), dres=dx), None
             if hold:
                 deferred.append(pending)
                 deferred_layers.append(layer)
@@ -435,59 +445,89 @@ _stack_sides = {}
 
 
 def _ptr_table(ptrs):
-    import ctypes
     arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
     return arr, ctypes.addressof(arr)
 
 
-def _unimol_stack_tables(mod, M):
-    """Pointer tables of the encoder's layers for the stack calls (cached on the parameter arena), or None when the stack calls do not
-    cover this model: parameters outside one arena or frozen, layers of different shapes, dimensions the grouped weight-gradient kernels
-    do not take."""
+def bert_weights(layer) -> SimpleNamespace:
+    """Parameter view of an HF RobertaLayer / mm_module BertCrossAttentionLayer (identical sub-module names)."""
+    a, o = layer.attention.self, layer.attention.output
+    return SimpleNamespace(q_w=a.query.weight, q_b=a.query.bias, k_w=a.key.weight, k_b=a.key.bias, v_w=a.value.weight, v_b=a.value.bias,
+                           o_w=o.dense.weight, o_b=o.dense.bias, ln1_w=o.LayerNorm.weight, ln1_b=o.LayerNorm.bias,
+                           i_w=layer.intermediate.dense.weight, i_b=layer.intermediate.dense.bias,
+                           o2_w=layer.output.dense.weight, o2_b=layer.output.dense.bias,
+                           ln2_w=layer.output.LayerNorm.weight, ln2_b=layer.output.LayerNorm.bias)
+
+
+# What a tower's stack calls take of one layer (csrc/layers.hip): params -- every parameter; w16 -- the forward GEMM weights, which the
+# tables address through the arena's 16-bit shadows (everything else through the parameter itself); fwd / bwd / grads -- the order of the
+# three pointer tables; recast -- the weights whose shadow is refreshed after an in-place write; probe -- the [F, D] weight that shapes the
+# layer and whose bindings are re-checked per call; eps -- LayerNorm epsilons that must all be one value; runs -- parameters that must sit
+# back to back in the arena (the call reads each run as one matrix / one bias).
+def _unimol_stack_desc(l):
+    a, ln1, ln2 = l.self_attn, l.self_attn_layer_norm, l.final_layer_norm
+    w_in, b_in, w_out, b_out, w1, b1, w2, b2 = a.in_proj.weight, a.in_proj.bias, a.out_proj.weight, a.out_proj.bias, l.fc1.weight, l.fc1.bias, l.fc2.weight, l.fc2.bias
+    g1, bt1, g2, bt2 = ln1.weight, ln1.bias, ln2.weight, ln2.bias
+    ps = [w_in, b_in, w_out, b_out, g2, bt2, w1, b1, w2, b2, g1, bt1]
+    return SimpleNamespace(params=ps, w16=(w_in, w_out, w1, w2), fwd=ps, bwd=(w2, w1, w_out, w_in, g2, g1), recast=(w_in, w_out, w1, w2), probe=w1,
+                           grads=(w2, w1, w_out, w_in, b2, b1, b_out, b_in, g2, bt2, g1, bt1), eps=(ln2.eps, ln1.eps), runs=())
+
+
+def _bert_stack_desc(l):
+    W = bert_weights(l)
+    return SimpleNamespace(params=[W.q_w, W.k_w, W.v_w, W.q_b, W.k_b, W.v_b, W.o_w, W.o_b, W.ln1_w, W.ln1_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln2_w, W.ln2_b],
+                           w16=(W.q_w, W.o_w, W.i_w, W.o2_w),        # (q_w: where the fused [3D, D] query | key | value matrix starts)
+                           fwd=(W.q_w, W.q_b, W.o_w, W.o_b, W.ln1_w, W.ln1_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln2_w, W.ln2_b),
+                           bwd=(W.q_w, W.o_w, W.i_w, W.o2_w, W.ln1_w, W.ln2_w), recast=(W.q_w, W.k_w, W.v_w, W.o_w, W.i_w, W.o2_w), probe=W.i_w,
+                           grads=(W.q_w, W.q_b, W.o_w, W.o_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b), eps=(),
+                           runs=((W.q_w, W.k_w, W.v_w), (W.q_b, W.k_b, W.v_b)))
+
+
+_unimol_stack_desc.probe = lambda l: l.fc1.weight
+_bert_stack_desc.probe = lambda l: l.intermediate.dense.weight
+
+
+def _stack_tables(desc, mod, rows, sw, attn_ok=True):
+    """Pointer tables of a tower's layers for its stack calls (desc: _unimol_stack_desc / _bert_stack_desc; cached on the parameter arena),
+    or None when the stack calls do not cover this model or call (paths.stack_call, paths.stack_model)."""
     layers = list(mod.layers)
-    l0 = layers[0]
-    arena = getattr(l0.fc1.weight, "_mmdti_arena", None)
-    if arena is None or not ops.GROUPED_DW or M < ops.GROUPED_DW_MIN_ROWS:
+    probe0 = desc.probe(layers[0])               # (per call: only this one look-up; the descriptions are built on a cache miss)
+    arena = getattr(probe0, "_mmdti_arena", None)
+    F, D = probe0.shape
+    if paths.stack_call(sw, arena is not None, D, F, rows, attn_ok) != paths.STACK:
         return None
     cache = arena.__dict__.setdefault("_stack_tables", {})
     # (a weak reference: an id is recycled once the module dies; the flags: a parameter frozen after the first step must not be written
     #  through the raw gradient table -- the stack calls take every parameter of every layer as trainable)
-    key = (weakref.ref(mod), ops.FWD_F16, trainable_flags(q for l in layers for q in l.parameters()))
+    flags = trainable_flags(q for l in layers for q in l.parameters())
+    key = (weakref.ref(mod), ops.FWD_F16, desc, flags)
     T = cache.get(key)
     if T is None:
-        D, F = l0.fc1.weight.shape[1], l0.fc1.weight.shape[0]
-        eps = l0.final_layer_norm.eps
-
-        def plist(l):
-            a = l.self_attn
-            return [a.in_proj.weight, a.in_proj.bias, a.out_proj.weight, a.out_proj.bias, l.final_layer_norm.weight, l.final_layer_norm.bias,
-                    l.fc1.weight, l.fc1.bias, l.fc2.weight, l.fc2.bias, l.self_attn_layer_norm.weight, l.self_attn_layer_norm.bias]
-        ok = D % 256 == 0 and F % 256 == 0
-        for l in layers:
-            ps = plist(l)
-            ok = ok and all(q is not None and q.requires_grad and getattr(q, "_mmdti_arena", None) is arena for q in ps)
-            ok = ok and tuple(l.fc1.weight.shape) == (F, D) and l.final_layer_norm.eps == eps and l.self_attn_layer_norm.eps == eps
-            ok = ok and len(list(l.parameters())) == 12
-        if not ok:
+        ds = [desc(l) for l in layers]
+        d0 = ds[0]
+        off = arena.offsets
+        same_arena = all(q is not None and getattr(q, "_mmdti_arena", None) is arena for d in ds for q in d.params)
+        uniform = all(tuple(d.probe.shape) == (F, D) and len(list(l.parameters())) == len(d.params) and all(e == d0.eps[0] for e in d.eps)
+                      for l, d in zip(layers, ds))
+        # (offsets are read only once every parameter is known to have one)
+        adjacent = same_arena and all(off[id(q)] == off[id(p)] + p.numel() for d in ds for run in d.runs for p, q in zip(run, run[1:]))
+        if paths.stack_model(flags, same_arena, uniform, adjacent) != paths.STACK:
             cache[key] = False
             return None
         if ops.FWD_F16:
             arena._fresh16()
         sh16 = (arena.shadow16 if ops.FWD_F16 else arena.shadow).data_ptr()
-        shb, gr, off = arena.shadow.data_ptr(), arena.grad.data_ptr(), arena.offsets
-        fwd, bwd, grads, weights, params = [], [], [], [], []
-        for l in layers:
-            ps = plist(l)
-            params += ps
-            w_in, b_in, w_out, b_out, g2, bt2, w1, b1, w2, b2, g1, bt1 = ps
-            for i, q in enumerate(ps):
-                fwd.append(sh16 + 2 * off[id(q)] if i in (0, 2, 6, 8) else q.data_ptr())
-            bwd += [shb + 2 * off[id(w2)], shb + 2 * off[id(w1)], shb + 2 * off[id(w_out)], shb + 2 * off[id(w_in)], g2.data_ptr(), g1.data_ptr()]
-            grads += [gr + 4 * off[id(q)] for q in (w2, w1, w_out, w_in, b2, b1, b_out, b_in, g2, bt2, g1, bt1)]
-            weights += [(q, id(q)) for q in (w_in, w_out, w1, w2)]
-        T = cache[key] = SimpleNamespace(nl=len(layers), D=D, F=F, eps=eps, fwd=_ptr_table(fwd), bwd=_ptr_table(bwd), grads=_ptr_table(grads),
-                                         weights=weights, params=params, arena=arena, f16=ops.FWD_F16, n_shadow16=arena.shadow16 is not None,
-                                         probes=[(l.fc1.weight, l.fc1.weight.data_ptr(), gr + 4 * off[id(l.fc1.weight)]) for l in layers])
+        shb, gr = arena.shadow.data_ptr(), arena.grad.data_ptr()
+        fwd, bwd, grads, weights, probes = [], [], [], [], []
+        for d in ds:
+            w16 = {id(q) for q in d.w16}
+            fwd += [sh16 + 2 * off[id(q)] if id(q) in w16 else q.data_ptr() for q in d.fwd]
+            bwd += [shb + 2 * off[id(q)] if id(q) in w16 else q.data_ptr() for q in d.bwd]
+            grads += [gr + 4 * off[id(q)] for q in d.grads]
+            weights += [(q, id(q)) for q in d.recast]
+            probes.append((d.probe, d.probe.data_ptr(), gr + 4 * off[id(d.probe)]))
+        T = cache[key] = SimpleNamespace(nl=len(layers), D=D, F=F, fwd=_ptr_table(fwd), bwd=_ptr_table(bwd), grads=_ptr_table(grads), weights=weights,
+                                         params=[q for d in ds for q in d.params], f16=ops.FWD_F16, probes=probes)
     if T is False:
         return None
     ver = arena._version
@@ -503,15 +543,40 @@ def _unimol_stack_tables(mod, M):
     return T
 
 
-def _unimol_stack_layout(M, D, F, s_bytes):
-    key = (M, D, F, s_bytes)
+# Byte counts the library checks against its own arithmetic (csrc/layers.hip).  A Uni-Mol layer and a BERT self-attention layer hand the
+# grouped weight-gradient launch the same set of matrices -- four of [D, D] (in_proj's three and out_proj; query, key, value and the output
+# dense) and two of [F, D] -- whose split-K partial sums take one fp32 slab per split.
+def _dw_slab_bytes(D, F, rows):
+    tiles = (D // 256) * (F // 256) * 2 + (D // 256) ** 2 * 4
+    return ops.lib()._dll.mmdti_linear_dw_grouped_splits(tiles, rows) * (2 * D * F + 4 * D * D) * 4
+
+
+def _unimol_layer_ws_bytes(M, D, F):           # one layer's backward temporaries: mmdti_unimol_layer_bwd
+    return (M * F + 7 * M * D) * 2 + M * D * 4 + _dw_slab_bytes(D, F, M)
+
+
+def _bert_layer_ws_bytes(Mq, D, F, nrow):      # mmdti_bert_layer_bwd (nrow: _attn_stat_rows)
+    return (Mq * F + 7 * Mq * D) * 2 + Mq * D * 4 + (nrow * 4 + 15) // 16 * 16 + _dw_slab_bytes(D, F, Mq)
+
+
+def _bert_cross_layer_ws_bytes(Mq, D, nrow):   # mmdti_bert_cross_layer_bwd (its weight gradients are launched by the host: no slab)
+    return 4 * Mq * D + 4 * Mq * D + (nrow * 4 + 15) // 16 * 16
+
+
+def _attn_stat_rows(st, heads):
+    """Rows of the fused attention's per-row statistics."""
+    return heads * st.Mq if st.vl is not None else st.B * heads * st.Lq
+
+
+def _stack_layout(query, rows, D, F, *sizes):
+    """-> (arena bytes per layer, workspace bytes, weight-gradient slab bytes) of a tower's stack calls, asked of the library (`query`:
+    mmdti_unimol_stack_layout / mmdti_bert_stack_layout; sizes: its own arguments) once per shape."""
+    key = (query, rows, D, F) + sizes
     r = _stack_layouts.get(key)
     if r is None:
-        import ctypes
-        tiles = (D // 256) * (F // 256) * 2 + (D // 256) ** 2 * 4
-        slab = ops.lib()._dll.mmdti_linear_dw_grouped_splits(tiles, M) * (2 * D * F + 4 * D * D) * 4
+        slab = _dw_slab_bytes(D, F, rows)
         out = (ctypes.c_longlong * 2)()
-        ops.lib().mmdti_unimol_stack_layout(M, D, F, s_bytes, slab, ctypes.addressof(out))
+        getattr(ops.lib(), query)(rows, D, F, *sizes, slab, ctypes.addressof(out))
         if len(_stack_layouts) > 4096:
             _stack_layouts.clear()
         r = _stack_layouts[key] = (int(out[0]), int(out[1]), slab)
@@ -544,7 +609,7 @@ def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, key_tiles, rag_store_last,
     e = torch.empty
     s_last = torch.empty_like(s_prev) if tiled else e(B, H, N, ld, device=dev, dtype=F32)
     s_bytes = s_last.numel() * s_last.element_size()
-    stride, ws_bytes, slab = _unimol_stack_layout(M, D, F, s_bytes)
+    stride, ws_bytes, slab = _stack_layout("mmdti_unimol_stack_layout", M, D, F, s_bytes)
     arena = e(stride * T.nl, device=dev, dtype=torch.uint8)
     x_last, out = e(M, D, device=dev, dtype=F32), e(M, D, device=dev, dtype=F32)
     st.f_mean, st.f_rstd = e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
@@ -554,7 +619,7 @@ def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, key_tiles, rag_store_last,
     ops.lib().mmdti_unimol_stack_fwd(
         ops._stream(), T.nl, M, B, N, H, D, F, ld, float(scale), float(st.p_res), float(st.p_att), int(st.seed), site0, x.data_ptr(), h1.data_ptr(),
         s_prev.data_ptr(), p(key_pad), ops._pair_layout_s(s_prev, "pair_attn.bias"), p(key_tiles), int(rag_store_last), p(row_off), T.fwd[1],
-        ops.ACT_GELU_FWD, float(T.eps), fl.weight.data_ptr(), fl.bias.data_ptr(), float(fl.eps), ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, arena.data_ptr(),
+        ops.ACT_GELU_FWD, float(l0.final_layer_norm.eps), fl.weight.data_ptr(), fl.bias.data_ptr(), float(fl.eps), ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, arena.data_ptr(),
         arena.numel(), s_bytes, x_last.data_ptr(), s_last.data_ptr(), out.data_ptr(), st.f_mean.data_ptr(), st.f_rstd.data_ptr(),
         int(h1.dtype == torch.float16))
     st.stack = SimpleNamespace(T=T, arena=arena, s_bytes=s_bytes, ws_bytes=ws_bytes, slab=slab, site0=site0, x0=x, h1=h1, m1=m1, r1=r1, s_last=s_last)
@@ -567,7 +632,7 @@ def _unimol_stack_bwd(st, dx, dx16, scale):
     T = S.T
     M, D = st.M, st.D
     dev = dx.device
-    G = (torch.empty if st.kt is None else torch.zeros)(S.s_last.shape, device=dev, dtype=ops.pair_grad_dtype(S.s_last))
+    G = _pair_grad_chain(S.s_last, st.kt)
     layout = ops._pair_layout_s(S.s_last, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0)
     dx_final = torch.empty_like(dx)
     ws = torch.empty(S.ws_bytes, device=dev, dtype=torch.uint8)
@@ -612,22 +677,17 @@ def _unimol_layer_fwd_seq(st, layer, L, s_prev, key_pad, key_tiles, rag_store, r
     return x_out, ln_out, mn, rn
 
 
-def _unimol_seq_workspace(st, mod, full):
-    """-> (usable, workspace) for mmdti_unimol_layer_bwd: the variant the library sequences is the hot one -- every parameter of the layer
-    trainable (full: per running layer), dimensions the grouped weight-gradient kernels take, no per-launch event timing requested.  The
-    workspace holds one layer's temporaries and is shared by all layers of this backward."""
-    lay = mod.layers[0]
-    D, F, M = st.D, lay.fc1.weight.shape[0], st.M
-    L0 = st.layers[st.plan.lowest]
-    ok = ((L0.h1.dtype != torch.float16 or L0.s.dtype == torch.float16)      # (fp16 operands: the sequencer covers the compact pair planes)
-          and not ops.kernel_timer.names and ops.GROUPED_DW and D % 256 == 0 and F % 256 == 0 and M >= ops.GROUPED_DW_MIN_ROWS
-          and any(full))
-    if not ok:
-        return False, None
-    tiles = (D // 256) * (F // 256) * 2 + (D // 256) ** 2 * 4
-    sk = ops.lib()._dll.mmdti_linear_dw_grouped_splits(tiles, M)
-    nbytes = (M * F + 7 * M * D) * 2 + M * D * 4 + sk * (2 * D * F + 4 * D * D) * 4
-    return True, torch.empty(nbytes + 256, device=st.emb.device, dtype=torch.uint8)
+def _unimol_seq_workspace(st, mod, full, on_gpu):
+    """-> (paths.LAYER, workspace) when layers of this backward may take mmdti_unimol_layer_bwd (paths.unimol_tower_bwd; full: per layer,
+    every parameter trains), else (paths.OPS, None).  The workspace holds one layer's temporaries and is shared by all layers."""
+    nkept, lowest = len(st.layers), st.plan.lowest
+    D, F, M = st.D, (mod.layers[0].fc1.weight.shape[0] if nkept else 0), st.M
+    L0 = st.layers[lowest] if lowest < nkept else None          # (the lowest layer that runs: what the forward kept of it)
+    path = paths.unimol_tower_bwd(_switches(), on_gpu, nkept, lowest, L0 is not None and L0.h1.dtype == torch.float16,
+                                  L0 is not None and L0.s.dtype == torch.float16, D, F, M, full)
+    if path != paths.LAYER:
+        return path, None
+    return path, torch.empty(_unimol_layer_ws_bytes(M, D, F) + 256, device=st.emb.device, dtype=torch.uint8)
 
 
 def _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, ws, below):
@@ -818,14 +878,11 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
         L.fw, L.fb = fused_views(plist_w), fused_views(plist_b)
         if L.fw is None or L.fb is None:
             L.fw = L.fb = None
-    L.seq = False
-    if (LAYER_SEQ and self_attn and L.fw is not None and s1_32.is_cuda and not ops.kernel_timer.names and D % 256 == 0
-            and W.i_w.shape[0] % 256 == 0 and Mq >= ops.GROUPED_DW_MIN_ROWS and ops.GROUPED_DW):
+    L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq)
+    if L.path == paths.LAYER:
         # the layer's six launches from ONE library call (csrc/layers.hip: the same kernels, arguments and order as below)
-        return _bert_layer_fwd_seq(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
-    if (LAYER_SEQ and not self_attn and L.fw is not None and L.fused and s1_32.is_cuda and not ops.kernel_timer.names and D % 8 == 0
-            and W.i_w.shape[0] % 8 == 0 and W.q_b is not None):
-        # the cross-attention layer's six launches from ONE library call (csrc/layers.hip: mmdti_bert_cross_layer_fwd)
+        if self_attn:
+            return _bert_layer_fwd_seq(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
         return _bert_cross_layer_fwd_seq(st, L, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
     if L.fw is not None:
         if self_attn:
@@ -868,6 +925,14 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
     return L, out32, out16
 
 
+def _grad_buffers_live(W, self_attn):
+    """The re-check of a sequenced layer's backward: every gradient buffer that the library call writes through itself still exists (a
+    parameter frozen between forward and backward has none).  The fused q | k | v buffers were taken as views in the forward; the
+    cross-attention call leaves the weight gradients to the host, which looks each one up."""
+    ps = (W.o_w, W.o_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b) if self_attn else (W.o_b, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b)
+    return all(gbuf(p) is not None for p in ps)
+
+
 def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
     """-> (ds1 fp32 [B*Lq,D], ds2 fp32 [B*Lk,D] or None when self_attn (then ds1 holds the sum)).  want: (ds1, ds2) are needed -- an
     input gradient nobody reads is returned as None and its dX products are skipped where the path launches them itself (the
@@ -876,10 +941,9 @@ def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
     Mq, Mk, vl = st.Mq, st.Mk, st.vl
     W, heads, ld = L.W, L.heads, L.ld
     hd = D // heads
-    if getattr(L, "seq", False) is True and not ops.kernel_timer.names and all(gbuf(p) is not None for p in (W.o_w, W.o_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln1_w, W.ln1_b,
-                                                                                                        W.ln2_w, W.ln2_b)):
-        return _bert_layer_bwd_seq(st, L, dout, seed), None
-    if getattr(L, "seq", False) == "cross" and not ops.kernel_timer.names and all(gbuf(p) is not None for p in (W.o_b, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b)):
+    if L.path == paths.LAYER and paths.bert_layer_bwd(L.path, bool(ops.kernel_timer.names), _grad_buffers_live(W, L.self_attn)) == paths.LAYER:
+        if L.self_attn:
+            return _bert_layer_bwd_seq(st, L, dout, seed), None
         return _bert_cross_layer_bwd_seq(st, L, dout, seed, want)
     pend, raw = [], []                     # the layer's weight gradients leave as one grouped launch (see _lin_bwd_params_many)
     dz, dzb = ops.layernorm_bwd(dout, L.z, W.ln2_w, L.zm, L.zr, gbuf(W.ln2_w), gbuf(W.ln2_b), bf16_copy=(L.p_hid, L.site_f, gbuf(W.o2_b)))
@@ -967,7 +1031,7 @@ def _bert_cross_layer_fwd_seq(st, L, s1_32, s1_16, s2_16, key_add, W, heads, p_h
     L.am, L.ar, L.zm, L.zr = (e(Mq, device=dev, dtype=F32) for _ in range(4))
     L.u, L.i = e(Mq, F, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=a16)
     L.z, out32, out16 = e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=a16)
-    L.seq, L.p_hid, L.p_att = "cross", p_hid, p_att
+    L.p_hid, L.p_att = p_hid, p_att
     p = ops._p
     ops.lib().mmdti_bert_cross_layer_fwd(
         ops._stream(), Mq, Mk, B, Lq, Lk, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(p_hid), float(p_att), int(seed), int(L.site_att),
@@ -992,8 +1056,7 @@ def _bert_cross_layer_bwd_seq(st, L, dout, seed, want=(True, True)):
     ds1, ds2 = e(Mq, D, device=dev, dtype=F32), (e(Mk, D, device=dev, dtype=F32) if want[1] else None)   # (ds2 null: not launched)
     dzb, du, dyb = e(Mq, D, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=BF16), e(Mq, D, device=dev, dtype=BF16)
     dq, dqkv = e(Mq, D, device=dev, dtype=BF16), torch.empty_like(L.qkv)
-    nrow = heads * Mq if vl is not None else B * heads * Lq
-    ws = e(4 * Mq * D + 4 * Mq * D + (nrow * 4 + 15) // 16 * 16 + 256, device=dev, dtype=torch.uint8)
+    ws = e(_bert_cross_layer_ws_bytes(Mq, D, _attn_stat_rows(st, heads)) + 256, device=dev, dtype=torch.uint8)
     p = ops._p
     ops.lib().mmdti_bert_cross_layer_bwd(
         ops._stream(), Mq, Mk, B, Lq, Lk, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(L.p_hid), float(L.p_att), int(seed), int(L.site_att),
@@ -1025,7 +1088,7 @@ def _bert_layer_fwd_seq(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, ep
     L.am, L.ar, L.zm, L.zr = (e(Mq, device=dev, dtype=F32) for _ in range(4))
     L.u, L.i = e(Mq, F, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=a16)
     L.z, out32, out16 = e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=a16)
-    L.fused, L.seq, L.p_hid, L.p_att = True, True, p_hid, p_att
+    L.fused, L.p_hid, L.p_att = True, p_hid, p_att
     p = ops._p
     ops.lib().mmdti_bert_layer_fwd(
         ops._stream(), Mq, B, Lq, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(p_hid), float(p_att), int(seed), int(L.site_att), int(L.site_o),
@@ -1045,11 +1108,7 @@ def _bert_layer_bwd_seq(st, L, dout, seed):
     F = W.i_w.shape[0]
     dout = dout.contiguous()
     ds1 = torch.empty(Mq, D, device=dout.device, dtype=F32)
-    tiles = 3 * (D // 256) ** 2 + 2 * (D // 256) * (F // 256) + (D // 256) ** 2
-    sk = ops.lib()._dll.mmdti_linear_dw_grouped_splits(tiles, Mq)
-    nrow = heads * Mq if vl is not None else B * heads * Lq
-    nbytes = (Mq * F + 7 * Mq * D) * 2 + Mq * D * 4 + (nrow * 4 + 15) // 16 * 16 + sk * (4 * D * D + 2 * D * F) * 4
-    ws = torch.empty(nbytes + 256, device=dout.device, dtype=torch.uint8)
+    ws = torch.empty(_bert_layer_ws_bytes(Mq, D, F, _attn_stat_rows(st, heads)) + 256, device=dout.device, dtype=torch.uint8)
     p = ops._p
     ops.lib().mmdti_bert_layer_bwd(
         ops._stream(), Mq, B, Lq, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(L.p_hid), float(L.p_att), int(seed), int(L.site_att), int(L.site_o),
@@ -1063,93 +1122,11 @@ def _bert_layer_bwd_seq(st, L, dout, seed):
     return ds1
 
 
-def _bert_stack_tables(mod, st):
-    """Pointer tables of tower 2's layers for mmdti_bert_stack_fwd / _bwd (cached on the parameter arena), or None when the stack
-    calls do not cover this model: parameters outside one arena or frozen, q | k | v not back to back, shapes the fused attention /
-    grouped weight-gradient kernels do not take."""
-    layers = list(mod.layers)
-    W0 = bert_weights(layers[0])
-    arena = getattr(W0.i_w, "_mmdti_arena", None)
-    heads = mod.cfg.heads
-    D, F = W0.i_w.shape[1], W0.i_w.shape[0]
-    if (arena is None or not ops.GROUPED_DW or st.Mq < ops.GROUPED_DW_MIN_ROWS or D % heads or not ops.attn_eligible(st.Lq, st.Lk, D // heads, D)):
-        return None
-    cache = arena.__dict__.setdefault("_stack_tables", {})
-    key = (weakref.ref(mod), ops.FWD_F16, "bert", trainable_flags(q for l in layers for q in l.parameters()))
-    T = cache.get(key)
-    if T is None:
-        ok = D % 256 == 0 and F % 256 == 0
-        Ws = [bert_weights(l) for l in layers]
-        off = arena.offsets
-
-        def plist(W):
-            return [W.q_w, W.k_w, W.v_w, W.q_b, W.k_b, W.v_b, W.o_w, W.o_b, W.ln1_w, W.ln1_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln2_w, W.ln2_b]
-        for l, W in zip(layers, Ws):
-            ps = plist(W)
-            ok = ok and all(q is not None and q.requires_grad and getattr(q, "_mmdti_arena", None) is arena for q in ps)
-            ok = ok and tuple(W.i_w.shape) == (F, D) and len(list(l.parameters())) == 16
-            if ok:      # q | k | v (weights and biases) back to back in the arena: one [3D, D] matrix, one [3D] bias
-                ok = (off[id(W.k_w)] == off[id(W.q_w)] + W.q_w.numel() and off[id(W.v_w)] == off[id(W.k_w)] + W.k_w.numel()
-                      and off[id(W.k_b)] == off[id(W.q_b)] + W.q_b.numel() and off[id(W.v_b)] == off[id(W.k_b)] + W.k_b.numel())
-        if not ok:
-            cache[key] = False
-            return None
-        if ops.FWD_F16:
-            arena._fresh16()
-        sh16 = (arena.shadow16 if ops.FWD_F16 else arena.shadow).data_ptr()
-        shb, gr = arena.shadow.data_ptr(), arena.grad.data_ptr()
-        fwd, bwd, grads, weights, params, probes = [], [], [], [], [], []
-        for W in Ws:
-            params += plist(W)
-            w16 = lambda q: sh16 + 2 * off[id(q)]
-            wb = lambda q: shb + 2 * off[id(q)]
-            g = lambda q: gr + 4 * off[id(q)]
-            fwd += [w16(W.q_w), W.q_b.data_ptr(), w16(W.o_w), W.o_b.data_ptr(), W.ln1_w.data_ptr(), W.ln1_b.data_ptr(), w16(W.i_w), W.i_b.data_ptr(),
-                    w16(W.o2_w), W.o2_b.data_ptr(), W.ln2_w.data_ptr(), W.ln2_b.data_ptr()]
-            bwd += [wb(W.q_w), wb(W.o_w), wb(W.i_w), wb(W.o2_w), W.ln1_w.data_ptr(), W.ln2_w.data_ptr()]
-            grads += [g(W.q_w), g(W.q_b), g(W.o_w), g(W.o_b), g(W.i_w), g(W.i_b), g(W.o2_w), g(W.o2_b), g(W.ln1_w), g(W.ln1_b), g(W.ln2_w), g(W.ln2_b)]
-            weights += [(q, id(q)) for q in (W.q_w, W.k_w, W.v_w, W.o_w, W.i_w, W.o2_w)]
-            probes.append((W.i_w, W.i_w.data_ptr(), g(W.i_w)))
-        T = cache[key] = SimpleNamespace(nl=len(layers), D=D, F=F, heads=heads, fwd=_ptr_table(fwd), bwd=_ptr_table(bwd), grads=_ptr_table(grads),
-                                         weights=weights, params=params, f16=ops.FWD_F16, probes=probes)
-    if T is False:
-        return None
-    ver = arena._version
-    for q, i in T.weights:
-        if q._version != ver[i]:
-            arena._fresh(q)
-    if T.f16:
-        arena._fresh16()
-    for q, dptr, gptr in T.probes:
-        g = q.grad
-        if g is None or g.data_ptr() != gptr or q.data_ptr() != dptr:
-            return None
-    return T
-
-
-_bert_layouts = {}
-
-
-def _bert_stack_layout(st, T):
-    heads, D, F = T.heads, T.D, T.F
-    nrow = heads * st.Mq if st.vl is not None else st.B * heads * st.Lq
-    key = (st.Mq, D, F, nrow)
-    r = _bert_layouts.get(key)
-    if r is None:
-        import ctypes
-        tiles = 3 * (D // 256) ** 2 + 2 * (D // 256) * (F // 256) + (D // 256) ** 2
-        slab = ops.lib()._dll.mmdti_linear_dw_grouped_splits(tiles, st.Mq) * (4 * D * D + 2 * D * F) * 4
-        out = (ctypes.c_longlong * 2)()
-        ops.lib().mmdti_bert_stack_layout(st.Mq, D, F, nrow * 8, nrow, slab, ctypes.addressof(out))
-        if len(_bert_layouts) > 4096:
-            _bert_layouts.clear()
-        r = _bert_layouts[key] = (int(out[0]), int(out[1]), slab, nrow * 8)
-    return r
-
-
 def _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites):
     """All layers of tower 2 as ONE library call -> the tower's fp32 output [Mq, D]."""
-    stride, ws_bytes, slab, stats_bytes = _bert_stack_layout(st, T)
+    nrow = _attn_stat_rows(st, st.heads)
+    stats_bytes = nrow * 8
+    stride, ws_bytes, slab = _stack_layout("mmdti_bert_stack_layout", st.Mq, T.D, T.F, stats_bytes, nrow)
     dev = x32.device
     arena = torch.empty(stride * T.nl, device=dev, dtype=torch.uint8)
     out32 = torch.empty(st.Mq, T.D, device=dev, dtype=F32)
@@ -1157,7 +1134,7 @@ def _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites):
     sites.n += 3 * T.nl
     vl = st.vl
     ops.lib().mmdti_bert_stack_fwd(
-        ops._stream(), T.nl, st.Mq, st.B, st.Lq, T.heads, T.D, T.F, float(1.0 / math.sqrt(T.D // T.heads)), float(p_hid), float(p_att), int(seed), site0,
+        ops._stream(), T.nl, st.Mq, st.B, st.Lq, st.heads, T.D, T.F, float(1.0 / math.sqrt(T.D // st.heads)), float(p_hid), float(p_att), int(seed), site0,
         x32.data_ptr(), x16.data_ptr(), ops._p(key_add), *(ops._NO_VARLEN if vl is None else vl.args()), T.fwd[1], ops.ACT_GELU_FWD, float(cfg.ln_eps),
         ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, arena.data_ptr(), arena.numel(), stats_bytes, out32.data_ptr(), int(x16.dtype == torch.float16))
     st.stack = SimpleNamespace(T=T, arena=arena, ws_bytes=ws_bytes, slab=slab, stats_bytes=stats_bytes, site0=site0, x16=x16, key_add=key_add, p_hid=p_hid,
@@ -1174,21 +1151,11 @@ def _bert_stack_bwd(st, dout):
     ws = torch.empty(S.ws_bytes, device=dev, dtype=torch.uint8)
     vl = st.vl
     ops.lib().mmdti_bert_stack_bwd(
-        ops._stream(), T.nl, st.Mq, st.B, st.Lq, T.heads, T.D, T.F, float(1.0 / math.sqrt(T.D // T.heads)), float(S.p_hid), float(S.p_att), int(st.seed),
+        ops._stream(), T.nl, st.Mq, st.B, st.Lq, st.heads, T.D, T.F, float(1.0 / math.sqrt(T.D // st.heads)), float(S.p_hid), float(S.p_att), int(st.seed),
         S.site0, dout.data_ptr(), ds1.data_ptr(), S.x16.data_ptr(), ops._p(S.key_add), *(ops._NO_VARLEN if vl is None else vl.args()), T.bwd[1],
         ops.ACT_GELU_DX, T.grads[1], T.D, S.arena.data_ptr(), S.arena.numel(), S.stats_bytes, ws.data_ptr(), ws.numel(), S.slab,
         int(S.x16.dtype == torch.float16))
     return ds1
-
-
-def bert_weights(layer) -> SimpleNamespace:
-    """Parameter view of an HF RobertaLayer / mm_module BertCrossAttentionLayer (identical sub-module names)."""
-    a, o = layer.attention.self, layer.attention.output
-    return SimpleNamespace(q_w=a.query.weight, q_b=a.query.bias, k_w=a.key.weight, k_b=a.key.bias, v_w=a.value.weight, v_b=a.value.bias,
-                           o_w=o.dense.weight, o_b=o.dense.bias, ln1_w=o.LayerNorm.weight, ln1_b=o.LayerNorm.bias,
-                           i_w=layer.intermediate.dense.weight, i_b=layer.intermediate.dense.bias,
-                           o2_w=layer.output.dense.weight, o2_b=layer.output.dense.bias,
-                           ln2_w=layer.output.LayerNorm.weight, ln2_b=layer.output.LayerNorm.bias)
 
 
 class RobertaEncoderFn(torch.autograd.Function):
@@ -1217,7 +1184,8 @@ class RobertaEncoderFn(torch.autograd.Function):
             vl, Mq, Lq = ops.AttnVarlen(pack, pack), pack.M, pack.max_rows
         e = ops.embedding_fwd3(ids, mod.word, pos, mod.position, mod.token_type)      # word + position + token type 0, one pass
         zeros = None
-        st = SimpleNamespace(B=B, Lq=Lq, Lk=Lq if vl is None else vl.Lk, D=D, seed=seed, ids=ids, pos=pos, zeros=zeros, e=e, layers=[], p_hid=p_hid, Mq=Mq, Mk=Mq, vl=vl)
+        st = SimpleNamespace(B=B, Lq=Lq, Lk=Lq if vl is None else vl.Lk, D=D, seed=seed, ids=ids, pos=pos, zeros=zeros, e=e, layers=[], p_hid=p_hid, Mq=Mq, Mk=Mq, vl=vl,
+                             heads=cfg.heads)
         keep = any(ctx.needs_input_grad)      # inference (or a frozen tower): no per-layer activations are kept
         if keep:
             # the backward stops at the lowest layer that trains unless the embeddings train (freeze.plan_tower)
@@ -1228,8 +1196,10 @@ class RobertaEncoderFn(torch.autograd.Function):
         key_add = ((1.0 - attention_mask.to(F32)) * torch.finfo(torch.float32).min).contiguous() if vl is None else None
         # small batches: ALL layers from one library call (see _bert_stack_fwd); the per-layer loop then has nothing left to do
         st.stack = None
-        T = (_bert_stack_tables(mod, st) if (LAYER_SEQ and STACK_SEQ and keep and x32.is_cuda and Mq < STACK_MAX_ROWS and len(mod.layers)
-                                             and not ops.kernel_timer.names) else None)
+        T = None
+        sw = _switches()
+        if paths.bert_tower_fwd(sw, x32.is_cuda, keep, len(mod.layers), Mq) == paths.STACK:
+            T = _stack_tables(_bert_stack_desc, mod, Mq, sw, D % cfg.heads == 0 and ops.attn_eligible(Lq, st.Lk, D // cfg.heads, D))
         if T is not None:
             x32 = _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites)
         for li, layer in enumerate(mod.layers if T is None else ()):
