@@ -63,7 +63,10 @@ int mmdti_abi_version(void);
  * upper-cased name, e.g. MMDTI_GEMM_BIG).  Known names: "gemm_big" (0 off, 1 where the shape fills the chip, 2 every
  * eligible shape); "gemm_dbg" (measurement only: 1 = the large-tile GEMM skips its epilogue); "gemm_small" (1: 64 x 64 tiles for launches of
  * few tiles -- small batches; 0: 128 x 128 everywhere) and "gemm_deep" (1: four-stage LDS-DMA ring for launches of at most one
- * workgroup per CU); all paths give bit-identical results.  Returns MMDTI_ERR_INVALID for an unknown name.  Not part of any reference interface. */
+ * workgroup per CU); all paths give bit-identical results.  The switches that are otherwise read from the environment once, at the first
+ * call of their entry point, can be written too: "gemm_glds" (MMDTI_GEMM_GLDS), "gemm_tall" (MMDTI_GEMM_TALL), "gemm_small_tiles"
+ * (MMDTI_GEMM_SMALL_TILES), "gemm_stream_mb" (MMDTI_GEMM_STREAM_MB), "gemm_ln_rows" (MMDTI_GEMM_LN_ROWS) and "grouped_small_rows"
+ * (MMDTI_GROUPED_SMALL_ROWS).  Returns MMDTI_ERR_INVALID for an unknown name.  Not part of any reference interface. */
 int mmdti_set_option(const char* name, int value);
 
 /* ---- GEMM: C = epi(alpha * A.B^T) ----------------------------------------------------------
@@ -89,6 +92,20 @@ int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void* B, void* C
                     unsigned long long seed, unsigned int site, float* colsum_out, float* arowsum_out, void* workspace,
                     long long workspace_bytes);
 
+/* What mmdti_gemm_bf16 would launch for the same arguments, without launching: the same validation and the same plan
+ * (csrc/gemm_plan.h), pointers tested for null and alignment only -- it runs on a machine without a GPU.  plan_out receives 15 ints:
+ * family (0 register-staged 128 x 128, 1 LDS-DMA single-buffered, 2 double-buffered, 3 four-stage "deep", 4 tall, 5 small 64 x 64,
+ * 6 big 256 x 256), the instance's template key TA, TB, FAST, F16, BCVT (0 where the family has no such parameter), grid x,
+ * grid z, workgroup size, dynamic LDS bytes, effective K split, rows per tile of the tall kernel (else 0), slabs (1: partials go
+ * through the workspace and a second pass adds them into C), streaming stores for C, and who computes arowsum (0 nobody, 1 the
+ * kernel, 2 a separate column-sum pass over A). */
+int mmdti_gemm_plan(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB,
+                    int batch_outer, int batch_inner, long long sAo, long long sAi, long long sBo, long long sBi, long long sCo,
+                    long long sCi, int splitk, float alpha, float beta, const float* bias, const float* residual, int ldr, int act,
+                    const void* aux_in, void* aux_out, int ld_aux, int c_dtype, float drop_p, unsigned long long seed,
+                    unsigned int site, float* colsum_out, float* arowsum_out, void* workspace, long long workspace_bytes,
+                    int* plan_out);
+
 /* ---- Linear + residual + LayerNorm in one kernel ------------------------------------------------
  * The Linear that closes a residual branch and the LayerNorm that follows it: unicore out_proj -> final_layer_norm and fc2 -> the
  * next layer's self_attn_layer_norm / the encoder's final_layer_norm (pre-LN, models/transformers.py:137-139,160-161); HF / BertCross
@@ -101,6 +118,8 @@ int mmdti_gemm_ln_bf16(mmdti_stream_t stream, const void* A_bf16, const void* W_
                        int N, int K, int lda, int ldb, int ldr, float drop_p, unsigned long long seed, unsigned int site, float* x_out,
                        const float* gamma, const float* beta, float eps, float* ln_f32, void* ln_bf16, float* mean, float* rstd,
                        int f16 /* bit 0: A and W hold fp16; bit 1: ln_bf16 receives fp16 */);
+/* rows per tile (64 or 80) mmdti_gemm_ln_bf16 uses for M rows: its grid is ceil(M / rows) workgroups of 512 threads */
+int mmdti_gemm_ln_rows(int M);
 
 /* ---- Grouped weight gradients of one transformer layer -----------------------------------------
  * The weight half of nn.Linear's backward for up to 8 Linears that saw the SAME token rows (unicore in_proj / out_proj /
@@ -117,6 +136,13 @@ int mmdti_linear_dw_grouped(mmdti_stream_t stream, int nprob, const void* const*
                             int x_f16 /* 1: every x[i] holds fp16 (saved forward activations of the fp16 forward-operand mode),
                                          converted to bf16 between LDS and the matrix pipe -- see MMDTI_DT_B_F16 */);
 int mmdti_linear_dw_grouped_splits(int tiles, int rows);
+/* What mmdti_linear_dw_grouped would launch for these problems, without launching.  plan_out receives 9 ints: small (1: the 64 x 64
+ * kernel without a K split, plain +=; 0: the 256 x 256 kernel), grid x, grid z, workgroup size, dynamic LDS bytes, K splits, K-tail
+ * instance (rows % 64 != 0), atomic (1: the splits add into dw with fp32 atomics, no second pass), BCVT
+ * (the fp16-x instance: x_f16 != 0); *workspace_bytes_out: the workspace
+ * the launch demands (0 for the small form). */
+int mmdti_linear_dw_grouped_plan(int nprob, const int* n_out, const int* n_in, int rows, int x_f16, int* plan_out,
+                                 long long* workspace_bytes_out);
 
 /* ---- one Uni-Mol encoder layer's forward / backward behind one call each (launch sequencing in the library: at 16-32 molecules
  * the Python side of ~500 launches per step sets the pace).  Replaces the per-layer body of the encoder forward / backward -- unicore

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "gemm_plan.h"   // tile geometry, options and the launch plans
 
 namespace mmdti {
 
@@ -60,8 +61,6 @@ __device__ __forceinline__ bf16x8 frag_cvt(const bf16x8& v) {
   else return v;
 }
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int LDT = BK;      // [row][k] image: unpadded 128-B rows, 16-B chunks XOR-swizzled by (row & 7) -> conflict-free ds_read_b128
 constexpr int LDTR = BM;     // [k][row] image: unpadded 256-B rows, 8-B units XOR-swizzled by k -> conflict-free ds_read_b64_tr_b16
 
 struct GemmArgs {
@@ -249,8 +248,6 @@ __device__ __forceinline__ void epi_elem(const GemmArgs& a, float accv, int row,
 }
 
 constexpr int LDC_W = 68;  // fp32 row stride of a wave's 16x64 epilogue patch (68 = 4 mod 8: conflict-free C-layout writes)
-
-constexpr int LDC_S = BN + 4;  // fp32 row stride of the epilogue's staging image (528 B)
 
 // 16-byte streaming store: the outputs of these GEMMs are 34-270 MB written once and read by a LATER kernel -- kept out of
 // the L2's way (measured: -10...-25 % on the N >= 1536 outputs at 65536 rows, -22 % on the fc1 + GELU epilogue at 33280)
@@ -653,7 +650,6 @@ __device__ __forceinline__ void glds_tile(const bf16_t* kbase, const Off4& off, 
 // across raw s_barriers, retired with counted s_waitcnt vmcnt -- for launches of at most one workgroup per CU (small
 // batches: 13-56 tiles), where nothing else on the CU hides a K-step's ~1 us fetch latency.  Same products in the same
 // order as the other two forms: bit-identical results.
-constexpr int DEEP_STAGES = 4;
 template <bool TA, bool TB, int DBUF, bool F16 = false, bool BCVT = false>
 __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_kernel(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
@@ -826,8 +822,6 @@ __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_k
 // stages stay in flight across the barrier).  A row-major ([M,K]) only; B row-major ([N,K]) or k-major ([K,N]); the
 // vector epilogue only (the dispatch keeps everything else on the 128 x 128 kernels).  Products are summed in the same
 // order as there: results are bit-identical.
-constexpr int SBM = 64, SBN = 64, SM_STAGES = 4;
-constexpr int SM_TILE = SBM * BK;      // elements of one operand tile (8 KB)
 constexpr int LDC_SM = SBN + 4;        // fp32 row stride of the epilogue's [64][68] staging image
 // [k][64] image of a k-major operand: 128-byte rows, so two consecutive k share the 64 banks; the 32-byte pieces of a row are
 // XOR-ed by ((k >> 1) & 1) | ((k >> 3) & 1) << 1 -- the eight k rows a tr-read half-wave touches (q and 8 + q, q = 0..3)
@@ -942,7 +936,6 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(GemmArgs a) {
 // 4.06 would do (16 tiles past a full round cost a whole extra round: 26.0 -> 36.1 us at N = K = 512).  With mstep =
 // 130 the same GEMMs are exactly 1 / 3 / 4 rounds of 12.5 % taller tiles.  A row-major ([M,K]) operands only; waves
 // split the tile 1 x 4 along N (144 x 32 each, 9 x 2 accumulator tiles).
-constexpr int BMT = 144;
 constexpr int TALL_ROWS_PER_PASS = 48;
 
 template <bool TB, bool F16 = false>
@@ -1070,9 +1063,6 @@ __global__ __launch_bounds__(256, 4) void gemm_glds_tall_kernel(GemmArgs a, int 
 // have landed and the closing barrier publishes them before phase 4 reads them; phase 4's wait does the same for A1(t+1),
 // read in phase 1 of tile t+1 (a staged buffer is read one phase after the wait that retires it).  Tiles past the end of
 // the K range re-fetch the last tile (harmless: those regions are never read again).
-constexpr int BBM = 256, BBN = 256;
-constexpr int BIG_PIECE = 128 * BK;          // elements of one 16 KB piece
-constexpr int BIG_BUF = 4 * BIG_PIECE;       // A0 | A1 | B0 | B1
 constexpr int LDC_B = BBN + 4;               // fp32 row stride of the epilogue's [64][260] staging image
 
 // byte offset (relative to the operand's K-tile origin) of chunk c (0..1023) of piece 0; same source-side swizzles as glds_offset1
@@ -1399,7 +1389,6 @@ __global__ __launch_bounds__(512, 1) void gemm_big_kernel(GemmArgs a) {
 // range (33 280 / 65 536 rows).  One at a time, each is 4-16 output tiles of 256 x 256 and needs a 16- to 64-way K split
 // to fill 256 CUs -- and every split costs a 4 MB pass over dW (fp32 partials).  Launched together the layer's GEMMs are
 // 48 tiles, a 5-way split fills the chip, and the partial-sum traffic falls four-fold (255 -> 60 MB per tower-1 layer).
-constexpr int GROUP_MAX = 8;
 struct GroupProb {
   const bf16_t* A;      // dy  [rows, N_out] (k-major: rows = tokens)
   const bf16_t* B;      // x   [rows, N_in]
@@ -1582,8 +1571,6 @@ __global__ __launch_bounds__(256) void grouped_reduce_kernel(GroupArgs g) {
 // slice in LDS, 32 threads per row (two 8-column pieces each) form x, reduce mean and the centred second moment inside their
 // half-wave (two passes, as layernorm.hip), write x, h, mean, rstd.  The dropout counters are those of the plain GEMM epilogue
 // (element row * N + col), so the fused and the unfused path draw the same mask.
-constexpr int LN_BN = 512;
-constexpr int LDC_LN = LN_BN + 4;
 
 struct GemmLnArgs {
   const bf16_t* A;
@@ -1754,12 +1741,9 @@ __global__ __launch_bounds__(512, 4) void gemm_ln_kernel(GemmLnArgs a) {
 
 }  // namespace mmdti
 
+
 MMDTI_DEFINE_SALT_PULL(gemm)
 using namespace mmdti;
-
-static int g_gemm_big = getenv("MMDTI_GEMM_BIG") ? atoi(getenv("MMDTI_GEMM_BIG")) : 1;
-static int g_gemm_small = getenv("MMDTI_GEMM_SMALL") ? atoi(getenv("MMDTI_GEMM_SMALL")) : 1;   // 64 x 64 tiles for small launches
-static int g_gemm_deep = getenv("MMDTI_GEMM_DEEP") ? atoi(getenv("MMDTI_GEMM_DEEP")) : 1;      // four-stage ring at <= 1 workgroup per CU
 
 // 256 zero bytes in device memory (see GemmArgs::zeros); allocated at the first call that needs it
 static const void* zero_page() {
@@ -1770,39 +1754,78 @@ static const void* zero_page() {
   }
   return page;
 }
-static int g_gemm_dbg = 0;     // measurement only: 1 = gemm_big_kernel returns after its K loop (no epilogue, no slab pass)
+
+static GemmOptions& g_gemm_opt = gemm_options_raw();   // (big / small / deep are read from the environment here, at load)
 
 extern "C" int mmdti_set_option(const char* name, int value) {
   MMDTI_REQUIRE(name != nullptr, "set_option: null name");
-  if (strcmp(name, "gemm_big") == 0) { g_gemm_big = value; return MMDTI_OK; }
-  if (strcmp(name, "gemm_dbg") == 0) { g_gemm_dbg = value; return MMDTI_OK; }
-  if (strcmp(name, "gemm_small") == 0) { g_gemm_small = value; return MMDTI_OK; }
-  if (strcmp(name, "gemm_deep") == 0) { g_gemm_deep = value; return MMDTI_OK; }
+  static const struct { const char* name; int GemmOptions::*field; } known[] = {
+      {"gemm_big", &GemmOptions::big}, {"gemm_dbg", &GemmOptions::dbg}, {"gemm_small", &GemmOptions::small}, {"gemm_deep", &GemmOptions::deep},
+      {"gemm_glds", &GemmOptions::glds}, {"gemm_tall", &GemmOptions::tall}, {"gemm_small_tiles", &GemmOptions::small_max_tiles},
+      {"gemm_stream_mb", &GemmOptions::stream_mb}, {"gemm_ln_rows", &GemmOptions::ln_rows}, {"grouped_small_rows", &GemmOptions::grouped_small_rows}};
+  for (const auto& k : known)
+    if (strcmp(name, k.name) == 0) { g_gemm_opt.*k.field = value; return MMDTI_OK; }
   set_error("set_option: unknown option '%s'", name);
   return MMDTI_ERR_INVALID;
 }
 
-// Shapes on which the 256 x 256 kernel (one workgroup per CU) beats the 128 x 128 ones (four per CU): enough tiles to fill
-// the 256 CUs with little waste in the last round (measured table: DESIGN.md section 4 "GEMM").
-static bool big_shape_pays(int M, int N, int K, int splitk, int transA, int transB, bool reads_aux) {
-  // Measured on MI355X against the 128 x 128 kernels (scratch/gemm_big_test.py, profiles/r02_gemm_big_ab.json).  The K loop
-  // of this kernel runs at 900-1300 TF/s, but with ONE workgroup per CU nothing overlaps a tile's epilogue (an HBM / VALU
-  // burst of 15-20 us for a 256 x 256 fp32 / GELU tile) with another tile's loop, and 33 280-row outputs quantise badly on
-  // 256 CUs (130 row tiles).  It pays where the loop dominates and the tile count divides the chip:
-  const long long tiles = (long long)cdiv(M, 256) * cdiv(N, 256);
-  if (splitk > 1) return K >= 16384 && 256 % tiles == 0 && tiles >= 4;     // long-K weight gradients: 4 or 16 output tiles (x1.02...1.25)
-  // tower-2 shapes in whole rounds: forward x1.03...1.10; input gradients (k-major B) x1.09...1.10 when the epilogue reads nothing
-  // (with the saved-activation multiply the 128 x 128 kernels win, 266 vs 304 us); 512 x 512 x 512 stays with them too (72 vs 77 us)
-  return tiles % 256 == 0 && K >= 512 && N <= 2048 && M >= 65536 && (long long)N * K >= 512 * 1024 && !(transB && reads_aux);
+// > 64 KiB of dynamic LDS: opt in once per kernel
+static int ensure_dynamic_lds(const void* fn, int bytes, const char* who) {
+  static const void* done[64];
+  static int ndone = 0;
+  if (bytes <= 64 * 1024) return MMDTI_OK;
+  for (int i = 0; i < ndone; ++i)
+    if (done[i] == fn) return MMDTI_OK;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+    set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", who, (size_t)bytes);
+    return MMDTI_ERR_LAUNCH;
+  }
+  if (ndone < 64) done[ndone++] = fn;
+  return MMDTI_OK;
 }
 
-extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void* B, void* C, int M, int N, int K,
-                               int lda, int ldb, int ldc, int transA, int transB, int batch_outer, int batch_inner,
-                               long long sAo, long long sAi, long long sBo, long long sBi, long long sCo,
-                               long long sCi, int splitk, float alpha, float beta, const float* bias,
-                               const float* residual, int ldr, int act, const void* aux_in, void* aux_out,
-                               int ld_aux, int c_dtype, float drop_p, unsigned long long seed, unsigned int site,
-                               float* colsum_out, float* arowsum_out, void* workspace, long long workspace_bytes) {
+// every instance of the mmdti_gemm_bf16 families, by (family, template key); the tall kernel takes (GemmArgs, int mstep), the rest (GemmArgs)
+#define KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+static const struct GemmKernel { int family, ta, tb, fast, f16, bcvt; const void* fn; } g_gemm_kernels[] = {
+    {GEMM_REG, 0, 0, 0, 0, 0, KFN(gemm_bf16_kernel<false, false, false>)}, {GEMM_REG, 0, 0, 1, 0, 0, KFN(gemm_bf16_kernel<false, false, true>)},
+    {GEMM_REG, 0, 1, 0, 0, 0, KFN(gemm_bf16_kernel<false, true, false>)},  {GEMM_REG, 0, 1, 1, 0, 0, KFN(gemm_bf16_kernel<false, true, true>)},
+    {GEMM_REG, 1, 0, 0, 0, 0, KFN(gemm_bf16_kernel<true, false, false>)},  {GEMM_REG, 1, 0, 1, 0, 0, KFN(gemm_bf16_kernel<true, false, true>)},
+    {GEMM_REG, 1, 1, 0, 0, 0, KFN(gemm_bf16_kernel<true, true, false>)},   {GEMM_REG, 1, 1, 1, 0, 0, KFN(gemm_bf16_kernel<true, true, true>)},
+    {GEMM_REG, 0, 0, 0, 1, 0, KFN(gemm_bf16_kernel<false, false, false, true>)},        // fp16 operands (forward shapes)
+    {GEMM_REG, 0, 0, 1, 1, 0, KFN(gemm_bf16_kernel<false, false, true, true>)},
+    {GEMM_REG, 1, 1, 0, 0, 1, KFN(gemm_bf16_kernel<true, true, false, false, true>)},   // fp16 B converted in registers (weight gradients)
+    {GEMM_REG, 1, 1, 1, 0, 1, KFN(gemm_bf16_kernel<true, true, true, false, true>)},
+    {GEMM_GLDS, 0, 0, 0, 0, 0, KFN(gemm_glds_kernel<false, false, false>)}, {GEMM_GLDS, 0, 1, 0, 0, 0, KFN(gemm_glds_kernel<false, true, false>)},
+    {GEMM_GLDS, 1, 0, 0, 0, 0, KFN(gemm_glds_kernel<true, false, false>)},  {GEMM_GLDS, 1, 1, 0, 0, 0, KFN(gemm_glds_kernel<true, true, false>)},
+    {GEMM_GLDS, 0, 0, 0, 1, 0, KFN(gemm_glds_kernel<false, false, false, true>)},
+    {GEMM_DBUF, 0, 0, 0, 0, 0, KFN(gemm_glds_kernel<false, false, true>)},  {GEMM_DBUF, 0, 1, 0, 0, 0, KFN(gemm_glds_kernel<false, true, true>)},
+    {GEMM_DBUF, 1, 0, 0, 0, 0, KFN(gemm_glds_kernel<true, false, true>)},   {GEMM_DBUF, 1, 1, 0, 0, 0, KFN(gemm_glds_kernel<true, true, true>)},
+    {GEMM_DBUF, 1, 1, 0, 0, 1, KFN(gemm_glds_kernel<true, true, 1, false, true>)},
+    {GEMM_DEEP, 0, 0, 0, 0, 0, KFN(gemm_glds_kernel<false, false, 2>)},     {GEMM_DEEP, 0, 1, 0, 0, 0, KFN(gemm_glds_kernel<false, true, 2>)},
+    {GEMM_DEEP, 1, 0, 0, 0, 0, KFN(gemm_glds_kernel<true, false, 2>)},      {GEMM_DEEP, 1, 1, 0, 0, 0, KFN(gemm_glds_kernel<true, true, 2>)},
+    {GEMM_DEEP, 0, 0, 0, 1, 0, KFN(gemm_glds_kernel<false, false, 2, true>)},
+    {GEMM_TALL, 0, 0, 0, 0, 0, KFN(gemm_glds_tall_kernel<false>)},          {GEMM_TALL, 0, 1, 0, 0, 0, KFN(gemm_glds_tall_kernel<true>)},
+    {GEMM_TALL, 0, 0, 0, 1, 0, KFN(gemm_glds_tall_kernel<false, true>)},
+    {GEMM_SMALL, 0, 0, 0, 0, 0, KFN(gemm_small_kernel<false, false>)},      {GEMM_SMALL, 0, 1, 0, 0, 0, KFN(gemm_small_kernel<true, false>)},
+    {GEMM_SMALL, 0, 0, 0, 1, 0, KFN(gemm_small_kernel<false, true>)},
+    {GEMM_BIG, 0, 0, 0, 0, 0, KFN(gemm_big_kernel<false, false>)},          {GEMM_BIG, 0, 1, 0, 0, 0, KFN(gemm_big_kernel<false, true>)},
+    {GEMM_BIG, 1, 0, 0, 0, 0, KFN(gemm_big_kernel<true, false>)},           {GEMM_BIG, 1, 1, 0, 0, 0, KFN(gemm_big_kernel<true, true>)},
+    {GEMM_BIG, 0, 0, 0, 1, 0, KFN(gemm_big_kernel<false, false, true>)},    {GEMM_BIG, 1, 1, 0, 0, 1, KFN(gemm_big_kernel<true, true, false, true>)},
+};
+static const void* gemm_kernel(const GemmPlan& p) {
+  for (const GemmKernel& k : g_gemm_kernels)
+    if (k.family == p.family && k.ta == p.ta && k.tb == p.tb && k.fast == p.fast && k.f16 == p.f16 && k.bcvt == p.bcvt) return k.fn;
+  return nullptr;
+}
+
+// What mmdti_gemm_bf16 and mmdti_gemm_plan share: validate, plan, fill the kernel arguments.  Pointers are tested for null and
+// alignment only.
+static int gemm_prepare(GemmArgs& a, GemmPlan& plan, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
+                        int transA, int transB, int batch_outer, int batch_inner, long long sAo, long long sAi, long long sBo,
+                        long long sBi, long long sCo, long long sCi, int splitk, float alpha, float beta, const float* bias,
+                        const float* residual, int ldr, int act, const void* aux_in, void* aux_out, int ld_aux, int c_dtype, float drop_p,
+                        unsigned long long seed, unsigned int site, float* colsum_out, float* arowsum_out, void* workspace,
+                        long long workspace_bytes) {
   MMDTI_REQUIRE(M > 0 && N > 0 && K > 0, "gemm: M,N,K must be positive (got %d,%d,%d)", M, N, K);
   MMDTI_REQUIRE(A && B && C, "gemm: null operand");
   MMDTI_REQUIRE(aligned16(A) && aligned16(B), "gemm: A and B must be 16-byte aligned");
@@ -1829,27 +1852,8 @@ extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void*
   MMDTI_REQUIRE(batch_outer * batch_inner == 1 || (!residual && !aux_in && !aux_out && drop_p == 0.f),
                 "gemm: residual/aux/dropout epilogues are unbatched only");
   MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gemm: dropout p out of range");
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C;
-  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  a.batch_inner = batch_inner;
-  a.sAo = sAo; a.sAi = sAi; a.sBo = sBo; a.sBi = sBi; a.sCo = sCo; a.sCi = sCi;
-  a.splitk = splitk; a.alpha = alpha; a.beta = beta; a.bias = bias; a.residual = residual; a.ldr = ldr;
-  a.act = act; a.aux_in = (const bf16_t*)aux_in; a.aux_out = (bf16_t*)aux_out; a.ld_aux = ld_aux; a.c_dtype = c_dtype; a.c_f16 = c_f16;
-  a.drop_thresh = dropout_thresh(drop_p); a.drop_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  a.seed = seed; a.site = site;
-  a.colsum = colsum_out;
-  a.arowsum = nullptr;
-  a.zeros = nullptr;
-  a.slab = 0;
-  a.dbg = g_gemm_dbg;
-  {
-    // streaming stores for outputs of at least MMDTI_GEMM_STREAM_MB (default 96 MB; 0 = always, negative = never)
-    static const long long stream_mb = getenv("MMDTI_GEMM_STREAM_MB") ? atoll(getenv("MMDTI_GEMM_STREAM_MB")) : 96;
-    const long long cbytes = (long long)M * N * (c_dtype == MMDTI_DT_BF16 ? 2 : 4) * batch_outer * batch_inner;
-    a.stream_c = (stream_mb >= 0 && cbytes >= stream_mb * 1000000LL && beta == 0.f) ? 1 : 0;
-  }
   MMDTI_REQUIRE(!arowsum_out || (transA && batch_outer * batch_inner == 1), "gemm: arowsum_out needs a k-major A (transA) and no batch");
+  bool vec_ok;
   {
     const bool bf = c_dtype == MMDTI_DT_BF16;
     const int cal = bf ? 8 : 4;
@@ -1858,206 +1862,97 @@ extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void*
     if (residual) ok = ok && aligned16(residual) && (ldr % 4 == 0);
     if (aux_in) ok = ok && aligned16(aux_in) && (ld_aux % 8 == 0);
     if (aux_out) ok = ok && aligned16(aux_out) && (ld_aux % 8 == 0);
-    a.vec_ok = ok ? 1 : 0;
+    vec_ok = ok;
   }
-  MMDTI_REQUIRE(!colsum_out || (a.vec_ok && splitk == 1 && batch_outer * batch_inner == 1 && c_dtype != MMDTI_DT_F32_ATOMIC),
+  MMDTI_REQUIRE(!colsum_out || (vec_ok && splitk == 1 && batch_outer * batch_inner == 1 && c_dtype != MMDTI_DT_F32_ATOMIC),
                 "gemm: colsum_out needs the aligned, unbatched, unsplit output path");
-  const int tiles = cdiv(M, BM) * cdiv(N, BN);
-  dim3 grid(tiles, 1, batch_outer * batch_inner * splitk), block(256);
-  MMDTI_REQUIRE(grid.z <= 65535u, "gemm: batch*splitk too large (%u)", grid.z);
-  // two (A|B) tile buffers, re-used by the epilogue's per-wave patches
-  // one (A|B) tile pair (32,768 B), re-used by the epilogue's [64][132] fp32 staging image (33,792 B)
-  const size_t smem = (size_t)64 * LDC_S * sizeof(float);
+  const unsigned grid_z = batch_outer * batch_inner * splitk;
+  MMDTI_REQUIRE(grid_z <= 65535u, "gemm: batch*splitk too large (%u)", grid_z);
+
+  const GemmOptions& opt = gemm_options(ENTRY_GEMM);
+  GemmShape s;
+  s.M = M; s.N = N; s.K = K; s.lda = lda; s.ldb = ldb; s.transA = transA != 0; s.transB = transB != 0;
+  s.batch = batch_outer * batch_inner; s.splitk = splitk;
+  s.c_bf16 = c_dtype == MMDTI_DT_BF16; s.c_atomic = c_dtype == MMDTI_DT_F32_ATOMIC;
+  s.ab16 = ab16; s.bcvt = bcvt; s.vec_ok = vec_ok;
+  s.has_aux_in = aux_in != nullptr; s.has_colsum = colsum_out != nullptr; s.has_arowsum = arowsum_out != nullptr;
+  s.beta_zero = beta == 0.f;
+  s.ws_ok = workspace && aligned16(workspace); s.ws_bytes = workspace_bytes;
+  s.slab_epilogue_ok = alpha == 1.f && !bias && !residual && act == MMDTI_ACT_NONE && aligned16(C) && ldc % 4 == 0;
+  plan = gemm_plan(s, opt);
+
+  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.batch_inner = batch_inner;
+  a.sAo = sAo; a.sAi = sAi; a.sBo = sBo; a.sBi = sBi; a.sCo = sCo; a.sCi = sCi;
+  a.splitk = plan.splitk; a.alpha = alpha; a.beta = beta; a.bias = bias; a.residual = residual; a.ldr = ldr;
+  a.act = act; a.aux_in = (const bf16_t*)aux_in; a.aux_out = (bf16_t*)aux_out; a.ld_aux = ld_aux; a.c_dtype = c_dtype; a.c_f16 = c_f16;
+  a.drop_thresh = dropout_thresh(drop_p); a.drop_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  a.seed = seed; a.site = site;
+  a.colsum = colsum_out;
+  a.arowsum = plan.arowsum == AROWSUM_IN_KERNEL ? arowsum_out : nullptr;
+  a.zeros = nullptr;
+  a.slab = 0;
+  a.dbg = opt.dbg;
+  a.stream_c = plan.stream_c;
+  a.vec_ok = vec_ok ? 1 : 0;
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_gemm_plan(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB,
+                               int batch_outer, int batch_inner, long long sAo, long long sAi, long long sBo, long long sBi, long long sCo,
+                               long long sCi, int splitk, float alpha, float beta, const float* bias, const float* residual, int ldr, int act,
+                               const void* aux_in, void* aux_out, int ld_aux, int c_dtype, float drop_p, unsigned long long seed,
+                               unsigned int site, float* colsum_out, float* arowsum_out, void* workspace, long long workspace_bytes,
+                               int* plan_out) {
+  MMDTI_REQUIRE(plan_out != nullptr, "gemm_plan: null plan_out");
+  GemmArgs a;
+  GemmPlan plan;
+  if (int e = gemm_prepare(a, plan, A, B, C, M, N, K, lda, ldb, ldc, transA, transB, batch_outer, batch_inner, sAo, sAi, sBo, sBi, sCo, sCi, splitk,
+                           alpha, beta, bias, residual, ldr, act, aux_in, aux_out, ld_aux, c_dtype, drop_p, seed, site, colsum_out, arowsum_out,
+                           workspace, workspace_bytes))
+    return e;
+  static_assert(GEMM_PLAN_INTS == 15, "mmdti_hip.h documents 15 ints");
+  memcpy(plan_out, &plan, sizeof(plan));
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void* B, void* C, int M, int N, int K,
+                               int lda, int ldb, int ldc, int transA, int transB, int batch_outer, int batch_inner,
+                               long long sAo, long long sAi, long long sBo, long long sBi, long long sCo,
+                               long long sCi, int splitk, float alpha, float beta, const float* bias,
+                               const float* residual, int ldr, int act, const void* aux_in, void* aux_out,
+                               int ld_aux, int c_dtype, float drop_p, unsigned long long seed, unsigned int site,
+                               float* colsum_out, float* arowsum_out, void* workspace, long long workspace_bytes) {
+  GemmArgs a;
+  GemmPlan plan;
+  if (int e = gemm_prepare(a, plan, A, B, C, M, N, K, lda, ldb, ldc, transA, transB, batch_outer, batch_inner, sAo, sAi, sBo, sBi, sCo, sCi, splitk,
+                           alpha, beta, bias, residual, ldr, act, aux_in, aux_out, ld_aux, c_dtype, drop_p, seed, site, colsum_out, arowsum_out,
+                           workspace, workspace_bytes))
+    return e;
+  const void* fn = gemm_kernel(plan);
+  MMDTI_REQUIRE(fn != nullptr, "gemm: no kernel instance for the planned family %d", plan.family);
+  if (int e = ensure_dynamic_lds(fn, plan.lds, "gemm")) return e;
+  if (plan.arowsum == AROWSUM_COLSUM_PASS)
+    if (int e = mmdti_colsum_bf16(stream, A, K, M, lda, arowsum_out)) return e;
   hipStream_t s = (hipStream_t)stream;
-  // > 64 KiB of dynamic LDS: opt in once per instantiation.
-  typedef void (*kern_t)(GemmArgs);
-  static const kern_t kerns[2][2][2] = {
-      {{gemm_bf16_kernel<false, false, false>, gemm_bf16_kernel<false, false, true>},
-       {gemm_bf16_kernel<false, true, false>, gemm_bf16_kernel<false, true, true>}},
-      {{gemm_bf16_kernel<true, false, false>, gemm_bf16_kernel<true, false, true>},
-       {gemm_bf16_kernel<true, true, false>, gemm_bf16_kernel<true, true, true>}}};
-  static bool attr_done = false;
-  if (!attr_done) {
-    for (int i = 0; i < 8; ++i) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[i >> 2][(i >> 1) & 1][i & 1]),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-        set_error("gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem);
-        return MMDTI_ERR_LAUNCH;
-      }
-    }
-    attr_done = true;
+  const long long slab = (long long)M * N;
+  if (plan.slabs) {
+    // split ks stores its partial tile into slab ks (vector epilogue, plain stores); splitk_reduce_kernel adds the sum into C
+    a.C = workspace; a.ldc = N; a.c_dtype = MMDTI_DT_F32; a.beta = 0.f; a.vec_ok = 1; a.slab = slab;
   }
-  // bare-load fast path: no K tail, no ragged 8-row chunk on a k-major operand, offsets fit 32 bits
-  const bool fast = (K % BK == 0) && (!transA || M % 8 == 0) && (!transB || N % 8 == 0) && M >= 8 && N >= 8 &&
-                    ((long long)(transA ? BK : M) * lda * 2 < 0x7fffffffLL) && ((long long)(transB ? BK : N) * ldb * 2 < 0x7fffffffLL);
-  static const kern_t gkerns[2][2] = {{gemm_glds_kernel<false, false, false>, gemm_glds_kernel<false, true, false>},
-                                      {gemm_glds_kernel<true, false, false>, gemm_glds_kernel<true, true, false>}};
-  static const kern_t gkerns2[2][2] = {{gemm_glds_kernel<false, false, true>, gemm_glds_kernel<false, true, true>},
-                                       {gemm_glds_kernel<true, false, true>, gemm_glds_kernel<true, true, true>}};
-  static const kern_t gkerns3[2][2] = {{gemm_glds_kernel<false, false, 2>, gemm_glds_kernel<false, true, 2>},
-                                       {gemm_glds_kernel<true, false, 2>, gemm_glds_kernel<true, true, 2>}};
-  // LDS-DMA tile fetch for every bare-load shape except the split-K weight gradients (measured: -15...-20 % on the
-  // N >= 1536 / K >= 1536 shapes, equal at 512x512, +9 % on the atomic split-K ones); MMDTI_GEMM_GLDS=0 turns it off
-  static const int use_glds = getenv("MMDTI_GEMM_GLDS") ? atoi(getenv("MMDTI_GEMM_GLDS")) : 1;
-  // split-K weight gradients: double-buffered DMA from 48 output tiles up (-5...-13 %), register staging below (+13 %)
-  // arowsum rides on the kernel that has register room for it (double-buffered DMA: the large weight gradients); on
-  // the other paths it is the plain column-sum pass over A's memory image ([K][M] row-major)
-  // (a small split-K weight gradient that also carries its bias gradient takes the double-buffered kernel too: +6 us
-  //  there against a 35-50 us column-sum pass over dy)
-  const bool dbuf_path = fast && use_glds && ((splitk > 1 && (tiles >= 48 || (arowsum_out && transA))) || use_glds == 3);
-  // 256 x 256 tiles with the DMA in flight across barriers (gemm_big_kernel): MMDTI_GEMM_BIG=0 off, 1 (default) where
-  // the shape fills the chip, 2 every eligible shape
-  const int use_big = g_gemm_big;
-  const bool big_ok = fast && use_big && batch_outer * batch_inner == 1 && !colsum_out && M >= 256 && N >= 256 &&
-                      (c_dtype == MMDTI_DT_F32_ATOMIC || a.vec_ok) && M % 256 == 0 && N % 256 == 0;
-  if (big_ok && (use_big == 2 || big_shape_pays(M, N, K, splitk, transA, transB, aux_in != nullptr))) {
-    typedef void (*bkern_t)(GemmArgs);
-    static const bkern_t bkerns[2][2] = {{gemm_big_kernel<false, false>, gemm_big_kernel<false, true>},
-                                         {gemm_big_kernel<true, false>, gemm_big_kernel<true, true>}};
-    // [4]: fp16 operands (forward shapes); [5]: fp16 B converted in registers (weight gradients)
-    static const bkern_t bkerns_all[6] = {bkerns[0][0], bkerns[0][1], bkerns[1][0], bkerns[1][1], gemm_big_kernel<false, false, true>,
-                                          gemm_big_kernel<true, true, false, true>};
-    const bkern_t bk = ab16 ? bkerns_all[4] : (bcvt ? bkerns_all[5] : bkerns[transA ? 1 : 0][transB ? 1 : 0]);
-    const size_t smem_b = (size_t)2 * BIG_BUF * sizeof(bf16_t);
-    static bool big_attr = false;
-    if (!big_attr) {
-      for (int i = 0; i < 6; ++i)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(bkerns_all[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b) != hipSuccess) {
-          set_error("gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem_b);
-          return MMDTI_ERR_LAUNCH;
-        }
-      big_attr = true;
-    }
-    const int btiles = cdiv(M, BBM) * cdiv(N, BBN);
-    int sk = splitk;
-    if (splitk > 1) {   // weight gradients: about one workgroup per CU, at least 4 K-tiles per split
-      sk = max(1, min(K / BK / 4, 256 / btiles));      // floor: one round of workgroups (a 257th would cost a whole second round)
-      const int kts = K / BK, per = cdiv(kts, sk);
-      sk = cdiv(kts, per);          // no empty split (the slab form sums EVERY slab)
-    }
-    a.splitk = sk;
-    a.arowsum = arowsum_out;
-    dim3 bgrid(btiles, 1, sk);
-    const long long slab = (long long)M * N;
-    const bool slabs = sk > 1 && workspace && aligned16(workspace) && workspace_bytes >= (long long)sk * slab * 4 && N % 8 == 0 &&
-                       alpha == 1.f && !bias && !residual && act == MMDTI_ACT_NONE && slab % 4 == 0 && aligned16(C) && ldc % 4 == 0;
-    if (slabs && !(g_gemm_dbg & 1)) {
-      // split ks stores its partial tile into slab ks (vector epilogue, plain stores); splitk_reduce_kernel adds the sum into C
-      GemmArgs p = a;
-      p.C = workspace; p.ldc = N; p.c_dtype = MMDTI_DT_F32; p.beta = 0.f; p.vec_ok = 1; p.stream_c = 0; p.slab = slab;
-      hipLaunchKernelGGL(bk, bgrid, dim3(512), smem_b, s, p);
-      const long long n4 = slab / 4;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)min((n4 + 255) / 256, 4096LL)), dim3(256), 0, s, (const float*)workspace,
-                         reinterpret_cast<float*>(C), M, N, ldc, sk);
-    } else {
-      hipLaunchKernelGGL(bk, bgrid, dim3(512), smem_b, s, a);
-    }
-    MMDTI_LAUNCH_CHECK();
-    return MMDTI_OK;
+  void* kargs[2] = {&a, &plan.mstep};     // (only the tall kernel has the second parameter)
+  (void)hipLaunchKernel(fn, dim3(plan.grid_x, 1, plan.grid_z), dim3(plan.block), kargs, (size_t)plan.lds, s);
+  if (plan.slabs) {
+    const long long n4 = slab / 4;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)min((n4 + 255) / 256, 4096LL)), dim3(256), 0, s, (const float*)workspace,
+                       reinterpret_cast<float*>(C), M, N, ldc, plan.splitk);
   }
-  if (arowsum_out) {
-    if (dbuf_path || (bcvt && fast && use_glds)) {
-      a.arowsum = arowsum_out;
-    } else if (int e = mmdti_colsum_bf16(stream, A, K, M, lda, arowsum_out)) {
-      return e;
-    }
-  }
-  if (bcvt) {
-    // weight gradient with an fp16 activation operand: the double-buffered LDS-DMA kernel on bare-load shapes (whatever the split), the
-    // register-staged one otherwise
-    if (fast && use_glds) {
-      a.arowsum = arowsum_out;
-      hipLaunchKernelGGL((gemm_glds_kernel<true, true, 1, false, true>), grid, block, 4 * (size_t)BM * LDT * sizeof(bf16_t), s, a);
-    } else {
-      static bool attr_cv = false;
-      if (!attr_cv) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<true, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<true, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-          set_error("gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem);
-          return MMDTI_ERR_LAUNCH;
-        }
-        attr_cv = true;
-      }
-      if (fast) hipLaunchKernelGGL((gemm_bf16_kernel<true, true, true, false, true>), grid, block, smem, s, a);
-      else hipLaunchKernelGGL((gemm_bf16_kernel<true, true, false, false, true>), grid, block, smem, s, a);
-    }
-  }
-  else if (dbuf_path)
-    hipLaunchKernelGGL(gkerns2[transA ? 1 : 0][transB ? 1 : 0], grid, block, 4 * (size_t)BM * LDT * sizeof(bf16_t), s, a);
-  else if (fast && use_glds && splitk == 1) {
-    // tall tiles when they save a whole round of the 1024 resident workgroups (see gemm_glds_tall_kernel)
-    int mstep = 0;
-    static const int use_tall = getenv("MMDTI_GEMM_TALL") ? atoi(getenv("MMDTI_GEMM_TALL")) : 1;
-    const int use_small = g_gemm_small;
-    static const int small_max_tiles = getenv("MMDTI_GEMM_SMALL_TILES") ? atoi(getenv("MMDTI_GEMM_SMALL_TILES")) : 128;
-    const int use_deep = g_gemm_deep;
-    const int deep_max_wgs = 256;                     // (one workgroup per CU)
-    if (use_tall && !transA && a.vec_ok && grid.z == 1 && M >= 1024) {
-      const int slots = 1024, tn = cdiv(N, BN);
-      const int r128 = cdiv(tiles, slots);
-      if (r128 >= 2 && (r128 - 1) * slots >= tn) {
-        const int rows_fit = ((r128 - 1) * slots) / tn;           // row-tiles that fit in one round fewer
-        const int sneed = cdiv(M, rows_fit);
-        // (measured: 2 -> 1 rounds is -12...-16 %; 4 -> 3 and 5 -> 4 rounds lose to the taller tile's own cost)
-        if (sneed > 128 && sneed <= BMT && 1.125 * (r128 - 1) < 0.75 * r128) mstep = sneed;
-      }
-    }
-    if (mstep) {
-      grid.x = cdiv(M, mstep) * cdiv(N, BN);
-      const size_t smem_t = (size_t)(BMT + BN) * LDT * sizeof(bf16_t);
-      if (ab16) hipLaunchKernelGGL((gemm_glds_tall_kernel<false, true>), grid, block, smem_t, s, a, mstep);
-      else if (transB) hipLaunchKernelGGL(gemm_glds_tall_kernel<true>, grid, block, smem_t, s, a, mstep);
-      else hipLaunchKernelGGL(gemm_glds_tall_kernel<false>, grid, block, smem_t, s, a, mstep);
-    } else if (use_small && !transA && a.vec_ok && c_dtype != MMDTI_DT_F32_ATOMIC && !colsum_out && grid.z == 1 && tiles <= small_max_tiles &&
-               !(ab16 && transB)) {
-      // small launches: a quarter of the tile per workgroup, four times the CUs (see gemm_small_kernel)
-      const dim3 sgrid(cdiv(M, SBM) * cdiv(N, SBN));
-      const size_t smem_s = (size_t)SM_STAGES * 2 * SM_TILE * sizeof(bf16_t);
-      if (ab16) hipLaunchKernelGGL((gemm_small_kernel<false, true>), sgrid, block, smem_s, s, a);
-      else if (transB) hipLaunchKernelGGL((gemm_small_kernel<true, false>), sgrid, block, smem_s, s, a);
-      else hipLaunchKernelGGL((gemm_small_kernel<false, false>), sgrid, block, smem_s, s, a);
-    } else if (use_deep && tiles * (int)grid.z <= deep_max_wgs && K >= 4 * BK) {
-      // at most one workgroup per CU: the four-stage ring hides the fetch latency nothing else would (small batches)
-      const size_t smem_d = (size_t)DEEP_STAGES * 2 * BM * LDT * sizeof(bf16_t);
-      static bool deep_attr = false;
-      if (!deep_attr) {
-        const void* fns[5] = {reinterpret_cast<const void*>(gkerns3[0][0]), reinterpret_cast<const void*>(gkerns3[0][1]),
-                              reinterpret_cast<const void*>(gkerns3[1][0]), reinterpret_cast<const void*>(gkerns3[1][1]),
-                              reinterpret_cast<const void*>(gemm_glds_kernel<false, false, 2, true>)};
-        for (int i = 0; i < 5; ++i)
-          if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_d) != hipSuccess) {
-            set_error("gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem_d);
-            return MMDTI_ERR_LAUNCH;
-          }
-        deep_attr = true;
-      }
-      if (ab16) hipLaunchKernelGGL((gemm_glds_kernel<false, false, 2, true>), grid, block, smem_d, s, a);
-      else hipLaunchKernelGGL(gkerns3[transA ? 1 : 0][transB ? 1 : 0], grid, block, smem_d, s, a);
-    } else if (ab16) {
-      hipLaunchKernelGGL((gemm_glds_kernel<false, false, false, true>), grid, block, smem, s, a);
-    } else {
-      hipLaunchKernelGGL(gkerns[transA ? 1 : 0][transB ? 1 : 0], grid, block, smem, s, a);
-    }
-  }
-  else if (ab16) {
-    static bool attr16 = false;
-    if (!attr16) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-        set_error("gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem);
-        return MMDTI_ERR_LAUNCH;
-      }
-      attr16 = true;
-    }
-    if (fast) hipLaunchKernelGGL((gemm_bf16_kernel<false, false, true, true>), grid, block, smem, s, a);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<false, false, false, true>), grid, block, smem, s, a);
-  }
-  else
-    hipLaunchKernelGGL(kerns[transA ? 1 : 0][transB ? 1 : 0][fast ? 1 : 0], grid, block, smem, s, a);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
+extern "C" int mmdti_gemm_ln_rows(int M) { return gemm_ln_rows(M, gemm_options(ENTRY_GEMM_LN)); }
 
 extern "C" int mmdti_gemm_ln_bf16(mmdti_stream_t stream, const void* A_bf16, const void* W_bf16, const float* bias, const float* residual,
                                   int M, int N, int K, int lda, int ldb, int ldr, float drop_p, unsigned long long seed, unsigned int site,
@@ -2078,113 +1973,90 @@ extern "C" int mmdti_gemm_ln_bf16(mmdti_stream_t stream, const void* A_bf16, con
   a.drop_thresh = dropout_thresh(drop_p); a.drop_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
   a.seed = seed; a.site = site;
   a.ln_f16 = (f16 >> 1) & 1;          // bit 0: A and W are fp16; bit 1: the 16-bit LayerNorm output is fp16
-  const bool ab16 = f16 & 1;
-  // rows per tile: 64 or 80 -- whichever needs less (rounds of the 512 resident workgroups) x (rows per tile)
-  static const int force_r = getenv("MMDTI_GEMM_LN_ROWS") ? atoi(getenv("MMDTI_GEMM_LN_ROWS")) : 0;
-  const long long cost4 = (long long)cdiv(cdiv(M, 64), 512) * 4, cost5 = (long long)cdiv(cdiv(M, 80), 512) * 5;
-  const int R = force_r == 64 ? 4 : (force_r == 80 ? 5 : (cost5 < cost4 ? 5 : 4));
-  const size_t smem = max((size_t)(16 * R + LN_BN) * LDT * sizeof(bf16_t), (size_t)(16 * LDC_LN + 3 * LN_BN) * sizeof(float));
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ln_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ln_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ln_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ln_kernel<5, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) {
-      set_error("gemm_ln: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-      return MMDTI_ERR_LAUNCH;
-    }
-    attr = true;
-  }
-  if (ab16) {
-    if (R == 5) hipLaunchKernelGGL((gemm_ln_kernel<5, true>), dim3(cdiv(M, 80)), dim3(512), smem, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((gemm_ln_kernel<4, true>), dim3(cdiv(M, 64)), dim3(512), smem, (hipStream_t)stream, a);
-  } else if (R == 5) hipLaunchKernelGGL(gemm_ln_kernel<5>, dim3(cdiv(M, 80)), dim3(512), smem, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(gemm_ln_kernel<4>, dim3(cdiv(M, 64)), dim3(512), smem, (hipStream_t)stream, a);
+  const int rows = mmdti_gemm_ln_rows(M);
+  static const void* const kerns[2][2] = {{KFN(gemm_ln_kernel<4>), KFN(gemm_ln_kernel<4, true>)}, {KFN(gemm_ln_kernel<5>), KFN(gemm_ln_kernel<5, true>)}};
+  const void* fn = kerns[rows == 80][f16 & 1];
+  const int lds = gemm_ln_lds(rows);
+  if (int e = ensure_dynamic_lds(fn, lds, "gemm_ln")) return e;
+  void* kargs[1] = {&a};
+  (void)hipLaunchKernel(fn, dim3(cdiv(M, rows)), dim3(512), kargs, (size_t)lds, (hipStream_t)stream);
   MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+// What mmdti_linear_dw_grouped and its query share: the shape rules of the problem list, and the plan
+static int grouped_dw_prepare(GroupedDwPlan& plan, int nprob, const int* n_out, const int* n_in, int rows, int x_f16) {
+  MMDTI_REQUIRE(nprob >= 1 && nprob <= GROUP_MAX, "linear_dw_grouped: 1..%d problems (got %d)", GROUP_MAX, nprob);
+  MMDTI_REQUIRE(n_out && n_in, "linear_dw_grouped: null argument table");
+  MMDTI_REQUIRE(rows >= 64, "linear_dw_grouped: at least 64 rows (got %d)", rows);   // (any count: a K tail is zero-filled in the kernel)
+  int tiles256 = 0, tiles64 = 0;
+  long long elems = 0;
+  for (int i = 0; i < nprob; ++i) {
+    MMDTI_REQUIRE(n_out[i] > 0 && n_in[i] > 0 && n_out[i] % BBM == 0 && n_in[i] % BBN == 0, "linear_dw_grouped: dimensions must be multiples of 256 (problem %d: %d x %d)", i, n_out[i], n_in[i]);
+    tiles256 += (n_out[i] / BBM) * (n_in[i] / BBN);
+    tiles64 += (n_out[i] / SBM) * (n_in[i] / SBN);
+    elems += (long long)n_out[i] * n_in[i];
+  }
+  plan = grouped_dw_plan(tiles256, tiles64, elems, rows, x_f16 != 0, gemm_options(ENTRY_GROUPED_DW));
+  return MMDTI_OK;
+}
+static const void* grouped_dw_kernel(const GroupedDwPlan& p) {
+  static const void* const small_kerns[2] = {KFN(gemm_small_dw_grouped_kernel<3, false>), KFN(gemm_small_dw_grouped_kernel<3, true>)};
+  static const void* const big_kerns[2][2] = {{KFN(gemm_big_grouped_kernel<false, false>), KFN(gemm_big_grouped_kernel<false, true>)},
+                                              {KFN(gemm_big_grouped_kernel<true, false>), KFN(gemm_big_grouped_kernel<true, true>)}};
+  return p.small ? small_kerns[p.bcvt] : big_kerns[p.bcvt][p.ktail];
+}
+
+extern "C" int mmdti_linear_dw_grouped_plan(int nprob, const int* n_out, const int* n_in, int rows, int x_f16, int* plan_out,
+                                            long long* workspace_bytes_out) {
+  MMDTI_REQUIRE(plan_out && workspace_bytes_out, "linear_dw_grouped_plan: null output");
+  GroupedDwPlan plan;
+  if (int e = grouped_dw_prepare(plan, nprob, n_out, n_in, rows, x_f16)) return e;
+  const int out[9] = {plan.small, plan.grid_x, plan.grid_z, plan.block, plan.lds, plan.splitk, plan.ktail, plan.atomic, plan.bcvt};
+  memcpy(plan_out, out, sizeof(out));
+  *workspace_bytes_out = plan.ws_bytes;
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_linear_dw_grouped(mmdti_stream_t stream, int nprob, const void* const* dy_bf16, const void* const* x_bf16,
                                        float* const* dw, float* const* db, const int* n_out, const int* n_in, const int* ldy,
                                        const int* ldx, const int* lddw, int rows, void* workspace, long long workspace_bytes, int x_f16) {
-  MMDTI_REQUIRE(nprob >= 1 && nprob <= GROUP_MAX, "linear_dw_grouped: 1..%d problems (got %d)", GROUP_MAX, nprob);
-  MMDTI_REQUIRE(dy_bf16 && x_bf16 && dw && n_out && n_in && ldy && ldx && lddw, "linear_dw_grouped: null argument table");
-  MMDTI_REQUIRE(rows >= 64, "linear_dw_grouped: at least 64 rows (got %d)", rows);   // (any count: a K tail is zero-filled in the kernel)
+  GroupedDwPlan plan;
+  if (int e = grouped_dw_prepare(plan, nprob, n_out, n_in, rows, x_f16)) return e;       // (problem count, row count and dimensions)
+  MMDTI_REQUIRE(dy_bf16 && x_bf16 && dw && ldy && ldx && lddw, "linear_dw_grouped: null argument table");
   MMDTI_REQUIRE(workspace && aligned16(workspace), "linear_dw_grouped: a 16-byte aligned workspace is required");
   GroupArgs g;
   g.nprob = nprob; g.K = rows;
   g.zeros = zero_page();
   MMDTI_REQUIRE(g.zeros != nullptr, "linear_dw_grouped: could not allocate the zero page");
-  int tiles = 0;
-  long long elems = 0;
   for (int i = 0; i < nprob; ++i) {
     MMDTI_REQUIRE(dy_bf16[i] && x_bf16[i] && dw[i], "linear_dw_grouped: null operand in problem %d", i);
-    MMDTI_REQUIRE(n_out[i] > 0 && n_in[i] > 0 && n_out[i] % BBM == 0 && n_in[i] % BBN == 0, "linear_dw_grouped: dimensions must be multiples of 256 (problem %d: %d x %d)", i, n_out[i], n_in[i]);
     MMDTI_REQUIRE(ldy[i] % 8 == 0 && ldx[i] % 8 == 0 && lddw[i] % 4 == 0 && aligned16(dy_bf16[i]) && aligned16(x_bf16[i]) && aligned16(dw[i]),
                   "linear_dw_grouped: alignment (problem %d)", i);
     MMDTI_REQUIRE((long long)BK * ldy[i] * 2 < 0x7fffffffLL && (long long)BK * ldx[i] * 2 < 0x7fffffffLL, "linear_dw_grouped: row stride too large");
+  }
+  MMDTI_REQUIRE(workspace_bytes >= plan.ws_bytes, "linear_dw_grouped: workspace too small (%lld bytes needed for %d splits)", plan.ws_bytes, plan.splitk);
+  // problem i owns tiles [tile0, tile0 + its tile count) of the plan's tile size, and splitk slabs of the workspace
+  const int tm = plan.small ? SBM : BBM, tn = plan.small ? SBN : BBN;
+  float* ws = reinterpret_cast<float*>(workspace);
+  int tiles = 0;
+  for (int i = 0; i < nprob; ++i) {
     GroupProb& p = g.p[i];
     p.A = (const bf16_t*)dy_bf16[i]; p.B = (const bf16_t*)x_bf16[i]; p.C = dw[i]; p.arowsum = db ? db[i] : nullptr;
     p.M = n_out[i]; p.N = n_in[i]; p.lda = ldy[i]; p.ldb = ldx[i]; p.ldc = lddw[i];
-    p.tile0 = tiles; p.tiles_n = n_in[i] / BBN;
-    tiles += (n_out[i] / BBM) * p.tiles_n;
-    elems += (long long)n_out[i] * n_in[i];
+    p.tile0 = tiles; p.tiles_n = n_in[i] / tn;
+    tiles += (n_out[i] / tm) * p.tiles_n;
+    p.slab = ws;
+    ws += (long long)plan.splitk * p.M * p.N;
   }
   for (int i = nprob; i < GROUP_MAX; ++i) { g.p[i] = g.p[0]; g.p[i].tile0 = 0x7fffffff; }
+  g.ntiles = tiles; g.splitk = plan.splitk; g.atomic = plan.atomic;
+  const void* fn = grouped_dw_kernel(plan);
+  if (int e = ensure_dynamic_lds(fn, plan.lds, "linear_dw_grouped")) return e;
   hipStream_t s = (hipStream_t)stream;
-  // small token counts: 64 x 64 tiles, no K split, plain += (gemm_small_dw_grouped_kernel)
-  static const int small_rows = getenv("MMDTI_GROUPED_SMALL_ROWS") ? atoi(getenv("MMDTI_GROUPED_SMALL_ROWS")) : 4096;
-  if (rows <= small_rows && g_gemm_small) {
-    GroupArgs gs = g;
-    int st = 0;
-    for (int i = 0; i < nprob; ++i) {
-      gs.p[i].tile0 = st; gs.p[i].tiles_n = n_in[i] / SBN;
-      st += (n_out[i] / SBM) * gs.p[i].tiles_n;
-    }
-    gs.ntiles = st; gs.splitk = 1; gs.atomic = 0;
-    // (three stages = 48 KB: three workgroups per CU; measured -2 % on the step against a four-stage ring at two per CU)
-    if (x_f16) hipLaunchKernelGGL((gemm_small_dw_grouped_kernel<3, true>), dim3(st), dim3(256), (size_t)3 * 2 * SM_TILE * sizeof(bf16_t), s, gs);
-    else hipLaunchKernelGGL((gemm_small_dw_grouped_kernel<3, false>), dim3(st), dim3(256), (size_t)3 * 2 * SM_TILE * sizeof(bf16_t), s, gs);
-    MMDTI_LAUNCH_CHECK();
-    return MMDTI_OK;
-  }
-  g.ntiles = tiles;
-  const int kts = cdiv(rows, BK);
-  int sk = max(1, min(kts / 4, 256 / max(1, tiles)));   // floor: all workgroups resident in ONE round
-  sk = cdiv(kts, cdiv(kts, sk));                     // no empty split: every slab is summed
-  g.splitk = sk;
-  MMDTI_REQUIRE(workspace_bytes >= (long long)sk * elems * 4, "linear_dw_grouped: workspace too small (%lld bytes needed for %d splits)",
-                (long long)sk * elems * 4, sk);
-  float* ws = reinterpret_cast<float*>(workspace);
-  for (int i = 0; i < nprob; ++i) {
-    g.p[i].slab = ws;
-    ws += (long long)sk * g.p[i].M * g.p[i].N;
-  }
-  const size_t smem_b = (size_t)2 * BIG_BUF * sizeof(bf16_t);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_grouped_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_grouped_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_grouped_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_big_grouped_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b) != hipSuccess) {
-      set_error("linear_dw_grouped: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem_b);
-      return MMDTI_ERR_LAUNCH;
-    }
-    attr = true;
-  }
-  // Small token counts (the reference's real batch sizes, 16-32 molecules): the step is a chain of ~20 us kernels, and the slab
-  // pass is one more of them per layer -- the K-splits add into dW with fp32 atomics instead (a few MB of them: cheaper than a launch)
-  // (reached only with the 64 x 64 kernel switched off: gemm_small = 0)
-  g.atomic = rows <= 4096 ? 1 : 0;
-  const bool ktail = rows % BK != 0;
-  if (x_f16) {
-    if (ktail) hipLaunchKernelGGL((gemm_big_grouped_kernel<true, true>), dim3(tiles, 1, sk), dim3(512), smem_b, s, g);
-    else hipLaunchKernelGGL((gemm_big_grouped_kernel<true, false>), dim3(tiles, 1, sk), dim3(512), smem_b, s, g);
-  } else {
-    if (ktail) hipLaunchKernelGGL((gemm_big_grouped_kernel<false, true>), dim3(tiles, 1, sk), dim3(512), smem_b, s, g);
-    else hipLaunchKernelGGL((gemm_big_grouped_kernel<false, false>), dim3(tiles, 1, sk), dim3(512), smem_b, s, g);
-  }
-  if (!g.atomic) {
+  void* kargs[1] = {&g};
+  (void)hipLaunchKernel(fn, dim3(plan.grid_x, 1, plan.grid_z), dim3(plan.block), kargs, (size_t)plan.lds, s);
+  if (!plan.small && !plan.atomic) {
     long long max_n4 = 0;
     for (int i = 0; i < nprob; ++i) max_n4 = max(max_n4, (long long)g.p[i].M * g.p[i].N / 4);
     hipLaunchKernelGGL(grouped_reduce_kernel, dim3((unsigned)min((max_n4 + 255) / 256, 2048LL), nprob), dim3(256), 0, s, g);
@@ -2196,7 +2068,5 @@ extern "C" int mmdti_linear_dw_grouped(mmdti_stream_t stream, int nprob, const v
 /* splits the grouped weight-gradient launch will use for `tiles` output tiles over `rows` tokens (workspace sizing) */
 extern "C" int mmdti_linear_dw_grouped_splits(int tiles, int rows) {
   if (tiles <= 0 || rows < BK) return 1;
-  const int kts = cdiv(rows, BK);
-  const int sk = max(1, min(kts / 4, 256 / max(1, tiles)));
-  return cdiv(kts, cdiv(kts, sk));
+  return slab_splits(cdiv(rows, BK), tiles);
 }

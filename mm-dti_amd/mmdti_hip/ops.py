@@ -207,6 +207,20 @@ DW_BIAS = os.environ.get("MMDTI_DW_BIAS", "1") != "0"
 SPLITK_SLABS = os.environ.get("MMDTI_SPLITK_SLABS", "1") != "0"
 
 
+def dw_workspace_floats(N, K, M):
+    """fp32 elements of split-K scratch linear_bwd_weight hands to the GEMM for dw [N, K] over M rows (0: none)"""
+    if not (SPLITK_SLABS and N % 256 == 0 and K % 256 == 0 and M >= 4096):
+        return 0
+    tiles = (N // 256) * (K // 256)
+    return max(1, min(256 // tiles, M // 256)) * N * K
+
+
+def grouped_dw_workspace_floats(shapes, rows):
+    """fp32 elements of scratch linear_bwd_weight_grouped hands to one grouped launch over dw shapes [(N_out, N_in)]"""
+    tiles = sum((no // 256) * (ni // 256) for no, ni in shapes)
+    return lib()._dll.mmdti_linear_dw_grouped_splits(tiles, rows) * sum(no * ni for no, ni in shapes)
+
+
 def linear_bwd_weight(dy, x, dw, *, rows=None, db=None):
     """dw[N,K] += dy[M,N]^T . x[M,K]   (fp32 atomic accumulate into the gradient arena);  db[N] += column sums of dy (the
     bias gradient, taken inside the same pass over dy)."""
@@ -221,10 +235,8 @@ def linear_bwd_weight(dy, x, dw, *, rows=None, db=None):
             db = None
     # split-K scratch for the large-tile kernel (one fp32 partial per split, summed by a second pass: no atomics); from the
     # caching allocator, so it is tied to the launch stream like any other temporary
-    ws = None
-    if SPLITK_SLABS and N % 256 == 0 and K % 256 == 0 and M >= 4096:
-        tiles = (N // 256) * (K // 256)
-        ws = torch.empty(max(1, min(256 // tiles, M // 256)) * N * K, device=dy.device, dtype=F32)
+    nws = dw_workspace_floats(N, K, M)
+    ws = torch.empty(nws, device=dy.device, dtype=F32) if nws else None
     gemm(dy, x, M=N, N=K, K=M, lda=dy.stride(0), ldb=x.stride(0), transA=True, transB=True, out=dw, ldc=dw.stride(0),
          atomic=True, splitk=_splitk_for(N, K, M), arowsum=db, workspace=ws)
     return dw
@@ -266,9 +278,7 @@ def linear_bwd_weight_grouped(items):
                 linear_bwd_weight(it[0], it[1], it[2], rows=rows, db=it[3])
                 continue
             n = len(chunk)
-            tiles = sum((it[2].shape[0] // 256) * (it[2].shape[1] // 256) for it in chunk)
-            sk = lib()._dll.mmdti_linear_dw_grouped_splits(tiles, rows)
-            ws = torch.empty(sk * sum(it[2].shape[0] * it[2].shape[1] for it in chunk), device=chunk[0][0].device, dtype=F32)
+            ws = torch.empty(grouped_dw_workspace_floats([tuple(it[2].shape) for it in chunk], rows), device=chunk[0][0].device, dtype=F32)
             vp, ip = ctypes.c_void_p * n, ctypes.c_int * n
             t0 = kernel_timer.begin("gemm")
             lib().mmdti_linear_dw_grouped(_stream(), n, vp(*[it[0].data_ptr() for it in chunk]), vp(*[it[1].data_ptr() for it in chunk]),

@@ -217,8 +217,19 @@ def test_weight_gradients_convert_fp16_activations_inside_the_kernel(ops, rows):
     """dW += dy^T.x with x a saved fp16 activation (MMDTI_DT_B_F16 / x_f16): the tile is fetched as fp16 and rounded to bf16 between LDS
     and the matrix pipe.  The grouped kernels (slab split-K above 4096 rows, one workgroup per tile below) have no atomics, so the
     result must equal -- bit for bit -- the same launch on the separately converted tensor (ops.to_bf16: the pass this replaces)."""
+    from mmdti_hip import _abi
+    from gemm_plan_helpers import dw_case, grouped_plan, plan_of
+    lib = _abi.lib()
     g = G(rows)
     shapes = [(512, 2048), (2048, 512), (1536, 512), (512, 512)]
+    # the fp16-x instance (BCVT) of the kernel the row count selects; the converted tensor takes the same launch on the bf16 instance
+    (name, gx, gz, block, lds, sk, atomic, second_pass), _ = grouped_plan(lib, shapes, rows, x_f16=1)
+    if rows <= 4096:
+        assert (name, gz, sk) == ("gemm_small_dw_grouped_kernel<3, true>", 1, 1)
+    else:
+        assert name == "gemm_big_grouped_kernel<true, %s>" % str(rows % 64 != 0).lower() and sk > 1 and not atomic and second_pass
+    plain = grouped_plan(lib, shapes, rows, x_f16=0)[0]
+    assert plain[1:] == (gx, gz, block, lds, sk, atomic, second_pass) and plain[0] == name.replace("<3, true>", "<3, false>").replace("<true, ", "<false, ")
     base = []
     for i, (no, ni) in enumerate(shapes):
         dy = bf(torch.randn(rows, no, generator=g)).cuda()
@@ -243,6 +254,9 @@ def test_weight_gradients_convert_fp16_activations_inside_the_kernel(ops, rows):
         dy = bf(torch.randn(rows, no, generator=g)).cuda()
         x = (torch.randn(rows, ni, generator=g) * 3).half().cuda()
         dw, db = torch.ones(no, ni).cuda(), torch.ones(no).cuda()
+        single = plan_of(lib, dw_case(ops, no, ni, rows, db=True, x_f16=1))
+        assert single[0] == ("gemm_glds_kernel<true, true, 1, false, true>" if rows % 64 == 0 else "gemm_bf16_kernel<true, true, false, false, true>")
+        assert single[9] == (1 if rows % 64 == 0 else 2)                 # db inside the kernel / by the column-sum pass
         ops.linear_bwd_weight(dy, x, dw, db=db)
         close(dw, 1.0 + dy.float().t() @ x.float().bfloat16().float(), 2e-3, 2e-2)
         close(db, 1.0 + dy.float().sum(0), 2e-3, 2e-2)
@@ -257,9 +271,13 @@ def test_gemm_256_tiles_with_fp16_operands(ops, M, N, K):
     x, w = h16(torch.randn(M, K, generator=g)).cuda(), h16(torch.randn(N, K, generator=g) * 0.1).cuda()
     b = torch.randn(N, generator=g).cuda()
     u = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+    from gemm_plan_helpers import case as plan_case, plan_of
+    pc = plan_case(M, N, K, ab16=1, out="f16", bias=1, act=ops.ACT_GELU_FWD, aux_out=1)
+    assert plan_of(lib, pc)[0] == "gemm_big_kernel<false, false, true, false, false>"
     y_big = ops.linear_fwd(x, w, b, act=ops.ACT_GELU_FWD, aux_out=u)
     try:
         lib.mmdti_set_option(b"gemm_big", 0)
+        assert not plan_of(lib, pc)[0].startswith("gemm_big_kernel")
         u0 = torch.empty_like(u)
         y_128 = ops.linear_fwd(x, w, b, act=ops.ACT_GELU_FWD, aux_out=u0)
     finally:
@@ -281,11 +299,16 @@ def test_fp16_stores_saturate_instead_of_overflowing(ops, fp16_mode):
     y = ops.cast_act16(x).float()
     assert y.dtype == torch.float32 and float(y[0, 0]) == 65504.0 and float(y[0, 1]) == -65504.0 and float(y[0, 2]) == 1.0
     assert float(y[0, 3]) == 65504.0 and float(y[0, 4]) == -65504.0 and math.isfinite(float(y[0, 5])) and float(y[0, 7]) == 65504.0
-    # GEMM epilogue (fp16 out, + GELU) -- 128 x 128, small-tile and 256 x 256 kernels
-    for M in (256, 2048, 65536):
-        a = torch.full((M, 512), 16.0).half().cuda()
-        w = torch.full((512, 512), 16.0).half().cuda()
-        w[1::2] = -16.0                                                        # odd output columns: -131072
+    # GEMM epilogue (fp16 out, + GELU) -- small-tile (twice), 128 x 128 and 256 x 256 kernels
+    from mmdti_hip import _abi
+    from gemm_plan_helpers import case as plan_case, plan_of
+    for M, K, kernel in ((256, 512, "gemm_small_kernel<false, true>"), (2048, 512, "gemm_small_kernel<false, true>"),
+                         (65536, 512, "gemm_glds_kernel<false, false, 0, true, false>"), (65536, 1024, "gemm_big_kernel<false, false, true, false, false>")):
+        assert plan_of(_abi.lib(), plan_case(M, 512, K, ab16=1, out="f16"))[0] == kernel
+        assert plan_of(_abi.lib(), plan_case(M, 512, K, ab16=1, out="f16", act=ops.ACT_GELU_FWD, aux_out=1))[0] == kernel
+        a = torch.full((M, K), 16.0).half().cuda()
+        w = torch.full((512, K), 16.0).half().cuda()
+        w[1::2] = -16.0                                                        # odd output columns: -131072 (-262144 at K = 1024)
         out = ops.linear_fwd(a, w, None)
         assert out.dtype == torch.float16 and torch.isfinite(out).all()
         assert float(out[:, 0].min()) == 65504.0 and float(out[:, 1].max()) == -65504.0

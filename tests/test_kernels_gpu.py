@@ -1142,6 +1142,15 @@ def test_weight_gradient_carries_the_bias_gradient(ops, rows, N, K):
     """linear_bwd_weight(db=...): dW += dy^T x and db += column sums of dy in ONE pass over dy (an extra MFMA per dy
     fragment against a ones operand in the double-buffered split-K kernel; the column-sum kernel on the other paths).
     Both accumulate (+=).  Shapes: the in_proj gradient of the bench, a smaller one, ragged rows, small / unaligned outputs."""
+    from mmdti_hip import _abi
+    from gemm_plan_helpers import dw_case, plan_of
+    # bare-load shapes (rows % 64 == 0): the double-buffered kernel sums dy itself; the others: register-staged kernel + column-sum pass
+    with_db, without = plan_of(_abi.lib(), dw_case(ops, N, K, rows, db=True)), plan_of(_abi.lib(), dw_case(ops, N, K, rows, db=False))
+    if rows % 64 == 0:
+        assert with_db[0] == "gemm_glds_kernel<true, true, 1, false, false>" and with_db[9] == 1, with_db
+    else:
+        assert with_db[0] == "gemm_bf16_kernel<true, true, false, false, false>" and with_db[9] == 2, with_db
+    assert without[9] == 0 and with_db[5] > 1
     dy = dev(bf(torch.randn(rows, N, generator=G(1))))
     x = dev(bf(torch.randn(rows, K, generator=G(2))))
     dw, db = torch.full((N, K), 0.5, device="cuda"), torch.full((N,), -0.25, device="cuda")
@@ -1165,7 +1174,12 @@ def test_gemm_tall_tiles_match_square_tiles(ops, transB, monkeypatch):
     """M = 256 x 130 rows, N = 512: the shape that switches to 144-row tiles advancing by 130 rows (one round of resident
     workgroups instead of two).  Same numbers as the 128-row tiling, including the fused epilogue and the column sums."""
     import os
+    from mmdti_hip import _abi
+    from gemm_plan_helpers import case as plan_case, plan_of
     M, N, K = 256 * 130, 512, 192
+    for pc in (plan_case(M, N, K, tB=int(transB), bias=1, residual=1, out="f32", colsum=1), plan_case(M, N, K, tB=int(transB), bias=1)):
+        name, gx, gz, block, lds, sk, mstep = plan_of(_abi.lib(), pc)[:7]
+        assert name == "gemm_glds_tall_kernel<%s, false>" % str(transB).lower() and mstep == 130 and gx == 256 * 4, (name, mstep, gx)
     x = dev(bf(torch.randn(M, K, generator=G(1))))
     w = dev(bf(torch.randn(K, N, generator=G(2)))) if transB else dev(bf(torch.randn(N, K, generator=G(2))))
     bias, res = dev(torch.randn(N, generator=G(3))), dev(torch.randn(M, N, generator=G(4)))
@@ -1184,7 +1198,29 @@ def test_gemm_tall_tiles_match_square_tiles(ops, transB, monkeypatch):
     assert torch.isfinite(yb.float()).all()
 
 
-@pytest.mark.parametrize("M,N,K", [(1695, 512, 2048), (1311, 2048, 512), (8, 64, 64), (77, 520, 128), (3000, 1536, 512), (640, 512, 192)])
+SMALL_LAUNCH_SHAPES = [(1695, 512, 2048), (1311, 2048, 512), (8, 64, 64), (77, 520, 128), (3000, 1536, 512), (640, 512, 192)]
+
+
+def _small_launch_variant(M, N, K, transB, small, deep):
+    """the kernel a bare-load forward shape is meant to take under (gemm_small, gemm_deep): 64 x 64 tiles up to 128 tiles of 128 x 128,
+    the four-stage ring up to 256 of them when K has four K-tiles, else the single-buffered kernel"""
+    tiles = -(-M // 128) * -(-N // 128)
+    return ("gemm_small_kernel" if small and tiles <= 128 else
+            "gemm_glds_kernel<false, %s, 2," % str(transB).lower() if deep and tiles <= 256 and K >= 256 else
+            "gemm_glds_kernel<false, %s, 0," % str(transB).lower())
+
+
+def test_gemm_small_launch_shapes_reach_all_three_variants():
+    """(3000, 1536, 512) has 288 tiles and runs the single-buffered kernel under every setting: it is the past-both-limits case.  The
+    next largest, (1311, 2048, 512) with 176 tiles, takes the four-stage ring even under gemm_small.  The other four take the 64 x 64 kernel under gemm_small, and some of them the four-stage ring / the plain kernel with it off."""
+    for transB in (False, True):
+        variants = lambda small, deep: [_small_launch_variant(M, N, K, transB, small, deep) for M, N, K in SMALL_LAUNCH_SHAPES]
+        assert sum(v == "gemm_small_kernel" for v in variants(1, 1)) == 4 and sum(v.endswith(", 2,") for v in variants(1, 1)) == 1
+        assert sum(v.endswith(", 2,") for v in variants(0, 1)) >= 2 and sum(v.endswith(", 0,") for v in variants(0, 1)) >= 2
+        assert all(v.endswith(", 0,") for v in variants(0, 0))
+
+
+@pytest.mark.parametrize("M,N,K", SMALL_LAUNCH_SHAPES)
 @pytest.mark.parametrize("transB", [False, True])
 def test_gemm_small_launch_paths_are_bitwise_the_128_tile_kernel(ops, M, N, K, transB):
     """Small launches (the reference's default batch of 16-32 molecules) take 64 x 64 tiles behind a four-stage LDS-DMA ring
@@ -1192,6 +1228,7 @@ def test_gemm_small_launch_paths_are_bitwise_the_128_tile_kernel(ops, M, N, K, t
     same order as the single-buffered 128 x 128 kernel, so every fused epilogue gives the SAME BITS on all three paths."""
     from mmdti_hip import _abi
     lib = _abi.lib()
+    from gemm_plan_helpers import case as plan_case, plan_of
     x = dev(bf(torch.randn(M, K, generator=G(1))))
     w = dev(bf(torch.randn(K, N, generator=G(2)))) if transB else dev(bf(torch.randn(N, K, generator=G(2))))
     bias, res = dev(torch.randn(N, generator=G(3))), dev(torch.randn(M, N, generator=G(4)))
@@ -1204,6 +1241,10 @@ def test_gemm_small_launch_paths_are_bitwise_the_128_tile_kernel(ops, M, N, K, t
     try:
         for name, (small, deep) in {"small": (1, 1), "deep": (0, 1), "plain": (0, 0)}.items():
             lib.mmdti_set_option(b"gemm_small", small); lib.mmdti_set_option(b"gemm_deep", deep)
+            # the variant this setting is meant to reach (all shapes here are bare-load shapes: K % 64 == 0)
+            want = _small_launch_variant(M, N, K, transB, small, deep)
+            for pc in (plan_case(M, N, K, tB=int(transB), bias=1), plan_case(M, N, K, tB=int(transB), out="f32")):
+                assert plan_of(lib, pc)[0].startswith(want), (name, plan_of(lib, pc))
             outs[name] = []
             for kw in cases:
                 kw = dict(kw)
@@ -1229,6 +1270,15 @@ def test_gemm_ln_fused_matches_gemm_then_layernorm(ops, M, K, R, monkeypatch):
     if R:
         monkeypatch.setenv("MMDTI_GEMM_LN_ROWS", str(R))       # (read once per process: the first parametrisation that sets it wins)
     monkeypatch.setattr(ops, "GEMM_LN_MAX_K", 4096)            # (the product only sends K <= 1024 to the fused kernel: measured)
+    from mmdti_hip import _abi
+    rows_per_tile = _abi.lib()._dll.mmdti_gemm_ln_rows(M)
+    auto = 80 if -(-(-(-M // 80)) // 512) * 5 < -(-(-(-M // 64)) // 512) * 4 else 64
+    # R is forced only if its parametrisation makes the first fused call of the process: MMDTI_GEMM_LN_ROWS is read once, and in file
+    # order (1, 512, 0) reads it unset (so does tests/test_gemm_plan_cpu.py, whose options() writes gemm_ln_rows back to 0) -- then
+    # both forced cases run the automatic choice, as they always have.  The forced values are pinned in test_gemm_plan_cpu.py.
+    assert rows_per_tile in {auto, R or auto}
+    if not R:
+        assert rows_per_tile == (80 if M == 33280 else 64)       # R = 5 at the bench's tower-1 row count, R = 4 on the others
     N = 512
     g = G(M + K)
     x = dev(bf(torch.randn(M, K, generator=g)))
@@ -1418,6 +1468,15 @@ def test_grouped_weight_gradients(ops, rows):
     are exact-size allocations followed by NaN-poisoned neighbours would not matter: they are never addressed)."""
     g = G(11)
     shapes = [(512, 2048), (2048, 512), (1536, 512), (512, 512), (256, 768)]
+    from mmdti_hip import _abi
+    from gemm_plan_helpers import grouped_plan
+    (name, gx, gz, block, lds, sk, atomic, second_pass), _ = grouped_plan(_abi.lib(), shapes, rows)
+    # 64 x 64 tiles up to 4096 rows; above, 256 x 256 tiles with K splits through slabs (K-tail instance for ragged row counts)
+    if rows <= 4096:
+        assert (name, gx, sk) == ("gemm_small_dw_grouped_kernel<3, false>", sum(a * b for a, b in shapes) // 4096, 1)
+    else:
+        assert (name, gx) == ("gemm_big_grouped_kernel<false, %s>" % str(rows % 64 != 0).lower(), sum(a * b for a, b in shapes) // 65536)
+        assert sk > 1 and gz == sk and not atomic and second_pass
     items, refs = [], []
     for i, (no, ni) in enumerate(shapes):
         big = torch.randn(rows, no + 64, generator=g)          # dy as a column slice of a wider buffer (row stride != N_out)
@@ -1460,11 +1519,16 @@ def test_grouped_weight_gradients_small_token_counts_are_reproducible(ops, rows)
         ops.linear_bwd_weight_grouped(items)
         return [(it[2], it[3]) for it in items]
 
+    from gemm_plan_helpers import grouped_plan
+    assert grouped_plan(lib, shapes, rows)[0][0] == "gemm_small_dw_grouped_kernel<3, false>"      # the 64 x 64 kernel ...
     a, b = run(), run()
     for (dwa, dba), (dwb, dbb) in zip(a, b):
         assert torch.equal(dwa, dwb) and (dba is None or torch.equal(dba, dbb))
     try:
         lib.mmdti_set_option(b"gemm_small", 0)
+        (name, gx, gz, block, lds, sk, atomic, second_pass), _ = grouped_plan(lib, shapes, rows)
+        # ... against the 256 x 256 split-K launch with atomics
+        assert (name, gx, atomic, second_pass) == ("gemm_big_grouped_kernel<false, %s>" % str(rows % 64 != 0).lower(), 48, 1, 0)
         c = run()
     finally:
         lib.mmdti_set_option(b"gemm_small", 1)
