@@ -475,6 +475,22 @@ int mmdti_attn_bwd(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16
                    int lddq, int lddk, float scale, float drop_p, unsigned long long seed, unsigned int site,
                    const int* q_off, const int* k_off, const int* k_cnt, int q_rows /* packed sequences, as in the forward; the
                    key-side rows past k_cnt[b] (the representative pad row) receive dk = dv = 0 */);
+/* The same attention for 1 <= Lq, Lk <= 512 (SMILES up to the tokenizer's 512 tokens, mm_model.py:671; 258 atoms x more than 256
+ * tokens in the cross-modal block): arguments, layouts (stats, drow, packed sequences) and numerics of mmdti_attn_fwd / _bwd --
+ * the softmax still runs over the whole row in registers, a row of 24 (Lk <= 384) or 32 sixteen-key tiles, against 384- / 512-row
+ * LDS images (one workgroup per CU).  With Lq, Lk <= 256 they launch what mmdti_attn_fwd / _bwd launch; longer rows add exact
+ * zeros, so without dropout the results on a shared shape are bit-identical.  The dropout counter strides by the padded key
+ * count (16 x tiles): the mask of a (seed, site) is one and the same in the three kernels of this pair, and differs from the
+ * short pair's above 256 keys.  The forward and the backward of one attention must come from the same pair. */
+int mmdti_attn_long_fwd(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                        const float* key_add, void* ctx_bf16, float* stats, int B, int heads, int Lq, int Lk, int head_dim,
+                        int ldq, int ldk, int ldo, float scale, float drop_p, unsigned long long seed, unsigned int site,
+                        const int* q_off, const int* k_off, const int* k_cnt, int q_rows, int ctx_f16);
+int mmdti_attn_long_bwd(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                        const float* key_add, const void* dctx_bf16, const float* stats, float* drow, void* dq_bf16,
+                        void* dk_bf16, void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo,
+                        int lddq, int lddk, float scale, float drop_p, unsigned long long seed, unsigned int site,
+                        const int* q_off, const int* k_off, const int* k_cnt, int q_rows);
 
 /* ---- GELU on bf16 (kept for un-fused call sites) ------------------------------------------- */
 int mmdti_gelu_fwd_bf16(mmdti_stream_t stream, const void* u_bf16, void* y_bf16, long long n);

@@ -1,4 +1,5 @@
-// Fused BERT-style multi-head attention for gfx950 (head_dim 16, 32 or 64, up to 256 queries x 256 keys per head).
+// Fused BERT-style multi-head attention for gfx950 (head_dim 16, 32 or 64; mmdti_attn_*: up to 256 queries x 256 keys per head,
+// mmdti_attn_long_*: up to 512 x 512 -- the same kernels with 24- / 32-tile score rows and 512-row LDS images, see attn_nt).
 //
 // Replaces, for the ChemBERTa tower (HF eager_attention_forward, modeling_roberta.py:158-183, called through
 // mm_model.py:562) and the cross-modal layers (BertCoAttention, mm_module.py:470-514), the chain
@@ -135,11 +136,37 @@ __device__ __forceinline__ void attn_store4(bf16_t* dst, const f32x4& a) {
   pk.y = (uint32_t)f2bf(a[2]) | ((uint32_t)f2bf(a[3]) << 16);
   *reinterpret_cast<uint2*>(dst) = pk;
 }
+// One probability from the saved row statistics (max in base-2 units, 1 / sum): THE expression of the dQ kernel's sweeps (both forms)
+// and of the dK/dV kernel -- their bit-identity rests on it being one.
+__device__ __forceinline__ float attn_prob(float s, float scale2, float ka, float m, float inv) {
+  return __builtin_amdgcn_exp2f(s * scale2 + ka - m) * inv;
+}
 #define ATTN_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
+// Images of more than 256 rows (NT > 16) pass the 64 KiB that a ds_read's immediate offset reaches.  Left alone, the compiler gives
+// every fragment address past it a register of its own, hoists them all out of the query-tile loop and spills them to scratch.  So
+// the second image, and the rows from 256 on of each, are addressed from bases whose distance the compiler does not see (an empty
+// asm on the row count): one more address register per fragment pattern, immediates for the rest.  NT <= 16: nothing changes.
+template <int NT>
+__device__ __forceinline__ int attn_far_rows(int r) {
+  if constexpr (NT > 16) asm volatile("" : "+s"(r));
+  return r;
+}
+#define ATTN_IMG(lo, hi, t) ((t) < 16 ? (lo) : (hi))
 
 // ------------------------------------------------------------------------------------------------------ forward
+// (NT > 16, the long entry points: a row of 24 / 32 score tiles is 96 / 128 registers per lane and the 384- / 512-key image pair
+//  fills most of a CU's LDS, so one workgroup owns the CU: 2 waves per SIMD, a 256-register ceiling)
+//  -- except head_dim 16 with 32 tiles, which the compiler cannot hold in 256: that one instantiation runs 4 waves per workgroup,
+//  one per SIMD, and keeps its overflow in the accumulation registers instead of scratch)
 template <int HD, int NT>
-__global__ __launch_bounds__(512, HD == 16 ? 2 : 4) void attn_fwd_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+constexpr int attn_fwd_threads() { return HD == 16 && NT == 32 ? 256 : 512; }
+template <int HD, int NT>
+constexpr int attn_fwd_min_waves() {      // per SIMD: what the register budget is sized for
+  if (NT <= 16) return HD == 16 ? 2 : 4;
+  return HD == 16 && NT == 32 ? 1 : 2;
+}
+template <int HD, int NT>
+__global__ __launch_bounds__((attn_fwd_threads<HD, NT>()), (attn_fwd_min_waves<HD, NT>())) void attn_fwd_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                        const bf16_t* __restrict__ v, const float* __restrict__ key_add,
                                                        bf16_t* __restrict__ ctx, float* __restrict__ stats, int heads, int Lq,
                                                        int Lk, int ldq, int ldk, int ldo, float scale, uint32_t thresh16,
@@ -147,8 +174,12 @@ __global__ __launch_bounds__(512, HD == 16 ? 2 : 4) void attn_fwd_kernel(const b
   extern __shared__ __attribute__((aligned(16))) unsigned char attn_smem[];
   constexpr int STR = AttnShape<HD>::STR, KC = AttnShape<HD>::KC, NB = AttnShape<HD>::NB, NP = NT * 16;
   bf16_t* sK = reinterpret_cast<bf16_t*>(attn_smem);
-  bf16_t* sV = sK + NP * STR;
+  bf16_t* sV = sK + attn_far_rows<NT>(NP) * STR;
   float* sKA = reinterpret_cast<float*>(sV + NP * STR);
+  const int hi = attn_far_rows<NT>(256);
+  const bf16_t* sKh = sK + hi * STR;
+  const bf16_t* sVh = sV + hi * STR;
+  const float* sKAh = sKA + hi;
   const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const AttnSeq sq = attn_seq(vl, b, Lq, Lk);
@@ -173,8 +204,8 @@ __global__ __launch_bounds__(512, HD == 16 ? 2 : 4) void attn_fwd_kernel(const b
     for (int t = 0; t < NT; ++t) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int c = 0; c < KC; ++c) acc = ATTN_MFMA(attn_frag_rm<HD>(sK, t * 16, c, lane), qf[c], acc);
-      const f32x4 ka = *reinterpret_cast<const f32x4*>(&sKA[t * 16 + 4 * g]);
+      for (int c = 0; c < KC; ++c) acc = ATTN_MFMA(attn_frag_rm<HD>(ATTN_IMG(sK, sKh, t), (t & 15) * 16, c, lane), qf[c], acc);
+      const f32x4 ka = *reinterpret_cast<const f32x4*>(&ATTN_IMG(sKA, sKAh, t)[(t & 15) * 16 + 4 * g]);
       acc = acc * scale2 + ka;     // (vector form: two v_pk_fma_f32)
       m = fmaxf(fmaxf(m, fmaxf(acc[0], acc[1])), fmaxf(acc[2], acc[3]));
       S[t] = acc;
@@ -219,7 +250,8 @@ __global__ __launch_bounds__(512, HD == 16 ? 2 : 4) void attn_fwd_kernel(const b
       }
       const bf16x8 pf = attn_pack(p0, p1);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) o[nb] = ATTN_MFMA(attn_frag_tr<HD>(sV, 32 * u, 32 * u + 16, nb * 16, lane), pf, o[nb]);
+      for (int nb = 0; nb < NB; ++nb)
+        o[nb] = ATTN_MFMA(attn_frag_tr<HD>(ATTN_IMG(sV, sVh, 2 * u), 32 * (u & 7), 32 * (u & 7) + 16, nb * 16, lane), pf, o[nb]);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (qv) {
@@ -241,7 +273,7 @@ __global__ __launch_bounds__(512, HD == 16 ? 2 : 4) void attn_fwd_kernel(const b
 
 // ------------------------------------------------------------------------------------------------------ backward: dQ
 template <int HD, int NT>
-__global__ __launch_bounds__(512) void attn_bwd_q_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+__global__ __launch_bounds__(NT > 16 ? 1024 : 512) void attn_bwd_q_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                          const bf16_t* __restrict__ v, const float* __restrict__ key_add,
                                                          const bf16_t* __restrict__ dout, const float* __restrict__ stats,
                                                          bf16_t* __restrict__ dq, float* __restrict__ drow, int heads, int Lq,
@@ -277,58 +309,112 @@ __global__ __launch_bounds__(512) void attn_bwd_q_kernel(const bf16_t* __restric
     float2 st = make_float2(0.f, 0.f);
     if (qv) st = *reinterpret_cast<const float2*>(stats + attn_stat_row(vl, sq, bh, h, Lq, qi) * 2);
     const uint32_t t8 = thresh16 ? attn_row_t8(rkey, (uint32_t)qi, thresh16) : 0u;
-    // sweep 1: probabilities (kept in registers, sign bit = "dropped") and the row term D = sum_j dP'_ij p_ij
-    f32x4 P[NT];
-    float dsum = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        acc = ATTN_MFMA(attn_frag_rm<HD>(sK, t * 16, c, lane), qf[c], acc);
-        dacc = ATTN_MFMA(attn_frag_rm<HD>(sV, t * 16, c, lane), dof[c], dacc);
-      }
-      const f32x4 ka = *reinterpret_cast<const f32x4*>(&sKA[t * 16 + 4 * g]);
-      // (the quad's four uniform bytes are compared where they are used -- one byte compare + select per element, as in the forward;
-      //  building a 4-bit mask first and testing its bits cost three more instructions per element and spilled compare results.
-      //  Without dropout t8 == 0: every byte keeps.)
-      const uint32_t hw = thresh16 ? attn_hash24(rkey, (uint32_t)qi * (NP / 4) + t * 4 + g) : 0u;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(acc[r] * scale2 + ka[r] - st.x) * st.y;
-        const bool keep = ((hw >> (8 * r)) & 0xffu) >= t8;
-        dsum += keep ? dacc[r] * p : 0.f;
-        acc[r] = keep ? p : -p;
-      }
-      P[t] = acc;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    dsum *= dscale;
-    dsum += __shfl_xor(dsum, 16, 64);
-    dsum += __shfl_xor(dsum, 32, 64);
-    if (g == 0 && qv) drow[attn_stat_row(vl, sq, bh, h, Lq, qi)] = dsum;
-    // sweep 2: dP again (two MFMAs per tile are cheaper than 64 more live registers), dS, dQ^T += K^T.dS^T
     f32x4 da[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) da[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (NT <= 16) {
+      // sweep 1: probabilities (kept in registers, sign bit = "dropped") and the row term D = sum_j dP'_ij p_ij
+      f32x4 P[NT];
+      float dsum = 0.f;
 #pragma unroll
-    for (int u = 0; u < NT / 2; ++u) {
-      f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < NT; ++t) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        s0 = ATTN_MFMA(attn_frag_rm<HD>(sV, 32 * u, c, lane), dof[c], s0);
-        s1 = ATTN_MFMA(attn_frag_rm<HD>(sV, 32 * u + 16, c, lane), dof[c], s1);
+        for (int c = 0; c < KC; ++c) {
+          acc = ATTN_MFMA(attn_frag_rm<HD>(sK, t * 16, c, lane), qf[c], acc);
+          dacc = ATTN_MFMA(attn_frag_rm<HD>(sV, t * 16, c, lane), dof[c], dacc);
+        }
+        const f32x4 ka = *reinterpret_cast<const f32x4*>(&sKA[t * 16 + 4 * g]);
+        // (the quad's four uniform bytes are compared where they are used -- one byte compare + select per element, as in the forward;
+        //  building a 4-bit mask first and testing its bits cost three more instructions per element and spilled compare results.
+        //  Without dropout t8 == 0: every byte keeps.)
+        const uint32_t hw = thresh16 ? attn_hash24(rkey, (uint32_t)qi * (NP / 4) + t * 4 + g) : 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = attn_prob(acc[r], scale2, ka[r], st.x, st.y);
+          const bool keep = ((hw >> (8 * r)) & 0xffu) >= t8;
+          dsum += keep ? dacc[r] * p : 0.f;
+          acc[r] = keep ? p : -p;
+        }
+        P[t] = acc;
+        __builtin_amdgcn_sched_barrier(0);
       }
+      dsum *= dscale;
+      dsum += __shfl_xor(dsum, 16, 64);
+      dsum += __shfl_xor(dsum, 32, 64);
+      if (g == 0 && qv) drow[attn_stat_row(vl, sq, bh, h, Lq, qi)] = dsum;
+      // sweep 2: dP again (two MFMAs per tile are cheaper than 64 more live registers), dS, dQ^T += K^T.dS^T
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p0 = P[2 * u][r], p1 = P[2 * u + 1][r];
-        s0[r] = fabsf(p0) * ((__float_as_uint(p0) >> 31 ? 0.f : s0[r] * dscale) - dsum) * scale;
-        s1[r] = fabsf(p1) * ((__float_as_uint(p1) >> 31 ? 0.f : s1[r] * dscale) - dsum) * scale;
+      for (int u = 0; u < NT / 2; ++u) {
+        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+          s0 = ATTN_MFMA(attn_frag_rm<HD>(sV, 32 * u, c, lane), dof[c], s0);
+          s1 = ATTN_MFMA(attn_frag_rm<HD>(sV, 32 * u + 16, c, lane), dof[c], s1);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p0 = P[2 * u][r], p1 = P[2 * u + 1][r];
+          s0[r] = fabsf(p0) * ((__float_as_uint(p0) >> 31 ? 0.f : s0[r] * dscale) - dsum) * scale;
+          s1[r] = fabsf(p1) * ((__float_as_uint(p1) >> 31 ? 0.f : s1[r] * dscale) - dsum) * scale;
+        }
+        const bf16x8 sf = attn_pack(s0, s1);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) da[nb] = ATTN_MFMA(attn_frag_tr<HD>(sK, 32 * u, 32 * u + 16, nb * 16, lane), sf, da[nb]);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      const bf16x8 sf = attn_pack(s0, s1);
+    } else {
+      // NT > 16 (mmdti_attn_long_bwd): a row of 24 / 32 probability tiles next to the rest of this kernel does not fit 256 registers, so
+      // nothing is kept: sweep 2 computes K.Q^T and the probabilities again -- the same expressions on the same operands in the same
+      // order, hence the same values as above.  Both sweeps are real loops (dynamic LDS addresses; unrolled, the compiler would
+      // merge the two sweeps' products and keep them all live).
+      float dsum = 0.f;
+#pragma unroll 1
+      for (int t = 0; t < NT; ++t) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) da[nb] = ATTN_MFMA(attn_frag_tr<HD>(sK, 32 * u, 32 * u + 16, nb * 16, lane), sf, da[nb]);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int c = 0; c < KC; ++c) {
+          acc = ATTN_MFMA(attn_frag_rm<HD>(sK, t * 16, c, lane), qf[c], acc);
+          dacc = ATTN_MFMA(attn_frag_rm<HD>(sV, t * 16, c, lane), dof[c], dacc);
+        }
+        const f32x4 ka = *reinterpret_cast<const f32x4*>(&sKA[t * 16 + 4 * g]);
+        const uint32_t hw = thresh16 ? attn_hash24(rkey, (uint32_t)qi * (NP / 4) + t * 4 + g) : 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = attn_prob(acc[r], scale2, ka[r], st.x, st.y);
+          const bool keep = ((hw >> (8 * r)) & 0xffu) >= t8;
+          dsum += keep ? dacc[r] * p : 0.f;
+        }
+      }
+      dsum *= dscale;
+      dsum += __shfl_xor(dsum, 16, 64);
+      dsum += __shfl_xor(dsum, 32, 64);
+      if (g == 0 && qv) drow[attn_stat_row(vl, sq, bh, h, Lq, qi)] = dsum;
+#pragma unroll 1
+      for (int u = 0; u < NT / 2; ++u) {
+        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f}, s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+          a0 = ATTN_MFMA(attn_frag_rm<HD>(sK, 32 * u, c, lane), qf[c], a0);
+          a1 = ATTN_MFMA(attn_frag_rm<HD>(sK, 32 * u + 16, c, lane), qf[c], a1);
+          s0 = ATTN_MFMA(attn_frag_rm<HD>(sV, 32 * u, c, lane), dof[c], s0);
+          s1 = ATTN_MFMA(attn_frag_rm<HD>(sV, 32 * u + 16, c, lane), dof[c], s1);
+        }
+        const f32x4 ka0 = *reinterpret_cast<const f32x4*>(&sKA[32 * u + 4 * g]);
+        const f32x4 ka1 = *reinterpret_cast<const f32x4*>(&sKA[32 * u + 16 + 4 * g]);
+        const uint32_t q4 = (uint32_t)qi * (NP / 4) + (2 * u) * 4 + g;
+        const uint32_t h0 = thresh16 ? attn_hash24(rkey, q4) : 0u, h1 = thresh16 ? attn_hash24(rkey, q4 + 4) : 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p0 = attn_prob(a0[r], scale2, ka0[r], st.x, st.y);
+          const float p1 = attn_prob(a1[r], scale2, ka1[r], st.x, st.y);
+          s0[r] = p0 * ((((h0 >> (8 * r)) & 0xffu) >= t8 ? s0[r] * dscale : 0.f) - dsum) * scale;
+          s1[r] = p1 * ((((h1 >> (8 * r)) & 0xffu) >= t8 ? s1[r] * dscale : 0.f) - dsum) * scale;
+        }
+        const bf16x8 sf = attn_pack(s0, s1);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) da[nb] = ATTN_MFMA(attn_frag_tr<HD>(sK, 32 * u, 32 * u + 16, nb * 16, lane), sf, da[nb]);
+      }
     }
     if (qv) {
       bf16_t* dst = dq + ((long long)sq.q0 + qi) * lddq + h * HD + 4 * g;
@@ -428,7 +514,7 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_kv_kernel(const bf16_t* __res
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(acc[r] * scale2 + ka - m4[r]) * i4[r];
+          const float p = attn_prob(acc[r], scale2, ka, m4[r], i4[r]);
           const bool keep = (kb >> r) & 1u;
           const float w = keep ? dacc[r] * dscale : 0.f;     // (dscale = 1 without dropout)
           pd[hf][r] = keep ? p * dscale : 0.f;
@@ -455,25 +541,35 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_kv_kernel(const bf16_t* __res
 }
 
 static inline uint32_t thresh16_of(float p) { return dropout_thresh8(p); }
-static inline int attn_nt(int Lk) { return Lk <= 160 ? 10 : 16; }
-// largest dynamic LDS any launch of these kernels asks for: 2 x 256 rows x (64+16) bf16 + 3 x 256 floats
+// 16-key tiles of a score row (the forward / dQ kernels' NT; times 16, the key stride of the dropout counter).  Up to 256 keys: the
+// two sizes of mmdti_attn_*; 24 and 32 tiles are reached through mmdti_attn_long_* only.
+static inline int attn_nt(int Lk) { return Lk <= 160 ? 10 : Lk <= 256 ? 16 : Lk <= 384 ? 24 : 32; }
+// largest dynamic LDS any launch of mmdti_attn_* asks for: 2 x 256 rows x (64+16) bf16 + 3 x 256 floats
 constexpr size_t smem_max = (size_t)2 * 256 * 80 * 2 + 4 * 256 * 4;
+// ... and of mmdti_attn_long_*: the dK/dV kernel's Q + dO images of 512 rows x (64+8) bf16 + four 512-float row vectors = 155 648 B
+// (forward / dQ: K + V images + 512 floats of key mask = 149 504 B) of the CU's 160 KiB
+constexpr size_t smem_max_long = (size_t)2 * 512 * 72 * 2 + 4 * 512 * 4;
+constexpr int ATTN_MAX_LEN = 256, ATTN_LONG_MAX_LEN = 512;
 
+// (the attribute is raised per kernel, once per size: a process that never calls the long entry points sets what it always set)
+// (*have is a plain per-instantiation static, as the flag before it: one value for all devices, no synchronisation -- launches come from
+//  one host thread per process here; a second thread could read it before hipFuncSetAttribute has returned)
 template <typename K>
-static int attn_set_smem(K kern, size_t smem) {
-  if (smem <= 65536) return MMDTI_OK;
+static int attn_set_smem(K kern, size_t smem, size_t* have) {
+  if (*have >= smem) return MMDTI_OK;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
     set_error("attn: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem);
     return MMDTI_ERR_LAUNCH;
   }
+  *have = smem;
   return MMDTI_OK;
 }
 
-static int attn_check(const char* name, const void* q, const void* k, const void* v, int B, int heads, int Lq, int Lk, int hd,
+static int attn_check(const char* name, int max_len, const void* q, const void* k, const void* v, int B, int heads, int Lq, int Lk, int hd,
                       int ldq, int ldk, float drop_p) {
   MMDTI_REQUIRE(q && k && v && B > 0 && heads > 0 && Lq > 0 && Lk > 0, "%s: bad arguments", name);
   MMDTI_REQUIRE(hd == 16 || hd == 32 || hd == 64, "%s: head_dim must be 16, 32 or 64 (got %d)", name, hd);
-  MMDTI_REQUIRE(Lq <= 256 && Lk <= 256, "%s: at most 256 queries / keys per head (got %d / %d)", name, Lq, Lk);
+  MMDTI_REQUIRE(Lq <= max_len && Lk <= max_len, "%s: at most %d queries / keys per head (got %d / %d)", name, max_len, Lq, Lk);
   MMDTI_REQUIRE(ldq >= heads * hd && ldk >= heads * hd && ldq % 8 == 0 && ldk % 8 == 0, "%s: row strides must cover heads*head_dim and be multiples of 8", name);
   MMDTI_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v), "%s: 16-byte alignment required", name);
   MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: dropout p out of range", name);
@@ -487,6 +583,94 @@ static int attn_check_varlen(const char* name, const float* key_add, const int* 
   return MMDTI_OK;
 }
 
+// One body for mmdti_attn_fwd (max_len 256) and mmdti_attn_long_fwd (512): up to 256 keys both launch the same instantiation with
+// the same arguments; the 24- and 32-tile instantiations exist for the long entry point only.
+static int attn_fwd_launch(const char* name, int max_len, mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                           const float* key_add, void* ctx_bf16, float* stats, int B, int heads, int Lq, int Lk, int head_dim, int ldq,
+                           int ldk, int ldo, float scale, float drop_p, unsigned long long seed, unsigned int site, const int* q_off,
+                           const int* k_off, const int* k_cnt, int q_rows, int ctx_f16) {
+  if (int e = attn_check(name, max_len, q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
+  if (int e = attn_check_varlen(name, key_add, q_off, k_off, k_cnt, q_rows)) return e;
+  const AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
+  MMDTI_REQUIRE(ctx_bf16 && stats && ldo >= heads * head_dim && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(ctx_bf16) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(stats) & 7) == 0, "%s: bad output arguments", name);
+  const uint32_t th = thresh16_of(drop_p);
+  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  const int nt = attn_nt(Lk);
+  const size_t smem = (size_t)2 * nt * 16 * (head_dim + 8) * 2 + (size_t)nt * 16 * 4;
+#define ATTN_F(HD, NT)                                                                                                   \
+  do {                                                                                                                   \
+    static size_t attr_have = 65536;                                                                                     \
+    if (int e = attn_set_smem(attn_fwd_kernel<HD, NT>, NT > 16 ? smem_max_long : smem_max, &attr_have)) return e;        \
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, NT>), dim3(B * heads), dim3(attn_fwd_threads<HD, NT>()), smem, (hipStream_t)stream,                 \
+                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add, (bf16_t*)ctx_bf16,  \
+                       stats, heads, Lq, Lk, ldq, ldk, ldo, scale, th, sc, (uint64_t)seed, (uint32_t)site, vl, ctx_f16); \
+  } while (0)
+#define ATTN_F_NT(HD)                                                                                                    \
+  do {                                                                                                                   \
+    if (nt == 10) ATTN_F(HD, 10); else if (nt == 16) ATTN_F(HD, 16); else if (nt == 24) ATTN_F(HD, 24); else ATTN_F(HD, 32); \
+  } while (0)
+  if (head_dim == 64) ATTN_F_NT(64); else if (head_dim == 32) ATTN_F_NT(32); else ATTN_F_NT(16);
+#undef ATTN_F_NT
+#undef ATTN_F
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+static int attn_bwd_launch(const char* name, int max_len, mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                           const float* key_add, const void* dctx_bf16, const float* stats, float* drow, void* dq_bf16, void* dk_bf16,
+                           void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo, int lddq, int lddk,
+                           float scale, float drop_p, unsigned long long seed, unsigned int site, const int* q_off, const int* k_off,
+                           const int* k_cnt, int q_rows) {
+  if (int e = attn_check(name, max_len, q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
+  if (int e = attn_check_varlen(name, key_add, q_off, k_off, k_cnt, q_rows)) return e;
+  const AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
+  MMDTI_REQUIRE(dctx_bf16 && stats && drow && dq_bf16 && dk_bf16 && dv_bf16, "%s: null argument", name);
+  MMDTI_REQUIRE(ldo >= heads * head_dim && ldo % 8 == 0 && aligned16(dctx_bf16), "%s: dctx stride/alignment", name);
+  MMDTI_REQUIRE(lddq >= heads * head_dim && lddk >= heads * head_dim && lddq % 4 == 0 && lddk % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(dq_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(dk_bf16) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(dv_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
+                "%s: output stride/alignment", name);
+  const uint32_t th = thresh16_of(drop_p);
+  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  const int nt = attn_nt(Lk);
+  const size_t smem_q = (size_t)2 * nt * 16 * (head_dim + 8) * 2 + (size_t)nt * 16 * 4;
+  const int lqp = ((Lq + 31) / 32) * 32;
+  const size_t smem_kv = (size_t)2 * lqp * (head_dim + 8) * 2 + (size_t)4 * lqp * 4;
+  // (dQ: 4 waves up to 16 tiles; with 24 / 32 tiles the image pair leaves room for one workgroup per CU, which then brings 16 --
+  //  that form keeps no probability row and needs about 100 registers)
+#define ATTN_BQ(HD, NT)                                                                                                    \
+  do {                                                                                                                     \
+    static size_t attr_have = 65536;                                                                                       \
+    if (int e = attn_set_smem(attn_bwd_q_kernel<HD, NT>, NT > 16 ? smem_max_long : smem_max, &attr_have)) return e;        \
+    hipLaunchKernelGGL((attn_bwd_q_kernel<HD, NT>), dim3(B * heads), dim3(NT > 16 ? 1024 : 256), smem_q, (hipStream_t)stream, \
+                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add,                       \
+                       (const bf16_t*)dctx_bf16, stats, (bf16_t*)dq_bf16, drow, heads, Lq, Lk, ldq, ldk, ldo, lddq, scale, \
+                       th, sc, (uint64_t)seed, (uint32_t)site, vl);                                                        \
+  } while (0)
+#define ATTN_BQ_NT(HD)                                                                                                     \
+  do {                                                                                                                     \
+    if (nt == 10) ATTN_BQ(HD, 10); else if (nt == 16) ATTN_BQ(HD, 16); else if (nt == 24) ATTN_BQ(HD, 24); else ATTN_BQ(HD, 32); \
+  } while (0)
+#define ATTN_BKV(HD)                                                                                                       \
+  do {                                                                                                                     \
+    static size_t attr_have = 65536;                                                                                       \
+    if (int e = attn_set_smem(attn_bwd_kv_kernel<HD>, smem_kv > smem_max ? smem_max_long : smem_max, &attr_have)) return e; \
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<HD>), dim3(B * heads), dim3(512), smem_kv, (hipStream_t)stream,                 \
+                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add,                       \
+                       (const bf16_t*)dctx_bf16, stats, drow, (bf16_t*)dk_bf16, (bf16_t*)dv_bf16, heads, Lq, Lk, ldq, ldk, \
+                       ldo, lddk, scale, th, sc, (uint64_t)seed, (uint32_t)site, nt * 16, vl);                             \
+  } while (0)
+  if (head_dim == 64) ATTN_BQ_NT(64); else if (head_dim == 32) ATTN_BQ_NT(32); else ATTN_BQ_NT(16);
+  MMDTI_LAUNCH_CHECK();
+  if (head_dim == 64) ATTN_BKV(64); else if (head_dim == 32) ATTN_BKV(32); else ATTN_BKV(16);
+#undef ATTN_BQ_NT
+#undef ATTN_BQ
+#undef ATTN_BKV
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
 }  // namespace mmdti
 MMDTI_DEFINE_SALT_PULL(attn)
 using namespace mmdti;
@@ -495,29 +679,8 @@ extern "C" int mmdti_attn_fwd(mmdti_stream_t stream, const void* q_bf16, const v
                               const float* key_add, void* ctx_bf16, float* stats, int B, int heads, int Lq, int Lk,
                               int head_dim, int ldq, int ldk, int ldo, float scale, float drop_p, unsigned long long seed,
                               unsigned int site, const int* q_off, const int* k_off, const int* k_cnt, int q_rows, int ctx_f16) {
-  if (int e = attn_check("attn_fwd", q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
-  if (int e = attn_check_varlen("attn_fwd", key_add, q_off, k_off, k_cnt, q_rows)) return e;
-  const AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
-  MMDTI_REQUIRE(ctx_bf16 && stats && ldo >= heads * head_dim && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(ctx_bf16) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(stats) & 7) == 0, "attn_fwd: bad output arguments");
-  const uint32_t th = thresh16_of(drop_p);
-  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  const int nt = attn_nt(Lk);
-  const size_t smem = (size_t)2 * nt * 16 * (head_dim + 8) * 2 + (size_t)nt * 16 * 4;
-#define ATTN_F(HD, NT)                                                                                                   \
-  do {                                                                                                                   \
-    static bool attr_done = false;                                                                                       \
-    if (!attr_done) { if (int e = attn_set_smem(attn_fwd_kernel<HD, NT>, smem_max)) return e; attr_done = true; }        \
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, NT>), dim3(B * heads), dim3(512), smem, (hipStream_t)stream,                 \
-                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add, (bf16_t*)ctx_bf16,  \
-                       stats, heads, Lq, Lk, ldq, ldk, ldo, scale, th, sc, (uint64_t)seed, (uint32_t)site, vl, ctx_f16); \
-  } while (0)
-  if (head_dim == 64)      { if (nt == 10) ATTN_F(64, 10); else ATTN_F(64, 16); }
-  else if (head_dim == 32) { if (nt == 10) ATTN_F(32, 10); else ATTN_F(32, 16); }
-  else                     { if (nt == 10) ATTN_F(16, 10); else ATTN_F(16, 16); }
-#undef ATTN_F
-  MMDTI_LAUNCH_CHECK();
-  return MMDTI_OK;
+  return attn_fwd_launch("attn_fwd", ATTN_MAX_LEN, stream, q_bf16, k_bf16, v_bf16, key_add, ctx_bf16, stats, B, heads, Lq, Lk, head_dim, ldq,
+                         ldk, ldo, scale, drop_p, seed, site, q_off, k_off, k_cnt, q_rows, ctx_f16);
 }
 
 extern "C" int mmdti_attn_bwd(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
@@ -525,46 +688,24 @@ extern "C" int mmdti_attn_bwd(mmdti_stream_t stream, const void* q_bf16, const v
                               void* dk_bf16, void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk,
                               int ldo, int lddq, int lddk, float scale, float drop_p, unsigned long long seed,
                               unsigned int site, const int* q_off, const int* k_off, const int* k_cnt, int q_rows) {
-  if (int e = attn_check("attn_bwd", q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
-  if (int e = attn_check_varlen("attn_bwd", key_add, q_off, k_off, k_cnt, q_rows)) return e;
-  const AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
-  MMDTI_REQUIRE(dctx_bf16 && stats && drow && dq_bf16 && dk_bf16 && dv_bf16, "attn_bwd: null argument");
-  MMDTI_REQUIRE(ldo >= heads * head_dim && ldo % 8 == 0 && aligned16(dctx_bf16), "attn_bwd: dctx stride/alignment");
-  MMDTI_REQUIRE(lddq >= heads * head_dim && lddk >= heads * head_dim && lddq % 4 == 0 && lddk % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(dq_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(dk_bf16) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(dv_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
-                "attn_bwd: output stride/alignment");
-  const uint32_t th = thresh16_of(drop_p);
-  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  const int nt = attn_nt(Lk);
-  const size_t smem_q = (size_t)2 * nt * 16 * (head_dim + 8) * 2 + (size_t)nt * 16 * 4;
-  const int lqp = ((Lq + 31) / 32) * 32;
-  const size_t smem_kv = (size_t)2 * lqp * (head_dim + 8) * 2 + (size_t)4 * lqp * 4;
-#define ATTN_BQ(HD, NT)                                                                                                    \
-  do {                                                                                                                     \
-    static bool attr_done = false;                                                                                         \
-    if (!attr_done) { if (int e = attn_set_smem(attn_bwd_q_kernel<HD, NT>, smem_max)) return e; attr_done = true; }        \
-    hipLaunchKernelGGL((attn_bwd_q_kernel<HD, NT>), dim3(B * heads), dim3(256), smem_q, (hipStream_t)stream,               \
-                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add,                       \
-                       (const bf16_t*)dctx_bf16, stats, (bf16_t*)dq_bf16, drow, heads, Lq, Lk, ldq, ldk, ldo, lddq, scale, \
-                       th, sc, (uint64_t)seed, (uint32_t)site, vl);                                                        \
-  } while (0)
-#define ATTN_BKV(HD)                                                                                                       \
-  do {                                                                                                                     \
-    static bool attr_done = false;                                                                                         \
-    if (!attr_done) { if (int e = attn_set_smem(attn_bwd_kv_kernel<HD>, smem_max)) return e; attr_done = true; }           \
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<HD>), dim3(B * heads), dim3(512), smem_kv, (hipStream_t)stream,                 \
-                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add,                       \
-                       (const bf16_t*)dctx_bf16, stats, drow, (bf16_t*)dk_bf16, (bf16_t*)dv_bf16, heads, Lq, Lk, ldq, ldk, \
-                       ldo, lddk, scale, th, sc, (uint64_t)seed, (uint32_t)site, nt * 16, vl);                             \
-  } while (0)
-  if (head_dim == 64)      { if (nt == 10) ATTN_BQ(64, 10); else ATTN_BQ(64, 16); }
-  else if (head_dim == 32) { if (nt == 10) ATTN_BQ(32, 10); else ATTN_BQ(32, 16); }
-  else                     { if (nt == 10) ATTN_BQ(16, 10); else ATTN_BQ(16, 16); }
-  MMDTI_LAUNCH_CHECK();
-  if (head_dim == 64) ATTN_BKV(64); else if (head_dim == 32) ATTN_BKV(32); else ATTN_BKV(16);
-#undef ATTN_BQ
-#undef ATTN_BKV
-  MMDTI_LAUNCH_CHECK();
-  return MMDTI_OK;
+  return attn_bwd_launch("attn_bwd", ATTN_MAX_LEN, stream, q_bf16, k_bf16, v_bf16, key_add, dctx_bf16, stats, drow, dq_bf16, dk_bf16, dv_bf16,
+                         B, heads, Lq, Lk, head_dim, ldq, ldk, ldo, lddq, lddk, scale, drop_p, seed, site, q_off, k_off, k_cnt, q_rows);
+}
+
+extern "C" int mmdti_attn_long_fwd(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                                   const float* key_add, void* ctx_bf16, float* stats, int B, int heads, int Lq, int Lk,
+                                   int head_dim, int ldq, int ldk, int ldo, float scale, float drop_p, unsigned long long seed,
+                                   unsigned int site, const int* q_off, const int* k_off, const int* k_cnt, int q_rows, int ctx_f16) {
+  return attn_fwd_launch("attn_long_fwd", ATTN_LONG_MAX_LEN, stream, q_bf16, k_bf16, v_bf16, key_add, ctx_bf16, stats, B, heads, Lq, Lk,
+                         head_dim, ldq, ldk, ldo, scale, drop_p, seed, site, q_off, k_off, k_cnt, q_rows, ctx_f16);
+}
+
+extern "C" int mmdti_attn_long_bwd(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                                   const float* key_add, const void* dctx_bf16, const float* stats, float* drow, void* dq_bf16,
+                                   void* dk_bf16, void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk,
+                                   int ldo, int lddq, int lddk, float scale, float drop_p, unsigned long long seed,
+                                   unsigned int site, const int* q_off, const int* k_off, const int* k_cnt, int q_rows) {
+  return attn_bwd_launch("attn_long_bwd", ATTN_LONG_MAX_LEN, stream, q_bf16, k_bf16, v_bf16, key_add, dctx_bf16, stats, drow, dq_bf16,
+                         dk_bf16, dv_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, ldo, lddq, lddk, scale, drop_p, seed, site, q_off, k_off,
+                         k_cnt, q_rows);
 }

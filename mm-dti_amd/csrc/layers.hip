@@ -165,6 +165,21 @@ extern "C" int mmdti_unimol_layer_bwd(mmdti_stream_t stream, int M, int B, int N
                                ws, ws_bytes, fwd_f16, nullptr, nullptr, nullptr);
 }
 
+/* The fused attention of the BERT-style sequencers below: mmdti_attn_* up to 256 queries x 256 keys, mmdti_attn_long_* beyond (the rule of
+ * the host's ops.attn_dispatch, so that a sequenced layer launches what the op-by-op path launches).  Forward and backward of a layer
+ * see the same Lq / Lk, hence the same pair -- and the same dropout mask. */
+static inline bool attn_is_long(int Lq, int Lk) { return (Lq > Lk ? Lq : Lk) > 256; }
+template <typename... A>
+static int attn_pair_fwd(mmdti_stream_t stream, const void* q, const void* k, const void* v, const float* key_add, void* ctx, float* stats, int B,
+                         int heads, int Lq, int Lk, A... rest) {
+  return (attn_is_long(Lq, Lk) ? mmdti_attn_long_fwd : mmdti_attn_fwd)(stream, q, k, v, key_add, ctx, stats, B, heads, Lq, Lk, rest...);
+}
+template <typename... A>
+static int attn_pair_bwd(mmdti_stream_t stream, const void* q, const void* k, const void* v, const float* key_add, const void* dctx,
+                         const float* stats, float* drow, void* dq, void* dk, void* dv, int B, int heads, int Lq, int Lk, A... rest) {
+  return (attn_is_long(Lq, Lk) ? mmdti_attn_long_bwd : mmdti_attn_bwd)(stream, q, k, v, key_add, dctx, stats, drow, dq, dk, dv, B, heads, Lq, Lk, rest...);
+}
+
 /* The CROSS-attention variant of the same layer (BertCrossAttentionLayer, mm_module.py:615-626 through :663-677: the queries come from
  * s1, keys and values from s2): the six forward launches behind one call -- query projection, fused key | value projection, fused
  * attention (Lq queries x Lk keys per sequence; packed: q_off / k_off / k_cnt as mmdti_attn_fwd), output.dense + residual + LayerNorm,
@@ -187,7 +202,7 @@ extern "C" int mmdti_bert_cross_layer_fwd(mmdti_stream_t stream, int Mq, int Mk,
   const char* kp = reinterpret_cast<const char*>(kv);
   if (int e = fwd_gemm(stream, s1_16, D, w_q, D, b_q, q, Mq, D, D, MMDTI_ACT_NONE, nullptr, nullptr, MMDTI_DT_BF16 | ab, 0.f, 0ull, 0u)) return e;
   if (int e = fwd_gemm(stream, s2_16, D, w_kv, D, b_kv, kv, Mk, 2 * D, D, MMDTI_ACT_NONE, nullptr, nullptr, MMDTI_DT_BF16 | ab, 0.f, 0ull, 0u)) return e;
-  if (int e = mmdti_attn_fwd(stream, q, kp, kp + (size_t)D * 2, key_add, ctx, stats, B, heads, Lq, Lk, hd, D, 2 * D, D, scale, p_att, seed, site_att, q_off,
+  if (int e = attn_pair_fwd(stream, q, kp, kp + (size_t)D * 2, key_add, ctx, stats, B, heads, Lq, Lk, hd, D, 2 * D, D, scale, p_att, seed, site_att, q_off,
                              k_off, k_cnt, q_rows, fwd_f16 ? 1 : 0))
     return e;
   if (int e = closer(stream, ctx, w_o, b_o, s1_32, Mq, D, D, p_hid, seed, site_o, y, g_ln1, bt_ln1, eps, a32, a16, am, ar, ln_max_k, fwd_f16)) return e;
@@ -233,7 +248,7 @@ extern "C" int mmdti_bert_cross_layer_bwd(mmdti_stream_t stream, int Mq, int Mk,
   if (int e = dx_gemm(stream, dyb, D, w_o, D, dctx, Mq, D, D, MMDTI_ACT_NONE, nullptr, 0)) return e;
   const char* kp = reinterpret_cast<const char*>(kv);
   char* dkp = reinterpret_cast<char*>(dkv);
-  if (int e = mmdti_attn_bwd(stream, q, kp, kp + (size_t)D * 2, key_add, dctx, stats, drow, dq, dkp, dkp + (size_t)D * 2, B, heads, Lq, Lk, hd, D, 2 * D, D, D,
+  if (int e = attn_pair_bwd(stream, q, kp, kp + (size_t)D * 2, key_add, dctx, stats, drow, dq, dkp, dkp + (size_t)D * 2, B, heads, Lq, Lk, hd, D, 2 * D, D, D,
                              2 * D, scale, p_att, seed, site_att, q_off, k_off, k_cnt, q_rows))
     return e;
   // ds1 += dq . W_q   (fp32, beta = 1);  ds2 = dkv . W_kv
@@ -410,7 +425,7 @@ extern "C" int mmdti_bert_layer_fwd(mmdti_stream_t stream, int Mq, int B, int L,
   // attention kernels' operand type in every mode), u_aux too
   const int ab = fwd_f16 ? MMDTI_DT_AB_F16 : 0;
   if (int e = fwd_gemm(stream, s1_16, D, w_qkv, D, b_qkv, qkv, Mq, 3 * D, D, MMDTI_ACT_NONE, nullptr, nullptr, MMDTI_DT_BF16 | ab, 0.f, 0ull, 0u)) return e;
-  if (int e = mmdti_attn_fwd(stream, qp, qp + (size_t)D * 2, qp + (size_t)2 * D * 2, key_add, ctx, stats, B, heads, L, L, hd, 3 * D, 3 * D, D,
+  if (int e = attn_pair_fwd(stream, qp, qp + (size_t)D * 2, qp + (size_t)2 * D * 2, key_add, ctx, stats, B, heads, L, L, hd, 3 * D, 3 * D, D,
                              scale, p_att, seed, site_att, q_off, k_off, k_cnt, q_rows, fwd_f16 ? 1 : 0))
     return e;
   if (int e = closer(stream, ctx, w_o, b_o, s1_32, Mq, D, D, p_hid, seed, site_o, y, g_ln1, bt_ln1, eps, a32, a16, am, ar, ln_max_k, fwd_f16)) return e;
@@ -462,7 +477,7 @@ extern "C" int mmdti_bert_layer_bwd(mmdti_stream_t stream, int Mq, int B, int L,
     return e;
   if (int e = dx_gemm(stream, dyb, D, w_o, D, dctx, Mq, D, D, MMDTI_ACT_NONE, nullptr, 0)) return e;
   const char* qp = reinterpret_cast<const char*>(qkv);
-  if (int e = mmdti_attn_bwd(stream, qp, qp + (size_t)D * 2, qp + (size_t)2 * D * 2, key_add, dctx, stats, drow, dqkv, dqkv + (size_t)D * 2,
+  if (int e = attn_pair_bwd(stream, qp, qp + (size_t)D * 2, qp + (size_t)2 * D * 2, key_add, dctx, stats, drow, dqkv, dqkv + (size_t)D * 2,
                              dqkv + (size_t)2 * D * 2, B, heads, L, L, hd, 3 * D, 3 * D, D, 3 * D, 3 * D, scale, p_att, seed, site_att, q_off,
                              k_off, k_cnt, q_rows))
     return e;

@@ -870,6 +870,8 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
     L = SimpleNamespace(s1_16=s1_16, s2_16=s2_16, ld=ld, heads=heads, self_attn=self_attn, W=W, eps=eps)
     L.site_att = sites.next()
     L.key_add, L.fused = key_add, ops.attn_eligible(Lq, Lk, hd, D)
+    if not L.fused:
+        ops.warn_unfused_length(Lq, Lk)
     # query/key/value as ONE GEMM when their parameters sit back to back in the arena (trainer._qkv_groups) and the fused
     # attention kernels (which take row-strided q/k/v) run: [3D, D] for self-attention, [2D, D] (key|value) otherwise
     L.fw = L.fb = None
@@ -900,10 +902,10 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
         L.v = ops.linear_fwd(s2_16, wfwd(W.v_w), W.v_b, out_dtype=BF16)
     if L.fused:
         # scores, softmax, dropout and context in one kernel: the [B,heads,Lq,Lk] tensor never reaches HBM
-        L.ctx, L.stats = ops.attn_fwd(L.q, L.k, L.v, key_add, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), p_att, seed, L.site_att, vl=vl)
+        L.ctx, L.stats = ops.attn_dispatch(Lq, Lk)[0](L.q, L.k, L.v, key_add, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), p_att, seed, L.site_att, vl=vl)
     else:
         if vl is not None:
-            raise ops.MMDTIError("packed sequences need the fused attention kernels (head_dim 32 / 64, at most 256 tokens)")
+            raise ops.MMDTIError("packed sequences need the fused attention kernels (head_dim 16 / 32 / 64, at most 512 tokens)")
         S = torch.empty(B, heads, Lq, ld, device=s1_32.device, dtype=F32)
         ops.gemm(L.q, L.k, M=Lq, N=Lk, K=hd, lda=D, ldb=D, out=S, ldc=ld, batch=(B, heads), sA=(Lq * D, hd), sB=(Lk * D, hd),
                  sC=(heads * Lq * ld, Lq * ld), alpha=1.0 / math.sqrt(hd))
@@ -964,7 +966,7 @@ def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
             outv = (dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:])
         else:
             outv = (torch.empty(Mq, D, device=dev, dtype=BF16), dqkv[:, :D], dqkv[:, D:])
-        dq, dk, dv = ops.attn_bwd(L.q, L.k, L.v, L.key_add, dctx, L.stats, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), L.p_att, seed, L.site_att,
+        dq, dk, dv = ops.attn_dispatch(Lq, Lk)[1](L.q, L.k, L.v, L.key_add, dctx, L.stats, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), L.p_att, seed, L.site_att,
                                   out=outv, vl=vl)
         raw.append((dqkv, L.s1_16 if L.self_attn else L.s2_16, L.fw[2], L.fb[2].view(-1), None))
         ds1 = dy if want[0] else None
@@ -980,7 +982,7 @@ def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
         _lin_bwd_params_many(pend, raw)
         return ds1, ds2
     if L.fused:
-        dq, dk, dv = ops.attn_bwd(L.q, L.k, L.v, L.key_add, dctx, L.stats, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), L.p_att, seed, L.site_att, vl=vl)
+        dq, dk, dv = ops.attn_dispatch(Lq, Lk)[1](L.q, L.k, L.v, L.key_add, dctx, L.stats, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), L.p_att, seed, L.site_att, vl=vl)
     else:
         dP = torch.empty(B, heads, Lq, ld, device=dev, dtype=F32)
         ops.gemm(dctx, L.v, M=Lq, N=Lk, K=hd, lda=D, ldb=D, out=dP, ldc=ld, batch=(B, heads), sA=(Lq * D, hd), sB=(Lk * D, hd),

@@ -351,7 +351,10 @@ class MM_Model(nn.Module):
             D2, D1 = self.bert.cfg.dim, self.args.encoder_embed_dim
             hd_ok = all(ops.attn_eligible(pk1.max_rows, pk2.max_rows, D // h, D) for D, h in
                         ((D2, self.bert.cfg.heads), (self.cross_cfg.hidden_size, self.cross_cfg.num_attention_heads)))
-            if hd_ok and max(pk1.max_rows, pk2.max_rows) <= 256 and D1 == self.cross_cfg.hidden_size:
+            # (length: attn_eligible's -- ops.ATTN_LONG_MAX_LEN rows a side.  The other packed kernels on this path have no limit of
+            #  their own: mmdti_seq_mean_packed_fwd / _bwd and the InfoNCE head walk row_off row by row at any S, and tower 1's pair
+            #  kernels are bounded by pair_tiled_ok(N) above)
+            if hd_ok and D1 == self.cross_cfg.hidden_size:
                 packs = (pk1.to(src_tokens.device), pk2.to(src_tokens.device))
         self._pack_cache = (atom_counts, token_counts, (B, N, L, src_tokens.device), packs)
         return packs

@@ -775,11 +775,33 @@ def softmax_bwd(p, dp, B, heads, Lq, Lk, ld, scale, drop_p=0.0, seed=0, site=0):
 
 
 # --------------------------------------------------------------------------------------------- fused attention
-FUSED_ATTN = True      # tests flip this to exercise the materialised-scores path that longer sequences take
+FUSED_ATTN = True      # tests flip this to exercise the materialised-scores path that sequences longer than ATTN_LONG_MAX_LEN take
+ATTN_MAX_LEN = 256         # mmdti_attn_fwd / _bwd: queries / keys per head
+ATTN_LONG_MAX_LEN = 512    # mmdti_attn_long_fwd / _bwd
 
 
 def attn_eligible(Lq, Lk, hd, D):
-    return FUSED_ATTN and hd in (16, 32, 64) and Lq <= 256 and Lk <= 256 and D % 8 == 0
+    return FUSED_ATTN and hd in (16, 32, 64) and Lq <= ATTN_LONG_MAX_LEN and Lk <= ATTN_LONG_MAX_LEN and D % 8 == 0
+
+
+def attn_is_long(Lq, Lk):
+    """The pair of kernels an eligible attention runs on: the long one as soon as either side passes 256 (csrc/layers.hip decides by
+    the same rule, so a sequenced layer launches what the op-by-op path launches)."""
+    return max(Lq, Lk) > ATTN_MAX_LEN
+
+
+_warned_long = False
+
+
+def warn_unfused_length(Lq, Lk):
+    """Once per process: a batch longer than the fused kernels take runs the materialised-scores chain (slower, and it keeps two
+    [B, heads, Lq, Lk] tensors per layer for the backward)."""
+    global _warned_long
+    if not _warned_long and FUSED_ATTN and max(Lq, Lk) > ATTN_LONG_MAX_LEN:
+        _warned_long = True
+        import warnings
+        warnings.warn(f"attention over {Lq} queries x {Lk} keys: longer than the fused kernels' {ATTN_LONG_MAX_LEN}; this batch takes the "
+                      "materialised-scores path (slower, more memory)", RuntimeWarning, stacklevel=3)
 
 
 class AttnVarlen:
@@ -800,7 +822,7 @@ class AttnVarlen:
 _NO_VARLEN = (0, 0, 0, 0)
 
 
-def attn_fwd(q, k, v, key_add, B, heads, Lq, Lk, scale, drop_p=0.0, seed=0, site=0, vl=None):
+def _attn_fwd(name, q, k, v, key_add, B, heads, Lq, Lk, scale, drop_p=0.0, seed=0, site=0, vl=None):
     """q [B*Lq, D], k/v [B*Lk, D] bf16 -> (ctx [B*Lq, D] bf16, stats [B,heads,Lq,2] fp32).  vl (AttnVarlen): packed sequences --
     q [vl.q_rows, D], k/v [vl.k_rows, D], Lq / Lk the longest sequence of each side; stats is [heads, q_rows, 2]."""
     for t_, n_ in ((q, "attn.q"), (k, "attn.k"), (v, "attn.v")):
@@ -811,40 +833,63 @@ def attn_fwd(q, k, v, key_add, B, heads, Lq, Lk, scale, drop_p=0.0, seed=0, site
     hd = D // heads
     rows_q = B * Lq if vl is None else vl.q_rows
     if q.shape[0] != rows_q or k.shape[0] != (B * Lk if vl is None else vl.k_rows) or (vl is not None and key_add is not None):
-        raise MMDTIError("attn_fwd: row counts do not match the layout (packed sequences take no key_add)")
+        raise MMDTIError(f"{name}: row counts do not match the layout (packed sequences take no key_add)")
     ctx = torch.empty(rows_q, D, device=q.device, dtype=act16())         # (feeds the output projection's forward GEMM)
     stats = torch.empty((B, heads, Lq, 2) if vl is None else (heads, rows_q, 2), device=q.device, dtype=F32)
-    t0 = kernel_timer.begin("attn_fwd")
-    lib().mmdti_attn_fwd(_stream(), q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(key_add), ctx.data_ptr(), stats.data_ptr(), B, heads, Lq, Lk,
+    t0 = kernel_timer.begin(name)
+    getattr(lib(), "mmdti_" + name)(_stream(), q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(key_add), ctx.data_ptr(), stats.data_ptr(), B, heads, Lq, Lk,
                          hd, q.stride(0), k.stride(0), D, float(scale), float(drop_p), int(seed), int(site), *(_NO_VARLEN if vl is None else vl.args()),
                          int(ctx.dtype == F16))
-    kernel_timer.end("attn_fwd", t0, 4.0 * heads * hd * (B * Lq * Lk if vl is None else vl.pairs))          # flops: q.k^T and p.v
+    kernel_timer.end(name, t0, 4.0 * heads * hd * (B * Lq * Lk if vl is None else vl.pairs))          # flops: q.k^T and p.v
     return ctx, stats
 
 
-def attn_bwd(q, k, v, key_add, dctx, stats, B, heads, Lq, Lk, scale, drop_p=0.0, seed=0, site=0, out=None, vl=None):
+def _attn_bwd(name, q, k, v, key_add, dctx, stats, B, heads, Lq, Lk, scale, drop_p=0.0, seed=0, site=0, out=None, vl=None):
     """out: optional (dq, dk, dv) destination views (unit column stride; dk and dv share one row stride)."""
     _chk(dctx, BF16, "attn.dctx")
     D = q.shape[1]
     hd = D // heads
     rows_q, rows_k = (B * Lq, B * Lk) if vl is None else (vl.q_rows, vl.k_rows)
     if q.shape[0] != rows_q or k.shape[0] != rows_k or dctx.shape[0] != rows_q:
-        raise MMDTIError("attn_bwd: row counts do not match the layout")
+        raise MMDTIError(f"{name}: row counts do not match the layout")
     if out is not None:
         dq, dk, dv = out
         if dk.stride(0) != dv.stride(0) or any(t.stride(1) != 1 or t.dtype != BF16 for t in out) or dq.shape[0] != rows_q or dk.shape[0] != rows_k:
-            raise MMDTIError("attn_bwd: bad output views")
+            raise MMDTIError(f"{name}: bad output views")
     else:
         dq = torch.empty(rows_q, D, device=q.device, dtype=BF16)
         dk = torch.empty(rows_k, D, device=q.device, dtype=BF16)
         dv = torch.empty(rows_k, D, device=q.device, dtype=BF16)
     drow = torch.empty((B, heads, Lq) if vl is None else (heads, rows_q), device=q.device, dtype=F32)
-    t0 = kernel_timer.begin("attn_bwd")
-    lib().mmdti_attn_bwd(_stream(), q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(key_add), dctx.data_ptr(), stats.data_ptr(), drow.data_ptr(),
+    t0 = kernel_timer.begin(name)
+    getattr(lib(), "mmdti_" + name)(_stream(), q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(key_add), dctx.data_ptr(), stats.data_ptr(), drow.data_ptr(),
                          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, heads, Lq, Lk, hd, q.stride(0), k.stride(0), dctx.stride(0), dq.stride(0), dk.stride(0),
                          float(scale), float(drop_p), int(seed), int(site), *(_NO_VARLEN if vl is None else vl.args()))
-    kernel_timer.end("attn_bwd", t0, 10.0 * heads * hd * (B * Lq * Lk if vl is None else vl.pairs))         # flops of the five products an attention backward needs (scores once)
+    kernel_timer.end(name, t0, 10.0 * heads * hd * (B * Lq * Lk if vl is None else vl.pairs))         # flops of the five products an attention backward needs (scores once)
     return dq, dk, dv
+
+
+def attn_fwd(*a, **kw):
+    """Up to 256 queries x 256 keys (mmdti_attn_fwd; longer raises).  Arguments: _attn_fwd."""
+    return _attn_fwd("attn_fwd", *a, **kw)
+
+
+def attn_bwd(*a, **kw):
+    return _attn_bwd("attn_bwd", *a, **kw)
+
+
+def attn_long_fwd(*a, **kw):
+    """Up to 512 x 512 (mmdti_attn_long_fwd): the signature, results and accounting of attn_fwd."""
+    return _attn_fwd("attn_long_fwd", *a, **kw)
+
+
+def attn_long_bwd(*a, **kw):
+    return _attn_bwd("attn_long_bwd", *a, **kw)
+
+
+def attn_dispatch(Lq, Lk):
+    """-> (forward, backward) of the fused attention for an eligible shape (attn_eligible): THE place where a kernel pair is chosen."""
+    return (attn_long_fwd, attn_long_bwd) if attn_is_long(Lq, Lk) else (attn_fwd, attn_bwd)
 
 
 # --------------------------------------------------------------------------------------------- InfoNCE pieces
