@@ -590,6 +590,26 @@ int mmdti_ce_loss(mmdti_stream_t stream, const float* logits, const long long* t
 /* nn.BCEWithLogitsLoss() -- the 'bce' entry of the multilabel_classification loss table (models/nnmodel.py:28-29) -- over n = B * C
  * logits against 0 / 1 targets given as fp32: mean-reduced loss + dlogits in one pass. */
 int mmdti_bce_logits_loss(mmdti_stream_t stream, const float* logits, const float* target, int n, float* loss, float* dlogits);
+/* FocalLossWithLogits -- the 'focal' entry of that table and the default of a multilabel_classification model (models/nnmodel.py:31,
+ * 90-93; models/loss.py:233-276) -- over n = B * C logits against targets given as fp32.  An entry is valid iff its target is exactly
+ * 0 or 1; NaN and every other value (-1) mark a missing label.  Per valid entry p = sigmoid(x), q = clamp(y ? p : 1 - p, 1e-5, 1),
+ * l = -alpha (1 - q)^gamma log q (the clamped q in the modulating factor, one alpha for both classes: loss.py:253-254); loss = sum of
+ * l / valid count.  dlogits in closed form in the same pass: / valid count, exactly 0 at missing entries and where the clamp holds q at
+ * 1e-5.  gamma: any positive value (2 takes a path without powf).  No valid entry at all gives what the reference gives: a NaN loss
+ * (the mean of an empty tensor) and dlogits = 0 everywhere.  Such a step is NOT skipped by skip_nonfinite: its gradients are finite.
+ * One workgroup, fixed summation order, no floating-point atomics. */
+int mmdti_focal_logits_loss(mmdti_stream_t stream, const float* logits, const float* target, int n, float alpha, float gamma,
+                            float* loss, float* dlogits);
+/* GHMC_Loss(bins, alpha) -- the 'ghm' entry (models/nnmodel.py:30; models/loss.py:63-132) -- in one launch: the histogram of
+ * g = |sigmoid(x) - y| over bins floor(g (bins - 1e-4)) (integer counters), count = alpha * last + (1 - alpha) * count when the state
+ * has history, beta_b = N / max(count_b * #{count > 0}, 1e-4) with N = n, loss = mean over N of beta_bin * bce_with_logits,
+ * dlogits = beta_bin (sigmoid(x) - y) / N (the weights carry no gradient).  state: [bins + 1] fp32 on the device, zero-initialised =
+ * no history; [0, bins) the counts this call leaves for the next, [bins] the "has history" flag.  EVERY call updates it, training and
+ * validation alike (the reference's single loss object sees both).  bins <= 256.  Entries whose target is not exactly 0 or 1 -- where
+ * the reference raises IndexError -- stay out of the histogram and get zero weight and gradient; N stays n.  Same reproducibility as
+ * above. */
+int mmdti_ghmc_logits_loss(mmdti_stream_t stream, const float* logits, const float* target, int n, int bins, float alpha,
+                           float* state, float* loss, float* dlogits);
 
 /* ---- optimizer step on the flat arenas (tasks/trainer.py:160,270-282) ---------------------- */
 /* out[0] += sum of squares of g (zero first).  ws (nullable, ws_floats >= 1; 2048 used at most): one partial per workgroup folded in a

@@ -768,6 +768,118 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ lg, c
   if (threadIdx.x == 0) *loss = s / (float)B;
 }
 
+// ---------------------------------------------------------------- multilabel task losses with missing labels
+// A label is valid iff it is exactly 0 or 1; NaN and every other value (the -1 of Tox21 / ToxCast / SIDER / MUV) mark an assay
+// that was not measured (models/loss.py:269-272).  One workgroup, strided per-thread partial sums folded in a fixed order: the value
+// and every gradient are the same to the bit from run to run (no floating-point atomics).
+__device__ __forceinline__ float sigmoid_stable(float x) {      // (the form bce_logits_kernel uses)
+  const float e = expf(-fabsf(x));
+  return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+__device__ __forceinline__ int block_sum_int(int v, int* red) {  // 256 threads
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// FocalLossWithLogits (models/loss.py:233-276): q = clamp(y ? p : 1 - p, 1e-5, 1), l = -alpha (1 - q)^gamma log q, mean over the valid
+// entries.  d l / d x = -alpha s [(1 - q)^(gamma + 1) - gamma q (1 - q)^gamma log q] with s = +1 (y = 1) / -1 (y = 0), since
+// dq/dx = s q (1 - q); 0 where the clamp holds q at 1e-5.  GAMMA2: gamma == 2 without powf.
+template <bool GAMMA2>
+__global__ __launch_bounds__(256) void focal_logits_kernel(const float* __restrict__ x, const float* __restrict__ t, int n, float alpha, float gamma,
+                                                           float* __restrict__ loss, float* __restrict__ dx) {
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  int c = 0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float ti = t[i];
+    c += (ti == 0.f || ti == 1.f) ? 1 : 0;
+  }
+  const int cnt = block_sum_int(c, redi);
+  const float cntf = (float)cnt;      // (no valid entry: the loss is 0 / 0 = NaN, the mean of an empty tensor; every gradient is 0)
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float ti = t[i];
+    float li = 0.f, gi = 0.f;
+    if (ti == 0.f || ti == 1.f) {
+      const float p = sigmoid_stable(x[i]);
+      const float qr = ti == 1.f ? p : 1.f - p;
+      const float q = fminf(fmaxf(qr, 1e-5f), 1.f);
+      const float omq = 1.f - q, lq = logf(q);
+      const float mod = GAMMA2 ? omq * omq : powf(omq, gamma);      // (powf(0, gamma > 0) = 0)
+      li = -alpha * mod * lq;
+      if (qr >= 1e-5f) gi = -alpha * (ti == 1.f ? 1.f : -1.f) * (mod * omq - gamma * q * mod * lq);
+    }
+    s += li;
+    dx[i] = gi != 0.f ? gi / cntf : 0.f;
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) *loss = s / cntf;
+}
+
+// GHMC_Loss (models/loss.py:63-132): gradient-harmonised BCE-with-logits in ONE launch.  Written for one launch and a fixed summation
+// order, not for speed: 256 threads whatever n is, and each entry's sigmoid is evaluated in the histogram pass and again in the loss pass.  state[bins + 1]: the previous call's bin
+// counts and a "has history" flag (the reference's `_last_bin_count is None`).
+constexpr int GHM_MAX_BINS = 256;
+__device__ __forceinline__ int ghm_bin(float p, float ti, float binsf, int bins) {      // _g2bin: floor(|p - y| (bins - 1e-4))
+  const float pos = floorf(__fmul_rn(fabsf(p - ti), binsf));
+  return pos >= 0.f ? min((int)pos, bins - 1) : 0;      // (a NaN logit lands in bin 0: the LDS counters stay in bounds)
+}
+__global__ __launch_bounds__(256) void ghmc_logits_kernel(const float* __restrict__ x, const float* __restrict__ t, int n, int bins, float binsf,
+                                                          float alpha, float one_minus_alpha, float* __restrict__ state,
+                                                          float* __restrict__ loss, float* __restrict__ dx) {
+  __shared__ float red[4];
+  __shared__ int hist[GHM_MAX_BINS];
+  __shared__ float beta[GHM_MAX_BINS];
+  for (int b = threadIdx.x; b < bins; b += 256) hist[b] = 0;
+  __syncthreads();
+  // (a) histogram of the gradient norm g = |sigmoid(x) - y| over the valid entries: integer LDS counters, exact in any order
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float ti = t[i];
+    if (ti == 0.f || ti == 1.f) atomicAdd(&hist[ghm_bin(sigmoid_stable(x[i]), ti, binsf, bins)], 1);
+  }
+  __syncthreads();
+  // (b) the moving average over calls (loss.py:81-85), written back; separately rounded products as torch evaluates them
+  // (every thread reads the flag here; thread 0 rewrites it in (c), two barriers later)
+  const bool has_history = state[bins] != 0.f;
+  for (int b = threadIdx.x; b < bins; b += 256) {
+    float cb = (float)hist[b];
+    if (has_history) cb = __fadd_rn(__fmul_rn(alpha, state[b]), __fmul_rn(one_minus_alpha, cb));
+    beta[b] = cb;
+  }
+  __syncthreads();
+  // (c) beta_b = N / max(count_b * nonempty, 1e-4) with N = all n entries (loss.py:79,87-91); every thread folds the <= 256 counts
+  int nonempty = 0;
+  for (int b = 0; b < bins; ++b) nonempty += beta[b] > 0.f ? 1 : 0;
+  __syncthreads();
+  for (int b = threadIdx.x; b < bins; b += 256) {
+    const float cb = beta[b];
+    state[b] = cb;
+    beta[b] = (float)n / fmaxf(__fmul_rn(cb, (float)nonempty), 1e-4f);
+  }
+  if (threadIdx.x == 0) state[bins] = 1.f;
+  __syncthreads();
+  // (d) mean over N of beta_bin * bce_with_logits; the weights carry no gradient
+  const float invn = 1.f / (float)n;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float xi = x[i], ti = t[i];
+    float gi = 0.f;
+    if (ti == 0.f || ti == 1.f) {
+      const float p = sigmoid_stable(xi);
+      const float w = beta[ghm_bin(p, ti, binsf, bins)];
+      s += w * (fmaxf(xi, 0.f) - xi * ti + log1pf(expf(-fabsf(xi))));
+      gi = w * (p - ti) * invn;
+    }
+    dx[i] = gi;
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) *loss = s / (float)n;
+}
+
 }  // namespace mmdti
 using namespace mmdti;
 
@@ -950,6 +1062,28 @@ extern "C" int mmdti_bce_logits_loss(mmdti_stream_t stream, const float* logits,
 extern "C" int mmdti_ce_loss(mmdti_stream_t stream, const float* logits, const long long* target, int B, int C, float* loss, float* dlogits) {
   MMDTI_REQUIRE(logits && target && loss && dlogits && B > 0 && C > 0, "ce_loss: bad arguments");
   hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, B, C, loss, dlogits);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_focal_logits_loss(mmdti_stream_t stream, const float* logits, const float* target, int n, float alpha, float gamma,
+                                       float* loss, float* dlogits) {
+  MMDTI_REQUIRE(logits && target && loss && dlogits && n > 0, "focal_logits_loss: bad arguments");
+  MMDTI_REQUIRE(gamma > 0.f && alpha == alpha, "focal_logits_loss: gamma must be positive (got %g)", (double)gamma);
+  if (gamma == 2.0f)
+    hipLaunchKernelGGL(focal_logits_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, n, alpha, gamma, loss, dlogits);
+  else
+    hipLaunchKernelGGL(focal_logits_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, n, alpha, gamma, loss, dlogits);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_ghmc_logits_loss(mmdti_stream_t stream, const float* logits, const float* target, int n, int bins, float alpha,
+                                      float* state, float* loss, float* dlogits) {
+  MMDTI_REQUIRE(logits && target && state && loss && dlogits && n > 0, "ghmc_logits_loss: bad arguments");
+  MMDTI_REQUIRE(bins >= 1 && bins <= GHM_MAX_BINS, "ghmc_logits_loss: bins %d outside 1..%d", bins, GHM_MAX_BINS);
+  MMDTI_REQUIRE(alpha >= 0.f && alpha <= 1.f, "ghmc_logits_loss: the moving-average factor must lie in [0, 1] (got %g)", (double)alpha);
+  // the two scalars of loss.py:40,84 rounded as torch rounds a Python float that meets an fp32 tensor
+  const float binsf = (float)((double)bins - 0.0001), oma = (float)(1.0 - (double)alpha);
+  hipLaunchKernelGGL(ghmc_logits_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, n, bins, binsf, alpha, oma, state, loss, dlogits);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

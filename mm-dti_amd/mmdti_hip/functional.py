@@ -1580,3 +1580,32 @@ class BCELogitsLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dl):
         return ctx.d * dl, None
+
+
+class FocalLogitsLossFn(torch.autograd.Function):
+    """FocalLossWithLogits on [B, C] logits (models/loss.py:233-276; the default multilabel_classification loss, models/nnmodel.py:
+    90-93).  Targets of any dtype: the kernel reads them as fp32 and takes every value other than 0 and 1 (NaN, -1) as a missing label."""
+
+    @staticmethod
+    def forward(ctx, logits, target, alpha=0.25, gamma=2.0):
+        loss, d = ops.focal_logits_loss(logits.contiguous(), target.contiguous().to(F32), alpha, gamma)
+        ctx.d = d
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dl):
+        return ctx.d * dl, None, None, None
+
+
+class GHMCLogitsLossFn(torch.autograd.Function):
+    """GHMC_Loss on [B, C] logits (models/loss.py:63-132).  ``state``: the [bins + 1] device buffer of the bin counts, updated by the call."""
+
+    @staticmethod
+    def forward(ctx, logits, target, state, bins=10, alpha=0.5):
+        loss, d = ops.ghmc_logits_loss(logits.contiguous(), target.contiguous().to(F32), state, bins, alpha)
+        ctx.d = d
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dl):
+        return ctx.d * dl, None, None, None, None

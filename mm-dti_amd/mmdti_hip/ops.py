@@ -1078,6 +1078,33 @@ def bce_logits_loss(logits, target):
     return loss, d
 
 
+def focal_logits_loss(logits, target, alpha=0.25, gamma=2.0):
+    """FocalLossWithLogits over the entries whose target is exactly 0 or 1 (NaN / -1: missing) -> (loss[1], dlogits)."""
+    _chk(logits, F32, "focal_logits.logits"); _chk(target, F32, "focal_logits.target")
+    if target.shape != logits.shape:
+        raise MMDTIError(f"focal_logits_loss: target shape {tuple(target.shape)} != logits shape {tuple(logits.shape)}")
+    loss = torch.empty(1, device=logits.device, dtype=F32)
+    d = torch.empty_like(logits)
+    lib().mmdti_focal_logits_loss(_stream(), logits.data_ptr(), target.data_ptr(), logits.numel(), float(alpha), float(gamma), loss.data_ptr(),
+                                  d.data_ptr())
+    return loss, d
+
+
+def ghmc_logits_loss(logits, target, state, bins=10, alpha=0.5):
+    """GHMC_Loss(bins, alpha) in one launch -> (loss[1], dlogits).  state: [bins + 1] fp32 (last bin counts | has-history flag),
+    updated in place by every call."""
+    _chk(logits, F32, "ghmc_logits.logits"); _chk(target, F32, "ghmc_logits.target"); _chk(state, F32, "ghmc_logits.state")
+    if target.shape != logits.shape:
+        raise MMDTIError(f"ghmc_logits_loss: target shape {tuple(target.shape)} != logits shape {tuple(logits.shape)}")
+    if state.numel() != int(bins) + 1:
+        raise MMDTIError(f"ghmc_logits_loss: state holds {state.numel()} values, bins + 1 = {int(bins) + 1} expected")
+    loss = torch.empty(1, device=logits.device, dtype=F32)
+    d = torch.empty_like(logits)
+    lib().mmdti_ghmc_logits_loss(_stream(), logits.data_ptr(), target.data_ptr(), logits.numel(), int(bins), float(alpha), state.data_ptr(),
+                                 loss.data_ptr(), d.data_ptr())
+    return loss, d
+
+
 def sumsq(g, out, ws=None):
     """out[0] += sum of squares of g.  ws: fp32 scratch (up to 2048 values) -- per-workgroup partials folded in a fixed order: reproducible."""
     lib().mmdti_sumsq_f32(_stream(), g.data_ptr(), g.numel(), out.data_ptr(), _p(ws), 0 if ws is None else ws.numel())

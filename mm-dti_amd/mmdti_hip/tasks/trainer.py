@@ -149,10 +149,25 @@ class EpochMetric:
             if n not in _METRIC_TABLE:
                 raise ValueError('Unknown metric: {}'.format(n))
         self.names = names
+        self.task = task
 
     def cal_metric(self, label, predict, nan_value=-1.0, threshold=0.5, label_cnt=None):
+        """Classification tasks (utils/metrics.py:30-56,156-170, ``cal_nan_metric(..., classification=True)``): every label column is
+        scored over its entries with label 0 or 1 and ``!= nan_value`` only -- the unmeasured assays of Tox21 / ToxCast / SIDER / MUV
+        (NaN or -1) do not enter; a column without such an entry is left out of the mean, and with no column left the mean of nothing
+        is NaN, as the reference's ``np.mean([])``.  Regression metrics take every entry."""
         label, predict = np.asarray(label, dtype=np.float64), np.asarray(predict, dtype=np.float64)
-        return {n: float(np.mean([_METRIC_TABLE[n][0](label[:, c], predict[:, c]) for c in range(label.shape[1])])) for n in self.names}
+        if self.task not in ("classification", "multilabel_classification"):
+            return {n: float(np.mean([_METRIC_TABLE[n][0](label[:, c], predict[:, c]) for c in range(label.shape[1])])) for n in self.names}
+        mask = (label == 0.0) | (label == 1.0)          # (false for NaN)
+        if nan_value is not None:
+            mask &= label != nan_value
+        cols = [c for c in range(label.shape[1]) if mask[:, c].any()]
+        out = {}
+        for n in self.names:
+            scores = [_METRIC_TABLE[n][0](label[mask[:, c], c], predict[mask[:, c], c]) for c in cols]
+            out[n] = float(np.mean(scores)) if scores else float("nan")
+        return out
 
     def is_increase(self, name):
         return _METRIC_TABLE[name][1]
@@ -162,6 +177,21 @@ def _is_increase(metrics, task, name):
     if isinstance(metrics, EpochMetric):
         return metrics.is_increase(name)
     return bool(metrics.METRICS_REGISTER[name][1])          # the reference's utils.Metrics
+
+
+def normalise_target(task, net_target):
+    """The target dtype rule of tasks/trainer.py:113-120 on a device tensor, without a host synchronisation.  For
+    multilabel_classification a floating target marks a missing label with NaN: those become -1 BEFORE the integer cast (what a NaN
+    converts to is left to the hardware, and 0 would train the missing label as a negative); integer targets pass through untouched."""
+    if task == 'repr':
+        return None
+    if task == 'multilabel_classification':
+        if net_target.is_floating_point():
+            net_target = torch.where(torch.isnan(net_target), torch.full_like(net_target, -1.0), net_target)
+        return net_target.long()
+    if task in ('classification', 'multiclass'):
+        return net_target.long()
+    return net_target.float()
 
 
 # ------------------------------------------------------------------------------------------------ the trainer
@@ -200,6 +230,7 @@ class Trainer(object):
         self.num_workers = int(params.get('num_workers', 0))
         self.narrow_inputs = bool(params.get('narrow_inputs', True))
         self.rank = torch.distributed.get_rank() if (self.distributed and torch.distributed.is_initialized()) else 0
+        self._loss_cache = {}       # id(loss_func) -> (loss_func, its kernel-backed loss): see _task_loss
 
     # -------------------------------------------------------------- batches
     def decorate_batch(self, batch, feature_name=None):
@@ -217,13 +248,7 @@ class Trainer(object):
                 net_input = pad_to_global_lengths(net_input)        # the unmasked InfoNCE mean needs one padded length on all ranks
         else:
             net_input = {'net_input': net_input.to(self.device)}
-        net_target = net_target.to(self.device, non_blocking=True)
-        if self.task == 'repr':
-            net_target = None
-        elif self.task in ['classification', 'multiclass', 'multilabel_classification']:
-            net_target = net_target.long()
-        else:
-            net_target = net_target.float()
+        net_target = normalise_target(self.task, net_target.to(self.device, non_blocking=True))
         return net_input, net_target
 
     _n_edge_types = None
@@ -252,13 +277,7 @@ class Trainer(object):
             if self.distributed:
                 from ..parallel import pad_to_global_lengths
                 net_input = pad_to_global_lengths(net_input)        # the unmasked InfoNCE mean needs one padded length on all ranks
-            if self.task == 'repr':
-                net_target = None
-            elif self.task in ['classification', 'multiclass', 'multilabel_classification']:
-                net_target = net_target.long()
-            else:
-                net_target = net_target.float()
-            yield net_input, net_target
+            yield net_input, normalise_target(self.task, net_target)
 
     def _collate_for(self, model):
         """The model's own ``batch_collate_fn`` in-process; with worker processes, the same collate as a small picklable
@@ -319,7 +338,7 @@ class Trainer(object):
                            max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite)
         engine.warmup = int(num_training_steps * self.warmup_ratio)
         self._engine = engine
-        task_loss = None if _is_builtin_loss(loss_func, self.task) else loss_func
+        task_loss = self._task_loss(loss_func)
         self.history = []
         epoch = 0
         for epoch in range(self.max_epochs):
@@ -420,12 +439,12 @@ class Trainer(object):
                                   collate_fn=self._collate_for(model), **self._loader_kwargs())
         model = model.eval()
         val_loss, y_preds, y_truths = [], [], []
-        builtin = _is_builtin_loss(loss_func, self.task)
+        task_loss = self._task_loss(loss_func) or _builtin_loss(self.task)
         with torch.no_grad():
             for net_input, net_target in self.device_batches(dataloader, feature_name):
                 outputs = model(**net_input)       # both auxiliary losses are force-disabled in the reference's predict (:427-428)
                 if not load_model:
-                    tl = _builtin_loss(self.task)(outputs, net_target) if builtin else loss_func(outputs, net_target)
+                    tl = task_loss(outputs, net_target)
                     val_loss.append(self.alpha * tl)
                 y_preds.append(activation_fn(outputs))
                 y_truths.append(net_target)
@@ -447,6 +466,18 @@ class Trainer(object):
             metric_score = {"ct_loss": float(np.mean(val_loss)) if val_loss else float("nan")}
         return y_preds, val_loss, metric_score
 
+    def _task_loss(self, loss_func):
+        """What the step applies for ``loss_func``: None -- the engine's own kernel for the task (MSE / cross-entropy / BCE-with-
+        logits); a kernel-backed object of ``mmdti_hip.losses`` for the reference's focal and GHM entries (one per Trainer and loss
+        object, so that training and validation share GHM's bin history as they do in the reference); else the callable as given."""
+        if not _is_builtin_loss(loss_func, self.task):
+            return loss_func
+        if self.task != "multilabel_classification" or loss_func is None or isinstance(loss_func, torch.nn.BCEWithLogitsLoss):
+            return None
+        if id(loss_func) not in self._loss_cache:       # (the entry keeps loss_func alive, so its id stays its own)
+            self._loss_cache[id(loss_func)] = (loss_func, _builtin_loss(self.task, loss_func))
+        return self._loss_cache[id(loss_func)][1]
+
     def set_seed(self, seed):
         torch.manual_seed(seed)
         if torch.cuda.is_available():
@@ -454,18 +485,51 @@ class Trainer(object):
         np.random.seed(seed)
 
 
-def _builtin_loss(task):
+def _builtin_loss(task, loss_func=None):
+    """The kernel-backed callable for a ``loss_func`` that _is_builtin_loss recognises (None: the task's default)."""
     from ..functional import CELossFn, MSELossFn, BCELogitsLossFn
     if task == "regression":
         return lambda o, t: MSELossFn.apply(o, t.float())
     if task == "multilabel_classification":
+        kind = _multilabel_kind(loss_func)
+        if kind == "self":
+            return loss_func
+        if kind == "focal":          # the function itself: called with its defaults alpha=0.25, gamma=2.0 (models/loss.py:257)
+            from ..losses import FocalLossWithLogits
+            return FocalLossWithLogits()
+        if kind == "ghm":            # the table's single GHMC_Loss object: its bins / alpha and the history it has seen so far
+            from ..losses import GHMCLoss
+            loss = GHMCLoss(bins=loss_func._bins, alpha=loss_func._alpha)
+            if loss_func._last_bin_count is not None:
+                loss.load_state_dict({"last_bin_count": loss_func._last_bin_count})
+            return loss
         return lambda o, t: BCELogitsLossFn.apply(o, t)
     return lambda o, t: CELossFn.apply(o, t)
 
 
+def _multilabel_kind(loss_func):
+    """Which entry of LOSS_RREGISTER['multilabel_classification'] (models/nnmodel.py:28-32) ``loss_func`` is, by what NNModel hands
+    over: the FUNCTION ``FocalLossWithLogits`` ('focal'), the ``GHMC_Loss`` object ('ghm'), ``nn.BCEWithLogitsLoss()`` ('bce'); 'self'
+    for the objects of ``mmdti_hip.losses``; None for anything else."""
+    from ..losses import FocalLossWithLogits, GHMCLoss
+    if isinstance(loss_func, (FocalLossWithLogits, GHMCLoss)):
+        return "self"
+    if loss_func is None:
+        return "bce"
+    if (isinstance(loss_func, torch.nn.BCEWithLogitsLoss) and loss_func.weight is None and loss_func.pos_weight is None
+            and loss_func.reduction == "mean"):
+        return "bce"
+    import types
+    if isinstance(loss_func, types.FunctionType) and loss_func.__name__ == "FocalLossWithLogits":
+        return "focal"
+    if type(loss_func).__name__ == "GHMC_Loss" and all(hasattr(loss_func, a) for a in ("_bins", "_alpha", "_last_bin_count")):
+        return "ghm"
+    return None
+
+
 def _is_builtin_loss(loss_func, task):
     """True when ``loss_func`` is the reference's task loss for this task (models/nnmodel.py:24-34: ``nn.MSELoss()`` /
-    ``myCrossEntropyLoss``) -- those run in the mse / cross-entropy kernels; any other callable is applied as given."""
+    ``myCrossEntropyLoss`` / the three multilabel entries) -- those run in kernels; any other callable is applied as given."""
     if loss_func is None:
         return task in ("regression", "classification", "multiclass", "multilabel_classification")
     if task == "regression":
@@ -476,9 +540,8 @@ def _is_builtin_loss(loss_func, task):
         # a configured nn.CrossEntropyLoss (class weights, label smoothing, another ignore_index / reduction) is NOT the plain kernel
         return (isinstance(loss_func, torch.nn.CrossEntropyLoss) and loss_func.weight is None and loss_func.label_smoothing == 0.0
                 and loss_func.ignore_index == -100 and loss_func.reduction == "mean")
-    if task == "multilabel_classification":      # the table's 'bce' entry; 'focal' / 'ghm' are applied as given
-        return (isinstance(loss_func, torch.nn.BCEWithLogitsLoss) and loss_func.weight is None and loss_func.pos_weight is None
-                and loss_func.reduction == "mean")
+    if task == "multilabel_classification":
+        return _multilabel_kind(loss_func) is not None
     return False
 
 

@@ -62,11 +62,14 @@ def _qkv_groups(model):
 
 class FineTuner:
     def __init__(self, model, task: str, learning_rate=1e-4, adam_eps=1e-6, warmup_ratio=0.03, total_steps=1000, alpha=1.0, beta=0.1,
-                 max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False):
+                 max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
+                 loss_key: Optional[str] = None):
         """skip_nonfinite: GradScaler.step's guard (tasks/trainer.py:268-282) -- a step whose gradient arena holds any inf / NaN element
         leaves the parameters, both Adam moments, Adam's step count and the 16-bit shadows as they were, while the learning-rate
         schedule advances.  The decision is taken on the device (no host synchronisation, captured inside graphed_step) from the
-        all-reduced gradients under data parallelism, so every rank takes the same one."""
+        all-reduced gradients under data parallelism, so every rank takes the same one.
+        loss_key: the multilabel_classification loss table's key (models/nnmodel.py:28-32): None / 'bce' the BCE-with-logits kernel,
+        'focal' / 'ghm' the kernels of ``losses.FocalLossWithLogits()`` / ``losses.GHMCLoss(10, 0.5)`` (kept as ``self.task_loss``)."""
         self.model, self.task = model, task
         self.lr, self.eps, self.alpha, self.beta, self.max_norm = learning_rate, adam_eps, alpha, beta, max_norm
         self.total_steps = total_steps
@@ -101,14 +104,20 @@ class FineTuner:
             # gradient buckets leave during backward (MMDTI_NO_REDUCE_OVERLAP=1: all of them after it)
             if os.environ.get("MMDTI_NO_REDUCE_OVERLAP") != "1":
                 add_grad_ready_hook(self, self.reducer.on_grads_ready)
-        # built-in task-loss kernels (models/nnmodel.py:24-34): MSE, cross-entropy, and BCE-with-logits for the multilabel table's
-        # 'bce' entry; every other task / loss (focal, GHM, MAE-with-NaN ...) runs as the callable the caller passes as `loss_func`
+        # built-in task-loss kernels (models/nnmodel.py:24-34): MSE, cross-entropy, and the multilabel table's three entries -- BCE-with-
+        # logits ('bce', and the default here), focal and GHM by `loss_key`; every other task / loss (MAE-with-NaN ...) runs as the
+        # callable the caller passes as `loss_func`
+        if loss_key is not None and task != "multilabel_classification":
+            raise ValueError(f"FineTuner: loss_key={loss_key!r} belongs to the multilabel_classification loss table, the task is {task!r}")
         if task == "regression":
             self.task_loss = lambda lg, y: MSELossFn.apply(lg, y.float())
         elif task in ("classification", "multiclass"):
             self.task_loss = lambda lg, y: CELossFn.apply(lg, y)
-        elif task == "multilabel_classification":
+        elif task == "multilabel_classification" and loss_key in (None, "bce"):
             self.task_loss = lambda lg, y: BCELogitsLossFn.apply(lg, y)
+        elif task == "multilabel_classification":
+            from .losses import from_key
+            self.task_loss = from_key(loss_key)
         else:
             self.task_loss = None
 
@@ -257,6 +266,10 @@ class FineTuner:
         # the state this step mutates
         saved = (self.arena.data.clone(), self.arena.adam_m.clone(), self.arena.adam_v.clone(), self._state.clone(), self._salt.clone(),
                  self.arena.step_count, None if self.guard is None else self.guard.clone())
+        # a task loss with device state of its own (losses.GHMCLoss: the bin counts every call averages into) is part of that state
+        lf = kw.get("loss_func") or self.task_loss
+        loss_state = lf.device_state(dev) if hasattr(lf, "device_state") else None
+        loss_saved = None if loss_state is None else loss_state.clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -268,6 +281,8 @@ class FineTuner:
         self.arena.step_count = saved[5]
         if self.guard is not None:
             self.guard.copy_(saved[6])
+        if loss_state is not None:
+            loss_state.copy_(loss_saved)
         self.arena.refresh_shadow()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
