@@ -69,6 +69,30 @@ int mmdti_abi_version(void);
  * (MMDTI_GROUPED_SMALL_ROWS).  Returns MMDTI_ERR_INVALID for an unknown name.  Not part of any reference interface. */
 int mmdti_set_option(const char* name, int value);
 
+/* ---- Deterministic mode: bit-identical parameter gradients run to run (DESIGN.md "Deterministic mode") ----
+ * Off by default; with it off no launch changes.  mmdti_set_deterministic(1) sets a process-wide flag.  While it is on, every launcher whose
+ * default form lets workgroups (or K splits) meet in fp32 atomics -- mmdti_layernorm_bwd, mmdti_colsum_bf16, the bias gradients and the
+ * split-K output of mmdti_gemm_bf16 / mmdti_linear_dw_grouped, mmdti_gbf_features_bwd -- stores per-workgroup partials into the workspace registered for ITS
+ * launch stream and folds them in a fixed order with a kernel queued directly behind on the same stream.  A launch whose stream has no
+ * workspace, or too small a one, returns MMDTI_ERR_INVALID before anything is launched (mmdti_last_error names the site): the mode never
+ * falls back to atomics.  (A split-K GEMM lowers its split count until its slabs fit instead; one split is always deterministic.)  Sites
+ * that have no fixed-order form refuse in the mode the same way: mmdti_gbf_bias_bwd (the fused per-pair half of the round-1 pair-bias
+ * chain), mmdti_gbf_bias_bwd_full without its workspace, mmdti_sumsq_f32 without ws and mmdti_ct_loss_fwd without row_ws.
+ * mmdti_gbf_bias_bwd_full (its waves then meet in wave / pair order in LDS), the general mmdti_pair_attn_bwd kernel (waves add in
+ * wave order) and mmdti_embedding_bwd (one adder per table element, in token order) take fixed-order forms that need no workspace.
+ * mmdti_det_workspace registers `ws` (16-byte aligned device memory, `bytes` long, owned by the caller and kept alive while registered)
+ * for `stream`; ws == NULL forgets the stream.  The table is mutex-guarded and read on the host only.
+ * mmdti_det_workspace_bytes: what ONE launch of `site` needs -- MMDTI_DET_LAYERNORM_BWD (rows, cols = D), MMDTI_DET_COLSUM (rows, cols),
+ * MMDTI_DET_GEMM_SLAB (rows, cols = the output's M, N: one split's slab; a launch wants one per K split), MMDTI_DET_GBF_FEATURES_BWD
+ * (rows = pairs P, cols = 2 E + 2 K).  Not part of any reference interface. */
+#define MMDTI_DET_LAYERNORM_BWD 1
+#define MMDTI_DET_COLSUM 2
+#define MMDTI_DET_GEMM_SLAB 3
+#define MMDTI_DET_GBF_FEATURES_BWD 4
+int mmdti_set_deterministic(int on);
+int mmdti_det_workspace(mmdti_stream_t stream, void* ws, long long bytes);
+int mmdti_det_workspace_bytes(int site, long long rows, long long cols, long long* bytes_out);
+
 /* ---- GEMM: C = epi(alpha * A.B^T) ----------------------------------------------------------
  * Replaces nn.Linear / torch.bmm fwd+bwd: unicore in_proj/out_proj/fc1/fc2 (models/transformers.py:137-139),
  * gbf_proj (models/mm_model.py:554), RobertaModel linears (mm_model.py:562), InfoNCE projections

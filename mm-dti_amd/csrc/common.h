@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "../../include/mmdti_hip.h"
+#include "det.h"
 
 namespace mmdti {
 
@@ -29,6 +30,70 @@ void set_error(const char* fmt, ...);
       return MMDTI_ERR_LAUNCH;                                            \
     }                                                                     \
   } while (0)
+
+// ---- deterministic mode (det.h): the reduction workspace registered for `stream`, at least `need` bytes -- or an error that names the
+// site, before anything is launched.  A launcher in the mode never falls back to atomics.
+static inline int det_workspace(mmdti_stream_t stream, long long need, const char* site, float** ws) {
+  DetSlot slot;
+  if (need < 0) {
+    set_error("%s: deterministic mode: no fixed-order form for this shape", site);
+    return MMDTI_ERR_INVALID;
+  }
+  if (!det_table().get(stream, &slot)) {
+    set_error("%s: deterministic mode is on and stream %p has no reduction workspace (mmdti_det_workspace)", site, stream);
+    return MMDTI_ERR_INVALID;
+  }
+  if (slot.bytes < need) {
+    set_error("%s: deterministic mode: the workspace of stream %p holds %lld bytes, %lld needed", site, stream, slot.bytes, need);
+    return MMDTI_ERR_INVALID;
+  }
+  *ws = reinterpret_cast<float*>(slot.ws);
+  return MMDTI_OK;
+}
+// a site without a fixed-order form refuses in the mode
+#define MMDTI_DET_REFUSE(site)                                                                                        \
+  MMDTI_REQUIRE(!::mmdti::det_table().on(), site ": no fixed-order form yet -- refused in the deterministic mode (its partial sums meet in atomics)")
+
+// dst_k[i] += sum over the slabs s < nslab of ws[s * stride + k * n + i], k < NDST (a null dst_k is skipped).  FIXED order: sixteen
+// threads per element each add every sixteenth slab in slab order, then the sixteen partials are added 0, 1, .. 15 -- the order
+// depends on the slab count alone.
+template <int NDST>
+struct DetDst {
+  float* p[NDST];
+};
+template <int NDST>
+__global__ __launch_bounds__(1024) void det_fold_kernel(const float* __restrict__ ws, int nslab, long long stride, int n, DetDst<NDST> d) {
+  __shared__ float part[16][64];
+  const int el = threadIdx.x & 63, q = threadIdx.x >> 6, k = blockIdx.y;
+  const int i = blockIdx.x * 64 + el;
+  float* __restrict__ dst = d.p[k];
+  if (!dst) return;          // (uniform over the workgroup)
+  float t = 0.f;
+  if (i < n) {
+    const float* sp = ws + (long long)k * n + i;
+    int s = q;
+    for (; s + 16 * 7 < nslab; s += 16 * 8) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = sp[(long long)(s + 16 * j) * stride];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t += v[j];
+    }
+    for (; s < nslab; s += 16) t += sp[(long long)s * stride];
+  }
+  part[q][el] = t;
+  __syncthreads();
+  if (q == 0 && i < n) {
+    float a = part[0][el];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) a += part[j][el];
+    dst[i] += a;
+  }
+}
+template <int NDST>
+static inline void det_fold(hipStream_t s, const float* ws, int nslab, long long stride, int n, DetDst<NDST> d) {
+  hipLaunchKernelGGL((det_fold_kernel<NDST>), dim3((n + 63) / 64, NDST), dim3(1024), 0, s, ws, nslab, stride, n, d);
+}
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

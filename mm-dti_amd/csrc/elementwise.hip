@@ -100,8 +100,9 @@ __global__ __launch_bounds__(256) void gelu_bf16_kernel(const bf16_t* __restrict
 
 // ---------------------------------------------------------------- column sum (bias gradients)
 // block = 256 threads: 32 column-chunks(8 cols each, 16 B) x 8 row lanes; grid.x over column groups of 256, grid.y rows
-__global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ x, int rows, int cols, int ld,
-                                                          float* __restrict__ out) {
+// SLAB (the deterministic mode): row group blockIdx.y stores its sums to row blockIdx.y of `out` ([gridDim.y][cols]); det_fold_kernel adds them
+template <bool SLAB>
+__device__ __forceinline__ void colsum_bf16_body(const bf16_t* __restrict__ x, int rows, int cols, int ld, float* __restrict__ out) {
   __shared__ float red[8][256 + 8];
   const int cc = threadIdx.x & 31, rl = threadIdx.x >> 5;
   const int c0 = blockIdx.x * 256 + cc * 8;
@@ -149,8 +150,17 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restri
     float s = 0.f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) s += red[r][threadIdx.x];
-    atomicAdd(out + c, s);
+    if (SLAB) out[(long long)blockIdx.y * cols + c] = s;
+    else atomicAdd(out + c, s);
   }
+}
+__global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ x, int rows, int cols, int ld,
+                                                          float* __restrict__ out) {
+  colsum_bf16_body<false>(x, rows, cols, ld, out);
+}
+__global__ __launch_bounds__(256) void colsum_bf16_slab_kernel(const bf16_t* __restrict__ x, int rows, int cols, int ld,
+                                                               float* __restrict__ slab) {
+  colsum_bf16_body<true>(x, rows, cols, ld, slab);
 }
 
 // ---------------------------------------------------------------- embeddings
@@ -181,6 +191,21 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const long long* __r
     long long id = ids[i];
     if (id == padding_idx || id < 0 || id >= vocab) continue;
     atomicAdd(dtable + id * D + c, dout[t]);
+  }
+}
+
+// The deterministic mode's form: workgroup (column chunk, part) owns the table rows with id % parts == part and walks the tokens in
+// token order -- one adder per table element, a fixed order (the ids are wave-uniform loads; only matching tokens touch memory).
+__global__ __launch_bounds__(256) void embedding_bwd_ordered_kernel(const long long* __restrict__ ids, const float* __restrict__ dout,
+                                                                    long long n, int D, int vocab, long long padding_idx,
+                                                                    float* __restrict__ dtable) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int parts = gridDim.y, part = blockIdx.y;
+  if (c >= D) return;
+  for (long long i = 0; i < n; ++i) {
+    const long long id = ids[i];
+    if (id == padding_idx || id < 0 || id >= vocab || (int)(id % parts) != part) continue;
+    dtable[id * D + c] += dout[i * D + c];
   }
 }
 
@@ -658,6 +683,23 @@ using namespace mmdti;
 extern "C" const char* mmdti_last_error(void) { return g_err; }
 extern "C" int mmdti_abi_version(void) { return 1; }
 
+// ---- deterministic mode: the flag and the per-stream workspace table (det.h) ----
+extern "C" int mmdti_set_deterministic(int on) {
+  det_table().set_on(on != 0);
+  return MMDTI_OK;
+}
+extern "C" int mmdti_det_workspace(mmdti_stream_t stream, void* ws, long long bytes) {
+  MMDTI_REQUIRE(det_table().put(stream, ws, bytes), "det_workspace: a workspace needs bytes > 0 and 16-byte alignment");
+  return MMDTI_OK;
+}
+extern "C" int mmdti_det_workspace_bytes(int site, long long rows, long long cols, long long* bytes_out) {
+  MMDTI_REQUIRE(bytes_out != nullptr, "det_workspace_bytes: null bytes_out");
+  const long long b = det_workspace_bytes(site, rows, cols);
+  MMDTI_REQUIRE(b >= 0, "det_workspace_bytes: unknown site %d or bad shape (%lld x %lld)", site, rows, cols);
+  *bytes_out = b;
+  return MMDTI_OK;
+}
+
 // Adam's bias corrections of step t as mmdti_adam_step computes them by value (host powf): also what mmdti_adam_bias_table lists,
 // so that a guarded eager step reproduces the unguarded one to the bit
 static void adam_bias_host(float beta1, float beta2, int step, float* bc1, float* bc2_sqrt) {
@@ -740,8 +782,17 @@ extern "C" int mmdti_colsum_bf16(mmdti_stream_t stream, const void* x_bf16, int 
   MMDTI_REQUIRE(ld % 8 == 0 && aligned16(x_bf16), "colsum_bf16: ld%%8 and 16-byte alignment required");
   // 8 rows per thread (two rounds of four 16-byte loads): enough workgroups to fill 256 CUs several times over --
   // the reduction is latency-bound at one workgroup per CU
-  int gy = cdiv(rows, 8 * 8);
-  if (gy > 1024) gy = 1024;
+  const int gy = colsum_grid_y(rows);
+  if (det_table().on()) {
+    // the deterministic mode: one row of the stream's workspace per row group, folded in row-group order (never atomics)
+    float* slab = nullptr;
+    if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_COLSUM, rows, cols), "colsum_bf16", &slab)) return e;
+    hipLaunchKernelGGL(colsum_bf16_slab_kernel, dim3(cdiv(cols, 256), gy), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x_bf16, rows,
+                       cols, ld, slab);
+    det_fold<1>((hipStream_t)stream, slab, gy, cols, cols, DetDst<1>{{out}});
+    MMDTI_LAUNCH_CHECK();
+    return MMDTI_OK;
+  }
   hipLaunchKernelGGL(colsum_bf16_kernel, dim3(cdiv(cols, 256), gy), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x_bf16, rows, cols, ld, out);
   MMDTI_LAUNCH_CHECK();
@@ -761,6 +812,12 @@ extern "C" int mmdti_embedding_fwd(mmdti_stream_t stream, const long long* ids, 
 extern "C" int mmdti_embedding_bwd(mmdti_stream_t stream, const long long* ids, const float* dout, long long n,
                                    int D, int vocab, long long padding_idx, float* dtable) {
   MMDTI_REQUIRE(ids && dout && dtable && n > 0 && D > 0 && vocab > 0, "embedding_bwd: bad arguments");
+  if (det_table().on()) {                // (the model takes mmdti_onehot_bf16 + the split-K GEMM; this is the general entry's ordered form)
+    hipLaunchKernelGGL(embedding_bwd_ordered_kernel, dim3(cdiv(D, 256), vocab < 64 ? vocab : 64), dim3(256), 0, (hipStream_t)stream, ids, dout,
+                       n, D, vocab, padding_idx, dtable);
+    MMDTI_LAUNCH_CHECK();
+    return MMDTI_OK;
+  }
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3(grid_for(n * D, 256)), dim3(256), 0, (hipStream_t)stream, ids, dout,
                      n, D, vocab, padding_idx, dtable);
   MMDTI_LAUNCH_CHECK();
@@ -885,6 +942,7 @@ extern "C" int mmdti_sumsq_f32(mmdti_stream_t stream, const float* g, long long 
     hipLaunchKernelGGL(sumsq_fold_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, wgs, out, nullptr, nullptr, nullptr, 0,
                        0.f, 0.f);
   } else {
+    MMDTI_REQUIRE(!det_table().on(), "sumsq_f32: deterministic mode needs the ws form (16-byte aligned g, ws_floats >= 1): without it the partials meet in an atomic");
     hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, g, n, out);
   }
   MMDTI_LAUNCH_CHECK();

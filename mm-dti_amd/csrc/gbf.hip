@@ -134,6 +134,103 @@ __global__ __launch_bounds__(256) void gbf_bwd_kernel(const float* __restrict__ 
   }
 }
 
+// The deterministic mode's form of gbf_bwd_kernel: the same per-pair arithmetic, but nothing meets in an atomic --
+//   * the 16 pairs of an iteration stage (edge type, dy * d, dy) in LDS and the thread that owns histogram bin c adds them in pair order;
+//   * the four waves' d means / d stds partials are added in wave order;
+//   * the workgroup stores its [2 E + 2 K] sums (mul | bias | means | stds) to its slot of `slab`; det_fold_kernel adds the slots.
+__global__ __launch_bounds__(256) void gbf_bwd_det_kernel(const float* __restrict__ dist, const long long* __restrict__ et,
+                                                          const float* __restrict__ mul, const float* __restrict__ bias,
+                                                          const float* __restrict__ means, const float* __restrict__ stds,
+                                                          long long P, int K, int E, const bf16_t* __restrict__ dfeat,
+                                                          float* __restrict__ slab) {
+  extern __shared__ float hist[];  // [2][E]
+  __shared__ int se[16];
+  __shared__ float sa[16], sb[16];
+  __shared__ float red[4][16][16];   // [wave][kc][amu 0..7 | asg 0..7]
+  float* const sl = slab + (long long)blockIdx.x * (2 * E + 2 * K);
+  for (int i = threadIdx.x; i < 2 * E; i += 256) hist[i] = 0.f;
+  __syncthreads();
+  const int kc = threadIdx.x & 15, pl = threadIdx.x >> 4, wave = threadIdx.x >> 6;
+  for (int kb = 0; kb < K; kb += 128) {  // uniform trip count: the body shuffles across lanes and meets at barriers
+    const int k0 = kb + kc * 8;
+    const bool kact = k0 < K;
+    float mu[8], sg[8], cf[8], amu[8], asg[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      mu[i] = kact ? means[k0 + i] : 0.f;
+      sg[i] = kact ? fabsf(stds[k0 + i]) + 1e-5f : 1.f;
+      cf[i] = 1.0f / (GBF_A * sg[i]);
+      amu[i] = asg[i] = 0.f;
+    }
+    for (long long p0 = (long long)blockIdx.x * 16; p0 < P; p0 += (long long)gridDim.x * 16) {
+      const long long p = p0 + pl;
+      float dy = 0.f;
+      long long e = 0;
+      float d = 0.f;
+      if (p < P && kact) {
+        e = et[p];
+        e = e < 0 ? 0 : (e >= E ? E - 1 : e);
+        d = dist[p];
+        const float y = mul[e] * d + bias[e];
+        const uint4 u = *reinterpret_cast<const uint4*>(dfeat + p * K + k0);
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float dv = __uint_as_float((i & 1) ? (w[i >> 1] & 0xffff0000u) : (w[i >> 1] << 16));
+          const float z = (y - mu[i]) / sg[i];
+          const float val = __expf(-0.5f * z * z) * cf[i];
+          const float t = dv * val;
+          const float zs = z / sg[i];
+          dy -= t * zs;
+          amu[i] += t * zs;
+          asg[i] += t * (z * zs - 1.0f / sg[i]);
+        }
+      }
+      dy += __shfl_xor(dy, 1, 64);
+      dy += __shfl_xor(dy, 2, 64);
+      dy += __shfl_xor(dy, 4, 64);
+      dy += __shfl_xor(dy, 8, 64);
+      if (kc == 0) {
+        se[pl] = p < P ? (int)e : -1;
+        sa[pl] = dy * d;
+        sb[pl] = dy;
+      }
+      __syncthreads();
+      for (int c = threadIdx.x; c < E; c += 256) {
+        float ha = hist[c], hb = hist[E + c];
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          if (se[q] == c) { ha += sa[q]; hb += sb[q]; }
+        hist[c] = ha;
+        hist[E + c] = hb;
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float a = amu[i], sv = asg[i];
+      a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
+      sv += __shfl_xor(sv, 16, 64); sv += __shfl_xor(sv, 32, 64);
+      if ((threadIdx.x & 63) < 16) {
+        red[wave][kc][i] = a;
+        red[wave][kc][8 + i] = sv;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 16 && kact) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float a = ((red[0][kc][i] + red[1][kc][i]) + red[2][kc][i]) + red[3][kc][i];
+        const float sv = ((red[0][kc][8 + i] + red[1][kc][8 + i]) + red[2][kc][8 + i]) + red[3][kc][8 + i];
+        sl[2 * E + k0 + i] = a;
+        sl[2 * E + K + k0 + i] = stds[k0 + i] < 0.f ? -sv : sv;  // d|std|/dstd
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i < 2 * E; i += 256) sl[i] = hist[i];
+}
+
 // [B,N,N,H] fp32 -> [B,H,N,ld] fp32.  One block per (b,i): the [N][H] slab is contiguous.
 __global__ __launch_bounds__(256) void pair_permute_fwd_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                                int N, int H, int ld) {
@@ -679,7 +776,13 @@ __device__ __forceinline__ gbf16x8 gbf_tr8(const bf16_t* a0, const bf16_t* a1) {
 }
 
 // TILED: a tile is one 4x4 block of pairs, tpm = ceil(N/4)^2 per molecule (only blocks that hold a real pair are enumerated).
-template <bool TILED, typename GT>
+// DET (the deterministic mode): the two places where the waves of a workgroup meet in LDS float atomics take a fixed order instead --
+//   * the per-pair dy partials of phase B1 go to a private row per wave (sDyW [8][128]) and are added in wave order;
+//   * phase B2 stages the tile's (edge type, dy * d, dy) per pair, and after the barrier the thread that owns histogram bin c adds the
+//     tile's pairs of that edge type in pair order.
+// With the per-workgroup slabs (required in the mode) every sum of this kernel then has an order that depends on the grid alone.
+constexpr size_t GBF_DET_SMEM = (size_t)(8 * 128 + 3 * 128) * 4;
+template <bool TILED, typename GT, bool DET = false>
 __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     const GT* __restrict__ gsrc, const float* __restrict__ dist, const void* __restrict__ et, int esz, const float* __restrict__ mul,
     const float* __restrict__ bias, const float* __restrict__ means, const float* __restrict__ stds, const bf16_t* __restrict__ W1,
@@ -701,6 +804,10 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
   float* hist = sDy + 128;                                       // [2][E]
   float* sMul = hist + 2 * E;                                    // [E]
   float* sBia = sMul + E;                                        // [E]
+  float* sDyW = sBia + E;                                        // DET only: [8 waves][128] dL/dy partials | [128] edge type | [128] dy * d | [128] dy
+  int* sHe = reinterpret_cast<int*>(sDyW + 8 * 128);
+  float* sHa = reinterpret_cast<float*>(sHe + 128);
+  float* sHb = sHa + 128;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int c = tid; c < E; c += 512) {
     sMul[c] = mul[c];
@@ -963,7 +1070,10 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
         float dy = dy2[0] + dy2[1];
         dy += __shfl_xor(dy, 16, 64);
         dy += __shfl_xor(dy, 32, 64);
-        if (g == 0) atomicAdd(&sDy[16 * j + i], dy);
+        if (g == 0) {
+          if constexpr (DET) sDyW[128 * wave + 16 * j + i] = dy;
+          else atomicAdd(&sDy[16 * j + i], dy);
+        }
       }
     }
     __syncthreads();                                   // every wave has read basis / du; sDy complete
@@ -981,14 +1091,39 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
       *reinterpret_cast<gbf16x8*>(r1hi + 32 + 8 * g) = oL[1];
     }
     if (g == 0) {
-      const float dyv = sDy[ploc];
-      sDy[ploc] = 0.f;
-      if (valid) {
-        atomicAdd(&hist[e], dyv * d);
-        atomicAdd(&hist[E + e], dyv);
+      if constexpr (DET) {
+        float dyv = sDyW[ploc];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) dyv += sDyW[128 * w + ploc];
+        sHe[ploc] = valid ? e : -1;
+        sHa[ploc] = dyv * d;
+        sHb[ploc] = dyv;
+      } else {
+        const float dyv = sDy[ploc];
+        sDy[ploc] = 0.f;
+        if (valid) {
+          atomicAdd(&hist[e], dyv * d);
+          atomicAdd(&hist[E + e], dyv);
+        }
       }
     }
     __syncthreads();
+    if constexpr (DET) {
+      // bin c's owner adds the tile's pairs of edge type c in pair order (the staging rows are rewritten after the next iteration's barriers)
+      for (int c = tid; c < E; c += 512) {
+        float ha = hist[c], hb = hist[E + c];
+#pragma unroll 4
+        for (int p4 = 0; p4 < 32; ++p4) {
+          const int4 ev = reinterpret_cast<const int4*>(sHe)[p4];
+          if (ev.x == c) { ha += sHa[4 * p4]; hb += sHb[4 * p4]; }
+          if (ev.y == c) { ha += sHa[4 * p4 + 1]; hb += sHb[4 * p4 + 1]; }
+          if (ev.z == c) { ha += sHa[4 * p4 + 2]; hb += sHb[4 * p4 + 2]; }
+          if (ev.w == c) { ha += sHa[4 * p4 + 3]; hb += sHb[4 * p4 + 3]; }
+        }
+        hist[c] = ha;
+        hist[E + c] = hb;
+      }
+    }
 #pragma unroll
     for (int sstep = 0; sstep < 4; ++sstep) {
       const gbf16x8 fb = GBF_TFRAG(t0w, sstep);                // hidden columns 16*wave ..
@@ -1169,6 +1304,22 @@ extern "C" int mmdti_gbf_features_bwd(mmdti_stream_t stream, const float* dist, 
   MMDTI_REQUIRE(dist && edge_type && mul && bias && means && stds && dfeat_bf16 && dmul && dbias && dmeans && dstds,
                 "gbf_features_bwd: null pointer");
   MMDTI_REQUIRE(aligned16(dfeat_bf16), "gbf_features_bwd: dfeat must be 16-byte aligned");
+  if (det_table().on()) {
+    // the deterministic mode: per-workgroup slabs [mul | bias | means | stds] in the stream's workspace, folded in workgroup order
+    MMDTI_REQUIRE(E <= GBF_MAXE, "gbf_features_bwd: deterministic mode keeps the mul / bias histograms in LDS (E <= %d, got %d)", GBF_MAXE, E);
+    const int SL = 2 * E + 2 * K, grid = gbf_features_bwd_grid(P);
+    float* slab = nullptr;
+    if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_GBF_FEATURES_BWD, P, SL), "gbf_features_bwd", &slab)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(gbf_bwd_det_kernel, dim3(grid), dim3(256), 2 * (size_t)E * sizeof(float), st, dist, edge_type, mul, bias, means, stds, P, K,
+                       E, (const bf16_t*)dfeat_bf16, slab);
+    det_fold<1>(st, slab, grid, SL, E, DetDst<1>{{dmul}});
+    det_fold<1>(st, slab + E, grid, SL, E, DetDst<1>{{dbias}});
+    det_fold<1>(st, slab + 2 * E, grid, SL, K, DetDst<1>{{dmeans}});
+    det_fold<1>(st, slab + 2 * E + K, grid, SL, K, DetDst<1>{{dstds}});
+    MMDTI_LAUNCH_CHECK();
+    return MMDTI_OK;
+  }
   long long blocks = (P + 15) / 16;
   if (blocks > 256 * 8) blocks = 256 * 8;
   const size_t smem = E <= GBF_MAXE ? 2 * (size_t)E * sizeof(float) : 0;
@@ -1266,6 +1417,7 @@ extern "C" int mmdti_gbf_bias_bwd(mmdti_stream_t stream, const void* g, const fl
   // bit 0: tiled pair layout; bit 1: u_bf16 holds gelu'(u); bit 2: compact planes (g is bf16; tiled only)
   const int tiled = flags & 1, ugrad = (flags >> 1) & 1, compact = (flags >> 2) & 1;
   MMDTI_REQUIRE(!compact || tiled, "gbf_bias_bwd: compact planes (flags bit 2) exist in the tiled layout only");
+  MMDTI_DET_REFUSE("gbf_bias_bwd (LDS float histograms of mul / bias)");
   MMDTI_REQUIRE(g && dist && edge_type && mul && bias && means && stds && w1_bf16 && w2_bf16 && u_bf16 && do_bf16 && du_bf16 && dmul &&
                     dbias && dmeans && dstds, "gbf_bias_bwd: null argument");
   MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_bwd: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
@@ -1320,7 +1472,27 @@ extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, con
   const int tpm = tiled ? nb * nb : cdiv((long long)N * ld, 16);
   const long long ntiles = (long long)B * tpm;
   const int grid = (int)((ntiles + 7) / 8 < 256 ? (ntiles + 7) / 8 : 256);
-  const size_t smem = gbf_full_smem(E);
+  const bool det = det_table().on();
+  const size_t smem = gbf_full_smem(E) + (det ? GBF_DET_SMEM : 0);
+  const long long SL = GBF_SLAB + 2 * (long long)E;
+  float* slab = (workspace && aligned16(workspace) && workspace_bytes >= (long long)grid * SL * 4) ? reinterpret_cast<float*>(workspace) : nullptr;
+  if (det) {
+    // the mode takes the slab form only (never the atomics of a launch without a workspace: MMDTI_GBF_SLABS=0), and its LDS staging rows
+    MMDTI_REQUIRE(slab != nullptr, "gbf_bias_bwd_full: deterministic mode needs the workspace of mmdti_gbf_bias_bwd_full_workspace (%lld bytes): without it the partial sums meet in atomics",
+                  (long long)grid * SL * 4);
+    MMDTI_REQUIRE(smem <= 160 * 1024, "gbf_bias_bwd_full: deterministic mode: %d edge types do not fit LDS next to the staging rows", E);
+    static bool det_attr_done = false;
+    if (!det_attr_done) {
+      const int cap = 160 * 1024;
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
+        set_error("gbf_bias_bwd_full: hipFuncSetAttribute failed");
+        return MMDTI_ERR_LAUNCH;
+      }
+      det_attr_done = true;
+    }
+  }
   static bool attr_done = false;
   if (!attr_done) {
     const int cap = (int)gbf_full_smem(GBF_FULL_MAXE);
@@ -1336,11 +1508,15 @@ extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, con
   hipLaunchKernelGGL((gbf_bias_bwd_full_kernel<TILED, GT>), dim3(grid), dim3(512), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, \
                      bias, means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds, B, \
                      N, ld, E, tpm, tile_prefix, row_blocks, slab)
+#define GBF_FD(TILED, GT)                                                                                                          \
+  hipLaunchKernelGGL((gbf_bias_bwd_full_kernel<TILED, GT, true>), dim3(grid), dim3(512), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, \
+                     bias, means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds, B, \
+                     N, ld, E, tpm, tile_prefix, row_blocks, slab)
   // (a workspace of at least grid slots: partial sums in per-workgroup slabs + a fixed-order reduce; else fp32 atomics)
-  const long long SL = GBF_SLAB + 2 * (long long)E;
-  float* slab = (workspace && aligned16(workspace) && workspace_bytes >= (long long)grid * SL * 4) ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (compact) GBF_FB(true, __bf16); else if (tiled) GBF_FB(true, float); else GBF_FB(false, float);
+  if (det) { if (compact) GBF_FD(true, __bf16); else if (tiled) GBF_FD(true, float); else GBF_FD(false, float); }
+  else if (compact) GBF_FB(true, __bf16); else if (tiled) GBF_FB(true, float); else GBF_FB(false, float);
 #undef GBF_FB
+#undef GBF_FD
   if (slab)
     hipLaunchKernelGGL(gbf_slab_reduce_kernel, dim3(cdiv(SL, 64)), dim3(256), 0, (hipStream_t)stream, slab, grid, E, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds);
   MMDTI_LAUNCH_CHECK();

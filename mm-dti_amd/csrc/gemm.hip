@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs a) {
   // unaligned outputs go through a private 16 x 68 fp32 LDS patch per wave so that a wave instruction covers 256
   // contiguous bytes of one C row.  Literal accumulator indices throughout (a rolled loop would index acc[][]
   // dynamically and push it to scratch).  The K-loop ends on a barrier, so the patches may overwrite the tiles.
-  const long long coff = zo * a.sCo + zi * a.sCi;
+  const long long coff = zo * a.sCo + zi * a.sCi + a.slab * ks;      // (slab mode: every split owns a private fp32 copy of the output)
   const bool lead = (ks == 0);
   const int g4 = (lane >> 4) * 4, l15 = lane & 15;
   if (a.c_dtype != MMDTI_DT_F32_ATOMIC && a.vec_ok) {
@@ -768,7 +768,7 @@ __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_k
 #undef GEMM_KK
 #undef MF
   if (TA && DBUF == 1 && do_rs) arowsum_flush(a, rs0, rs1, rs2, rs3, m0 + wr * 64, lane);
-  const long long coff = zo * a.sCo + zi * a.sCi;
+  const long long coff = zo * a.sCo + zi * a.sCi + a.slab * ks;      // (slab mode: every split owns a private fp32 copy of the output)
   const bool lead = (ks == 0);
   const int g4 = (lane >> 4) * 4, l15 = lane & 15;
   if (a.c_dtype != MMDTI_DT_F32_ATOMIC && a.vec_ok) {
@@ -1930,13 +1930,52 @@ extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void*
                            alpha, beta, bias, residual, ldr, act, aux_in, aux_out, ld_aux, c_dtype, drop_p, seed, site, colsum_out, arowsum_out,
                            workspace, workspace_bytes))
     return e;
+  hipStream_t s = (hipStream_t)stream;
+  const long long slab = (long long)M * N;
+  float* colsum_after = nullptr;
+  if (det_table().on()) {
+    // ---- the deterministic mode.  Nothing is launched before every requirement is known to hold.
+    //  * arowsum (a bias gradient): in the kernels every K split adds into it -- the fixed-order column-sum pass over A's image instead;
+    //  * colsum (a bias gradient from the epilogue, one adder per row tile): the fixed-order column-sum pass over the stored bf16 C instead;
+    //  * split-K into an atomic C: the splits store to slabs of the stream's workspace and splitk_reduce_kernel adds them in split
+    //    order; the split count is lowered until the slabs fit, down to one split (a single adder per element).
+    const bool split = a.c_dtype == MMDTI_DT_F32_ATOMIC && plan.splitk > 1;
+    DetSlot slot = {nullptr, nullptr, 0};
+    const bool have_ws = det_table().get(stream, &slot);
+    if (arowsum_out) {
+      MMDTI_REQUIRE(have_ws && slot.bytes >= det_workspace_bytes(MMDTI_DET_COLSUM, K, M),
+                    "gemm (arowsum bias gradient): deterministic mode is on and stream %p has no reduction workspace of %lld bytes (mmdti_det_workspace)",
+                    stream, det_workspace_bytes(MMDTI_DET_COLSUM, K, M));
+      a.arowsum = nullptr;
+      plan.arowsum = AROWSUM_COLSUM_PASS;
+    }
+    if (colsum_out) {
+      MMDTI_REQUIRE(a.c_dtype == MMDTI_DT_BF16 && !a.c_f16 && batch_outer * batch_inner == 1 && ldc % 8 == 0 && aligned16(C),
+                    "gemm (colsum bias gradient): deterministic mode sums the stored bf16 output; this output has no such pass");
+      MMDTI_REQUIRE(have_ws && slot.bytes >= det_workspace_bytes(MMDTI_DET_COLSUM, M, N),
+                    "gemm (colsum bias gradient): deterministic mode is on and stream %p has no reduction workspace of %lld bytes (mmdti_det_workspace)",
+                    stream, det_workspace_bytes(MMDTI_DET_COLSUM, M, N));
+      colsum_after = colsum_out;
+      a.colsum = nullptr;
+    }
+    if (split && !plan.slabs) {
+      const bool slab_ok = batch_outer * batch_inner == 1 && N % 8 == 0 && alpha == 1.f && !bias && !residual && act == MMDTI_ACT_NONE &&
+                           aligned16(C) && ldc % 4 == 0 && have_ws;
+      const int sk = slab_ok ? det_fit_splits(plan.splitk, cdiv(K, BK), slab, slot.bytes) : 1;
+      plan.grid_z = plan.grid_z / plan.splitk * sk;
+      plan.splitk = sk;
+      a.splitk = sk;
+      if (sk > 1) {
+        plan.slabs = 1;
+        workspace = slot.ws;
+      }
+    }
+  }
   const void* fn = gemm_kernel(plan);
   MMDTI_REQUIRE(fn != nullptr, "gemm: no kernel instance for the planned family %d", plan.family);
   if (int e = ensure_dynamic_lds(fn, plan.lds, "gemm")) return e;
   if (plan.arowsum == AROWSUM_COLSUM_PASS)
     if (int e = mmdti_colsum_bf16(stream, A, K, M, lda, arowsum_out)) return e;
-  hipStream_t s = (hipStream_t)stream;
-  const long long slab = (long long)M * N;
   if (plan.slabs) {
     // split ks stores its partial tile into slab ks (vector epilogue, plain stores); splitk_reduce_kernel adds the sum into C
     a.C = workspace; a.ldc = N; a.c_dtype = MMDTI_DT_F32; a.beta = 0.f; a.vec_ok = 1; a.slab = slab;
@@ -1949,6 +1988,7 @@ extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void*
                        reinterpret_cast<float*>(C), M, N, ldc, plan.splitk);
   }
   MMDTI_LAUNCH_CHECK();
+  if (colsum_after) return mmdti_colsum_bf16(stream, C, M, N, ldc, colsum_after);
   return MMDTI_OK;
 }
 
@@ -2054,6 +2094,28 @@ extern "C" int mmdti_linear_dw_grouped(mmdti_stream_t stream, int nprob, const v
   const void* fn = grouped_dw_kernel(plan);
   if (int e = ensure_dynamic_lds(fn, plan.lds, "linear_dw_grouped")) return e;
   hipStream_t s = (hipStream_t)stream;
+  if (det_table().on() && !plan.small) {
+    // the deterministic mode, big form: always the slab pass (the caller's workspace holds plan.splitk slabs), and the bias gradients --
+    // which every K split of the kernel would add into -- through the fixed-order column-sum pass over dy, checked before any launch
+    plan.atomic = 0; g.atomic = 0;
+    DetSlot slot = {nullptr, nullptr, 0};
+    const bool have_ws = det_table().get(stream, &slot);
+    for (int i = 0; i < nprob; ++i)
+      if (g.p[i].arowsum) {
+        // (everything mmdti_colsum_bf16 asks of dy_i, so that no pass can refuse once an earlier one is queued: alignment and
+        //  ldy % 8 are required above)
+        MMDTI_REQUIRE(ldy[i] >= n_out[i], "linear_dw_grouped (bias gradient): ldy %d below n_out %d (problem %d)", ldy[i], n_out[i], i);
+        MMDTI_REQUIRE(have_ws && slot.bytes >= det_workspace_bytes(MMDTI_DET_COLSUM, rows, n_out[i]),
+                      "linear_dw_grouped (bias gradient): deterministic mode is on and stream %p has no reduction workspace of %lld bytes (mmdti_det_workspace)",
+                      stream, det_workspace_bytes(MMDTI_DET_COLSUM, rows, n_out[i]));
+      }
+    for (int i = 0; i < nprob; ++i)
+      if (g.p[i].arowsum) {
+        if (int e = mmdti_colsum_bf16(stream, dy_bf16[i], rows, n_out[i], ldy[i], g.p[i].arowsum)) return e;
+        g.p[i].arowsum = nullptr;
+      }
+    for (int i = nprob; i < GROUP_MAX; ++i) g.p[i].arowsum = nullptr;
+  }
   void* kargs[1] = {&g};
   (void)hipLaunchKernel(fn, dim3(plan.grid_x, 1, plan.grid_z), dim3(plan.block), kargs, (size_t)plan.lds, s);
   if (!plan.small && !plan.atomic) {

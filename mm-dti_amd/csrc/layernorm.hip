@@ -77,17 +77,19 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // registers over the wave's rows, combined across the 4 waves in LDS and added to global with one atomic per column.
 constexpr int LN_BWD_MIN_ROWS_PER_WAVE = 4;
 
-template <int NV, bool DY_BF16>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy_, const float* __restrict__ dy_add,
-                                                     const float* __restrict__ x,
-                                                     const float* __restrict__ gamma, const float* __restrict__ mean_i,
-                                                     const float* __restrict__ rstd_i, int rows, int D,
-                                                     const float* __restrict__ dres, float* __restrict__ dx,
-                                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                     const unsigned char* __restrict__ row_zero, uint32_t thresh,
-                                                     float dscale, uint64_t seed, uint32_t site,
-                                                     bf16_t* __restrict__ dx_bf16, uint32_t thresh2, float dscale2,
-                                                     uint32_t site2, float* __restrict__ dx_colsum, int rpw) {
+// SLAB (the deterministic mode): the workgroup's three [D] partials go to its own slot of `slab` ([workgroups][3][D], plain stores)
+// and det_fold_kernel, queued directly behind, adds the slots in workgroup order into dgamma / dbeta / dx_colsum -- no atomics.
+template <int NV, bool DY_BF16, bool SLAB>
+__device__ __forceinline__ void ln_bwd_body(const void* __restrict__ dy_, const float* __restrict__ dy_add,
+                                            const float* __restrict__ x,
+                                            const float* __restrict__ gamma, const float* __restrict__ mean_i,
+                                            const float* __restrict__ rstd_i, int rows, int D,
+                                            const float* __restrict__ dres, float* __restrict__ dx,
+                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                            const unsigned char* __restrict__ row_zero, uint32_t thresh,
+                                            float dscale, uint64_t seed, uint32_t site,
+                                            bf16_t* __restrict__ dx_bf16, uint32_t thresh2, float dscale2,
+                                            uint32_t site2, float* __restrict__ dx_colsum, int rpw, float* __restrict__ slab) {
   extern __shared__ __attribute__((aligned(16))) float red[];  // [3][4][D]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nvec = D >> 2;
@@ -218,17 +220,42 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
   for (int c = threadIdx.x; c < D; c += 256) {
     float g = red[c] + red[D + c] + red[2 * D + c] + red[3 * D + c];
     float b = red[4 * D + c] + red[5 * D + c] + red[6 * D + c] + red[7 * D + c];
-    if (dgamma) atomicAdd(dgamma + c, g);
-    if (dbeta) atomicAdd(dbeta + c, b);
-    if (dx_colsum) atomicAdd(dx_colsum + c, red[8 * D + c] + red[9 * D + c] + red[10 * D + c] + red[11 * D + c]);
+    if (SLAB) {
+      float* sl = slab + (long long)blockIdx.x * 3 * D;
+      sl[c] = g;
+      sl[D + c] = b;
+      if (dx_colsum) sl[2 * D + c] = red[8 * D + c] + red[9 * D + c] + red[10 * D + c] + red[11 * D + c];
+    } else {
+      if (dgamma) atomicAdd(dgamma + c, g);
+      if (dbeta) atomicAdd(dbeta + c, b);
+      if (dx_colsum) atomicAdd(dx_colsum + c, red[8 * D + c] + red[9 * D + c] + red[10 * D + c] + red[11 * D + c]);
+    }
   }
 }
+
+#define LN_BWD_PARAMS                                                                                                          \
+  const void* __restrict__ dy_, const float* __restrict__ dy_add, const float* __restrict__ x, const float* __restrict__ gamma, \
+      const float* __restrict__ mean_i, const float* __restrict__ rstd_i, int rows, int D, const float* __restrict__ dres,     \
+      float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta, const unsigned char* __restrict__ row_zero, \
+      uint32_t thresh, float dscale, uint64_t seed, uint32_t site, bf16_t* __restrict__ dx_bf16, uint32_t thresh2, float dscale2, \
+      uint32_t site2, float* __restrict__ dx_colsum, int rpw
+#define LN_BWD_ARGS                                                                                                               \
+  dy_, dy_add, x, gamma, mean_i, rstd_i, rows, D, dres, dx, dgamma, dbeta, row_zero, thresh, dscale, seed, site, dx_bf16, thresh2, \
+      dscale2, site2, dx_colsum, rpw
+template <int NV, bool DY_BF16>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(LN_BWD_PARAMS) {
+  ln_bwd_body<NV, DY_BF16, false>(LN_BWD_ARGS, nullptr);
+}
+template <int NV, bool DY_BF16>
+__global__ __launch_bounds__(256) void ln_bwd_slab_kernel(LN_BWD_PARAMS, float* __restrict__ slab) {
+  ln_bwd_body<NV, DY_BF16, true>(LN_BWD_ARGS, slab);
+}
+#undef LN_BWD_PARAMS
+#undef LN_BWD_ARGS
 
 }  // namespace mmdti
 MMDTI_DEFINE_SALT_PULL(layernorm)
 using namespace mmdti;
-
-static int ln_nv(int D) { return (D / 4 + 63) / 64; }
 
 extern "C" int mmdti_layernorm_fwd(mmdti_stream_t stream, const float* x, const float* gamma, const float* beta,
                                    float eps, int rows, int D, float* y_f32, void* y_bf16, float* mean, float* rstd,
@@ -273,11 +300,31 @@ extern "C" int mmdti_layernorm_bwd(mmdti_stream_t stream, const void* dy, int dy
   const float sc2 = drop2_p > 0.f ? 1.f / (1.f - drop2_p) : 1.f;
   // rows per wave: enough that the whole grid is resident at once (3 workgroups of 4 waves per CU at this kernel's
   // register count, 2 for the wide-row variants) -- no second, partly filled round, and fewer dgamma / dbeta atomics
-  const int rpw = max(LN_BWD_MIN_ROWS_PER_WAVE, cdiv(rows, 4 * (ln_nv(D) <= 2 ? 3 : 2) * 256));
-  dim3 grid(cdiv(rows, 4 * rpw)), block(256);
+  const int rpw = ln_bwd_rows_per_wave(rows, D);
+  static_assert(LN_BWD_MIN_ROWS_PER_WAVE == 4, "det.h states the same floor");
+  dim3 grid(ln_bwd_grid(rows, D)), block(256);
   MMDTI_REQUIRE(!dx_colsum || dx_bf16, "layernorm_bwd: dx_colsum sums the bf16 copy, which was not requested");
   const size_t smem = 12 * (size_t)D * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
+  if (det_table().on() && (dgamma || dbeta || dx_colsum)) {
+    // the deterministic mode: per-workgroup slabs in the stream's workspace, folded in workgroup order (never atomics)
+    float* slab = nullptr;
+    if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_LAYERNORM_BWD, rows, D), "layernorm_bwd", &slab)) return e;
+#define LN_S(NV, BF)                                                                                                        \
+  hipLaunchKernelGGL((ln_bwd_slab_kernel<NV, BF>), grid, block, smem, s, dy, dy_add, x, gamma, mean, rstd, rows, D, dres, dx,   \
+                     dgamma, dbeta, row_zero, th, sc, (uint64_t)seed, (uint32_t)site, (bf16_t*)dx_bf16, th2, sc2, (uint32_t)site2, dx_colsum, rpw, slab)
+    const bool bf16 = dy_dtype == MMDTI_DT_BF16;
+    switch (ln_nv(D)) {
+      case 1: if (bf16) LN_S(1, true); else LN_S(1, false); break;
+      case 2: if (bf16) LN_S(2, true); else LN_S(2, false); break;
+      case 3: case 4: if (bf16) LN_S(4, true); else LN_S(4, false); break;
+      default: if (bf16) LN_S(8, true); else LN_S(8, false); break;
+    }
+#undef LN_S
+    det_fold<3>(s, slab, (int)grid.x, 3ll * D, D, DetDst<3>{{dgamma, dbeta, dx_colsum}});
+    MMDTI_LAUNCH_CHECK();
+    return MMDTI_OK;
+  }
 #define LN_B(NV, BF)                                                                                               \
   hipLaunchKernelGGL((ln_bwd_kernel<NV, BF>), grid, block, smem, s, dy, dy_add, x, gamma, mean, rstd, rows, D, dres, dx,  \
                      dgamma, dbeta, row_zero, th, sc, (uint64_t)seed, (uint32_t)site, (bf16_t*)dx_bf16, th2, sc2, (uint32_t)site2, dx_colsum, rpw)

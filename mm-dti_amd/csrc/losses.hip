@@ -976,6 +976,7 @@ extern "C" int mmdti_ct_loss_fwd(mmdti_stream_t stream, int mode, const float* f
   MMDTI_REQUIRE(mode != MMDTI_CT_REGRESS || pred, "ct_loss_fwd: regress needs predictions");
   const size_t smem = ((size_t)D + B + 4) * sizeof(float);
   MMDTI_REQUIRE(smem <= 64 * 1024, "ct_loss_fwd: B+D too large for LDS");
+  MMDTI_REQUIRE(row_ws || !det_table().on(), "ct_loss_fwd: deterministic mode needs row_ws (without it the per-row terms meet in an atomic)");
   hipStream_t s = (hipStream_t)stream;
   // (row_ws: the per-row terms are stored and summed in row order by one thread; without it they meet in an fp32 atomic)
   if (!row_ws && hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) { set_error("ct_loss_fwd: memset failed"); return MMDTI_ERR_LAUNCH; }

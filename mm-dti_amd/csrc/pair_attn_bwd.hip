@@ -3,7 +3,8 @@
 
 namespace mmdti {
 
-template <int NCH>
+// DET (the deterministic mode): the four waves add their dK / dV partials one wave after the other instead of meeting in LDS atomics
+template <int NCH, bool DET = false>
 __global__ __launch_bounds__(256) void pair_attn_bwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ s,
                                                             const bf16_t* __restrict__ dO, float* __restrict__ g,
                                                             bf16_t* __restrict__ dqkv, int N, int H, int ld,
@@ -123,6 +124,24 @@ __global__ __launch_bounds__(256) void pair_attn_bwd_kernel(const bf16_t* __rest
     if (lane < 8) dqkv[((long long)b * N + i) * D3 + h * HD + lane] = f2bf(tot);
   }
   // combine the 4 waves' dK / dV partials through LDS atomics
+  if constexpr (DET) {
+    for (int w = 0; w < 4; ++w) {        // (a lane owns key j of its wave's partial: plain adds, waves in order 0, 1, 2, 3)
+      if (wave == w) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const int j = c * 64 + lane;
+          if (j < N) {
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+              red[j][d] += dk[c][d] * scale;
+              red[j][8 + d] += dv[c][d];
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+  } else {
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int j = c * 64 + lane;
@@ -133,6 +152,7 @@ __global__ __launch_bounds__(256) void pair_attn_bwd_kernel(const bf16_t* __rest
         atomicAdd(&red[j][8 + d], dv[c][d]);
       }
     }
+  }
   }
   __syncthreads();
   for (int t = tid; t < N; t += 256) {
@@ -205,6 +225,22 @@ extern "C" int mmdti_pair_attn_bwd(mmdti_stream_t stream, const void* qkv_bf16, 
   hipLaunchKernelGGL((pair_attn_bwd_kernel<NCH>), grid, block, 0, st, (const bf16_t*)qkv_bf16, (const float*)s,    \
                      (const bf16_t*)do_bf16, (float*)g, (bf16_t*)dqkv_bf16, N, H, ld, scale, g_in_zero, th, sc,            \
                      (uint64_t)seed, (uint32_t)site)
+#define PA_D(NCH)                                                                                                   \
+  hipLaunchKernelGGL((pair_attn_bwd_kernel<NCH, true>), grid, block, 0, st, (const bf16_t*)qkv_bf16, (const float*)s, \
+                     (const bf16_t*)do_bf16, (float*)g, (bf16_t*)dqkv_bf16, N, H, ld, scale, g_in_zero, th, sc,            \
+                     (uint64_t)seed, (uint32_t)site)
+  if (det_table().on()) {      // the deterministic mode: the waves of a workgroup add in wave order
+    switch ((N + 63) / 64) {
+      case 1: PA_D(1); break;
+      case 2: PA_D(2); break;
+      case 3: PA_D(3); break;
+      case 4: PA_D(4); break;
+      default: PA_D(5); break;
+    }
+    MMDTI_LAUNCH_CHECK();
+    return MMDTI_OK;
+  }
+#undef PA_D
   switch ((N + 63) / 64) {
     case 1: PA_B(1); break;
     case 2: PA_B(2); break;

@@ -596,7 +596,7 @@ def _stack_side():
         for e in evs:
             e.record(main)                       # (creates the hipEvent_t behind the handle)
         ent = _stack_sides[key] = (side, evs, _ptr_table([e.cuda_event for e in evs]))
-    return ent[0].cuda_stream, ent[2][1]
+    return ops.det_register(ent[0].cuda_stream), ent[2][1]
 
 
 def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, key_tiles, rag_store_last, row_off, scale, sites, tiled):

@@ -61,6 +61,93 @@ def _stream():
     return _raw_stream(_raw_device())
 
 
+# ---------------------------------------------------------------------------------- deterministic mode
+# Bit-identical parameter gradients run to run (DESIGN.md "Deterministic mode"; mmdti_set_deterministic in the header).  Off by
+# default: nothing below runs, _stream() stays the two-call function above and the library's flag is never written.  On
+# (set_deterministic(True), FineTuner(deterministic=True) or MMDTI_DETERMINISTIC=1): every stream a launch is taken from gets ONE
+# reduction workspace at its first use, registered with the library and kept alive until the mode is switched off (FineTuner.graphed_step
+# is refused in the mode: a captured graph would bake these addresses in).  MMDTI_DET_WORKSPACE_MB: its size (default 32; the LayerNorm backward of 2048-wide rows wants 12.6 MB,
+# a column sum over 2048 columns 8.4 MB; a split-K weight gradient lowers its split count to what fits).
+DET_DEFAULT_MB = 32
+
+
+def deterministic_default(env=None):
+    """MMDTI_DETERMINISTIC as a bool: unset, '', '0', 'false', 'off', 'no' are off, anything else on."""
+    v = (os.environ if env is None else env).get("MMDTI_DETERMINISTIC", "")
+    return v.strip().lower() not in ("", "0", "false", "off", "no")
+
+
+def det_workspace_mb(env=None):
+    v = (os.environ if env is None else env).get("MMDTI_DET_WORKSPACE_MB", "")
+    mb = int(v) if v.strip() else DET_DEFAULT_MB
+    if mb < 1:
+        raise MMDTIError(f"MMDTI_DET_WORKSPACE_MB must be at least 1 (got {mb})")
+    return mb
+
+
+_det_on = False
+_det_ws = {}               # raw stream handle -> its workspace tensor
+_stream_fast = _stream
+
+
+def det_register(handle):
+    """In the mode: make sure the stream behind this raw handle has its workspace (the streams handed to the library's sequencers
+    by value -- the stack backward's weight-gradient stream -- come through here; launch streams through _stream())."""
+    if _det_on and handle not in _det_ws:
+        ws = torch.empty(det_workspace_mb() << 20, device=torch.device("cuda", _raw_device()), dtype=torch.uint8)
+        lib().mmdti_det_workspace(handle, ws.data_ptr(), ws.numel())
+        _det_ws[handle] = ws
+    return handle
+
+
+def _stream_det():
+    h = _raw_stream(_raw_device())
+    if h not in _det_ws:
+        det_register(h)
+    return h
+
+
+def set_deterministic(on: bool):
+    """Switch the deterministic mode of this process.  Off -> on sets the library's flag; on -> off clears it and forgets every workspace."""
+    global _det_on, _stream
+    if on and not _det_on:
+        lib().mmdti_set_deterministic(1)
+        _det_on, _stream = True, _stream_det
+    elif not on:
+        if _det_on:
+            if torch.cuda.is_available():
+                torch.cuda.synchronize()
+            for h in list(_det_ws):
+                lib().mmdti_det_workspace(h, 0, 0)
+            _det_ws.clear()
+            lib().mmdti_set_deterministic(0)
+        _det_on, _stream = False, _stream_fast
+
+
+def is_deterministic():
+    return _det_on
+
+
+def _stream_boot():
+    # MMDTI_DETERMINISTIC=1: the mode is entered at the first launch (importing this module loads no library)
+    set_deterministic(True)
+    return _stream_det()
+
+
+if deterministic_default():
+    _stream = _stream_boot
+
+
+def det_workspace_bytes(site, rows, cols):
+    """bytes one launch of `site` ('layernorm_bwd', 'colsum', 'gemm_slab', 'gbf_features_bwd') needs of its stream's workspace"""
+    import ctypes
+    code = lib().const["MMDTI_DET_" + {"layernorm_bwd": "LAYERNORM_BWD", "colsum": "COLSUM", "gemm_slab": "GEMM_SLAB",
+                                       "gbf_features_bwd": "GBF_FEATURES_BWD"}[site]]
+    out = ctypes.c_longlong(0)
+    lib().mmdti_det_workspace_bytes(code, int(rows), int(cols), ctypes.byref(out))
+    return out.value
+
+
 def _p(t):
     return 0 if t is None else t.data_ptr()
 

@@ -218,6 +218,8 @@ class Trainer(object):
         self.amp = params.get('use_amp', False)
         # the skip-on-inf/NaN half of the reference's GradScaler (use_amp, :268-282): on exactly where the reference has a scaler
         self.skip_nonfinite = bool(params.get('skip_nonfinite', self.amp))
+        # bit-identical parameter gradients run to run (FineTuner(deterministic=...)); None: MMDTI_DETERMINISTIC decides
+        self.deterministic = params.get('deterministic', None)
         self.device = torch.device("cuda" if torch.cuda.is_available() and self.cuda else "cpu")
         self.scaler = None          # bf16 MFMA compute with fp32 master weights: no loss scaling (the reference: fp16 + GradScaler)
         self.alpha = params.get('alpha', 1)
@@ -335,7 +337,8 @@ class Trainer(object):
         num_training_steps = len(train_dataloader) * self.max_epochs
         engine = FineTuner(model, self.task, learning_rate=self.learning_rate, adam_eps=1e-6, warmup_ratio=0.0,
                            total_steps=num_training_steps, alpha=self.alpha, beta=self.beta,
-                           max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite)
+                           max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite,
+                           deterministic=self.deterministic)
         engine.warmup = int(num_training_steps * self.warmup_ratio)
         self._engine = engine
         task_loss = self._task_loss(loss_func)

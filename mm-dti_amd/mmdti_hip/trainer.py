@@ -63,14 +63,22 @@ def _qkv_groups(model):
 class FineTuner:
     def __init__(self, model, task: str, learning_rate=1e-4, adam_eps=1e-6, warmup_ratio=0.03, total_steps=1000, alpha=1.0, beta=0.1,
                  max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
-                 loss_key: Optional[str] = None):
-        """skip_nonfinite: GradScaler.step's guard (tasks/trainer.py:268-282) -- a step whose gradient arena holds any inf / NaN element
+                 loss_key: Optional[str] = None, deterministic: Optional[bool] = None):
+        """deterministic: True enters the process-wide deterministic mode (ops.set_deterministic: every cross-workgroup sum into a
+        parameter gradient in a fixed order, one reduction workspace per launch stream); None follows MMDTI_DETERMINISTIC; False (and
+        an unset environment) touches nothing.  Sites that have no fixed-order form yet raise in the mode (DESIGN.md lists them), and so
+        does graphed_step: the mode covers step().
+        skip_nonfinite: GradScaler.step's guard (tasks/trainer.py:268-282) -- a step whose gradient arena holds any inf / NaN element
         leaves the parameters, both Adam moments, Adam's step count and the 16-bit shadows as they were, while the learning-rate
         schedule advances.  The decision is taken on the device (no host synchronisation, captured inside graphed_step) from the
         all-reduced gradients under data parallelism, so every rank takes the same one.
         loss_key: the multilabel_classification loss table's key (models/nnmodel.py:28-32): None / 'bce' the BCE-with-logits kernel,
         'focal' / 'ghm' the kernels of ``losses.FocalLossWithLogits()`` / ``losses.GHMCLoss(10, 0.5)`` (kept as ``self.task_loss``)."""
         self.model, self.task = model, task
+        from . import ops
+        self.deterministic = ops.deterministic_default() if deterministic is None else bool(deterministic)
+        if self.deterministic:
+            ops.set_deterministic(True)
         self.lr, self.eps, self.alpha, self.beta, self.max_norm = learning_rate, adam_eps, alpha, beta, max_norm
         self.total_steps = total_steps
         self.warmup = int(total_steps * warmup_ratio)
@@ -215,6 +223,10 @@ class FineTuner:
         read them before the next call.  Not available under data parallelism (collectives are left out of graphs here)."""
         if self.reducer is not None:
             raise RuntimeError("graphed_step: not supported with distributed=True (use step())")
+        from . import ops
+        if self.deterministic or ops.is_deterministic():
+            # (the mode is process-wide; a graph would bake in the addresses of the per-stream reduction workspaces)
+            raise RuntimeError("graphed_step: not supported in the deterministic mode (use step())")
         # Host-side batch descriptors (atom_counts, token_counts, ...) select kernels and tile counts on the HOST at capture time;
         # a replay with another batch of the same padded shape would run with the captured batch's lengths.  The graph therefore
         # runs the padded layout: correct for any batch of the shape.
