@@ -29,6 +29,10 @@ extern "C" {
 
 typedef void* mmdti_stream_t;
 
+/* What mmdti_abi_version() of a library built from this header returns.  It changes with every incompatible change of a signature, a
+ * struct or a layout below; a binding compares the two before its first call (the host package does: _abi.py). */
+#define MMDTI_ABI_VERSION 2
+
 #define MMDTI_OK 0
 #define MMDTI_ERR_INVALID 1
 #define MMDTI_ERR_LAUNCH 2
@@ -168,128 +172,165 @@ int mmdti_linear_dw_grouped_splits(int tiles, int rows);
 int mmdti_linear_dw_grouped_plan(int nprob, const int* n_out, const int* n_in, int rows, int x_f16, int* plan_out,
                                  long long* workspace_bytes_out);
 
-/* ---- one Uni-Mol encoder layer's forward / backward behind one call each (launch sequencing in the library: at 16-32 molecules
- * the Python side of ~500 launches per step sets the pace).  Replaces the per-layer body of the encoder forward / backward -- unicore
- * TransformerEncoderLayer as driven by models/transformers.py:136-139 -- with the SAME eight launches the op-by-op host path
- * issues (fc2 / fc1 input gradients, LayerNorm-2 backward, out_proj input gradient, pair-attention backward, in_proj input
- * gradient, LayerNorm-1 backward, grouped weight gradients): bit-identical results.  Shapes and the workspace layout: layers.hip. */
-int mmdti_unimol_layer_fwd(mmdti_stream_t stream, int M, int B, int N, int H, int D, int F, int ld, float scale, float p_res,
-                           float p_att, unsigned long long seed, unsigned int site_att, unsigned int site_o, unsigned int site_f,
-                           const float* x, const void* h1, const void* s_in, const unsigned char* key_pad, int pair_layout,
-                           const int* key_tiles, int rag_store, const int* row_off, const void* w_in, const float* b_in,
-                           const void* w_out, const float* b_out, const float* g_ln2, const float* bt_ln2, float eps2,
-                           const void* w_fc1, const float* b_fc1, int act_fwd, const void* w_fc2, const float* b_fc2,
-                           int next_mode, const float* g_next, const float* bt_next, float eps_next, int ln_max_k, void* qkv,
-                           void* s_out, void* o_att, float* x1, void* h2, float* m2, float* r2, void* u_aux, void* a_act,
-                           float* x_out, void* ln_out, float* mn, float* rn,
-                           int fwd_f16 /* 1: the fp16 forward-operand mode -- every 16-bit operand of a forward GEMM (h1, weights, q | k | v,
-                                          o_att, h2, a_act, a 16-bit ln_out) holds fp16; pair_layout 3 only */);
-int mmdti_unimol_layer_bwd(mmdti_stream_t stream, int M, int B, int N, int H, int D, int F, int ld, float scale,
-                           float p_res, float p_att, unsigned long long seed, unsigned int site_f_below, unsigned int site_o,
-                           unsigned int site_att, const float* dx_in, const void* dy2, float* dx_out, void* dx16_out,
-                           float* db_below, const void* a_act, const void* u_aux, int act_dx, const void* h2, const float* x1,
-                           const float* m2, const float* r2, const void* o_att, const void* qkv, const void* s_logits,
-                           const void* h1, const float* x0, const float* m1, const float* r1, const void* w_fc2,
-                           const void* w_fc1, const void* w_out, const void* w_in, const float* g_ln2, const float* g_ln1,
-                           float* dw_fc2, float* dw_fc1, float* dw_out, float* dw_in, float* db_fc1, float* db_out,
-                           float* db_in, float* dg_ln2, float* dbt_ln2, float* dg_ln1, float* dbt_ln1, void* G,
-                           int pair_layout, int g_in_zero, const int* key_tiles, const int* row_off, void* ws,
-                           long long ws_bytes, int fwd_f16 /* 1: the saved a_act, h2, o_att, h1, qkv hold fp16 (weights: the bf16 shadow) */);
+/* ---- Sequenced layers: a whole layer's launches, or a whole tower's, behind ONE call (launch sequencing in the library: at 16-32
+ * molecules the Python side of ~500 launches per step sets the pace).  The SAME kernels, arguments and order as the op-by-op host
+ * path: bit-identical results.  What a call takes is grouped by role into the structs below -- a run block (the same for every layer
+ * of one call), one parameter block per layer, one saved-tensor block per layer -- so that a host names every pointer it hands over.
+ * Only pointers, int / unsigned int / float / (unsigned) long long and mmdti_stream_t fields, widest first: a binding reproduces the
+ * layout from the field list alone.  A field a call does not use may stay null; every call refuses a null it needs before its
+ * first launch.  Shapes and the workspace layouts: layers.hip. */
 
-/* ---- ALL layers of the Uni-Mol encoder behind one call per direction (the loop of models/transformers.py:136-139 in :96-183).  At
- * the reference's 16-32 molecules even the per-layer calls leave ~90 us of Python per layer and direction; these take the layers'
- * parameters as pointer tables and keep every saved tensor at a fixed offset of ONE caller-owned arena.  The launches are those of
- * nl x mmdti_unimol_layer_fwd / _bwd: bit-identical results.
- *   mmdti_unimol_stack_layout: out[0] = arena bytes per layer, out[1] = bytes of the backward workspace (s_bytes: one layer's pair
- *     logits; dw_slab_bytes: split-K slabs of one layer's grouped weight gradients, see mmdti_linear_dw_grouped_splits).
- *   params [nl][12]: w_in, b_in, w_out, b_out, g_ln2, bt_ln2, w_fc1, b_fc1, w_fc2, b_fc2, g_ln1, bt_ln1 (16-bit forward weights).
- *   bparams [nl][6]: w_fc2, w_fc1, w_out, w_in (bf16), g_ln2, g_ln1.   grads [nl][12]: dw_fc2, dw_fc1, dw_out, dw_in, db_fc2, db_fc1,
- *     db_out, db_in, dg_ln2, dbt_ln2, dg_ln1, dbt_ln1 (fp32, accumulated).
+/* Tower 1 (Uni-Mol encoder; unicore TransformerEncoderLayer as driven by models/transformers.py:136-139). */
+typedef struct {
+  const int *key_tiles, *row_off;      /* ragged batches / packed rows, as mmdti_pair_attn_fwd (nullable) */
+  unsigned long long seed;
+  int M, B, N, H, D, F, ld;            /* M token rows; pair planes [B,H,N,ld] */
+  int pair_layout;                     /* as mmdti_pair_attn_fwd (forward) / mmdti_pair_attn_bwd (backward) */
+  int act_fwd, act_dx;                 /* MMDTI_ACT_* of fc1's epilogue (forward) and of fc2's input gradient (backward) */
+  int ln_max_k;                        /* deepest Linear + LayerNorm that runs as one kernel (0: never) */
+  int fwd_f16;                         /* 1: the fp16 forward-operand mode -- every 16-bit operand of a forward GEMM (h1, weights, q | k | v,
+                                          o, h2, a, a 16-bit ln_out) holds fp16; pair_layout 3 only.  The saved gelu' (u) stays bf16 */
+  float scale, p_res, p_att;
+} mmdti_unimol_run_t;
+
+typedef struct {
+  const void *w_in, *w_out, *w_fc1, *w_fc2;          /* forward: the 16-bit shadows (bf16, or fp16 under fwd_f16) */
+  const float *b_in, *b_out, *b_fc1, *b_fc2;         /* (nullable) */
+  const void *wb_in, *wb_out, *wb_fc1, *wb_fc2;      /* backward: the bf16 shadows */
+  const float *g_ln1, *bt_ln1, *g_ln2, *bt_ln2;      /* self_attn_layer_norm, final_layer_norm */
+  float *dw_in, *dw_out, *dw_fc1, *dw_fc2;           /* gradients: fp32, accumulated.  A forward-only caller leaves them null */
+  float *db_in, *db_out, *db_fc1, *db_fc2;
+  float *dg_ln1, *dbt_ln1, *dg_ln2, *dbt_ln2;
+  float eps_ln1, eps_ln2;
+} mmdti_unimol_layer_t;
+
+/* What the forward of one layer writes for its backward, behind the layer's inputs (which the backward reads again): x [M,D] fp32 the
+ * residual stream, h1 [M,D] its LayerNorm-1 output with m1 / r1 [M] (backward only).  qkv [M,3D], s (pair logits, layout as the input
+ * logits), o [M,D], x1 [M,D] f32, h2 [M,D], m2 / r2 [M], u (gelu' or pre-activation, as act_fwd says) / a [M,F]. */
+typedef struct {
+  const float* x;
+  const void* h1;
+  const float *m1, *r1;
+  void *qkv, *s, *o;
+  float* x1;
+  void* h2;
+  float *m2, *r2;
+  void *u, *a;
+} mmdti_unimol_saved_t;
+
+/* One layer.  Forward: in_proj, pair attention (s_in -> saved s), out_proj + residual + dropout + LayerNorm-2, fc1 + GELU, fc2 + residual +
+ * dropout -> x_out [M,D] fp32 and the LayerNorm that reads it (next_mode 1: the next layer's LayerNorm-1 -> 16-bit ln_out; 2: the
+ * encoder's final LayerNorm -> fp32 ln_out; 0: none) with its statistics mn / rn.
+ * Backward, eight launches: fc2 / fc1 input gradients, LayerNorm-2 backward, out_proj input gradient, pair-attention backward (G: the
+ * pair-gradient chain; g_in_zero: not yet written), in_proj input gradient, LayerNorm-1 backward, grouped weight gradients.  dx_in
+ * [M,D] fp32 / dy2 [M,D] bf16: the gradient of x_out and its dropout-backward copy; dx_out / dx16_out (nullable: the lowest layer):
+ * the same two for the layer below, whose fc2 bias gradient db_below (nullable) receives the column sums of dx16_out.
+ * ws: mmdti_unimol_stack_layout's out[2] bytes, 16-byte aligned. */
+int mmdti_unimol_layer_fwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run, const mmdti_unimol_layer_t* layer,
+                           const mmdti_unimol_saved_t* saved, unsigned int site_att, unsigned int site_o, unsigned int site_f,
+                           const void* s_in, const unsigned char* key_pad, int rag_store, int next_mode, const float* g_next,
+                           const float* bt_next, float eps_next, float* x_out, void* ln_out, float* mn, float* rn);
+int mmdti_unimol_layer_bwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run, const mmdti_unimol_layer_t* layer,
+                           const mmdti_unimol_saved_t* saved, unsigned int site_f_below, unsigned int site_o, unsigned int site_att,
+                           const float* dx_in, const void* dy2, float* dx_out, void* dx16_out, float* db_below, void* G,
+                           int g_in_zero, void* ws, long long ws_bytes);
+
+/* ALL nl layers of the encoder (the loop of models/transformers.py:136-139 in :96-183): nl x the calls above, the saved blocks being
+ * slices of ONE caller-owned arena.  mmdti_unimol_stack_layout (launch-free): out[0] = arena bytes per layer, out[1] = bytes of the stack
+ * backward's workspace, out[2] = bytes of ONE layer's backward workspace (s_bytes: one layer's pair logits; dw_slab_bytes: split-K
+ * slabs of one layer's grouped weight gradients, see mmdti_linear_dw_grouped_splits).
  *   x0 / h1_0 / m1_0 / r1_0: the stream entering layer 0 and its LayerNorm-1 output + statistics (the caller's); the last layer writes
  *   x_last, s_last and (g_final non-null) the final LayerNorm out_final / mean_final / rstd_final.  Dropout sites: site0 + 3 l + {0, 1, 2}.
  *   dw_stream + events (hipEvent_t [3]; both null: everything on `stream`): the grouped weight gradients of a layer run on dw_stream
  *   under the layer below; `stream` has joined dw_stream when mmdti_unimol_stack_bwd returns. */
 int mmdti_unimol_stack_layout(int M, int D, int F, long long s_bytes, long long dw_slab_bytes, long long* out);
-int mmdti_unimol_stack_fwd(mmdti_stream_t stream, int nl, int M, int B, int N, int H, int D, int F, int ld, float scale, float p_res,
-                           float p_att, unsigned long long seed, unsigned int site0, const float* x0, const void* h1_0,
-                           const void* s_in, const unsigned char* key_pad, int pair_layout, const int* key_tiles,
-                           int rag_store_last, const int* row_off, const void* const* params, int act_fwd, float eps_ln,
-                           const float* g_final, const float* bt_final, float eps_final, int ln_max_k, void* arena,
+int mmdti_unimol_stack_fwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run, const mmdti_unimol_layer_t* layers, int nl,
+                           unsigned int site0, const float* x0, const void* h1_0, const void* s_in, const unsigned char* key_pad,
+                           int rag_store_last, const float* g_final, const float* bt_final, float eps_final, void* arena,
                            long long arena_bytes, long long s_bytes, float* x_last, void* s_last, float* out_final,
-                           float* mean_final, float* rstd_final, int fwd_f16);
-int mmdti_unimol_stack_bwd(mmdti_stream_t stream, int nl, int M, int B, int N, int H, int D, int F, int ld, float scale, float p_res,
-                           float p_att, unsigned long long seed, unsigned int site0, const float* dx_in, const void* dy2_in,
-                           float* dx_final, const float* x0, const void* h1_0, const float* m1_0, const float* r1_0,
-                           const void* s_last, const void* const* bparams, int act_dx, void* const* grads, void* G, int pair_layout,
-                           int g_first_zero, const int* key_tiles, const int* row_off, const void* arena, long long arena_bytes,
-                           long long s_bytes, void* ws, long long ws_bytes, long long dw_slab_bytes, int fwd_f16,
-                           mmdti_stream_t dw_stream, void* const* events);
+                           float* mean_final, float* rstd_final);
+int mmdti_unimol_stack_bwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run, const mmdti_unimol_layer_t* layers, int nl,
+                           unsigned int site0, const float* dx_in, const void* dy2_in, float* dx_final, const float* x0,
+                           const void* h1_0, const float* m1_0, const float* r1_0, const void* s_last, void* G, int g_first_zero,
+                           const void* arena, long long arena_bytes, long long s_bytes, void* ws, long long ws_bytes,
+                           long long dw_slab_bytes, mmdti_stream_t dw_stream, void* const* events);
 
-/* The same for one post-LN BERT layer with self-attention, fused q | k | v projection and the fused attention kernels (HF RobertaLayer
- * reached from models/mm_model.py:562): six launches forward, eight backward.  Shapes and the workspace layout: layers.hip. */
-int mmdti_bert_layer_fwd(mmdti_stream_t stream, int Mq, int B, int L, int heads, int D, int F, float scale, float p_hid, float p_att,
-                         unsigned long long seed, unsigned int site_att, unsigned int site_o, unsigned int site_f,
-                         const float* s1_32, const void* s1_16, const float* key_add, const int* q_off, const int* k_off,
-                         const int* k_cnt, int q_rows, const void* w_qkv, const float* b_qkv, const void* w_o, const float* b_o,
-                         const float* g_ln1, const float* bt_ln1, const void* w_i, const float* b_i, int act_fwd,
-                         const void* w_o2, const float* b_o2, const float* g_ln2, const float* bt_ln2, float eps, int ln_max_k,
-                         void* qkv, void* ctx, float* stats, float* y, float* a32, void* a16, float* am, float* ar, void* u_aux,
-                         void* i_act, float* z, float* out32, void* out16, float* zm, float* zr,
-                         int fwd_f16 /* 1: s1_16, the weights, ctx, a16, i_act, out16 hold fp16 (q | k | v stay bf16) */);
-int mmdti_bert_layer_bwd(mmdti_stream_t stream, int Mq, int B, int L, int heads, int D, int F, float scale, float p_hid, float p_att,
-                         unsigned long long seed, unsigned int site_att, unsigned int site_o, unsigned int site_f,
-                         const float* dout, float* ds1, const void* s1_16, const float* key_add, const int* q_off,
-                         const int* k_off, const int* k_cnt, int q_rows, const void* qkv, const void* ctx, const float* stats,
-                         const float* y, const void* a16, const float* am, const float* ar, const void* u_aux, int act_dx,
-                         const void* i_act, const float* z, const float* zm, const float* zr, const void* w_qkv,
-                         const void* w_o, const void* w_i, const void* w_o2, const float* g_ln1, const float* g_ln2,
-                         float* dw_qkv, int lddw_qkv, float* db_qkv, float* dw_o, float* db_o, float* dw_i, float* db_i,
-                         float* dw_o2, float* db_o2, float* dg_ln1, float* dbt_ln1, float* dg_ln2, float* dbt_ln2, void* ws,
-                         long long ws_bytes, int fwd_f16 /* 1: the saved s1_16, ctx, a16, i_act hold fp16 (weights: the bf16 shadow) */);
-/* The CROSS-attention variant (BertCrossAttentionLayer, mm_module.py:615-626 through :663-677: queries from s1 [Mq rows], keys and values
- * from s2 [Mk rows]): the six forward launches behind one call (query projection, fused key | value projection, fused attention, the two
- * closers, intermediate + GELU), and the backward UP TO the weight gradients (ten launches; ds1 / ds2: the gradients of the two inputs).
- * The backward's five bf16 activation gradients (dzb, du, dyb, dq, dkv) are the caller's: they are the A operands of the layer's weight
- * gradients, which the caller launches (mmdti_linear_dw_grouped takes one token-row count per launch, this layer has two).
- * ws of the backward: da [Mq,D] | dctx [Mq,D] (bf16) | dz [Mq,D] f32 | the attention backward's row term.
- * ds2 may be null (s2 needs no gradient, e.g. a frozen tower 2): its GEMM is then not launched; dkv is still written. */
-int mmdti_bert_cross_layer_fwd(mmdti_stream_t stream, int Mq, int Mk, int B, int Lq, int Lk, int heads, int D, int F, float scale,
-                               float p_hid, float p_att, unsigned long long seed, unsigned int site_att, unsigned int site_o,
-                               unsigned int site_f, const float* s1_32, const void* s1_16, const void* s2_16, const float* key_add,
-                               const int* q_off, const int* k_off, const int* k_cnt, int q_rows, const void* w_q, const float* b_q,
-                               const void* w_kv, const float* b_kv, const void* w_o, const float* b_o, const float* g_ln1,
-                               const float* bt_ln1, const void* w_i, const float* b_i, int act_fwd, const void* w_o2,
-                               const float* b_o2, const float* g_ln2, const float* bt_ln2, float eps, int ln_max_k, void* q,
-                               void* kv, void* ctx, float* stats, float* y, float* a32, void* a16, float* am, float* ar,
-                               void* u_aux, void* i_act, float* z, float* out32, void* out16, float* zm, float* zr, int fwd_f16);
-int mmdti_bert_cross_layer_bwd(mmdti_stream_t stream, int Mq, int Mk, int B, int Lq, int Lk, int heads, int D, int F, float scale,
-                               float p_hid, float p_att, unsigned long long seed, unsigned int site_att, unsigned int site_o,
-                               unsigned int site_f, const float* dout, float* ds1, float* ds2, const float* key_add,
-                               const int* q_off, const int* k_off, const int* k_cnt, int q_rows, const void* q, const void* kv,
-                               const float* stats, const float* y, const float* am, const float* ar, const void* u_aux,
-                               int act_dx, const float* z, const float* zm, const float* zr, const void* w_q, const void* w_kv,
-                               const void* w_o, const void* w_i, const void* w_o2, const float* g_ln1, const float* g_ln2,
-                               float* db_o, float* db_o2, float* dg_ln1, float* dbt_ln1, float* dg_ln2, float* dbt_ln2, void* dzb,
-                               void* du, void* dyb, void* dq, void* dkv, void* ws, long long ws_bytes);
-/* ---- ALL layers of tower 2 behind one call per direction (HF RobertaEncoder's layer loop, reached from models/mm_model.py:562): as
- * the Uni-Mol stack above -- pointer tables for the parameters, one activation arena, nl x mmdti_bert_layer_fwd / _bwd, bit-identical.
- *   mmdti_bert_stack_layout: out[0] = arena bytes per layer, out[1] = backward workspace bytes (stats_bytes: one layer's softmax
- *     statistics; nrow: heads * q_rows packed, B * heads * L dense; dw_slab_bytes: split-K slabs of one layer's weight gradients).
- *   params [nl][12]: w_qkv, b_qkv, w_o, b_o, g_ln1, bt_ln1, w_i, b_i, w_o2, b_o2, g_ln2, bt_ln2 (16-bit forward weights, q | k | v fused).
- *   bparams [nl][6]: w_qkv, w_o, w_i, w_o2 (bf16), g_ln1, g_ln2.   grads [nl][12]: dw_qkv, db_qkv, dw_o, db_o, dw_i, db_i, dw_o2, db_o2,
- *     dg_ln1, dbt_ln1, dg_ln2, dbt_ln2 (fp32, accumulated).  Dropout sites: site0 + 3 l + {0: attention, 1: output.dense, 2: FFN}. */
+/* Tower 2 and the cross block: one post-LN BERT layer on the fused attention kernels (HF RobertaLayer reached from
+ * models/mm_model.py:562; BertCrossAttentionLayer, mm_module.py:615-626 through :663-677).  Self-attention: Mk = Mq, Lk = Lq. */
+typedef struct {
+  const float* key_add;                        /* [B,Lk] additive key mask (nullable) */
+  const int *q_off, *k_off, *k_cnt;            /* packed sequences, as mmdti_attn_fwd (null / q_rows 0: dense) */
+  unsigned long long seed;
+  int Mq, Mk, B, Lq, Lk, heads, D, F;          /* token rows of the query / key side; the longest sequences */
+  int q_rows;
+  int act_fwd, act_dx, ln_max_k;               /* as mmdti_unimol_run_t */
+  int fwd_f16;                                 /* 1: s1_16 / s2_16, the weights, ctx, a16, i, out16 hold fp16 (q | k | v and u stay bf16) */
+  float scale, p_hid, p_att, eps;
+} mmdti_bert_run_t;
+
+/* w_qkv [3D,D] / b_qkv [3D]: the fused query | key | value projection; in the cross layer the fused key | value one ([2D,D]) beside the
+ * separate query projection w_q / b_q.  The cross backward leaves the weight gradients to its caller: only db_o, db_o2 and the
+ * LayerNorm gradients are read there. */
+typedef struct {
+  const void *w_qkv, *w_q, *w_o, *w_i, *w_o2;
+  const float *b_qkv, *b_q, *b_o, *b_i, *b_o2;
+  const void *wb_qkv, *wb_q, *wb_o, *wb_i, *wb_o2;
+  const float *g_ln1, *bt_ln1, *g_ln2, *bt_ln2;      /* attention.output.LayerNorm, output.LayerNorm */
+  float *dw_qkv, *dw_q, *dw_o, *dw_i, *dw_o2;        /* gradients: fp32, accumulated.  A forward-only caller leaves them null */
+  float *db_qkv, *db_q, *db_o, *db_i, *db_o2;
+  float *dg_ln1, *dbt_ln1, *dg_ln2, *dbt_ln2;
+  int lddw_qkv;                                      /* row stride of dw_qkv */
+} mmdti_bert_layer_t;
+
+/* s1_32 / s1_16 [Mq,D]: the layer input (fp32 residual stream and its 16-bit copy); s2_16 [Mk,D]: the key / value side (cross only).
+ * qkv [Mq,3D] (cross: k | v [Mk,2D] beside q [Mq,D]), ctx [Mq,D], stats, y [Mq,D] f32 (pre-LN1), a32 / a16 (LN1 output), am / ar,
+ * u / i [Mq,F] (gelu' / the intermediate activation), z [Mq,D] f32 (pre-LN2), zm / zr. */
+typedef struct {
+  const float* s1_32;
+  const void *s1_16, *s2_16;
+  void *qkv, *q, *ctx;
+  float *stats, *y, *a32;
+  void* a16;
+  float *am, *ar;
+  void *u, *i;
+  float *z, *zm, *zr;
+} mmdti_bert_saved_t;
+
+/* Forward: the projection(s), fused attention, output.dense + residual + LayerNorm, intermediate + GELU,
+ * output + residual + LayerNorm -> out32 / out16 [Mq,D].  Backward of the self-attention layer: LayerNorm-2 backward, the FFN's two
+ * input gradients, LayerNorm-1 backward, the output projection's input gradient, the fused attention backward, the fused projection's
+ * input gradient accumulated into ds1, the four weight gradients as one grouped launch.  dout [Mq,D] fp32 -> ds1 [Mq,D] fp32.
+ * ws: mmdti_bert_stack_layout's out[2] bytes.
+ * The cross backward stops before the weight gradients (ten launches): its five bf16 activation gradients (dzb [Mq,D], du [Mq,F], dyb
+ * [Mq,D], dq [Mq,D], dkv [Mk,2D]) are the caller's -- the A operands of the weight gradients it launches itself (mmdti_linear_dw_grouped
+ * takes one token-row count per launch, this layer has two).  ds2 [Mk,D] may be null (s2 needs no gradient): its GEMM is then not
+ * launched; dkv is still written.  ws: out[3] bytes. */
+int mmdti_bert_layer_fwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, const mmdti_bert_layer_t* layer,
+                         const mmdti_bert_saved_t* saved, unsigned int site_att, unsigned int site_o, unsigned int site_f,
+                         float* out32, void* out16);
+int mmdti_bert_cross_layer_fwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, const mmdti_bert_layer_t* layer,
+                               const mmdti_bert_saved_t* saved, unsigned int site_att, unsigned int site_o, unsigned int site_f,
+                               float* out32, void* out16);
+int mmdti_bert_layer_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, const mmdti_bert_layer_t* layer,
+                         const mmdti_bert_saved_t* saved, unsigned int site_att, unsigned int site_o, unsigned int site_f,
+                         const float* dout, float* ds1, void* ws, long long ws_bytes);
+int mmdti_bert_cross_layer_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, const mmdti_bert_layer_t* layer,
+                               const mmdti_bert_saved_t* saved, unsigned int site_att, unsigned int site_o, unsigned int site_f,
+                               const float* dout, float* ds1, float* ds2, void* dzb, void* du, void* dyb, void* dq, void* dkv,
+                               void* ws, long long ws_bytes);
+
+/* ALL nl layers of tower 2 (HF RobertaEncoder's layer loop): as the Uni-Mol stack above.  mmdti_bert_stack_layout (launch-free): out[0] =
+ * arena bytes per layer, out[1] = the stack backward's workspace bytes, out[2] / out[3] = ONE self-attention / cross layer's backward
+ * workspace bytes (stats_bytes: one layer's softmax statistics; nrow: heads * q_rows packed, B * heads * Lq dense; dw_slab_bytes:
+ * split-K slabs of one layer's weight gradients -- the cross layer has none).  s1_32_0 / s1_16_0: the embeddings' LayerNorm output; the
+ * last layer's fp32 output goes to out32_last.  Dropout sites: site0 + 3 l + {0: attention, 1: output.dense, 2: FFN}. */
 int mmdti_bert_stack_layout(int Mq, int D, int F, long long stats_bytes, long long nrow, long long dw_slab_bytes, long long* out);
-int mmdti_bert_stack_fwd(mmdti_stream_t stream, int nl, int Mq, int B, int L, int heads, int D, int F, float scale, float p_hid,
-                         float p_att, unsigned long long seed, unsigned int site0, const float* s1_32_0, const void* s1_16_0,
-                         const float* key_add, const int* q_off, const int* k_off, const int* k_cnt, int q_rows,
-                         const void* const* params, int act_fwd, float eps, int ln_max_k, void* arena, long long arena_bytes,
-                         long long stats_bytes, float* out32_last, int fwd_f16);
-int mmdti_bert_stack_bwd(mmdti_stream_t stream, int nl, int Mq, int B, int L, int heads, int D, int F, float scale, float p_hid,
-                         float p_att, unsigned long long seed, unsigned int site0, const float* dout, float* ds1_final,
-                         const void* s1_16_0, const float* key_add, const int* q_off, const int* k_off, const int* k_cnt,
-                         int q_rows, const void* const* bparams, int act_dx, void* const* grads, int lddw_qkv, const void* arena,
-                         long long arena_bytes, long long stats_bytes, void* ws, long long ws_bytes, long long dw_slab_bytes,
-                         int fwd_f16);
+int mmdti_bert_stack_fwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, const mmdti_bert_layer_t* layers, int nl,
+                         unsigned int site0, const float* s1_32_0, const void* s1_16_0, void* arena, long long arena_bytes,
+                         long long stats_bytes, float* out32_last);
+int mmdti_bert_stack_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, const mmdti_bert_layer_t* layers, int nl,
+                         unsigned int site0, const float* dout, float* ds1_final, const void* s1_16_0, const void* arena,
+                         long long arena_bytes, long long stats_bytes, void* ws, long long ws_bytes, long long dw_slab_bytes);
 
 
 /* ---- LayerNorm (unicore LayerNorm eps 1e-5: transformers.py:69,71,114,161; BertLayerNorm eps 1e-12:

@@ -681,7 +681,7 @@ MMDTI_DEFINE_SALT_PULL(elementwise)
 using namespace mmdti;
 
 extern "C" const char* mmdti_last_error(void) { return g_err; }
-extern "C" int mmdti_abi_version(void) { return 1; }
+extern "C" int mmdti_abi_version(void) { return MMDTI_ABI_VERSION; }
 
 // ---- deterministic mode: the flag and the per-stream workspace table (det.h) ----
 extern "C" int mmdti_set_deterministic(int on) {

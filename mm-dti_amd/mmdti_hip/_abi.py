@@ -38,11 +38,35 @@ def _ctype(decl: str):
     return table[d]
 
 
-def parse_header(path: str = HEADER):
-    """-> {name: (restype, [argtypes], [argnames])} for every function the header declares."""
+def _source(path):
     src = open(path).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def parse_structs(path: str = HEADER):
+    """-> {name: ctypes.Structure subclass} for every `typedef struct { ... } mmdti_*_t;` of the header, fields in header order.  A
+    declaration is `type a, b;` or -- pointers -- `type *a, *b;` / `type* a;`; no arrays, bitfields or nested structs."""
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{([^{}]*)\}\s*(mmdti_[a-z0-9_]+_t)\s*;", _source(path)):
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            first, *more = [d.strip() for d in decl.split(",")]
+            base = re.sub(r"[A-Za-z_][A-Za-z_0-9]*$", "", first).replace("*", " ")
+            for d in [first] + more:
+                if not re.fullmatch(r"[A-Za-z_0-9 ]*\*?\s*[A-Za-z_][A-Za-z_0-9]*", d):
+                    raise MMDTIError(f"mmdti_hip.h: unsupported field {d!r} in {name}")
+                field = re.findall(r"[A-Za-z_][A-Za-z_0-9]*", d)[-1]
+                fields.append((field, _ctype(f"{base} {'*' if '*' in d else ''}{field}")))
+        # (no instance dictionary: ctypes would otherwise take a misspelt keyword for a new Python attribute and leave the field null)
+        structs[name] = type(name, (ctypes.Structure,), {"__slots__": (), "_fields_": fields})
+    return structs
+
+
+def parse_header(path: str = HEADER):
+    """-> {name: (restype, [argtypes], [argnames])} for every function the header declares.  A struct-pointer parameter is a plain
+    address (c_void_p): pass ctypes.addressof of a block built from lib().struct(name)."""
+    src = _source(path)
     protos = {}
     for m in re.finditer(r"(const\s+char\s*\*|int)\s+(mmdti_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
         ret, name, args = m.group(1), m.group(2), m.group(3)
@@ -71,7 +95,15 @@ class _Lib:
                 f"(make -C mm-dti_amd/csrc).  There is no CPU fallback for the product path.")
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
+        self.structs = parse_structs()
         self.const = header_constants()
+        try:
+            version = self._dll.mmdti_abi_version()
+        except AttributeError as e:
+            raise MMDTIError(f"{LIB_PATH} does not export mmdti_abi_version") from e
+        if version != self.const["MMDTI_ABI_VERSION"]:
+            raise MMDTIError(f"{LIB_PATH} was built for ABI version {version}, include/mmdti_hip.h declares "
+                             f"{self.const['MMDTI_ABI_VERSION']}: rebuild it (make -C mm-dti_amd/csrc)")
         for name, (restype, argtypes, _) in self.protos.items():
             try:
                 fn = getattr(self._dll, name)
@@ -80,6 +112,11 @@ class _Lib:
             fn.restype = restype
             fn.argtypes = argtypes
         self._last_error = self._dll.mmdti_last_error
+
+    def struct(self, name):
+        """The ctypes class of the header's `name`: build a block by keyword (an unknown field name is an AttributeError); a field left out is
+        null, which every entry point that needs it refuses before its first launch."""
+        return self.structs[name]
 
     def call(self, name, *args):
         rc = getattr(self._dll, name)(*args)

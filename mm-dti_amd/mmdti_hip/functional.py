@@ -241,7 +241,7 @@ class PairEncoderFn(torch.autograd.Function):
         if paths.unimol_tower_fwd(sw, path, keep, nlayers, M, aux_grads, mod.final_layer_norm is not None) == paths.STACK:
             T = _stack_tables(_unimol_stack_desc, mod, M, sw)
         if T is not None:
-            x, out, s_prev = _unimol_stack_fwd(st, T, mod, x, s_prev, kp0, key_tiles, pack is None, row_off, scale, sites, tiled)
+            x, out, s_prev = _unimol_stack_fwd(st, T, mod, x, s_prev, kp0, pack is None, scale, sites, tiled)
         for li, layer in enumerate(mod.layers if T is None else ()):
             L = SimpleNamespace(x=x)
             ln1, ln2 = layer.self_attn_layer_norm, layer.final_layer_norm
@@ -255,8 +255,8 @@ class PairEncoderFn(torch.autograd.Function):
                 L.site_att, L.site_o, L.site_f = sites.next(), sites.next(), sites.next()
                 last = li == nlayers - 1
                 nl = mod.layers[li + 1].self_attn_layer_norm if not last else mod.final_layer_norm
-                x, ln_out, mn, rn = _unimol_layer_fwd_seq(st, layer, L, s_prev, kp0 if li == 0 else None, key_tiles, last and pack is None, row_off,
-                                                          scale, nl, 0 if nl is None else (2 if last else 1))
+                x, ln_out, mn, rn = _unimol_layer_fwd_seq(st, layer, L, s_prev, kp0 if li == 0 else None, last and pack is None, scale, nl,
+                                                          0 if nl is None else (2 if last else 1))
                 s_prev = L.s
                 if not last:
                     nxt = (ln_out, mn, rn)
@@ -431,8 +431,8 @@ class PairEncoderFn(torch.autograd.Function):
 
 # ---- all layers of the tower behind one library call per direction (csrc/layers.hip: mmdti_unimol_stack_fwd / _bwd).  At the
 # reference's batch size (16-32 molecules) the step is paced by the host: the per-layer calls below still cost ~90 us of Python per
-# layer and direction (17 allocations, 60 marshalled arguments, shadow look-ups).  The stack calls take the parameters as pointer
-# tables cached per model and keep the saved tensors at fixed offsets of one arena: one allocation and one call for 15 layers.
+# layer and direction (17 allocations, the blocks' marshalling, shadow look-ups).  The stack calls take the parameters as an array of
+# layer blocks cached per model and keep the saved tensors at fixed offsets of one arena: one allocation and one call for 15 layers.
 # Above MMDTI_STACK_MAX_ROWS rows the GPU sets the pace and the per-layer path (which frees each layer's activations as the
 # backward advances and holds the last layers' weight gradients back) stays in charge.
 STACK_SEQ = os.environ.get("MMDTI_STACK_SEQ", "1") != "0"
@@ -459,27 +459,34 @@ def bert_weights(layer) -> SimpleNamespace:
                            ln2_w=layer.output.LayerNorm.weight, ln2_b=layer.output.LayerNorm.bias)
 
 
-# What a tower's stack calls take of one layer (csrc/layers.hip): params -- every parameter; w16 -- the forward GEMM weights, which the
-# tables address through the arena's 16-bit shadows (everything else through the parameter itself); fwd / bwd / grads -- the order of the
-# three pointer tables; recast -- the weights whose shadow is refreshed after an in-place write; probe -- the [F, D] weight that shapes the
-# layer and whose bindings are re-checked per call; eps -- LayerNorm epsilons that must all be one value; runs -- parameters that must sit
-# back to back in the arena (the call reads each run as one matrix / one bias).
+# ---- What the sequencers take, by NAME: the blocks of include/mmdti_hip.h (run: the same for every layer of one call; layer: one
+# layer's parameters; saved: what its forward writes for its backward).  ops.lib().struct(name) is the ctypes class of a header struct:
+# a block is built by keyword, so a misspelt field is an AttributeError here and a field left out arrives as null, which the library refuses
+# before its first launch.  A call takes the ADDRESS of a block; the block must outlive the call only.
+#
+# A layer's description (one per tower, for the per-layer and the stack calls alike): lin -- its Linears by field suffix {suffix:
+# (weight, bias)}, whose weights the forward reads through the 16-bit shadows; ln -- its LayerNorms {suffix: (weight, bias)}; extra --
+# scalar fields; params -- every parameter; recast -- the weights whose shadow is refreshed after an in-place write; probe -- the [F, D]
+# weight that shapes the layer and whose bindings are re-checked per call; eps -- LayerNorm epsilons that must all be one value; runs --
+# parameters that must sit back to back in the arena (the call reads each run as one matrix / one bias).
 def _unimol_stack_desc(l):
     a, ln1, ln2 = l.self_attn, l.self_attn_layer_norm, l.final_layer_norm
-    w_in, b_in, w_out, b_out, w1, b1, w2, b2 = a.in_proj.weight, a.in_proj.bias, a.out_proj.weight, a.out_proj.bias, l.fc1.weight, l.fc1.bias, l.fc2.weight, l.fc2.bias
-    g1, bt1, g2, bt2 = ln1.weight, ln1.bias, ln2.weight, ln2.bias
-    ps = [w_in, b_in, w_out, b_out, g2, bt2, w1, b1, w2, b2, g1, bt1]
-    return SimpleNamespace(params=ps, w16=(w_in, w_out, w1, w2), fwd=ps, bwd=(w2, w1, w_out, w_in, g2, g1), recast=(w_in, w_out, w1, w2), probe=w1,
-                           grads=(w2, w1, w_out, w_in, b2, b1, b_out, b_in, g2, bt2, g1, bt1), eps=(ln2.eps, ln1.eps), runs=())
+    lin = {"in": (a.in_proj.weight, a.in_proj.bias), "out": (a.out_proj.weight, a.out_proj.bias), "fc1": (l.fc1.weight, l.fc1.bias),
+           "fc2": (l.fc2.weight, l.fc2.bias)}
+    ln = {"ln1": (ln1.weight, ln1.bias), "ln2": (ln2.weight, ln2.bias)}
+    return SimpleNamespace(struct="mmdti_unimol_layer_t", lin=lin, ln=ln, extra=dict(eps_ln1=float(ln1.eps), eps_ln2=float(ln2.eps)),
+                           params=[q for pair in (*lin.values(), *ln.values()) for q in pair], recast=[w for w, _ in lin.values()], probe=l.fc1.weight,
+                           eps=(ln2.eps, ln1.eps), runs=())
 
 
 def _bert_stack_desc(l):
     W = bert_weights(l)
-    return SimpleNamespace(params=[W.q_w, W.k_w, W.v_w, W.q_b, W.k_b, W.v_b, W.o_w, W.o_b, W.ln1_w, W.ln1_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln2_w, W.ln2_b],
-                           w16=(W.q_w, W.o_w, W.i_w, W.o2_w),        # (q_w: where the fused [3D, D] query | key | value matrix starts)
-                           fwd=(W.q_w, W.q_b, W.o_w, W.o_b, W.ln1_w, W.ln1_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln2_w, W.ln2_b),
-                           bwd=(W.q_w, W.o_w, W.i_w, W.o2_w, W.ln1_w, W.ln2_w), recast=(W.q_w, W.k_w, W.v_w, W.o_w, W.i_w, W.o2_w), probe=W.i_w,
-                           grads=(W.q_w, W.q_b, W.o_w, W.o_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b), eps=(),
+    # (q_w / q_b: where the fused [3D, D] query | key | value matrix and its bias start)
+    lin = {"qkv": (W.q_w, W.q_b), "o": (W.o_w, W.o_b), "i": (W.i_w, W.i_b), "o2": (W.o2_w, W.o2_b)}
+    ln = {"ln1": (W.ln1_w, W.ln1_b), "ln2": (W.ln2_w, W.ln2_b)}
+    return SimpleNamespace(struct="mmdti_bert_layer_t", lin=lin, ln=ln, extra=dict(lddw_qkv=W.q_w.shape[1]),
+                           params=[W.q_w, W.k_w, W.v_w, W.q_b, W.k_b, W.v_b, W.o_w, W.o_b, W.ln1_w, W.ln1_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln2_w, W.ln2_b],
+                           recast=(W.q_w, W.k_w, W.v_w, W.o_w, W.i_w, W.o2_w), probe=W.i_w, eps=(),
                            runs=((W.q_w, W.k_w, W.v_w), (W.q_b, W.k_b, W.v_b)))
 
 
@@ -487,8 +494,61 @@ _unimol_stack_desc.probe = lambda l: l.fc1.weight
 _bert_stack_desc.probe = lambda l: l.intermediate.dense.weight
 
 
+_layer_descs = weakref.WeakKeyDictionary()
+
+
+def _layer_desc(desc, l):
+    """desc(l), kept per layer for the per-layer calls (building one walks two dozen module attributes: 16 us, more than the call it
+    feeds at small batches); built again when the probe parameter is no longer the layer's."""
+    d = _layer_descs.get(l)
+    if d is None or d.probe is not desc.probe(l):
+        d = _layer_descs[l] = desc(l)
+    return d
+
+
+def _layer_block(d, w16=None, wb=None, g=None, **extra):
+    """One layer's parameter block from its description d (d.struct names the type).  w16 / wb / g: the address of a weight's forward
+    shadow, of its bf16 shadow, of a parameter's gradient buffer.  A forward passes w16 alone -- the backward fields stay null --, a
+    backward wb and g, the stack calls' cached array all three."""
+    p = ops._p
+    f = dict(d.extra, **extra)
+    for k, (w, b) in d.lin.items():
+        if w16 is not None:
+            f["w_" + k], f["b_" + k] = w16(w), p(b)
+        if g is not None:
+            f["wb_" + k], f["dw_" + k], f["db_" + k] = wb(w), g(w), g(b)
+    for k, (gm, bt) in d.ln.items():
+        f["g_" + k], f["bt_" + k] = p(gm), p(bt)
+        if g is not None:
+            f["dg_" + k], f["dbt_" + k] = g(gm), g(bt)
+    return ops.lib().struct(d.struct)(**f)
+
+
+# (the per-layer calls look every address up per call, as the op-by-op path does: shadows are re-cast and gradient buffers created on demand)
+_w16_ptr = lambda w: wfwd(w).data_ptr()                          # noqa: E731
+_wb_ptr = lambda w: wbf16(w).data_ptr()                          # noqa: E731
+_grad_ptr = lambda q: 0 if q is None else ops._p(gbuf(q))        # noqa: E731
+
+
+def _saved_block(name, L, alloc=None, dev=None, **inputs):
+    """A layer's saved-tensor block (struct `name`), field by field from the tensor of the same name that L holds; inputs: fields the
+    caller owns and L does not keep.  alloc ({field: (shape, dtype)}, the forward): those tensors are allocated onto L first."""
+    if alloc is not None:
+        for k, (shape, dtype) in alloc.items():
+            setattr(L, k, torch.empty(shape, device=dev, dtype=dtype))
+    S = ops.lib().struct(name)
+    held = L.__dict__
+    f = {k: held[k].data_ptr() for k, _ in S._fields_ if held.get(k) is not None}
+    f.update((k, ops._p(t)) for k, t in inputs.items())
+    return S(**f)
+
+
+def _ln_max_k():
+    return ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0
+
+
 def _stack_tables(desc, mod, rows, sw, attn_ok=True):
-    """Pointer tables of a tower's layers for its stack calls (desc: _unimol_stack_desc / _bert_stack_desc; cached on the parameter arena),
+    """The array of a tower's layer blocks for its stack calls (desc: _unimol_stack_desc / _bert_stack_desc; cached on the parameter arena),
     or None when the stack calls do not cover this model or call (paths.stack_call, paths.stack_model)."""
     layers = list(mod.layers)
     probe0 = desc.probe(layers[0])               # (per call: only this one look-up; the descriptions are built on a cache miss)
@@ -498,7 +558,7 @@ def _stack_tables(desc, mod, rows, sw, attn_ok=True):
         return None
     cache = arena.__dict__.setdefault("_stack_tables", {})
     # (a weak reference: an id is recycled once the module dies; the flags: a parameter frozen after the first step must not be written
-    #  through the raw gradient table -- the stack calls take every parameter of every layer as trainable)
+    #  through the raw gradient fields -- the stack calls take every parameter of every layer as trainable)
     flags = trainable_flags(q for l in layers for q in l.parameters())
     key = (weakref.ref(mod), ops.FWD_F16, desc, flags)
     T = cache.get(key)
@@ -518,15 +578,11 @@ def _stack_tables(desc, mod, rows, sw, attn_ok=True):
             arena._fresh16()
         sh16 = (arena.shadow16 if ops.FWD_F16 else arena.shadow).data_ptr()
         shb, gr = arena.shadow.data_ptr(), arena.grad.data_ptr()
-        fwd, bwd, grads, weights, probes = [], [], [], [], []
-        for d in ds:
-            w16 = {id(q) for q in d.w16}
-            fwd += [sh16 + 2 * off[id(q)] if id(q) in w16 else q.data_ptr() for q in d.fwd]
-            bwd += [shb + 2 * off[id(q)] if id(q) in w16 else q.data_ptr() for q in d.bwd]
-            grads += [gr + 4 * off[id(q)] for q in d.grads]
-            weights += [(q, id(q)) for q in d.recast]
-            probes.append((d.probe, d.probe.data_ptr(), gr + 4 * off[id(d.probe)]))
-        T = cache[key] = SimpleNamespace(nl=len(layers), D=D, F=F, fwd=_ptr_table(fwd), bwd=_ptr_table(bwd), grads=_ptr_table(grads), weights=weights,
+        blocks = [_layer_block(d, w16=lambda q: sh16 + 2 * off[id(q)], wb=lambda q: shb + 2 * off[id(q)], g=lambda q: gr + 4 * off[id(q)]) for d in ds]
+        weights = [(q, id(q)) for d in ds for q in d.recast]
+        probes = [(d.probe, d.probe.data_ptr(), gr + 4 * off[id(d.probe)]) for d in ds]
+        arr = (type(blocks[0]) * len(blocks))(*blocks)
+        T = cache[key] = SimpleNamespace(nl=len(layers), D=D, F=F, layers=(arr, ctypes.addressof(arr)), weights=weights,
                                          params=[q for d in ds for q in d.params], f16=ops.FWD_F16, probes=probes)
     if T is False:
         return None
@@ -543,24 +599,12 @@ def _stack_tables(desc, mod, rows, sw, attn_ok=True):
     return T
 
 
-# Byte counts the library checks against its own arithmetic (csrc/layers.hip).  A Uni-Mol layer and a BERT self-attention layer hand the
-# grouped weight-gradient launch the same set of matrices -- four of [D, D] (in_proj's three and out_proj; query, key, value and the output
-# dense) and two of [F, D] -- whose split-K partial sums take one fp32 slab per split.
+# Byte counts come from the library's own arithmetic (csrc/layers.hip), asked once per shape.  A Uni-Mol layer and a BERT self-attention
+# layer hand the grouped weight-gradient launch the same set of matrices -- four of [D, D] (in_proj's three and out_proj; query, key, value
+# and the output dense) and two of [F, D] -- whose split-K partial sums take one fp32 slab per split.
 def _dw_slab_bytes(D, F, rows):
     tiles = (D // 256) * (F // 256) * 2 + (D // 256) ** 2 * 4
     return ops.lib()._dll.mmdti_linear_dw_grouped_splits(tiles, rows) * (2 * D * F + 4 * D * D) * 4
-
-
-def _unimol_layer_ws_bytes(M, D, F):           # one layer's backward temporaries: mmdti_unimol_layer_bwd
-    return (M * F + 7 * M * D) * 2 + M * D * 4 + _dw_slab_bytes(D, F, M)
-
-
-def _bert_layer_ws_bytes(Mq, D, F, nrow):      # mmdti_bert_layer_bwd (nrow: _attn_stat_rows)
-    return (Mq * F + 7 * Mq * D) * 2 + Mq * D * 4 + (nrow * 4 + 15) // 16 * 16 + _dw_slab_bytes(D, F, Mq)
-
-
-def _bert_cross_layer_ws_bytes(Mq, D, nrow):   # mmdti_bert_cross_layer_bwd (its weight gradients are launched by the host: no slab)
-    return 4 * Mq * D + 4 * Mq * D + (nrow * 4 + 15) // 16 * 16
 
 
 def _attn_stat_rows(st, heads):
@@ -569,18 +613,25 @@ def _attn_stat_rows(st, heads):
 
 
 def _stack_layout(query, rows, D, F, *sizes):
-    """-> (arena bytes per layer, workspace bytes, weight-gradient slab bytes) of a tower's stack calls, asked of the library (`query`:
-    mmdti_unimol_stack_layout / mmdti_bert_stack_layout; sizes: its own arguments) once per shape."""
+    """-> (arena bytes per layer, stack workspace bytes, weight-gradient slab bytes, workspace bytes of ONE layer's backward [, of a cross
+    layer's]) of a tower's sequencers, asked of the library (`query`: mmdti_unimol_stack_layout / mmdti_bert_stack_layout; sizes: its own
+    arguments) once per shape."""
     key = (query, rows, D, F) + sizes
     r = _stack_layouts.get(key)
     if r is None:
         slab = _dw_slab_bytes(D, F, rows)
-        out = (ctypes.c_longlong * 2)()
+        out = (ctypes.c_longlong * 4)()
         getattr(ops.lib(), query)(rows, D, F, *sizes, slab, ctypes.addressof(out))
         if len(_stack_layouts) > 4096:
             _stack_layouts.clear()
-        r = _stack_layouts[key] = (int(out[0]), int(out[1]), slab)
+        r = _stack_layouts[key] = (int(out[0]), int(out[1]), slab, int(out[2]), int(out[3]))
     return r
+
+
+def _layer_workspace(nbytes, dev):
+    """-> (tensor, 256-byte aligned address, bytes) of one layer's backward workspace."""
+    ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
+    return ws, (ws.data_ptr() + 255) // 256 * 256, nbytes
 
 
 def _stack_side():
@@ -599,30 +650,36 @@ def _stack_side():
     return ops.det_register(ent[0].cuda_stream), ent[2][1]
 
 
-def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, key_tiles, rag_store_last, row_off, scale, sites, tiled):
+def _unimol_run(st, F, layout, scale, f16):
+    """Tower 1's run block for one direction of one call (layout: the pair tensors' code for that direction)."""
+    return ops.lib().struct("mmdti_unimol_run_t")(
+        key_tiles=ops._p(st.kt), row_off=ops._p(st.row_off), seed=int(st.seed), M=st.M, B=st.B, N=st.N, H=st.H, D=st.D, F=F, ld=st.ld, pair_layout=layout,
+        act_fwd=ops.ACT_GELU_FWD, act_dx=ops.ACT_GELU_DX, ln_max_k=_ln_max_k(), fwd_f16=int(f16), scale=float(scale), p_res=float(st.p_res),
+        p_att=float(st.p_att))
+
+
+def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, rag_store_last, scale, sites, tiled):
     """All layers' forward as ONE library call -> (x_last fp32, final LayerNorm output fp32, S of the last layer)."""
     M, D, F, B, N, H, ld = st.M, st.D, T.F, st.B, st.N, st.H, st.ld
     dev = x.device
-    l0 = mod.layers[0]
-    ln1, fl = l0.self_attn_layer_norm, mod.final_layer_norm
+    ln1, fl = mod.layers[0].self_attn_layer_norm, mod.final_layer_norm
     _, h1, m1, r1 = ops.layernorm_fwd(x, ln1.weight, ln1.bias, ln1.eps)
     e = torch.empty
     s_last = torch.empty_like(s_prev) if tiled else e(B, H, N, ld, device=dev, dtype=F32)
     s_bytes = s_last.numel() * s_last.element_size()
-    stride, ws_bytes, slab = _stack_layout("mmdti_unimol_stack_layout", M, D, F, s_bytes)
+    stride, ws_bytes, slab = _stack_layout("mmdti_unimol_stack_layout", M, D, F, s_bytes)[:3]
     arena = e(stride * T.nl, device=dev, dtype=torch.uint8)
     x_last, out = e(M, D, device=dev, dtype=F32), e(M, D, device=dev, dtype=F32)
     st.f_mean, st.f_rstd = e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
     site0 = sites.n + 1
     sites.n += 3 * T.nl
-    p = ops._p
+    f16 = h1.dtype == torch.float16
+    run = _unimol_run(st, F, ops._pair_layout_s(s_prev, "pair_attn.bias"), scale, f16)
     ops.lib().mmdti_unimol_stack_fwd(
-        ops._stream(), T.nl, M, B, N, H, D, F, ld, float(scale), float(st.p_res), float(st.p_att), int(st.seed), site0, x.data_ptr(), h1.data_ptr(),
-        s_prev.data_ptr(), p(key_pad), ops._pair_layout_s(s_prev, "pair_attn.bias"), p(key_tiles), int(rag_store_last), p(row_off), T.fwd[1],
-        ops.ACT_GELU_FWD, float(l0.final_layer_norm.eps), fl.weight.data_ptr(), fl.bias.data_ptr(), float(fl.eps), ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, arena.data_ptr(),
-        arena.numel(), s_bytes, x_last.data_ptr(), s_last.data_ptr(), out.data_ptr(), st.f_mean.data_ptr(), st.f_rstd.data_ptr(),
-        int(h1.dtype == torch.float16))
-    st.stack = SimpleNamespace(T=T, arena=arena, s_bytes=s_bytes, ws_bytes=ws_bytes, slab=slab, site0=site0, x0=x, h1=h1, m1=m1, r1=r1, s_last=s_last)
+        ops._stream(), ctypes.addressof(run), T.layers[1], T.nl, site0, x.data_ptr(), h1.data_ptr(), s_prev.data_ptr(), ops._p(key_pad), int(rag_store_last),
+        fl.weight.data_ptr(), fl.bias.data_ptr(), float(fl.eps), arena.data_ptr(), arena.numel(), s_bytes, x_last.data_ptr(), s_last.data_ptr(),
+        out.data_ptr(), st.f_mean.data_ptr(), st.f_rstd.data_ptr())
+    st.stack = SimpleNamespace(T=T, arena=arena, s_bytes=s_bytes, ws_bytes=ws_bytes, slab=slab, site0=site0, x0=x, h1=h1, m1=m1, r1=r1, s_last=s_last, f16=f16)
     return x_last, out, s_last
 
 
@@ -630,35 +687,31 @@ def _unimol_stack_bwd(st, dx, dx16, scale):
     """All layers' backward as ONE library call -> (gradient of the stream entering layer 0, pair-gradient chain G)."""
     S = st.stack
     T = S.T
-    M, D = st.M, st.D
-    dev = dx.device
     G = _pair_grad_chain(S.s_last, st.kt)
-    layout = ops._pair_layout_s(S.s_last, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0)
+    run = _unimol_run(st, T.F, ops._pair_layout_s(S.s_last, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0), scale, S.f16)
     dx_final = torch.empty_like(dx)
-    ws = torch.empty(S.ws_bytes, device=dev, dtype=torch.uint8)
+    ws = torch.empty(S.ws_bytes, device=dx.device, dtype=torch.uint8)
     side, events = _stack_side()
-    p = ops._p
     ops.lib().mmdti_unimol_stack_bwd(
-        ops._stream(), T.nl, M, st.B, st.N, st.H, D, T.F, st.ld, float(scale), float(st.p_res), float(st.p_att), int(st.seed), S.site0, dx.data_ptr(),
-        dx16.data_ptr(), dx_final.data_ptr(), S.x0.data_ptr(), S.h1.data_ptr(), S.m1.data_ptr(), S.r1.data_ptr(), S.s_last.data_ptr(), T.bwd[1],
-        ops.ACT_GELU_DX, T.grads[1], G.data_ptr(), layout, 1, p(st.kt), p(st.row_off), S.arena.data_ptr(), S.arena.numel(), S.s_bytes, ws.data_ptr(),
-        ws.numel(), S.slab, int(S.h1.dtype == torch.float16), side, events)
+        ops._stream(), ctypes.addressof(run), T.layers[1], T.nl, S.site0, dx.data_ptr(), dx16.data_ptr(), dx_final.data_ptr(), S.x0.data_ptr(),
+        S.h1.data_ptr(), S.m1.data_ptr(), S.r1.data_ptr(), S.s_last.data_ptr(), G.data_ptr(), 1, S.arena.data_ptr(), S.arena.numel(), S.s_bytes,
+        ws.data_ptr(), ws.numel(), S.slab, side, events)
     return dx_final, G
 
 
-def _unimol_layer_fwd_seq(st, layer, L, s_prev, key_pad, key_tiles, rag_store, row_off, scale, nl, next_mode):
+def _unimol_layer_fwd_seq(st, layer, L, s_prev, key_pad, rag_store, scale, nl, next_mode):
     """One Uni-Mol layer's forward as ONE library call (csrc/layers.hip); fills L with the tensors the backward reads and returns
     (x_out fp32, LayerNorm output of x_out | None, its mean, its rstd)."""
-    att, ln2 = layer.self_attn, layer.final_layer_norm
     M, D, F = st.M, st.D, layer.fc1.weight.shape[0]
     dev = L.x.device
     e = torch.empty
     a16 = L.h1.dtype                          # bf16, or fp16 (fp16 forward operands): the type of every forward GEMM input of the layer
-    L.qkv, L.o = e(M, 3 * D, device=dev, dtype=a16), e(M, D, device=dev, dtype=a16)
+    if st.__dict__.get("run") is None:        # (one run block serves every layer of this forward)
+        st.run = _unimol_run(st, F, ops._pair_layout_s(s_prev, "pair_attn.bias"), scale, a16 == torch.float16)
     L.s = torch.empty_like(s_prev) if ops.pair_is_tiled(s_prev) else e(st.B, st.H, st.N, st.ld, device=dev, dtype=F32)
-    L.x1, L.h2 = e(M, D, device=dev, dtype=F32), e(M, D, device=dev, dtype=a16)
-    L.m2, L.r2 = e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
-    L.u, L.a = e(M, F, device=dev, dtype=BF16), e(M, F, device=dev, dtype=a16)
+    saved = _saved_block("mmdti_unimol_saved_t", L, dev=dev, alloc=dict(
+        qkv=((M, 3 * D), a16), o=((M, D), a16), x1=((M, D), F32), h2=((M, D), a16), m2=((M,), F32), r2=((M,), F32), u=((M, F), BF16), a=((M, F), a16)))
+    P = _layer_block(_layer_desc(_unimol_stack_desc, layer), w16=_w16_ptr)
     x_out = e(M, D, device=dev, dtype=F32)
     ln_out = mn = rn = None
     if next_mode:
@@ -666,14 +719,9 @@ def _unimol_layer_fwd_seq(st, layer, L, s_prev, key_pad, key_tiles, rag_store, r
         mn, rn = e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
     p = ops._p
     ops.lib().mmdti_unimol_layer_fwd(
-        ops._stream(), M, st.B, st.N, st.H, D, F, st.ld, float(scale), float(st.p_res), float(st.p_att), int(st.seed), int(L.site_att), int(L.site_o),
-        int(L.site_f), L.x.data_ptr(), L.h1.data_ptr(), s_prev.data_ptr(), p(key_pad), ops._pair_layout_s(s_prev, "pair_attn.bias"), p(key_tiles),
-        int(rag_store), p(row_off), wfwd(att.in_proj.weight).data_ptr(), p(att.in_proj.bias), wfwd(att.out_proj.weight).data_ptr(), p(att.out_proj.bias),
-        ln2.weight.data_ptr(), ln2.bias.data_ptr(), float(ln2.eps), wfwd(layer.fc1.weight).data_ptr(), p(layer.fc1.bias), ops.ACT_GELU_FWD,
-        wfwd(layer.fc2.weight).data_ptr(), p(layer.fc2.bias), next_mode, p(nl.weight) if nl is not None else 0, p(nl.bias) if nl is not None else 0,
-        float(nl.eps) if nl is not None else 0.0, ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, L.qkv.data_ptr(), L.s.data_ptr(), L.o.data_ptr(),
-        L.x1.data_ptr(), L.h2.data_ptr(), L.m2.data_ptr(), L.r2.data_ptr(), L.u.data_ptr(), L.a.data_ptr(), x_out.data_ptr(), p(ln_out), p(mn), p(rn),
-        int(a16 == torch.float16))
+        ops._stream(), ctypes.addressof(st.run), ctypes.addressof(P), ctypes.addressof(saved), int(L.site_att), int(L.site_o), int(L.site_f),
+        s_prev.data_ptr(), p(key_pad), int(rag_store), next_mode, p(nl.weight) if nl is not None else 0, p(nl.bias) if nl is not None else 0,
+        float(nl.eps) if nl is not None else 0.0, x_out.data_ptr(), p(ln_out), p(mn), p(rn))
     return x_out, ln_out, mn, rn
 
 
@@ -687,29 +735,24 @@ def _unimol_seq_workspace(st, mod, full, on_gpu):
                                   L0 is not None and L0.s.dtype == torch.float16, D, F, M, full)
     if path != paths.LAYER:
         return path, None
-    return path, torch.empty(_unimol_layer_ws_bytes(M, D, F) + 256, device=st.emb.device, dtype=torch.uint8)
+    return path, _layer_workspace(_stack_layout("mmdti_unimol_stack_layout", M, D, F, 0)[3], st.emb.device)
 
 
 def _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, ws, below):
     """One Uni-Mol layer's backward as ONE library call (csrc/layers.hip): -> (dx, dx16) for the layer below (dx16 None at the
     lowest layer).  Same launches, arguments and order as the op-by-op body of PairEncoderFn.backward."""
-    att, ln1, ln2 = layer.self_attn, layer.self_attn_layer_norm, layer.final_layer_norm
     M, D, F = st.M, st.D, layer.fc1.weight.shape[0]
     dx_out = torch.empty_like(dx)
     dx16_out = torch.empty(M, D, device=dx.device, dtype=BF16) if below is not None else None
-    layout = ops._pair_layout_s(L.s, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0)
+    if st.__dict__.get("run_bwd") is None:    # (one run block serves every layer of this backward: G's type is known from the first on)
+        st.run_bwd = _unimol_run(st, F, ops._pair_layout_s(L.s, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0), scale, L.h1.dtype == torch.float16)
+    saved = _saved_block("mmdti_unimol_saved_t", L)
+    P = _layer_block(_layer_desc(_unimol_stack_desc, layer), wb=_wb_ptr, g=_grad_ptr)
     p = ops._p
     ops.lib().mmdti_unimol_layer_bwd(
-        ops._stream(), M, st.B, st.N, st.H, D, F, st.ld, float(scale), float(st.p_res), float(st.p_att), int(st.seed),
-        int(below[0]) if below is not None else 0, int(L.site_o), int(L.site_att), dx.data_ptr(), dx16.data_ptr(), dx_out.data_ptr(), p(dx16_out),
-        p(below[1]) if below is not None else 0, L.a.data_ptr(), L.u.data_ptr(), ops.ACT_GELU_DX, L.h2.data_ptr(), L.x1.data_ptr(), L.m2.data_ptr(),
-        L.r2.data_ptr(), L.o.data_ptr(), L.qkv.data_ptr(), L.s.data_ptr(), L.h1.data_ptr(), L.x.data_ptr(), L.m1.data_ptr(), L.r1.data_ptr(),
-        wbf16(layer.fc2.weight).data_ptr(), wbf16(layer.fc1.weight).data_ptr(), wbf16(att.out_proj.weight).data_ptr(), wbf16(att.in_proj.weight).data_ptr(),
-        ln2.weight.data_ptr(), ln1.weight.data_ptr(), gbuf(layer.fc2.weight).data_ptr(), gbuf(layer.fc1.weight).data_ptr(),
-        gbuf(att.out_proj.weight).data_ptr(), gbuf(att.in_proj.weight).data_ptr(), gbuf(layer.fc1.bias).data_ptr(), gbuf(att.out_proj.bias).data_ptr(),
-        gbuf(att.in_proj.bias).data_ptr(), gbuf(ln2.weight).data_ptr(), gbuf(ln2.bias).data_ptr(), gbuf(ln1.weight).data_ptr(), gbuf(ln1.bias).data_ptr(),
-        G.data_ptr(), layout, int(g_zero), p(st.kt), p(st.row_off), (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256,
-        int(L.h1.dtype == torch.float16))
+        ops._stream(), ctypes.addressof(st.run_bwd), ctypes.addressof(P), ctypes.addressof(saved), int(below[0]) if below is not None else 0, int(L.site_o),
+        int(L.site_att), dx.data_ptr(), dx16.data_ptr(), dx_out.data_ptr(), p(dx16_out), p(below[1]) if below is not None else 0, G.data_ptr(), int(g_zero),
+        ws[1], ws[2])
     return dx_out, dx16_out
 
 
@@ -883,9 +926,7 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
     L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq)
     if L.path == paths.LAYER:
         # the layer's six launches from ONE library call (csrc/layers.hip: the same kernels, arguments and order as below)
-        if self_attn:
-            return _bert_layer_fwd_seq(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
-        return _bert_cross_layer_fwd_seq(st, L, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
+        return (_bert_layer_fwd_seq if self_attn else _bert_cross_layer_fwd_seq)(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
     if L.fw is not None:
         if self_attn:
             # (L.fw[3]: the forward-GEMM shadow of the fused weights; q, k, v are stored bf16 in every mode -- the attention kernels'
@@ -944,9 +985,7 @@ def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
     W, heads, ld = L.W, L.heads, L.ld
     hd = D // heads
     if L.path == paths.LAYER and paths.bert_layer_bwd(L.path, bool(ops.kernel_timer.names), _grad_buffers_live(W, L.self_attn)) == paths.LAYER:
-        if L.self_attn:
-            return _bert_layer_bwd_seq(st, L, dout, seed), None
-        return _bert_cross_layer_bwd_seq(st, L, dout, seed, want)
+        return (_bert_layer_bwd_seq if L.self_attn else _bert_cross_layer_bwd_seq)(st, L, dout, want)
     pend, raw = [], []                     # the layer's weight gradients leave as one grouped launch (see _lin_bwd_params_many)
     dz, dzb = ops.layernorm_bwd(dout, L.z, W.ln2_w, L.zm, L.zr, gbuf(W.ln2_w), gbuf(W.ln2_b), bf16_copy=(L.p_hid, L.site_f, gbuf(W.o2_b)))
     pend.append(((dzb, L.i, W.o2_w, W.o2_b), dict(bias_done=True)))
@@ -1018,56 +1057,82 @@ def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
     return ds1, ds2
 
 
-def _bert_cross_layer_fwd_seq(st, L, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, eps, seed, sites):
-    """_bert_layer_fwd's cross-attention variant (queries from s1, fused key | value projection of s2, fused attention) as ONE library call."""
-    B, Lq, Lk, D, Mq, Mk, vl = st.B, st.Lq, st.Lk, st.D, st.Mq, st.Mk, st.vl
+def _bert_run(st, heads, F, key_add, p_hid, p_att, eps, seed, f16):
+    """The run block of tower 2's calls and of the cross block's (self-attention: st.Mk / st.Lk are st.Mq / st.Lq)."""
+    vl = st.vl
+    q_off, k_off, k_cnt, q_rows = ops._NO_VARLEN if vl is None else vl.args()
+    return ops.lib().struct("mmdti_bert_run_t")(
+        key_add=ops._p(key_add), q_off=q_off, k_off=k_off, k_cnt=k_cnt, seed=int(seed), Mq=st.Mq, Mk=st.Mk, B=st.B, Lq=st.Lq, Lk=st.Lk, heads=heads, D=st.D, F=F,
+        q_rows=q_rows, act_fwd=ops.ACT_GELU_FWD, act_dx=ops.ACT_GELU_DX, ln_max_k=_ln_max_k(), fwd_f16=int(f16), scale=float(1.0 / math.sqrt(st.D // heads)),
+        p_hid=float(p_hid), p_att=float(p_att), eps=float(eps))
+
+
+def _bert_layer_desc(W, cross):
+    """A layer's description (see _layer_block) for the per-layer calls: the fused projection goes in by its views (L.fw / L.fb), the
+    cross layer's separate query projection beside it."""
+    lin = {"o": (W.o_w, W.o_b), "i": (W.i_w, W.i_b), "o2": (W.o2_w, W.o2_b)}
+    if cross:
+        lin["q"] = (W.q_w, W.q_b)
+    return SimpleNamespace(struct="mmdti_bert_layer_t", lin=lin, ln={"ln1": (W.ln1_w, W.ln1_b), "ln2": (W.ln2_w, W.ln2_b)}, extra={})
+
+
+def _bert_seq_fwd(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites):
+    """_bert_layer_fwd's fused-projection / fused-attention variants as ONE library call (csrc/layers.hip): self-attention (q | k | v one
+    GEMM), or -- L.self_attn false -- cross-attention (queries from s1, the fused key | value projection of L.s2_16)."""
+    cross = not L.self_attn
+    B, Lq, D, Mq, Mk, vl = st.B, st.Lq, st.D, st.Mq, st.Mk, st.vl
     F = W.i_w.shape[0]
     dev = s1_32.device
-    e = torch.empty
-    L.site_o, L.site_f = sites.next(), sites.next()
-    a16 = s1_16.dtype
-    L.q, L.qkv, L.ctx = e(Mq, D, device=dev, dtype=BF16), e(Mk, 2 * D, device=dev, dtype=BF16), e(Mq, D, device=dev, dtype=a16)
-    L.k, L.v = L.qkv[:, :D], L.qkv[:, D:]
-    L.stats = e((B, heads, Lq, 2) if vl is None else (heads, Mq, 2), device=dev, dtype=F32)
-    L.y, L.a32, L.a16 = e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=a16)
-    L.am, L.ar, L.zm, L.zr = (e(Mq, device=dev, dtype=F32) for _ in range(4))
-    L.u, L.i = e(Mq, F, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=a16)
-    L.z, out32, out16 = e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=a16)
-    L.p_hid, L.p_att = p_hid, p_att
-    p = ops._p
-    ops.lib().mmdti_bert_cross_layer_fwd(
-        ops._stream(), Mq, Mk, B, Lq, Lk, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(p_hid), float(p_att), int(seed), int(L.site_att),
-        int(L.site_o), int(L.site_f), s1_32.data_ptr(), s1_16.data_ptr(), s2_16.data_ptr(), p(key_add), *(ops._NO_VARLEN if vl is None else vl.args()),
-        wfwd(W.q_w).data_ptr(), p(W.q_b), L.fw[3].data_ptr(), L.fb[1].data_ptr(), wfwd(W.o_w).data_ptr(), p(W.o_b), W.ln1_w.data_ptr(), W.ln1_b.data_ptr(),
-        wfwd(W.i_w).data_ptr(), p(W.i_b), ops.ACT_GELU_FWD, wfwd(W.o2_w).data_ptr(), p(W.o2_b), W.ln2_w.data_ptr(), W.ln2_b.data_ptr(), float(eps),
-        ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, L.q.data_ptr(), L.qkv.data_ptr(), L.ctx.data_ptr(), L.stats.data_ptr(), L.y.data_ptr(), L.a32.data_ptr(),
-        L.a16.data_ptr(), L.am.data_ptr(), L.ar.data_ptr(), L.u.data_ptr(), L.i.data_ptr(), L.z.data_ptr(), out32.data_ptr(), out16.data_ptr(),
-        L.zm.data_ptr(), L.zr.data_ptr(), int(a16 == torch.float16))
+    L.site_o, L.site_f = sites.next(), sites.next()          # (L.site_att was drawn by the caller: the same numbering as the op-by-op path)
+    a16 = s1_16.dtype                         # bf16, or fp16 (fp16 forward operands); q | k | v and the saved gelu' stay bf16 in every mode
+    rows, f32 = ((Mq, D), F32), ((Mq,), F32)
+    alloc = dict(qkv=((Mk, 2 * D) if cross else (Mq, 3 * D), BF16), ctx=((Mq, D), a16), stats=((B, heads, Lq, 2) if vl is None else (heads, Mq, 2), F32),
+                 y=rows, a32=rows, a16=((Mq, D), a16), am=f32, ar=f32, u=((Mq, F), BF16), i=((Mq, F), a16), z=rows, zm=f32, zr=f32)
+    if cross:
+        alloc["q"] = ((Mq, D), BF16)
+    saved = _saved_block("mmdti_bert_saved_t", L, alloc, dev, s1_32=s1_32)
+    if cross:
+        L.k, L.v = L.qkv[:, :D], L.qkv[:, D:]
+    else:
+        L.q, L.k, L.v = L.qkv[:, :D], L.qkv[:, D:2 * D], L.qkv[:, 2 * D:]
+    out32, out16 = torch.empty(Mq, D, device=dev, dtype=F32), torch.empty(Mq, D, device=dev, dtype=a16)
+    L.fused, L.p_hid, L.p_att = True, p_hid, p_att
+    if st.__dict__.get("run") is None:        # (one run block serves every layer of a tower's forward -- and the backward)
+        st.run = _bert_run(st, heads, F, key_add, p_hid, p_att, eps, seed, a16 == torch.float16)
+    L.run = st.run
+    P = _layer_block(_bert_layer_desc(W, cross), w16=_w16_ptr, w_qkv=L.fw[3].data_ptr(), b_qkv=L.fb[1].data_ptr())
+    (ops.lib().mmdti_bert_cross_layer_fwd if cross else ops.lib().mmdti_bert_layer_fwd)(
+        ops._stream(), ctypes.addressof(L.run), ctypes.addressof(P), ctypes.addressof(saved), int(L.site_att), int(L.site_o), int(L.site_f),
+        out32.data_ptr(), out16.data_ptr())
     return L, out32, out16
 
 
-def _bert_cross_layer_bwd_seq(st, L, dout, seed, want=(True, True)):
-    """_bert_layer_bwd of a layer that went through _bert_cross_layer_fwd_seq: its ten launches up to the weight gradients as ONE library
-    call, then the weight gradients exactly as the op-by-op path launches them -> (ds1, ds2) fp32."""
-    B, Lq, Lk, D, Mq, Mk, vl = st.B, st.Lq, st.Lk, st.D, st.Mq, st.Mk, st.vl
+def _bert_seq_bwd(st, L, dout, want=(True, True)):
+    """_bert_layer_bwd of a layer that went through _bert_seq_fwd -> (ds1, ds2) fp32.  Self-attention: ONE library call, ds2 None.
+    Cross: its ten launches up to the weight gradients as one call, then the weight gradients exactly as the op-by-op path launches
+    them (the layer has two token-row counts)."""
+    cross = not L.self_attn
+    D, Mq, Mk = st.D, st.Mq, st.Mk
     W, heads = L.W, L.heads
     F = W.i_w.shape[0]
     dev = dout.device
     dout = dout.contiguous()
     e = torch.empty
-    ds1, ds2 = e(Mq, D, device=dev, dtype=F32), (e(Mk, D, device=dev, dtype=F32) if want[1] else None)   # (ds2 null: not launched)
+    ds1 = e(Mq, D, device=dev, dtype=F32)
+    nrow = _attn_stat_rows(st, heads)
+    _, ws, ws_bytes = _layer_workspace(_stack_layout("mmdti_bert_stack_layout", Mq, D, F, nrow * 8, nrow)[4 if cross else 3], dev)
+    saved = _saved_block("mmdti_bert_saved_t", L)
+    P = _layer_block(_bert_layer_desc(W, cross), wb=_wb_ptr, g=_grad_ptr, wb_qkv=L.fw[0].data_ptr(), dw_qkv=L.fw[2].data_ptr(), lddw_qkv=L.fw[2].stride(0),
+                     db_qkv=L.fb[2].view(-1).data_ptr())
+    head = (ops._stream(), ctypes.addressof(L.run), ctypes.addressof(P), ctypes.addressof(saved), int(L.site_att), int(L.site_o), int(L.site_f), dout.data_ptr(),
+            ds1.data_ptr())
+    if not cross:
+        ops.lib().mmdti_bert_layer_bwd(*head, ws, ws_bytes)
+        return ds1, None
+    ds2 = e(Mk, D, device=dev, dtype=F32) if want[1] else None   # (ds2 null: not launched)
     dzb, du, dyb = e(Mq, D, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=BF16), e(Mq, D, device=dev, dtype=BF16)
     dq, dqkv = e(Mq, D, device=dev, dtype=BF16), torch.empty_like(L.qkv)
-    ws = e(_bert_cross_layer_ws_bytes(Mq, D, _attn_stat_rows(st, heads)) + 256, device=dev, dtype=torch.uint8)
-    p = ops._p
-    ops.lib().mmdti_bert_cross_layer_bwd(
-        ops._stream(), Mq, Mk, B, Lq, Lk, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(L.p_hid), float(L.p_att), int(seed), int(L.site_att),
-        int(L.site_o), int(L.site_f), dout.data_ptr(), ds1.data_ptr(), p(ds2), p(L.key_add), *(ops._NO_VARLEN if vl is None else vl.args()),
-        L.q.data_ptr(), L.qkv.data_ptr(), L.stats.data_ptr(), L.y.data_ptr(), L.am.data_ptr(), L.ar.data_ptr(), L.u.data_ptr(), ops.ACT_GELU_DX,
-        L.z.data_ptr(), L.zm.data_ptr(), L.zr.data_ptr(), wbf16(W.q_w).data_ptr(), L.fw[0].data_ptr(), wbf16(W.o_w).data_ptr(), wbf16(W.i_w).data_ptr(),
-        wbf16(W.o2_w).data_ptr(), W.ln1_w.data_ptr(), W.ln2_w.data_ptr(), gbuf(W.o_b).data_ptr(), gbuf(W.o2_b).data_ptr(), gbuf(W.ln1_w).data_ptr(),
-        gbuf(W.ln1_b).data_ptr(), gbuf(W.ln2_w).data_ptr(), gbuf(W.ln2_b).data_ptr(), dzb.data_ptr(), du.data_ptr(), dyb.data_ptr(), dq.data_ptr(),
-        dqkv.data_ptr(), (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256)
+    ops.lib().mmdti_bert_cross_layer_bwd(*head, ops._p(ds2), dzb.data_ptr(), du.data_ptr(), dyb.data_ptr(), dq.data_ptr(), dqkv.data_ptr(), ws, ws_bytes)
     # the weight gradients, as the op-by-op path hands them over (same items, same order: _lin_bwd_params_many groups them by row count)
     pend = [((dzb, L.i, W.o2_w, W.o2_b), dict(bias_done=True)), ((du, L.a16, W.i_w, W.i_b), {}), ((dyb, L.ctx, W.o_w, W.o_b), dict(bias_done=True)),
             ((dq, L.s1_16, W.q_w, W.q_b), {})]
@@ -1075,72 +1140,28 @@ def _bert_cross_layer_bwd_seq(st, L, dout, seed, want=(True, True)):
     return (ds1 if want[0] else None), ds2
 
 
-def _bert_layer_fwd_seq(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites):
-    """_bert_layer_fwd's self-attention / fused-projection / fused-attention variant as ONE library call (csrc/layers.hip)."""
-    B, Lq, D, Mq, vl = st.B, st.Lq, st.D, st.Mq, st.vl
-    F = W.i_w.shape[0]
-    dev = s1_32.device
-    e = torch.empty
-    L.site_o, L.site_f = sites.next(), sites.next()          # (L.site_att was drawn by the caller: the same numbering as the op-by-op path)
-    a16 = s1_16.dtype                         # bf16, or fp16 (fp16 forward operands); q | k | v and the saved gelu' stay bf16 in every mode
-    L.qkv, L.ctx = e(Mq, 3 * D, device=dev, dtype=BF16), e(Mq, D, device=dev, dtype=a16)
-    L.q, L.k, L.v = L.qkv[:, :D], L.qkv[:, D:2 * D], L.qkv[:, 2 * D:]
-    L.stats = e((B, heads, Lq, 2) if vl is None else (heads, Mq, 2), device=dev, dtype=F32)
-    L.y, L.a32, L.a16 = e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=a16)
-    L.am, L.ar, L.zm, L.zr = (e(Mq, device=dev, dtype=F32) for _ in range(4))
-    L.u, L.i = e(Mq, F, device=dev, dtype=BF16), e(Mq, F, device=dev, dtype=a16)
-    L.z, out32, out16 = e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=F32), e(Mq, D, device=dev, dtype=a16)
-    L.fused, L.p_hid, L.p_att = True, p_hid, p_att
-    p = ops._p
-    ops.lib().mmdti_bert_layer_fwd(
-        ops._stream(), Mq, B, Lq, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(p_hid), float(p_att), int(seed), int(L.site_att), int(L.site_o),
-        int(L.site_f), s1_32.data_ptr(), s1_16.data_ptr(), p(key_add), *(ops._NO_VARLEN if vl is None else vl.args()), L.fw[3].data_ptr(),
-        L.fb[1].data_ptr(), wfwd(W.o_w).data_ptr(), p(W.o_b), W.ln1_w.data_ptr(), W.ln1_b.data_ptr(), wfwd(W.i_w).data_ptr(), p(W.i_b), ops.ACT_GELU_FWD,
-        wfwd(W.o2_w).data_ptr(), p(W.o2_b), W.ln2_w.data_ptr(), W.ln2_b.data_ptr(), float(eps), ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0,
-        L.qkv.data_ptr(), L.ctx.data_ptr(), L.stats.data_ptr(), L.y.data_ptr(), L.a32.data_ptr(), L.a16.data_ptr(), L.am.data_ptr(), L.ar.data_ptr(),
-        L.u.data_ptr(), L.i.data_ptr(), L.z.data_ptr(), out32.data_ptr(), out16.data_ptr(), L.zm.data_ptr(), L.zr.data_ptr(),
-        int(a16 == torch.float16))
-    return L, out32, out16
-
-
-def _bert_layer_bwd_seq(st, L, dout, seed):
-    """_bert_layer_bwd of a layer that went through _bert_layer_fwd_seq, as ONE library call -> ds1 (fp32)."""
-    B, Lq, D, Mq, vl = st.B, st.Lq, st.D, st.Mq, st.vl
-    W, heads = L.W, L.heads
-    F = W.i_w.shape[0]
-    dout = dout.contiguous()
-    ds1 = torch.empty(Mq, D, device=dout.device, dtype=F32)
-    ws = torch.empty(_bert_layer_ws_bytes(Mq, D, F, _attn_stat_rows(st, heads)) + 256, device=dout.device, dtype=torch.uint8)
-    p = ops._p
-    ops.lib().mmdti_bert_layer_bwd(
-        ops._stream(), Mq, B, Lq, heads, D, F, float(1.0 / math.sqrt(D // heads)), float(L.p_hid), float(L.p_att), int(seed), int(L.site_att), int(L.site_o),
-        int(L.site_f), dout.data_ptr(), ds1.data_ptr(), L.s1_16.data_ptr(), p(L.key_add), *(ops._NO_VARLEN if vl is None else vl.args()),
-        L.qkv.data_ptr(), L.ctx.data_ptr(), L.stats.data_ptr(), L.y.data_ptr(), L.a16.data_ptr(), L.am.data_ptr(), L.ar.data_ptr(), L.u.data_ptr(),
-        ops.ACT_GELU_DX, L.i.data_ptr(), L.z.data_ptr(), L.zm.data_ptr(), L.zr.data_ptr(), L.fw[0].data_ptr(), wbf16(W.o_w).data_ptr(),
-        wbf16(W.i_w).data_ptr(), wbf16(W.o2_w).data_ptr(), W.ln1_w.data_ptr(), W.ln2_w.data_ptr(), L.fw[2].data_ptr(), L.fw[2].stride(0),
-        L.fb[2].view(-1).data_ptr(), gbuf(W.o_w).data_ptr(), gbuf(W.o_b).data_ptr(), gbuf(W.i_w).data_ptr(), gbuf(W.i_b).data_ptr(),
-        gbuf(W.o2_w).data_ptr(), gbuf(W.o2_b).data_ptr(), gbuf(W.ln1_w).data_ptr(), gbuf(W.ln1_b).data_ptr(), gbuf(W.ln2_w).data_ptr(),
-        gbuf(W.ln2_b).data_ptr(), (ws.data_ptr() + 255) // 256 * 256, ws.numel() - 256, int(L.s1_16.dtype == torch.float16))
-    return ds1
+# (the self-attention and the cross layer enter the one body under their own names: the suite counts each kind's calls by them)
+_bert_layer_fwd_seq = lambda *args: _bert_seq_fwd(*args)         # noqa: E731
+_bert_layer_bwd_seq = lambda *args: _bert_seq_bwd(*args)         # noqa: E731
+_bert_cross_layer_fwd_seq = lambda *args: _bert_seq_fwd(*args)   # noqa: E731
+_bert_cross_layer_bwd_seq = lambda *args: _bert_seq_bwd(*args)   # noqa: E731
 
 
 def _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites):
     """All layers of tower 2 as ONE library call -> the tower's fp32 output [Mq, D]."""
     nrow = _attn_stat_rows(st, st.heads)
     stats_bytes = nrow * 8
-    stride, ws_bytes, slab = _stack_layout("mmdti_bert_stack_layout", st.Mq, T.D, T.F, stats_bytes, nrow)
+    stride, ws_bytes, slab = _stack_layout("mmdti_bert_stack_layout", st.Mq, T.D, T.F, stats_bytes, nrow)[:3]
     dev = x32.device
     arena = torch.empty(stride * T.nl, device=dev, dtype=torch.uint8)
     out32 = torch.empty(st.Mq, T.D, device=dev, dtype=F32)
     site0 = sites.n + 1
     sites.n += 3 * T.nl
-    vl = st.vl
-    ops.lib().mmdti_bert_stack_fwd(
-        ops._stream(), T.nl, st.Mq, st.B, st.Lq, st.heads, T.D, T.F, float(1.0 / math.sqrt(T.D // st.heads)), float(p_hid), float(p_att), int(seed), site0,
-        x32.data_ptr(), x16.data_ptr(), ops._p(key_add), *(ops._NO_VARLEN if vl is None else vl.args()), T.fwd[1], ops.ACT_GELU_FWD, float(cfg.ln_eps),
-        ops.GEMM_LN_MAX_K if ops.GEMM_LN else 0, arena.data_ptr(), arena.numel(), stats_bytes, out32.data_ptr(), int(x16.dtype == torch.float16))
-    st.stack = SimpleNamespace(T=T, arena=arena, ws_bytes=ws_bytes, slab=slab, stats_bytes=stats_bytes, site0=site0, x16=x16, key_add=key_add, p_hid=p_hid,
-                               p_att=p_att)
+    run = _bert_run(st, st.heads, T.F, key_add, p_hid, p_att, cfg.ln_eps, seed, x16.dtype == torch.float16)
+    ops.lib().mmdti_bert_stack_fwd(ops._stream(), ctypes.addressof(run), T.layers[1], T.nl, site0, x32.data_ptr(), x16.data_ptr(), arena.data_ptr(),
+                                   arena.numel(), stats_bytes, out32.data_ptr())
+    # (x16, key_add: the run block and the backward read them -- kept alive here)
+    st.stack = SimpleNamespace(T=T, arena=arena, ws_bytes=ws_bytes, slab=slab, stats_bytes=stats_bytes, site0=site0, x16=x16, key_add=key_add, run=run)
     return out32
 
 
@@ -1151,12 +1172,8 @@ def _bert_stack_bwd(st, dout):
     dev = dout.device
     ds1 = torch.empty(st.Mq, T.D, device=dev, dtype=F32)
     ws = torch.empty(S.ws_bytes, device=dev, dtype=torch.uint8)
-    vl = st.vl
-    ops.lib().mmdti_bert_stack_bwd(
-        ops._stream(), T.nl, st.Mq, st.B, st.Lq, st.heads, T.D, T.F, float(1.0 / math.sqrt(T.D // st.heads)), float(S.p_hid), float(S.p_att), int(st.seed),
-        S.site0, dout.data_ptr(), ds1.data_ptr(), S.x16.data_ptr(), ops._p(S.key_add), *(ops._NO_VARLEN if vl is None else vl.args()), T.bwd[1],
-        ops.ACT_GELU_DX, T.grads[1], T.D, S.arena.data_ptr(), S.arena.numel(), S.stats_bytes, ws.data_ptr(), ws.numel(), S.slab,
-        int(S.x16.dtype == torch.float16))
+    ops.lib().mmdti_bert_stack_bwd(ops._stream(), ctypes.addressof(S.run), T.layers[1], T.nl, S.site0, dout.data_ptr(), ds1.data_ptr(), S.x16.data_ptr(),
+                                   S.arena.data_ptr(), S.arena.numel(), S.stats_bytes, ws.data_ptr(), ws.numel(), S.slab)
     return ds1
 
 

@@ -31,7 +31,7 @@ def test_header_has_no_torch_types_and_cites_reference():
 
 def test_argument_validation_happens_before_any_launch():
     lib = _abi.lib()
-    assert lib._dll.mmdti_abi_version() == 1
+    assert lib._dll.mmdti_abi_version() == _abi.header_constants()["MMDTI_ABI_VERSION"]
     with pytest.raises(_abi.MMDTIError, match="multiples of 8"):
         lib.mmdti_gemm_bf16(0, 16, 16, 16, 8, 8, 12, 12, 12, 8, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 1, 1.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0)
     with pytest.raises(_abi.MMDTIError, match="exceeds"):

@@ -13,10 +13,10 @@ def test_header_declares_long_attention_with_the_short_argument_lists():
         assert protos[long_name][2] == protos[short_name][2]          # ... and names
 
 
-def test_library_exports_long_attention_and_abi_version_stays():
+def test_library_exports_long_attention_and_abi_version_is_the_headers():
     lib = _abi.lib()                                                   # raises if a declared symbol is not exported
     assert "mmdti_attn_long_fwd" in lib.protos and "mmdti_attn_long_bwd" in lib.protos
-    assert lib._dll.mmdti_abi_version() == 1
+    assert lib._dll.mmdti_abi_version() == lib.const["MMDTI_ABI_VERSION"]
 
 
 def test_attn_eligible_up_to_512():
