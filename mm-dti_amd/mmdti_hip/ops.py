@@ -916,6 +916,8 @@ def _attn_fwd(name, q, k, v, key_add, B, heads, Lq, Lk, scale, drop_p=0.0, seed=
         _chk(t_, BF16, n_, contiguous=False)
         if t_.stride(1) != 1:
             raise MMDTIError(f"{n_}: unit column stride required")
+    if v.stride(0) != k.stride(0):           # (the library takes ONE row stride for the key side)
+        raise MMDTIError(f"{name}: k and v must share one row stride (got {k.stride(0)} and {v.stride(0)})")
     D = q.shape[1]
     hd = D // heads
     rows_q = B * Lq if vl is None else vl.q_rows
@@ -933,7 +935,12 @@ def _attn_fwd(name, q, k, v, key_add, B, heads, Lq, Lk, scale, drop_p=0.0, seed=
 
 def _attn_bwd(name, q, k, v, key_add, dctx, stats, B, heads, Lq, Lk, scale, drop_p=0.0, seed=0, site=0, out=None, vl=None):
     """out: optional (dq, dk, dv) destination views (unit column stride; dk and dv share one row stride)."""
-    _chk(dctx, BF16, "attn.dctx")
+    for t_, n_ in ((q, "attn.q"), (k, "attn.k"), (v, "attn.v"), (dctx, "attn.dctx")):
+        _chk(t_, BF16, n_, contiguous=False)
+        if t_.stride(1) != 1:
+            raise MMDTIError(f"{n_}: unit column stride required")
+    if v.stride(0) != k.stride(0):
+        raise MMDTIError(f"{name}: k and v must share one row stride (got {k.stride(0)} and {v.stride(0)})")
     D = q.shape[1]
     hd = D // heads
     rows_q, rows_k = (B * Lq, B * Lk) if vl is None else (vl.q_rows, vl.k_rows)
