@@ -773,6 +773,17 @@ def pair_key_tiles_effective(kt, nt):
     return nt if k >= nt else k
 
 
+def _pair_numel(B, N, H, ld, tiled):
+    """elements the pair-attention kernels address in a pair tensor of the call: a smaller one would be read and written past its end"""
+    return B * H * (pair_plane(N) if tiled else N * ld)
+
+
+def _pair_numel_ok(t, B, N, H, ld, tiled):
+    """tiled planes have one size per N (the plane stride is computed from N, not passed); row-major planes must hold B H N ld elements"""
+    want = _pair_numel(B, N, H, ld, tiled)
+    return t.numel() == want if tiled else t.numel() >= want
+
+
 _pair_kept = 1.0       # fraction of the padded key columns the ragged kernels keep (work accounting of the timers only)
 
 
@@ -803,6 +814,8 @@ def pair_attn_fwd(qkv, bias_in, key_pad, B, N, H, ld, scale, drop_p=0.0, seed=0,
             raise MMDTIError("pair_attn_fwd: with packed rows key_pad is indexed by packed row")
     elif qkv.shape[0] != B * N:
         raise MMDTIError(f"pair_attn_fwd: qkv has {qkv.shape[0]} rows, expected B*N = {B * N}")
+    if not _pair_numel_ok(bias_in, B, N, H, ld, tiled):
+        raise MMDTIError(f"pair_attn_fwd: the bias holds {bias_in.numel()} elements, the planes of B={B}, H={H}, N={N}, ld={ld} need {_pair_numel(B, N, H, ld, tiled)}")
     s_out = torch.empty_like(bias_in) if tiled else torch.empty(B, H, N, ld, device=qkv.device, dtype=F32)
     o = torch.empty(rows, H * 8, device=qkv.device, dtype=qkv.dtype)
     kp = _u8(key_pad)
@@ -835,6 +848,8 @@ def pair_attn_bwd(qkv, s, do, g, B, N, H, ld, scale, g_in_zero, drop_p=0.0, seed
         raise MMDTIError("pair_attn_bwd: S and G must share one pair layout (fp32 gradients, or bf16 gradients with fp16 logits)")
     if g.dtype == BF16:
         layout |= 4
+    if not (_pair_numel_ok(s, B, N, H, ld, tiled) and g.numel() == s.numel()):
+        raise MMDTIError(f"pair_attn_bwd: S / G hold {s.numel()} / {g.numel()} elements, the planes of B={B}, H={H}, N={N}, ld={ld} need {_pair_numel(B, N, H, ld, tiled)}")
     t0 = kernel_timer.begin("pair_attn_bwd")
     lib().mmdti_pair_attn_bwd(_stream(), qkv.data_ptr(), s.data_ptr(), do.data_ptr(), g.data_ptr(), dqkv.data_ptr(), B, N, H, ld,
                               float(scale), int(g_in_zero), float(drop_p), int(seed), int(site), layout, _p(key_tiles), _p(row_off), int(qkv.dtype == F16))
