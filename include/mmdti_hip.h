@@ -449,6 +449,35 @@ int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, const float* d
                             long long workspace_bytes);
 /* bytes of workspace for mmdti_gbf_bias_bwd_full with E edge types (a value, not a status code) */
 int mmdti_gbf_bias_bwd_full_workspace(int E);
+/* ---- Pair inputs from coordinates.  The two [B,N,N] planes above are functions of the atoms: the reference builds them per
+ * molecule as distance_matrix(coord, coord) and tok_i * len(dictionary) + tok_j (data/conformer.py:204-212), right-pads them with 0.0
+ * and the pad index, and mm_model.py:553-556 consumes them.  These entry points take the atoms instead: one 16-byte record per atom,
+ * [B,N] { fp32 x, y, z, int32 token }, 16-byte aligned.  THE PAIR RULE (one device function, used by all four): either token equal to
+ * pad_idx -> (edge type, distance) = (pad_idx, 0.0f), whatever the slot's coordinates hold; otherwise edge type = tok_i * V + tok_j and
+ * distance = |c_i - c_j| in fp32 -- three subtractions, dx * dx, two fused multiply-adds, one correctly rounded square root; i == j
+ * gives exactly 0.  Every coords entry point checks, before any launch: records non-null and 16-byte aligned, N * N < 2^30 (the limit of
+ * the planes forms), V * V == E with V <= 181, 0 <= pad_idx < V.  Purely additive: MMDTI_ABI_VERSION does not move. */
+/* coord [B,N,3] fp32 + tokens [B,N] (token_bytes 8: int64 as the reference collates, or 4) -> records [B,N]
+ * (data/conformer.py:204-212, mm_model.py:553-556) */
+int mmdti_pair_records_pack(mmdti_stream_t stream, const float* coord, const void* tokens, int token_bytes, int B, int N, void* records);
+/* records -> dist [B,N,N] fp32 and edge_type [B,N,N] (edge_bytes 8 or 2), by the pair rule: the planes of data/conformer.py:204-212 as
+ * mm_model.py:553-556 reads them.  What a configuration without a fused coords kernel runs on. */
+int mmdti_pair_inputs_from_coords(mmdti_stream_t stream, const void* records, int B, int N, int V, int pad_idx, float* dist, void* edge_type,
+                                  int edge_bytes);
+/* mmdti_gbf_bias_fwd with the pair rule in place of the two plane loads (data/conformer.py:204-212 folded into mm_model.py:553-556):
+ * bit-identical to mmdti_pair_inputs_from_coords followed by mmdti_gbf_bias_fwd.  Saves no intermediates (it serves the configurations
+ * of mmdti_gbf_bias_bwd_full_coords); flags, tile_prefix and row_blocks as in mmdti_gbf_bias_fwd. */
+int mmdti_gbf_bias_fwd_coords(mmdti_stream_t stream, const void* records, int V, int pad_idx, const float* mul, const float* bias,
+                              const float* means, const float* stds, const void* w1_bf16, const float* b1, const void* w2_bf16,
+                              const float* b2, int B, int N, int ld, int K, int F, int H, int E, void* out, int flags,
+                              const int* tile_prefix, const int* row_blocks);
+/* mmdti_gbf_bias_bwd_full from the records (data/conformer.py:204-212, mm_model.py:553-556 backward): the same kernel body, the same
+ * deterministic form, bit-identical in that mode to the planes form run on mmdti_pair_inputs_from_coords' output. */
+int mmdti_gbf_bias_bwd_full_coords(mmdti_stream_t stream, const void* g, const void* records, int V, int pad_idx, const float* mul,
+                                   const float* bias, const float* means, const float* stds, const void* w1_bf16, const float* b1,
+                                   const void* w2_bf16, int B, int N, int ld, int K, int F, int H, int E, int flags, float* dw1,
+                                   float* db1, float* dw2, float* db2, float* dmul, float* dbias, float* dmeans, float* dstds,
+                                   const int* tile_prefix, const int* row_blocks, void* workspace, long long workspace_bytes);
 /* [B,N,N,H] fp32 -> [B,H,N,ld] fp32 (mm_model.py:555-556 permute(0,3,1,2).contiguous()) and its gradient
  * [B,H,N,ld] fp32 (or, tiled != 0, the blocked-row tile layout of mmdti_gbf_bias_fwd) -> [B,N,N,H] bf16 */
 int mmdti_pair_permute_fwd(mmdti_stream_t stream, const float* x, float* out, int B, int N, int H, int ld);

@@ -307,6 +307,55 @@ __device__ __forceinline__ int gbf_edge(const void* et, long long base, unsigned
 }
 __device__ __forceinline__ int gbf_edge(const void* et, long long p, int esz) { return gbf_edge(et, p, 0u, esz); }
 
+// ---- Pair inputs from coordinates (data/conformer.py:204-212: distance_matrix(coord, coord) and tok_i * len(dictionary) + tok_j;
+// MM_Model.batch_collate_fn right-pads the two planes with 0.0 / the pad index, mm_model.py:553-556 consumes them).
+// One 16-byte record per atom, [B, N]: the fp32 bits of x, y, z and the token index -- a molecule's records are 2 KB and stay in cache,
+// and a lane of the fused kernels fetches its pair with two 16-byte loads.
+// THE pair rule, shared by every kernel that derives a pair from two atoms: either atom pad -> (pad index, 0.0f); else
+// e = tok_i * V + tok_j, d = |c_i - c_j| in fp32 with the rounding points spelled out (three subtractions, dx * dx, two fused
+// multiply-adds, one correctly rounded square root) and contraction off -- this file is built with the backend's opportunistic
+// contraction, and two instantiations must not differ in where they fuse.  i == j gives exactly 0; whatever a pad slot holds as
+// coordinates (NaN included) is selected away.
+__device__ __forceinline__ void gbf_pair_rule(const uint4& ai, const uint4& aj, int V, int pad, int& e, float& d) {
+#pragma clang fp contract(off)
+  const int ti = (int)ai.w, tj = (int)aj.w;
+  const float dx = __uint_as_float(ai.x) - __uint_as_float(aj.x);
+  const float dy = __uint_as_float(ai.y) - __uint_as_float(aj.y);
+  const float dz = __uint_as_float(ai.z) - __uint_as_float(aj.z);
+  const float xx = dx * dx;
+  const float s = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, xx));
+  const bool padp = ti == pad || tj == pad;
+  e = padp ? pad : ti * V + tj;
+  d = padp ? 0.0f : __builtin_sqrtf(s);
+}
+
+// coord [B*N, 3] fp32 + tokens [B*N] (int64 as the reference collates them, or int32) -> records
+__global__ __launch_bounds__(256) void pair_records_pack_kernel(const float* __restrict__ coord, const void* __restrict__ tok, int tsz,
+                                                                long long n, uint4* __restrict__ rec) {
+  for (long long a = (long long)blockIdx.x * 256 + threadIdx.x; a < n; a += (long long)gridDim.x * 256) {
+    const int t = tsz == 8 ? (int)reinterpret_cast<const long long*>(tok)[a] : reinterpret_cast<const int*>(tok)[a];
+    rec[a] = make_uint4(__float_as_uint(coord[3 * a]), __float_as_uint(coord[3 * a + 1]), __float_as_uint(coord[3 * a + 2]), (unsigned)t);
+  }
+}
+
+// records -> the two [B,N,N] planes the reference collates (src_distance fp32, src_edge_type int64 or int16): what every configuration
+// without a fused coords kernel runs on, and the yardstick the fused coords kernels are held to bit for bit.
+template <typename ET>
+__global__ __launch_bounds__(256) void pair_inputs_from_coords_kernel(const uint4* __restrict__ rec, int N, long long P, int V, int pad,
+                                                                      float* __restrict__ dist, ET* __restrict__ et) {
+  const unsigned NN = (unsigned)N * (unsigned)N;
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long long)gridDim.x * 256) {
+    const long long b = p / NN;
+    const unsigned r = (unsigned)(p - b * NN), i = r / (unsigned)N, j = r - i * (unsigned)N;
+    const uint4* mr = rec + b * N;
+    int e;
+    float d;
+    gbf_pair_rule(mr[i], mr[j], V, pad, e, d);
+    dist[p] = d;
+    et[p] = (ET)e;
+  }
+}
+
 typedef float gf32x2 __attribute__((ext_vector_type(2)));
 constexpr float GBF_SQ = 0.84932180028801907f;   // sqrt(log2(e) / 2): exp(-z^2 / 2) = exp2(-(GBF_SQ * z)^2)
 
@@ -344,7 +393,8 @@ __device__ __forceinline__ float gbf_get(const __bf16* p) {
   return __builtin_bit_cast(float, (uint32_t)(*reinterpret_cast<const unsigned short*>(p)) << 16);
 }
 
-template <bool SAVE, bool TILED, typename OT>
+// COORDS: the pair's (edge type, distance) comes from the two atoms' records (gbf_pair_rule) instead of the two planes; only fetch differs.
+template <bool SAVE, bool TILED, typename OT, bool COORDS = false>
 __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __restrict__ dist, const void* __restrict__ et, int esz,
                                                               const float* __restrict__ mul, const float* __restrict__ bias,
                                                               const float* __restrict__ means, const float* __restrict__ stds,
@@ -353,7 +403,8 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
                                                               OT* __restrict__ out, bf16_t* __restrict__ feat_out,
                                                               bf16_t* __restrict__ u_out, bf16_t* __restrict__ h_out, int B, int N,
                                                               int ld, int E, int tpm, int ugrad, int ltab,
-                                                              const int* __restrict__ tile_prefix, const int* __restrict__ row_blocks) {
+                                                              const int* __restrict__ tile_prefix, const int* __restrict__ row_blocks,
+                                                              const uint4* __restrict__ rec, int V, int pad) {
   static_assert(TILED || sizeof(OT) == 4, "compact pair planes exist in the tiled layout only");
   extern __shared__ __attribute__((aligned(16))) unsigned char gbf_smem[];
   bf16_t* sW1 = reinterpret_cast<bf16_t*>(gbf_smem);       // [128][136]   W1[f][k]
@@ -404,7 +455,7 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
   const int nblk = (N + 3) >> 2;
   const long long plane = TILED ? pair_plane(N) : (long long)N * ld;
   // flags: bit 0 valid pair, bit 1 slot inside the plane, bit 2 whole block past N
-  auto fetch = [&](int tile, int& b, int& q, int& flags, unsigned& pl, int& e, float& d) {
+  auto fetch = [&](int tile, int& b, int& q, int& flags, unsigned& pl, int& e, float& d, uint4& ai, uint4& aj) {
     tile = __builtin_amdgcn_readfirstlane(tile < ntiles ? tile : ntiles - 1);
     int tq;
     if (rag) {
@@ -438,18 +489,29 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
     const bool valid = ii < N && jj < N;
     flags = (valid ? 1 : 0) | (inplane ? 2 : 0) | (past ? 4 : 0);
     pl = (unsigned)((valid ? ii : 0) * N + (valid ? jj : 0));
-    const long long mol = (long long)b * N * N;
-    const int e32 = gbf_edge(et, mol, pl, esz);
-    e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
-    d = (dist + mol)[pl];
+    if constexpr (COORDS) {       // (a pad lane reads atom 0 of its molecule, as it reads pair (0, 0) of the planes)
+      const uint4* mr = rec + (long long)b * N;
+      ai = mr[valid ? ii : 0];
+      aj = mr[valid ? jj : 0];
+    } else {
+      const long long mol = (long long)b * N * N;
+      const int e32 = gbf_edge(et, mol, pl, esz);
+      e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
+      d = (dist + mol)[pl];
+    }
   };
-  int b, q, flags, e, n_b, n_q, n_flags, n_e;
+  int b, q, flags, e = 0, n_b, n_q, n_flags, n_e = 0;
   unsigned pl, n_pl;
-  float d, n_d;
+  float d = 0.f, n_d = 0.f;
+  uint4 ai = {}, aj = {}, n_ai = {}, n_aj = {};
   int tile = (int)blockIdx.x * 8 + (tid >> 6);
-  fetch(tile, b, q, flags, pl, e, d);
+  fetch(tile, b, q, flags, pl, e, d, ai, aj);
   for (; tile < ntiles; tile += nwaves) {
-    fetch(tile + nwaves, n_b, n_q, n_flags, n_pl, n_e, n_d);
+    if constexpr (COORDS) {       // the records arrived an iteration ago: reduce them to (e, d) before the next pair's eight registers go live
+      gbf_pair_rule(ai, aj, V, pad, e, d);
+      e = e < 0 ? 0 : (e >= E ? E - 1 : e);
+    }
+    fetch(tile + nwaves, n_b, n_q, n_flags, n_pl, n_e, n_d, n_ai, n_aj);
     const bool valid = flags & 1, inplane = flags & 2, past = flags & 4;
     const float padv = TILED ? -INFINITY : 0.f;
     OT* ob = out + (long long)b * GBF_H * plane + q;
@@ -518,7 +580,8 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
       __builtin_amdgcn_sched_barrier(0);
     }
     }
-    b = n_b; q = n_q; flags = n_flags; pl = n_pl; e = n_e; d = n_d;
+    b = n_b; q = n_q; flags = n_flags; pl = n_pl;
+    if constexpr (COORDS) { ai = n_ai; aj = n_aj; } else { e = n_e; d = n_d; }
   }
 }
 
@@ -782,13 +845,15 @@ __device__ __forceinline__ gbf16x8 gbf_tr8(const bf16_t* a0, const bf16_t* a1) {
 //     tile's pairs of that edge type in pair order.
 // With the per-workgroup slabs (required in the mode) every sum of this kernel then has an order that depends on the grid alone.
 constexpr size_t GBF_DET_SMEM = (size_t)(8 * 128 + 3 * 128) * 4;
-template <bool TILED, typename GT, bool DET = false>
+// COORDS: as in the forward kernel -- fetch takes the two atoms' records, gbf_pair_rule turns them into (edge type, distance).
+template <bool TILED, typename GT, bool DET = false, bool COORDS = false>
 __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     const GT* __restrict__ gsrc, const float* __restrict__ dist, const void* __restrict__ et, int esz, const float* __restrict__ mul,
     const float* __restrict__ bias, const float* __restrict__ means, const float* __restrict__ stds, const bf16_t* __restrict__ W1,
     const float* __restrict__ b1, const bf16_t* __restrict__ W2, float* __restrict__ dW1, float* __restrict__ db1, float* __restrict__ dW2,
     float* __restrict__ db2, float* __restrict__ dmul, float* __restrict__ dbias, float* __restrict__ dmeans, float* __restrict__ dstds, int B,
-    int N, int ld, int E, int tpm, const int* __restrict__ tile_prefix, const int* __restrict__ row_blocks, float* __restrict__ slab) {
+    int N, int ld, int E, int tpm, const int* __restrict__ tile_prefix, const int* __restrict__ row_blocks, float* __restrict__ slab,
+    const uint4* __restrict__ rec, int V, int pad) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gbf_smem[];
   bf16_t* sW1 = reinterpret_cast<bf16_t*>(gbf_smem);            // [128 f][144]  W1[f][k]
   bf16_t* sW2T = sW1 + GBF_F * GBF_LW;                           // [128 f][72]   W2^T[f][h]
@@ -879,7 +944,7 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
 
   // Branch-free: a tile past the end is clamped to the last one and flagged inactive, a pad lane reads pair (0, 0) of its
   // molecule -- so every load of the NEXT iteration is in flight, unconditionally, while this one computes.
-  auto fetch = [&](int tile, bool& act, bool& valid, float& d, int& e, float (&gv)[16]) {
+  auto fetch = [&](int tile, bool& act, bool& valid, float& d, int& e, float (&gv)[16], uint4& ai, uint4& aj) {
     tile = __builtin_amdgcn_readfirstlane(tile);          // (wave-uniform: tile = 8 * workgroup + wave)
     act = tile < ntiles;
     tile = act ? tile : ntiles - 1;
@@ -906,11 +971,17 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     }
     valid = act && ii < N && jj < N;
     // scalar base of the molecule + 32-bit lane offsets (host: N*N and 64*plane fit 31 bits)
-    const long long mol = (long long)b * N * N;
-    const unsigned pl = (unsigned)((valid ? ii : 0) * N + (valid ? jj : 0));
-    const int e32 = gbf_edge(et, mol, pl, esz);
-    e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
-    d = (dist + mol)[pl];
+    if constexpr (COORDS) {
+      const uint4* mr = rec + (long long)b * N;
+      ai = mr[valid ? ii : 0];
+      aj = mr[valid ? jj : 0];
+    } else {
+      const long long mol = (long long)b * N * N;
+      const unsigned pl = (unsigned)((valid ? ii : 0) * N + (valid ? jj : 0));
+      const int e32 = gbf_edge(et, mol, pl, esz);
+      e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
+      d = (dist + mol)[pl];
+    }
     const GT* mb = gsrc + (long long)b * GBF_H * plane;
     const unsigned voff = (unsigned)(8 * g) * (unsigned)plane + (unsigned)(valid ? q : 0);
 #pragma unroll
@@ -920,11 +991,12 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
   };
 
   bool act, valid, n_act, n_valid;
-  float d, n_d, gv[16], n_gv[16];
-  int e, n_e;
+  float d = 0.f, n_d = 0.f, gv[16], n_gv[16];
+  int e = 0, n_e = 0;
+  uint4 ai = {}, aj = {}, n_ai = {}, n_aj = {};
   const int stride = (int)gridDim.x * 8;
   int tile = (int)blockIdx.x * 8 + wave;
-  fetch(tile, act, valid, d, e, gv);
+  fetch(tile, act, valid, d, e, gv, ai, aj);
   // (every wave of the workgroup runs the same number of iterations: the loop bound is on the workgroup's first tile)
   for (int base = (int)blockIdx.x * 8; base < ntiles; base += stride, tile += stride) {
     // The weight / constant images in LDS never change inside the loop, and the compiler knows: left alone it hoists some
@@ -937,7 +1009,11 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     const float* gconst = reinterpret_cast<const float*>(gbf_smem + o_gconst);
     const float* b1row = reinterpret_cast<const float*>(gbf_smem + o_b1row);
     const float* kconst = reinterpret_cast<const float*>(gbf_smem + o_kconst);
-    fetch(tile + stride, n_act, n_valid, n_d, n_e, n_gv);
+    if constexpr (COORDS) {       // (before the next fetch, as in the forward kernel)
+      gbf_pair_rule(ai, aj, V, pad, e, d);
+      e = e < 0 ? 0 : (e >= E ? E - 1 : e);
+    }
+    fetch(tile + stride, n_act, n_valid, n_d, n_e, n_gv, n_ai, n_aj);
     // ------------------------------------------------------------------------------------------------ phase A
     // The incoming gradient enters the two products that contract it -- du = (W2^T . dO) . gelu' here, dW2 / db2 in phase B2 -- as a
     // bf16 high part + a bf16 low part (16 mantissa bits, two MFMAs).  Rows of G sum to zero over the keys, and every (pad query,
@@ -1148,7 +1224,8 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
 #undef GBF_TFRAG
 #undef GBF_SWZ
     __syncthreads();                                   // tiles free for the next iteration
-    act = n_act; valid = n_valid; d = n_d; e = n_e;
+    act = n_act; valid = n_valid;
+    if constexpr (COORDS) { ai = n_ai; aj = n_aj; } else { d = n_d; e = n_e; }
 #pragma unroll
     for (int j = 0; j < 16; ++j) gv[j] = n_gv[j];
   }
@@ -1358,18 +1435,19 @@ extern "C" int mmdti_pair_permute_bwd(mmdti_stream_t stream, const float* g, voi
 
 static int edge_bytes_ok(int eb) { return eb == 8 || eb == 4 || eb == 2; }
 
-extern "C" int mmdti_gbf_bias_fwd(mmdti_stream_t stream, const float* dist, const void* edge_type, int edge_bytes, const float* mul,
-                                  const float* bias, const float* means, const float* stds, const void* w1_bf16,
-                                  const float* b1, const void* w2_bf16, const float* b2, int B, int N, int ld, int K, int F,
-                                  int H, int E, void* out, void* feat_bf16, void* u_bf16, void* h_bf16, int flags,
-                                  const int* tile_prefix, const int* row_blocks) {
+// Both forms of the forward entry point: rec == nullptr, the planes (dist, edge_type); else the atom records with V and pad.
+static int gbf_bias_fwd_any(mmdti_stream_t stream, const float* dist, const void* edge_type, int edge_bytes, const float* mul,
+                            const float* bias, const float* means, const float* stds, const void* w1_bf16,
+                            const float* b1, const void* w2_bf16, const float* b2, int B, int N, int ld, int K, int F,
+                            int H, int E, void* out, void* feat_bf16, void* u_bf16, void* h_bf16, int flags,
+                            const int* tile_prefix, const int* row_blocks, const uint4* rec, int V, int pad) {
   // bit 0: tiled pair layout; bit 1: u_bf16 receives gelu'(u) instead of u; bit 2: compact planes (out is fp16; tiled only)
   const int tiled = flags & 1, ugrad = (flags >> 1) & 1, compact = (flags >> 2) & 1;
   MMDTI_REQUIRE(!compact || tiled, "gbf_bias_fwd: compact planes (flags bit 2) exist in the tiled layout only");
   MMDTI_REQUIRE(!tile_prefix || tiled, "gbf_bias_fwd: tile_prefix (ragged batches) needs the tiled pair layout");
   MMDTI_REQUIRE(!row_blocks || tile_prefix, "gbf_bias_fwd: row_blocks (packed token rows) comes with tile_prefix");
-  MMDTI_REQUIRE(dist && edge_type && mul && bias && means && stds && w1_bf16 && b1 && w2_bf16 && b2 && out, "gbf_bias_fwd: null argument");
-  MMDTI_REQUIRE(edge_bytes_ok(edge_bytes), "gbf_bias_fwd: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
+  MMDTI_REQUIRE((rec || (dist && edge_type)) && mul && bias && means && stds && w1_bf16 && b1 && w2_bf16 && b2 && out, "gbf_bias_fwd: null argument");
+  MMDTI_REQUIRE(rec || edge_bytes_ok(edge_bytes), "gbf_bias_fwd: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
   MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_fwd: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
                 GBF_K, GBF_F, GBF_H, K, F, H);
   MMDTI_REQUIRE(B > 0 && N > 0 && ld >= N && ld % 4 == 0 && E > 0, "gbf_bias_fwd: bad shape");
@@ -1387,26 +1465,90 @@ extern "C" int mmdti_gbf_bias_fwd(mmdti_stream_t stream, const float* dist, cons
   static bool attr_done = false;
   if (!attr_done) {
     const int cap = (int)((size_t)(GBF_F + GBF_H) * GBF_WS * 2 + (size_t)(3 * GBF_K + GBF_F + GBF_H + 2 * GBF_FWD_MAXE) * 4);
-    const void* fns[6] = {reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, true, float>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, false, float>),
+    const void* fns[9] = {reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, float, true>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, false, float, true>),
+                          reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, _Float16, true>),
+                          reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, true, float>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, false, float>),
                           reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, float>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, false, float>),
                           reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, true, _Float16>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, _Float16>)};
-    for (int f = 0; f < 6; ++f)
+    for (int f = 0; f < 9; ++f)
       if (hipFuncSetAttribute(fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
         set_error("gbf_bias_fwd: hipFuncSetAttribute failed");
         return MMDTI_ERR_LAUNCH;
       }
     attr_done = true;
   }
-#define GBF_L(SAVE, TILED, OT)                                                                                                      \
-  hipLaunchKernelGGL((gbf_bias_fwd_kernel<SAVE, TILED, OT>), dim3(grid), dim3(512), smem, (hipStream_t)stream, dist, edge_type, edge_bytes, mul, bias, \
+#define GBF_LC(SAVE, TILED, OT, COORDS)                                                                                             \
+  hipLaunchKernelGGL((gbf_bias_fwd_kernel<SAVE, TILED, OT, COORDS>), dim3(grid), dim3(512), smem, (hipStream_t)stream, dist, edge_type, edge_bytes, mul, bias, \
                      means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, b2, (OT*)out, (bf16_t*)feat_bf16, (bf16_t*)u_bf16, \
-                     (bf16_t*)h_bf16, B, N, ld, E, tpm, ugrad, ltab, tile_prefix, row_blocks)
-  if (compact) { if (save) GBF_L(true, true, _Float16); else GBF_L(false, true, _Float16); }
+                     (bf16_t*)h_bf16, B, N, ld, E, tpm, ugrad, ltab, tile_prefix, row_blocks, rec, V, pad)
+#define GBF_L(SAVE, TILED, OT) GBF_LC(SAVE, TILED, OT, false)
+  if (rec) {      // (the coords form saves nothing: it exists for the configurations of the complete backward kernel)
+    if (compact) GBF_LC(false, true, _Float16, true); else if (tiled) GBF_LC(false, true, float, true); else GBF_LC(false, false, float, true);
+  } else if (compact) { if (save) GBF_L(true, true, _Float16); else GBF_L(false, true, _Float16); }
   else if (save) { if (tiled) GBF_L(true, true, float); else GBF_L(true, false, float); }
   else           { if (tiled) GBF_L(false, true, float); else GBF_L(false, false, float); }
 #undef GBF_L
+#undef GBF_LC
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
+}
+
+extern "C" int mmdti_gbf_bias_fwd(mmdti_stream_t stream, const float* dist, const void* edge_type, int edge_bytes, const float* mul,
+                                  const float* bias, const float* means, const float* stds, const void* w1_bf16,
+                                  const float* b1, const void* w2_bf16, const float* b2, int B, int N, int ld, int K, int F,
+                                  int H, int E, void* out, void* feat_bf16, void* u_bf16, void* h_bf16, int flags,
+                                  const int* tile_prefix, const int* row_blocks) {
+  return gbf_bias_fwd_any(stream, dist, edge_type, edge_bytes, mul, bias, means, stds, w1_bf16, b1, w2_bf16, b2, B, N, ld, K, F, H, E, out, feat_bf16,
+                          u_bf16, h_bf16, flags, tile_prefix, row_blocks, nullptr, 0, 0);
+}
+
+// What every coords entry point asks of its operands, before any launch.  N: the atom records address a molecule's pairs with the same
+// 32-bit offsets as the planes (N * N < 2^30) and the int16 / token arithmetic needs V * V = E <= 32768.
+static int gbf_coords_check(const char* fn, const void* rec, int B, int N, int V, int pad, int E) {
+  MMDTI_REQUIRE(rec != nullptr, "%s: null atom records", fn);
+  MMDTI_REQUIRE(aligned16(rec), "%s: the atom records must be 16-byte aligned", fn);
+  MMDTI_REQUIRE(B > 0 && N > 0 && (long long)N * N < (1ll << 30), "%s: bad shape, or N too large for 32-bit pair offsets (B=%d, N=%d)", fn, B, N);
+  MMDTI_REQUIRE(V > 0 && V <= 181 && (long long)V * V == E, "%s: V * V must be the edge-table size (V=%d, E=%d; V <= 181 keeps every edge type in 16 bits)", fn, V, E);
+  MMDTI_REQUIRE(pad >= 0 && pad < V, "%s: the pad index must be a token of the dictionary (pad=%d, V=%d)", fn, pad, V);
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_pair_records_pack(mmdti_stream_t stream, const float* coord, const void* tokens, int token_bytes, int B, int N, void* records) {
+  MMDTI_REQUIRE(coord && tokens && records, "pair_records_pack: null argument");
+  MMDTI_REQUIRE(token_bytes == 8 || token_bytes == 4, "pair_records_pack: tokens must be int64 or int32 (token_bytes=%d)", token_bytes);
+  MMDTI_REQUIRE(B > 0 && N > 0, "pair_records_pack: bad shape");
+  MMDTI_REQUIRE(aligned16(records), "pair_records_pack: the atom records must be 16-byte aligned");
+  const long long n = (long long)B * N;
+  hipLaunchKernelGGL(pair_records_pack_kernel, dim3((unsigned)(cdiv(n, 256) < 1024 ? cdiv(n, 256) : 1024)), dim3(256), 0, (hipStream_t)stream, coord, tokens,
+                     token_bytes, n, (uint4*)records);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_pair_inputs_from_coords(mmdti_stream_t stream, const void* records, int B, int N, int V, int pad_idx, float* dist, void* edge_type,
+                                             int edge_bytes) {
+  if (int e = gbf_coords_check("pair_inputs_from_coords", records, B, N, V, pad_idx, V * V)) return e;
+  MMDTI_REQUIRE(dist && edge_type, "pair_inputs_from_coords: null output");
+  MMDTI_REQUIRE(edge_bytes == 8 || edge_bytes == 2, "pair_inputs_from_coords: edge types leave as int64 or int16 (edge_bytes=%d)", edge_bytes);
+  const long long P = (long long)B * N * N;
+  const unsigned grid = (unsigned)(cdiv(P, 256) < 8192 ? cdiv(P, 256) : 8192);
+  if (edge_bytes == 8)
+    hipLaunchKernelGGL(pair_inputs_from_coords_kernel<long long>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, N, P, V, pad_idx, dist,
+                       (long long*)edge_type);
+  else
+    hipLaunchKernelGGL(pair_inputs_from_coords_kernel<short>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)records, N, P, V, pad_idx, dist,
+                       (short*)edge_type);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_gbf_bias_fwd_coords(mmdti_stream_t stream, const void* records, int V, int pad_idx, const float* mul, const float* bias,
+                                         const float* means, const float* stds, const void* w1_bf16, const float* b1, const void* w2_bf16,
+                                         const float* b2, int B, int N, int ld, int K, int F, int H, int E, void* out, int flags,
+                                         const int* tile_prefix, const int* row_blocks) {
+  if (int e = gbf_coords_check("gbf_bias_fwd_coords", records, B, N, V, pad_idx, E)) return e;
+  return gbf_bias_fwd_any(stream, nullptr, nullptr, 0, mul, bias, means, stds, w1_bf16, b1, w2_bf16, b2, B, N, ld, K, F, H, E, out, nullptr, nullptr,
+                          nullptr, flags, tile_prefix, row_blocks, (const uint4*)records, V, pad_idx);
 }
 
 extern "C" int mmdti_gbf_bias_bwd(mmdti_stream_t stream, const void* g, const float* dist, const void* edge_type, int edge_bytes,
@@ -1451,18 +1593,19 @@ extern "C" int mmdti_gbf_bias_bwd(mmdti_stream_t stream, const void* g, const fl
   return MMDTI_OK;
 }
 
-extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, const float* dist, const void* edge_type, int edge_bytes,
-                                       const float* mul, const float* bias, const float* means, const float* stds, const void* w1_bf16,
-                                       const float* b1, const void* w2_bf16, int B, int N, int ld, int K, int F, int H, int E, int flags,
-                                       float* dw1, float* db1, float* dw2, float* db2, float* dmul, float* dbias, float* dmeans,
-                                       float* dstds, const int* tile_prefix, const int* row_blocks, void* workspace, long long workspace_bytes) {
+static int gbf_bias_bwd_full_any(mmdti_stream_t stream, const void* g, const float* dist, const void* edge_type, int edge_bytes,
+                                 const float* mul, const float* bias, const float* means, const float* stds, const void* w1_bf16,
+                                 const float* b1, const void* w2_bf16, int B, int N, int ld, int K, int F, int H, int E, int flags,
+                                 float* dw1, float* db1, float* dw2, float* db2, float* dmul, float* dbias, float* dmeans,
+                                 float* dstds, const int* tile_prefix, const int* row_blocks, void* workspace, long long workspace_bytes,
+                                 const uint4* rec, int V, int pad) {
   const int tiled = flags & 1, compact = (flags >> 2) & 1;   // bit 0: tiled pair layout; bit 2: compact planes (g is bf16; tiled only)
   MMDTI_REQUIRE(!compact || tiled, "gbf_bias_bwd_full: compact planes (flags bit 2) exist in the tiled layout only");
   MMDTI_REQUIRE(!tile_prefix || tiled, "gbf_bias_bwd_full: tile_prefix (ragged batches) needs the tiled pair layout");
   MMDTI_REQUIRE(!row_blocks || tile_prefix, "gbf_bias_bwd_full: row_blocks (packed token rows) comes with tile_prefix");
-  MMDTI_REQUIRE(g && dist && edge_type && mul && bias && means && stds && w1_bf16 && b1 && w2_bf16 && dw1 && db1 && dw2 && db2 && dmul && dbias &&
+  MMDTI_REQUIRE(g && (rec || (dist && edge_type)) && mul && bias && means && stds && w1_bf16 && b1 && w2_bf16 && dw1 && db1 && dw2 && db2 && dmul && dbias &&
                     dmeans && dstds, "gbf_bias_bwd_full: null argument");
-  MMDTI_REQUIRE(edge_bytes_ok(edge_bytes), "gbf_bias_bwd_full: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
+  MMDTI_REQUIRE(rec || edge_bytes_ok(edge_bytes), "gbf_bias_bwd_full: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
   MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_bwd_full: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
                 GBF_K, GBF_F, GBF_H, K, F, H);
   MMDTI_REQUIRE(B > 0 && N > 0 && ld >= N && ld % 4 == 0 && E > 0 && E <= GBF_FULL_MAXE, "gbf_bias_bwd_full: bad shape (E <= %d)", GBF_FULL_MAXE);
@@ -1484,7 +1627,10 @@ extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, con
     static bool det_attr_done = false;
     if (!det_attr_done) {
       const int cap = 160 * 1024;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
           hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
           hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
         set_error("gbf_bias_bwd_full: hipFuncSetAttribute failed");
@@ -1496,7 +1642,10 @@ extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, con
   static bool attr_done = false;
   if (!attr_done) {
     const int cap = (int)gbf_full_smem(GBF_FULL_MAXE);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
       set_error("gbf_bias_bwd_full: hipFuncSetAttribute failed");
@@ -1504,23 +1653,40 @@ extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, con
     }
     attr_done = true;
   }
-#define GBF_FB(TILED, GT)                                                                                                          \
-  hipLaunchKernelGGL((gbf_bias_bwd_full_kernel<TILED, GT>), dim3(grid), dim3(512), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, \
+#define GBF_FX(TILED, GT, DET, COORDS)                                                                                             \
+  hipLaunchKernelGGL((gbf_bias_bwd_full_kernel<TILED, GT, DET, COORDS>), dim3(grid), dim3(512), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, \
                      bias, means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds, B, \
-                     N, ld, E, tpm, tile_prefix, row_blocks, slab)
-#define GBF_FD(TILED, GT)                                                                                                          \
-  hipLaunchKernelGGL((gbf_bias_bwd_full_kernel<TILED, GT, true>), dim3(grid), dim3(512), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, \
-                     bias, means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds, B, \
-                     N, ld, E, tpm, tile_prefix, row_blocks, slab)
+                     N, ld, E, tpm, tile_prefix, row_blocks, slab, rec, V, pad)
+#define GBF_FL(DET, COORDS) \
+  do { if (compact) GBF_FX(true, __bf16, DET, COORDS); else if (tiled) GBF_FX(true, float, DET, COORDS); else GBF_FX(false, float, DET, COORDS); } while (0)
   // (a workspace of at least grid slots: partial sums in per-workgroup slabs + a fixed-order reduce; else fp32 atomics)
-  if (det) { if (compact) GBF_FD(true, __bf16); else if (tiled) GBF_FD(true, float); else GBF_FD(false, float); }
-  else if (compact) GBF_FB(true, __bf16); else if (tiled) GBF_FB(true, float); else GBF_FB(false, float);
-#undef GBF_FB
-#undef GBF_FD
+  if (det) { if (rec) GBF_FL(true, true); else GBF_FL(true, false); }
+  else if (rec) GBF_FL(false, true); else GBF_FL(false, false);
+#undef GBF_FL
+#undef GBF_FX
   if (slab)
     hipLaunchKernelGGL(gbf_slab_reduce_kernel, dim3(cdiv(SL, 64)), dim3(256), 0, (hipStream_t)stream, slab, grid, E, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
+}
+
+extern "C" int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, const float* dist, const void* edge_type, int edge_bytes,
+                                       const float* mul, const float* bias, const float* means, const float* stds, const void* w1_bf16,
+                                       const float* b1, const void* w2_bf16, int B, int N, int ld, int K, int F, int H, int E, int flags,
+                                       float* dw1, float* db1, float* dw2, float* db2, float* dmul, float* dbias, float* dmeans,
+                                       float* dstds, const int* tile_prefix, const int* row_blocks, void* workspace, long long workspace_bytes) {
+  return gbf_bias_bwd_full_any(stream, g, dist, edge_type, edge_bytes, mul, bias, means, stds, w1_bf16, b1, w2_bf16, B, N, ld, K, F, H, E, flags, dw1, db1,
+                               dw2, db2, dmul, dbias, dmeans, dstds, tile_prefix, row_blocks, workspace, workspace_bytes, nullptr, 0, 0);
+}
+
+extern "C" int mmdti_gbf_bias_bwd_full_coords(mmdti_stream_t stream, const void* g, const void* records, int V, int pad_idx, const float* mul,
+                                              const float* bias, const float* means, const float* stds, const void* w1_bf16, const float* b1,
+                                              const void* w2_bf16, int B, int N, int ld, int K, int F, int H, int E, int flags, float* dw1,
+                                              float* db1, float* dw2, float* db2, float* dmul, float* dbias, float* dmeans, float* dstds,
+                                              const int* tile_prefix, const int* row_blocks, void* workspace, long long workspace_bytes) {
+  if (int e = gbf_coords_check("gbf_bias_bwd_full_coords", records, B, N, V, pad_idx, E)) return e;
+  return gbf_bias_bwd_full_any(stream, g, nullptr, nullptr, 0, mul, bias, means, stds, w1_bf16, b1, w2_bf16, B, N, ld, K, F, H, E, flags, dw1, db1, dw2, db2,
+                               dmul, dbias, dmeans, dstds, tile_prefix, row_blocks, workspace, workspace_bytes, (const uint4*)records, V, pad_idx);
 }
 
 /* bytes of workspace that make mmdti_gbf_bias_bwd_full reproducible (one slab per workgroup of its persistent grid, at most 256) */

@@ -61,14 +61,18 @@ def tokenize(tokenizer, smiles, truncation=True):
     return enc['input_ids'], enc['attention_mask']
 
 
-def collate_batch(samples, padding_idx, tokenizer):
+def collate_batch(samples, padding_idx, tokenizer, pair_inputs="planes"):
     """The whole of ``MM_Model.batch_collate_fn`` (models/mm_model.py:645-682) as a free function: list of
     (feature dict, label) -> (batch dict, label tensor | None).  A key without a layout rule re-uses the previous field's
-    value, as the reference's loop variable does (and raises if it comes first)."""
+    value, as the reference's loop variable does (and raises if it comes first).  pair_inputs="coords": the two [B,N,N] planes
+    are not built at all (their per-sample square pads are most of this function's time); the samples must carry ``src_coord``."""
+    _check_pair_inputs(pair_inputs)
     feats = [s[0] for s in samples]
+    if pair_inputs == "coords" and 'src_coord' not in feats[0]:
+        raise KeyError("collate_batch: pair_inputs='coords' needs 'src_coord' in every sample")
     batch, last = {}, None
     for key in feats[0]:
-        if key == 'smile':
+        if key == 'smile' or (pair_inputs == "coords" and key in PAIR_PLANES):
             continue
         v = collate_field(key, (f[key] for f in feats), padding_idx)
         if v is None:
@@ -81,8 +85,37 @@ def collate_batch(samples, padding_idx, tokenizer):
     return batch, stack_labels(samples)
 
 
+# -------------------------------------------------------------------------------------------------- pair inputs from coordinates
+PAIR_PLANES = ('src_distance', 'src_edge_type')
+PAIR_INPUT_MODES = ("planes", "coords")
+
+
+def _check_pair_inputs(mode):
+    if mode not in PAIR_INPUT_MODES:
+        raise ValueError(f"pair_inputs must be one of {PAIR_INPUT_MODES}, got {mode!r}")
+
+
+def pair_inputs_from_coords(src_coord, src_tokens, vocab, pad_idx):
+    """The host statement of the pair rule: (src_distance fp32, src_edge_type int64) [..., N, N] from ``src_coord`` [..., N, 3]
+    and ``src_tokens`` [..., N] -- one molecule or a right-padded batch.
+
+    The reference builds the planes per molecule as ``distance_matrix(coord, coord)`` and ``tok_i * len(dictionary) + tok_j``
+    (data/conformer.py:204-212) and ``MM_Model.batch_collate_fn`` right-pads them with 0.0 and the pad index; here: either atom
+    pad -> (pad index, 0.0), else ``tok_i * vocab + tok_j`` and the Euclidean distance evaluated in float64 on the stored
+    coordinates and rounded ONCE to fp32 -- which reproduces every stored plane of the golden fixtures bit for bit.  The device
+    kernels (ops.pair_inputs_from_coords and the fused coords kernels) evaluate the same rule in fp32, within 4 ulp of this."""
+    c = torch.as_tensor(src_coord).to(torch.float64)
+    tok = torch.as_tensor(src_tokens).to(torch.int64)
+    d = c.unsqueeze(-2) - c.unsqueeze(-3)
+    dist = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]).sqrt().to(torch.float32)
+    edge = tok.unsqueeze(-1) * int(vocab) + tok.unsqueeze(-2)
+    is_pad = tok.eq(pad_idx)
+    padp = is_pad.unsqueeze(-1) | is_pad.unsqueeze(-2)
+    return dist.masked_fill(padp, 0.0), edge.masked_fill(padp, int(pad_idx))
+
+
 # -------------------------------------------------------------------------------------------------- device payload (8f-3)
-NEVER_CONSUMED = ('src_coord',)     # collated by the reference, swallowed by **kwargs in MM_Model.forward (mm_model.py:540)
+NEVER_CONSUMED = ('src_coord',)     # planes mode: collated by the reference, swallowed by **kwargs in MM_Model.forward (mm_model.py:540)
 # stay on the host: MM_Model reads them to pick kernels and layouts without a device sync
 HOST_FIELDS = ('atom_counts', 'token_counts', 'token_pad_id', 'packable')
 INT16_MAX = 32767
@@ -101,12 +134,20 @@ def to_device(net_input, device, non_blocking=True):
     return {k: (v if k in HOST_FIELDS else v.to(device, non_blocking=non_blocking)) for k, v in net_input.items()}
 
 
-def device_payload(net_input, n_edge_types=None, pad_idx=0):
+def device_payload(net_input, n_edge_types=None, pad_idx=0, pair_inputs="planes"):
     """What of a collated batch actually has to cross PCIe: drops the fields no kernel reads and narrows
     ``src_edge_type`` from int64 to int16 (8 -> 2 bytes per atom pair; the pair-bias kernels take either width) when every
     index fits -- ``n_edge_types`` (= len(dictionary)**2, 961 for the reference's dictionary) decides without a scan, else
-    the tensor's own min / max do.  Values are unchanged; host tensors in, host tensors out."""
-    out = {k: v for k, v in net_input.items() if k not in NEVER_CONSUMED}
+    the tensor's own min / max do.  Values are unchanged; host tensors in, host tensors out.
+    pair_inputs="coords": ``src_coord`` [B,N,3] stays and the two [B,N,N] planes are dropped instead -- the kernels derive every
+    pair from its two atoms (12 bytes per atom cross PCIe instead of 6 per atom pair)."""
+    _check_pair_inputs(pair_inputs)
+    if pair_inputs == "coords":
+        if 'src_coord' not in net_input:
+            raise KeyError("device_payload: pair_inputs='coords' needs 'src_coord' in the batch")
+        out = {k: v for k, v in net_input.items() if k not in PAIR_PLANES}
+    else:
+        out = {k: v for k, v in net_input.items() if k not in NEVER_CONSUMED}
     et = out.get('src_edge_type')
     if et is not None and et.dtype == torch.int64:
         if n_edge_types is not None:
@@ -150,17 +191,21 @@ class HostCollate:
     ``model.batch_collate_fn``) followed by :func:`device_payload`, holding only the pad index, the tokenizer and the
     edge-type count -- so the workers never receive a copy of the model."""
 
-    def __init__(self, padding_idx, tokenizer, n_edge_types=None, narrow=True):
+    def __init__(self, padding_idx, tokenizer, n_edge_types=None, narrow=True, pair_inputs="planes"):
+        _check_pair_inputs(pair_inputs)
         self.padding_idx, self.tokenizer, self.n_edge_types, self.narrow = padding_idx, tokenizer, n_edge_types, narrow
+        self.pair_inputs = pair_inputs      # "coords": the planes are neither padded here nor shipped (the payload step then always runs)
 
     @classmethod
-    def of(cls, model, narrow=True):
+    def of(cls, model, narrow=True, pair_inputs="planes"):
         n = None
         d = getattr(model, 'dictionary', None)
         if d is not None:
             n = len(d) * len(d)
-        return cls(model.padding_idx, getattr(model, 'tokenizer', None), n, narrow)
+        return cls(model.padding_idx, getattr(model, 'tokenizer', None), n, narrow, pair_inputs)
 
     def __call__(self, samples):
-        batch, label = collate_batch(samples, self.padding_idx, self.tokenizer)
-        return (device_payload(batch, self.n_edge_types, self.padding_idx) if self.narrow else batch), label
+        batch, label = collate_batch(samples, self.padding_idx, self.tokenizer, self.pair_inputs)
+        if self.narrow or self.pair_inputs == "coords":
+            batch = device_payload(batch, self.n_edge_types, self.padding_idx, self.pair_inputs)
+        return batch, label

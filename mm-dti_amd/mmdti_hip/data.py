@@ -111,10 +111,11 @@ class DevicePrefetcher:
     critical path.
     """
 
-    def __init__(self, batches, device, narrow=True, n_edge_types=None, pad_idx=0, depth=2, threaded=False):
+    def __init__(self, batches, device, narrow=True, n_edge_types=None, pad_idx=0, depth=2, threaded=False, pair_inputs="planes"):
         import torch
         self._torch = torch
         self.narrow, self.n_edge_types, self.pad_idx = narrow, n_edge_types, pad_idx
+        self.pair_inputs = pair_inputs       # "coords": src_coord crosses instead of the two [B,N,N] planes (collate.device_payload)
         self.batches = batches
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
@@ -127,9 +128,9 @@ class DevicePrefetcher:
         """-> (staged: {name: pinned tensor | host field}, label pinned tensor).  Runs on the staging thread."""
         torch = self._torch
         net_input, label = item
-        if self.narrow:
+        if self.narrow or self.pair_inputs == "coords":
             from .collate import device_payload
-            net_input = device_payload(net_input, self.n_edge_types, self.pad_idx)
+            net_input = device_payload(net_input, self.n_edge_types, self.pad_idx, self.pair_inputs)
         def pin(name, t):
             if not torch.is_tensor(t) or t.device.type != "cpu" or self.stream is None or t.is_pinned():
                 return t                       # (pinned already -- a pin_memory DataLoader: copied from where it lies, torch's host allocator keeps it alive)

@@ -762,23 +762,38 @@ class PairBiasFn(torch.autograd.Function):
     bias [B,H,N,ld] fp32 -- or, on the fused hot path (K = F = 128, H = 64, N <= 272), the tiled pair layout, as fp16 unless
     MMDTI_PAIR_COMPACT=0.  The gradient chain of a compact bias is fp32 (or bf16), not fp16: PairEncoderFn.backward leaves it
     in the slot hung on the bias (``_mmdti_grad_slot``) and autograd only carries a placeholder; a gradient that reaches this
-    function through autograd from any other consumer is added on top."""
+    function through autograd from any other consumer is added on top.
+
+    Coords form (``coords=(V, pad_idx)``, edge_type None): ``dist`` is the batch's atom records ([B,N,4] int32, ops.pair_records) and no
+    [B,N,N] input exists -- on the hot path (fused forward + complete backward) the kernels derive each pair from its two atoms and the
+    records are what the backward keeps; every other configuration materialises the two planes once (ops.pair_inputs_from_records,
+    the same pair rule, so no bit depends on which way a configuration went) and runs the planes path below on them."""
 
     @staticmethod
-    def forward(ctx, anchor, dist, edge_type, gbf, proj, ld, key_tiles_host=None, rows_host=None):
+    def forward(ctx, anchor, dist, edge_type, gbf, proj, ld, key_tiles_host=None, rows_host=None, coords=None):
         # anchor: freeze.grad_anchor over gbf and proj (None when both are frozen): autograd reaches the backward whenever one of
         # them trains, whichever one it is
         # key_tiles_host ([B] ints on the HOST, ragged batches): real key tiles per molecule -- the fused compact path then
         # neither produces the bias of the all-padding key tiles nor visits them in the backward (PairEncoderFn skips them too)
         B, N, _ = dist.shape
         H = proj.linear2.weight.shape[0]
-        dist, edge_type = dist.contiguous(), edge_type.contiguous()
         args = [gbf.mul.weight.view(-1), gbf.bias.weight.view(-1), gbf.means.weight.view(-1), gbf.stds.weight.view(-1)]
         fused = ops.gbf_bias_eligible(args[2].numel(), proj.linear1.weight.shape[0], H, ld)
         # the complete backward kernel recomputes basis / hidden from the inputs: the forward then saves nothing
         full = fused and ops.GBF_FULL_BWD and args[0].numel() <= ops.GBF_FULL_MAXE
-        if edge_type.dtype != torch.int64 and not fused:
+        rec = None
+        if coords is not None:
+            if coords[0] * coords[0] != args[0].numel():
+                raise ops.MMDTIError(f"PairBiasFn: coords mode needs V * V edge types, got V = {coords[0]} and tables of {args[0].numel()}")
+            if full:
+                rec, dist = dist.contiguous(), None
+            else:      # no coords kernel for this configuration: the planes, once (int64 for the unfused kernels)
+                dist, edge_type = ops.pair_inputs_from_records(dist.contiguous(), coords[0], coords[1], torch.int16 if fused else torch.int64)
+        if rec is None:
+            dist, edge_type = dist.contiguous(), edge_type.contiguous()
+        if rec is None and edge_type.dtype != torch.int64 and not fused:
             edge_type = edge_type.long()      # (the unfused kernels read the reference's int64)
+        dev = (rec if rec is not None else dist).device
         if fused:
             # one kernel from distances to the [B,H,N,ld] bias (tiled pair layout whenever the MFMA pair-attention kernels can
             # take it: their loads become contiguous KiBs); without the complete backward kernel the three [P,128] intermediates
@@ -790,12 +805,16 @@ class PairBiasFn(torch.autograd.Function):
             if key_tiles_host is not None and compact and full:
                 # (rows_host -- packed token rows: the bias of the query rows past a molecule's representative pad row is never read)
                 if rows_host is not None:
-                    pre_f, pre_b, rb_f, rb_b = ops.gbf_tile_prefixes(key_tiles_host, N, dist.device, rows_host)
+                    pre_f, pre_b, rb_f, rb_b = ops.gbf_tile_prefixes(key_tiles_host, N, dev, rows_host)
                 else:
-                    pre_f, pre_b = ops.gbf_tile_prefixes(key_tiles_host, N, dist.device)
-            out, saved = ops.gbf_bias_fwd(dist, edge_type, *args, wbf16(proj.linear1.weight), proj.linear1.bias,
-                                          wbf16(proj.linear2.weight), proj.linear2.bias, ld, save=keep, tiled=tiled,
-                                          save_grad=ops.GELU_SAVE_GRAD, compact=compact, tile_prefix=pre_f, row_blocks=rb_f)
+                    pre_f, pre_b = ops.gbf_tile_prefixes(key_tiles_host, N, dev)
+            if rec is not None:
+                out, saved = ops.gbf_bias_fwd_coords(rec, coords[0], coords[1], *args, wbf16(proj.linear1.weight), proj.linear1.bias, wbf16(proj.linear2.weight),
+                                                     proj.linear2.bias, ld, tiled=tiled, compact=compact, tile_prefix=pre_f, row_blocks=rb_f), None
+            else:
+                out, saved = ops.gbf_bias_fwd(dist, edge_type, *args, wbf16(proj.linear1.weight), proj.linear1.bias,
+                                              wbf16(proj.linear2.weight), proj.linear2.bias, ld, save=keep, tiled=tiled,
+                                              save_grad=ops.GELU_SAVE_GRAD, compact=compact, tile_prefix=pre_f, row_blocks=rb_f)
             feat, u, h = saved if keep else (None, None, None)
             ugrad = ops.GELU_SAVE_GRAD
         else:
@@ -805,7 +824,7 @@ class PairBiasFn(torch.autograd.Function):
             ugrad = ops.GELU_SAVE_GRAD
             o = ops.linear_fwd(h, wbf16(proj.linear2.weight), proj.linear2.bias, out_dtype=F32)
             out = ops.pair_permute_fwd(o, B, N, H, ld)
-        ctx.st = SimpleNamespace(dist=dist, et=edge_type, feat=feat, u=u, h=h, B=B, N=N, H=H, ld=ld, fused=fused, ugrad=ugrad, full=full, slot=None,
+        ctx.st = SimpleNamespace(rec=rec, coords=coords, dist=dist, et=edge_type, feat=feat, u=u, h=h, B=B, N=N, H=H, ld=ld, fused=fused, ugrad=ugrad, full=full, slot=None,
                                  pre_b=pre_b if fused else None, rb_b=rb_b if fused else None)
         ctx.gbf, ctx.proj = gbf, proj
         if out.dtype == torch.float16:
@@ -832,8 +851,12 @@ class PairBiasFn(torch.autograd.Function):
             l1, l2 = proj.linear1, proj.linear2
             allp = [l1.weight, l1.bias, l2.weight, l2.bias] + ps
             grads = [gbuf(p) if p.requires_grad else torch.zeros_like(p) for p in allp]
-            ops.gbf_bias_bwd_full(g.contiguous(), st.dist, st.et, *[p.view(-1) for p in ps], wbf16(l1.weight), l1.bias, wbf16(l2.weight),
-                                  st.ld, *[gr.view(-1) for gr in grads], tile_prefix=st.pre_b, row_blocks=st.rb_b)
+            if st.rec is not None:
+                ops.gbf_bias_bwd_full_coords(g.contiguous(), st.rec, st.coords[0], st.coords[1], *[p.view(-1) for p in ps], wbf16(l1.weight), l1.bias,
+                                             wbf16(l2.weight), st.ld, *[gr.view(-1) for gr in grads], tile_prefix=st.pre_b, row_blocks=st.rb_b)
+            else:
+                ops.gbf_bias_bwd_full(g.contiguous(), st.dist, st.et, *[p.view(-1) for p in ps], wbf16(l1.weight), l1.bias, wbf16(l2.weight),
+                                      st.ld, *[gr.view(-1) for gr in grads], tile_prefix=st.pre_b, row_blocks=st.rb_b)
         elif st.fused and ps[0].numel() <= 4096:
             # one pass over G: re-layout, both dX products, GELU' and the Gaussian backward; only the two weight-gradient
             # GEMMs (contraction over all pairs) and their column sums remain
@@ -853,7 +876,7 @@ class PairBiasFn(torch.autograd.Function):
                 ops.gbf_features_bwd(st.dist, st.et, *[p.view(-1) for p in ps], dfeat, *[gr.view(-1) for gr in grads])
         notify_grads_ready(list(gbf.parameters()) + list(proj.parameters()))
         _join_stream_after_backward()
-        return None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None
 
 
 class PairCompactFn(torch.autograd.Function):

@@ -70,11 +70,17 @@ class UnimolEncoder(nn.Module):
             raise RuntimeError(f"Uni-Mol checkpoint {path} lacks {len(missing)} parameters, e.g. {missing[:5]}")
         self.load_state_dict({k: v for k, v in sd.items() if k in own}, strict=True)
 
-    def forward(self, src_tokens, src_distance, src_edge_type):
+    def forward(self, src_tokens, src_distance=None, src_edge_type=None, src_coord=None):
         padding_mask = src_tokens.eq(self.padding_idx)
         x = EmbeddingFn.apply(self.embed_tokens.weight, src_tokens, self.padding_idx)
-        N = src_distance.shape[-1]
-        bias = PairBiasFn.apply(grad_anchor(itertools.chain(self.gbf.parameters(), self.gbf_proj.parameters())), src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N))
+        anchor = grad_anchor(itertools.chain(self.gbf.parameters(), self.gbf_proj.parameters()))
+        if src_distance is not None and src_edge_type is not None:
+            N = src_distance.shape[-1]
+            bias = PairBiasFn.apply(anchor, src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N))
+        else:      # from the coordinates (MM_Model.pair_bias has the story); neither planes nor coordinates: pair_records_of raises
+            from .mm_model import pair_records_of
+            bias = PairBiasFn.apply(anchor, pair_records_of(self, src_coord, src_tokens), None, self.gbf, self.gbf_proj, ops.pair_ld(src_tokens.shape[1]),
+                                    None, None, (len(self.dictionary), self.padding_idx))
         encoder_rep, _, _ = self.encoder.encode(x, bias, padding_mask)
         return encoder_rep
 

@@ -184,6 +184,19 @@ class CrossAttentionModel(nn.Module):
         return text_to_graph, graph_to_text
 
 
+def pair_records_of(model, src_coord, src_tokens):
+    """The atom records (ops.pair_records) of a batch for ``model``'s dictionary; raises before any launch when the coordinates are
+    missing or the dictionary does not span the Gaussian layer's edge tables (edge type = tok_i * V + tok_j needs V * V rows)."""
+    if src_coord is None or src_tokens is None:
+        raise ValueError("pair bias: needs src_distance and src_edge_type, or src_coord and src_tokens")
+    V, E = len(model.dictionary), model.gbf.mul.weight.numel()
+    if V * V != E:
+        raise ValueError(f"pair bias from coordinates: len(dictionary)^2 = {V * V} is not the edge-table size {E}")
+    if src_coord.shape[:2] != src_tokens.shape or src_coord.shape[-1] != 3:
+        raise ValueError(f"pair bias from coordinates: src_coord must be [B,N,3] for src_tokens {tuple(src_tokens.shape)}, got {tuple(src_coord.shape)}")
+    return ops.pair_records(src_coord.float().contiguous(), src_tokens.contiguous())
+
+
 class MM_Model(nn.Module):
     def __init__(self, output_dim=2, **params):
         super().__init__()
@@ -320,12 +333,17 @@ class MM_Model(nn.Module):
         return self._side
 
     # ------------------------------------------------------------------ forward
-    def pair_bias(self, src_distance, src_edge_type, key_tiles_host=None, rows_host=None):
+    def pair_bias(self, src_distance, src_edge_type, key_tiles_host=None, rows_host=None, src_coord=None, src_tokens=None):
         """mm_model.py:553-556 fused: -> the pair bias ([B,H,N,ld] fp32, or the tiled pair layout on the hot path).  key_tiles_host
-        (ragged batches): [B] real key tiles per molecule, on the HOST; rows_host (packed token rows): [B] query rows per molecule."""
-        N = src_distance.shape[-1]
-        return PairBiasFn.apply(grad_anchor(itertools.chain(self.gbf.parameters(), self.gbf_proj.parameters())), src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N), key_tiles_host,
-                                rows_host)
+        (ragged batches): [B] real key tiles per molecule, on the HOST; rows_host (packed token rows): [B] query rows per molecule.
+        Without the two planes: from src_coord [B,N,3] and src_tokens [B,N] (the planes are functions of them, data/conformer.py:204-212):
+        the atoms are packed into 16-byte records once and the kernels derive every pair in registers (PairBiasFn, coords form)."""
+        anchor = grad_anchor(itertools.chain(self.gbf.parameters(), self.gbf_proj.parameters()))
+        if src_distance is not None and src_edge_type is not None:
+            N = src_distance.shape[-1]
+            return PairBiasFn.apply(anchor, src_distance.float(), src_edge_type, self.gbf, self.gbf_proj, ops.pair_ld(N), key_tiles_host, rows_host)
+        return PairBiasFn.apply(anchor, pair_records_of(self, src_coord, src_tokens), None, self.gbf, self.gbf_proj, ops.pair_ld(src_tokens.shape[1]),
+                                key_tiles_host, rows_host, (len(self.dictionary), self.padding_idx))
 
     def _packings(self, src_tokens, input_ids, atom_counts, token_counts, token_pad_id, packable):
         """-> (PackedRows of tower 1, PackedRows of tower 2) when this batch can and should run on packed token rows, else None.
@@ -359,9 +377,17 @@ class MM_Model(nn.Module):
         self._pack_cache = (atom_counts, token_counts, (B, N, L, src_tokens.device), packs)
         return packs
 
-    def forward(self, src_tokens, src_distance, src_edge_type, input_ids, attention_mask, weights=None,
+    def forward(self, src_tokens, src_distance=None, src_edge_type=None, input_ids=None, attention_mask=None, weights=None,
                 return_infonce_loss=False, return_ct_loss=False, return_feature=False, net_target=None, use_weight=None,
-                epoch=0, atom_counts=None, token_counts=None, token_pad_id=None, packable=False, **kwargs):
+                epoch=0, atom_counts=None, token_counts=None, token_pad_id=None, packable=False, src_coord=None, **kwargs):
+        # Pair inputs: the two [B,N,N] planes when the batch carries them (used exactly as ever, src_coord then stays unread as in the
+        # reference, mm_model.py:540); else src_coord [B,N,3], from which the kernels derive every pair (pair_bias).  Neither: an error.
+        if src_distance is None or src_edge_type is None:
+            if src_coord is None:
+                raise ValueError("MM_Model.forward needs src_distance and src_edge_type, or src_coord (pair_inputs='coords')")
+            src_distance = src_edge_type = None
+        if input_ids is None or attention_mask is None:
+            raise TypeError("MM_Model.forward: input_ids and attention_mask are required")
         padding_mask = src_tokens.eq(self.padding_idx)
         # Ragged batches.  atom_counts ([B] ints ON THE HOST: position of each molecule's last real token + 1, attached by
         # collate.device_payload) tells, without a device sync, whether some molecule is shorter than the padded length; then the
@@ -402,14 +428,14 @@ class MM_Model(nn.Module):
 
         if pk1 is None:
             xs = EmbeddingFn.apply(self.embed_tokens.weight, src_tokens, self.padding_idx)
-            bias_s = self.pair_bias(src_distance, src_edge_type, kt_host)
+            bias_s = self.pair_bias(src_distance, src_edge_type, kt_host, src_coord=src_coord, src_tokens=src_tokens)
             encoder_rep = self.encoder.encode(xs, bias_s, padding_mask, key_tiles)[0]
         else:
             # packed rows of tower 1: [M1] token ids / pad flags (integer plumbing; the representative pad row is the first padded
             # slot of its molecule, so it gathers the pad id), the pair bias stays positional
             ids1, pad1 = src_tokens.reshape(-1)[pk1.gather], padding_mask.reshape(-1)[pk1.gather]
             xs = EmbeddingFn.apply(self.embed_tokens.weight, ids1, self.padding_idx)
-            bias_s = self.pair_bias(src_distance, src_edge_type, kt_host, pk1.rows_host)
+            bias_s = self.pair_bias(src_distance, src_edge_type, kt_host, pk1.rows_host, src_coord=src_coord, src_tokens=src_tokens)
             if bias_s.dtype != torch.float16:         # (head / basis counts the fused pair-bias kernel is not built for: re-lay out)
                 bias_s = PairCompactFn.apply(bias_s, src_tokens.shape[1])
             encoder_rep = self.encoder.encode(xs, bias_s, pad1, key_tiles, pack=pk1)[0]

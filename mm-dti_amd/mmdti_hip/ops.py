@@ -642,6 +642,85 @@ def gbf_bias_bwd_full(g, dist, edge_type, mul, bias, means, stds, w1, b1, w2, ld
     kernel_timer.end("gbf_bias_bwd", t0, kept * float(P) * (6.0 * Fh * K + 4.0 * Hh * Fh))
 
 
+# ---- pair inputs from coordinates (data/conformer.py:204-212: the two [B,N,N] planes are functions of the atoms) ----------------------
+def pair_records(coord, tokens):
+    """coord [B,N,3] fp32 + tokens [B,N] int64 / int32 -> the atom records [B,N,4] int32 (fp32 bits of x, y, z | token) the coords
+    kernels read: 16 bytes per atom, packed once per forward."""
+    _chk(coord, F32, "pair_records.coord")
+    if tokens.dtype not in (torch.int64, torch.int32) or not tokens.is_cuda or not tokens.is_contiguous():
+        raise MMDTIError(f"pair_records.tokens: expected a contiguous int64 / int32 device tensor, got {tokens.dtype}")
+    B, N = tokens.shape
+    if tuple(coord.shape) != (B, N, 3):
+        raise MMDTIError(f"pair_records: coord must be [B,N,3] = {(B, N, 3)}, got {tuple(coord.shape)}")
+    rec = torch.empty(B, N, 4, device=coord.device, dtype=torch.int32)
+    lib().mmdti_pair_records_pack(_stream(), coord.data_ptr(), tokens.data_ptr(), tokens.element_size(), B, N, rec.data_ptr())
+    return rec
+
+
+def _chk_records(rec):
+    _chk(rec, torch.int32, "pair records")
+    if rec.dim() != 3 or rec.shape[2] != 4:
+        raise MMDTIError(f"pair records: expected [B,N,4] int32 (ops.pair_records), got {tuple(rec.shape)}")
+    return rec.shape[0], rec.shape[1]
+
+
+def pair_inputs_from_records(rec, vocab, pad_idx, edge_dtype=torch.int16):
+    """records -> (src_distance [B,N,N] fp32, src_edge_type [B,N,N] int16 | int64) by the kernels' pair rule."""
+    B, N = _chk_records(rec)
+    if edge_dtype not in (torch.int16, torch.int64):
+        raise MMDTIError(f"pair_inputs_from_records: edge types leave as int16 or int64, not {edge_dtype}")
+    dist = torch.empty(B, N, N, device=rec.device, dtype=F32)
+    et = torch.empty(B, N, N, device=rec.device, dtype=edge_dtype)
+    t0 = kernel_timer.begin("pair_inputs_from_coords")
+    lib().mmdti_pair_inputs_from_coords(_stream(), rec.data_ptr(), B, N, int(vocab), int(pad_idx), dist.data_ptr(), et.data_ptr(), et.element_size())
+    # bytes: 16 per atom in, distance + edge type per atom pair out
+    kernel_timer.end("pair_inputs_from_coords", t0, 16.0 * B * N + float(B * N * N) * (4 + et.element_size()))
+    return dist, et
+
+
+def pair_inputs_from_coords(coord, tokens, vocab, pad_idx, edge_dtype=torch.int16):
+    """The device statement of collate.pair_inputs_from_coords: (src_distance, src_edge_type) of a right-padded batch from its
+    coordinates and tokens (edge types exact; distances fp32 with one rounding per operation, within 4 ulp of the float64 value)."""
+    return pair_inputs_from_records(pair_records(coord.contiguous(), tokens.contiguous()), vocab, pad_idx, edge_dtype)
+
+
+def gbf_bias_fwd_coords(rec, vocab, pad_idx, mul, bias, means, stds, w1, b1, w2, b2, ld, tiled=False, compact=False, tile_prefix=None, row_blocks=None):
+    """:func:`gbf_bias_fwd` from the atom records: no [B,N,N] input exists; bit-identical to the planes kernel fed
+    :func:`pair_inputs_from_records`.  Saves nothing (the complete backward recomputes)."""
+    if compact and not tiled:
+        raise MMDTIError("gbf_bias_fwd_coords: compact pair planes exist in the tiled layout only")
+    B, N = _chk_records(rec); _chk(w1, BF16, "gbf.w1"); _chk(w2, BF16, "gbf.w2")
+    Hh, Fh = w2.shape
+    out = pair_empty(B, Hh, N, rec.device, tiled, dtype=F16 if compact else F32) if tiled else torch.empty(B, Hh, N, ld, device=rec.device, dtype=F32)
+    t0 = kernel_timer.begin("gbf_bias_fwd")
+    lib().mmdti_gbf_bias_fwd_coords(_stream(), rec.data_ptr(), int(vocab), int(pad_idx), mul.data_ptr(), bias.data_ptr(), means.data_ptr(), stds.data_ptr(),
+                                    w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, N, ld, w1.shape[1], Fh, Hh, mul.numel(), out.data_ptr(),
+                                    int(tiled) | (4 if compact else 0), _p(tile_prefix), _p(row_blocks))
+    # algorithmic bytes: 16 per atom in (the records), 64 heads x 4 B (compact: 2 B) of bias per atom pair out
+    kept = _pair_kept if tile_prefix is not None else 1.0
+    kernel_timer.end("gbf_bias_fwd", t0, 16.0 * B * N + kept * float(B * N * N) * Hh * out.element_size())
+    return out
+
+
+def gbf_bias_bwd_full_coords(g, rec, vocab, pad_idx, mul, bias, means, stds, w1, b1, w2, ld, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds,
+                             tile_prefix=None, row_blocks=None):
+    """:func:`gbf_bias_bwd_full` from the atom records (same kernel body, same deterministic form)."""
+    B, N = _chk_records(rec); _chk(w1, BF16, "gbf.w1"); _chk(w2, BF16, "gbf.w2")
+    for t, nm in ((dw1, "dw1"), (db1, "db1"), (dw2, "dw2"), (db2, "db2"), (dmul, "dmul"), (dbias, "dbias"), (dmeans, "dmeans"), (dstds, "dstds")):
+        _chk(t, F32, "gbf." + nm)
+    Hh, Fh = w2.shape
+    K = w1.shape[1]
+    ws = torch.empty(lib()._dll.mmdti_gbf_bias_bwd_full_workspace(mul.numel()), device=rec.device, dtype=torch.uint8) if GBF_SLABS else None
+    t0 = kernel_timer.begin("gbf_bias_bwd")
+    lib().mmdti_gbf_bias_bwd_full_coords(_stream(), g.data_ptr(), rec.data_ptr(), int(vocab), int(pad_idx), mul.data_ptr(), bias.data_ptr(), means.data_ptr(),
+                                         stds.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), B, N, ld, K, Fh, Hh, mul.numel(),
+                                         _pair_layout_g(g, "gbf_bias_bwd_full_coords"), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(),
+                                         dmul.data_ptr(), dbias.data_ptr(), dmeans.data_ptr(), dstds.data_ptr(), _p(tile_prefix), _p(row_blocks), _p(ws),
+                                         0 if ws is None else ws.numel())
+    kept = _pair_kept if tile_prefix is not None else 1.0
+    kernel_timer.end("gbf_bias_bwd", t0, kept * float(B * N * N) * (6.0 * Fh * K + 4.0 * Hh * Fh))    # (MFMA flops, as gbf_bias_bwd_full)
+
+
 def gbf_bias_eligible(K, Fh, Hh, ld):
     return K == 128 and Fh == 128 and Hh == 64 and ld % 4 == 0
 

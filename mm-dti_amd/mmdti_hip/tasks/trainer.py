@@ -34,7 +34,7 @@ import torch
 from torch.utils.data import DataLoader as TorchDataLoader
 
 from ..trainer import FineTuner
-from ..collate import HostCollate, device_payload, to_device
+from ..collate import HostCollate, device_payload, to_device, PAIR_INPUT_MODES
 
 logger = logging.getLogger("mmdti_hip")
 
@@ -231,6 +231,11 @@ class Trainer(object):
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
         self.num_workers = int(params.get('num_workers', 0))
         self.narrow_inputs = bool(params.get('narrow_inputs', True))
+        #   pair_inputs="coords" -> the batches carry src_coord and no [B,N,N] plane: neither padded by the collate nor shipped, the
+        #   pair-bias kernels derive every pair from its two atoms (the samples must carry src_coord; "planes": the reference's batches)
+        self.pair_inputs = params.get('pair_inputs', 'planes')
+        if self.pair_inputs not in PAIR_INPUT_MODES:
+            raise ValueError(f"Trainer: pair_inputs must be one of {PAIR_INPUT_MODES}, got {self.pair_inputs!r}")
         self.rank = torch.distributed.get_rank() if (self.distributed and torch.distributed.is_initialized()) else 0
         self._loss_cache = {}       # id(loss_func) -> (loss_func, its kernel-backed loss): see _task_loss
 
@@ -242,8 +247,8 @@ class Trainer(object):
         """Host -> device move of a collated batch and the target dtype rule (tasks/trainer.py:101-120)."""
         net_input, net_target = batch
         if isinstance(net_input, dict):
-            if self.narrow_inputs:
-                net_input = device_payload(net_input, self._n_edge_types, self._pad_idx)
+            if self.narrow_inputs or self.pair_inputs == "coords":
+                net_input = device_payload(net_input, self._n_edge_types, self._pad_idx, self.pair_inputs)
             net_input = to_device(net_input, self.device)
             if self.distributed:
                 from ..parallel import pad_to_global_lengths
@@ -275,7 +280,7 @@ class Trainer(object):
             return
         from ..data import DevicePrefetcher
         for net_input, net_target in DevicePrefetcher(batches, self.device, narrow=self.narrow_inputs, n_edge_types=self._n_edge_types,
-                                                      pad_idx=self._pad_idx):
+                                                      pad_idx=self._pad_idx, pair_inputs=self.pair_inputs):
             if self.distributed:
                 from ..parallel import pad_to_global_lengths
                 net_input = pad_to_global_lengths(net_input)        # the unmasked InfoNCE mean needs one padded length on all ranks
@@ -288,8 +293,8 @@ class Trainer(object):
         self._n_edge_types = len(d) * len(d) if d is not None else None
         self._pad_idx = getattr(model, 'padding_idx', 0)
         from ..models.mm_model import MM_Model
-        if self.num_workers > 0 and type(model).batch_collate_fn is MM_Model.batch_collate_fn:
-            return HostCollate.of(model, narrow=self.narrow_inputs)
+        if (self.num_workers > 0 or self.pair_inputs == "coords") and type(model).batch_collate_fn is MM_Model.batch_collate_fn:
+            return HostCollate.of(model, narrow=self.narrow_inputs, pair_inputs=self.pair_inputs)    # (coords: the square pads are never built)
         return model.batch_collate_fn
 
     def _loader_kwargs(self):
