@@ -651,6 +651,28 @@ int mmdti_fds_update_stats(mmdti_stream_t stream, const float* feats, const int*
 /* FDS._update_last_epoch_stats smoothing (fds.py:86-99): reflect-pad + conv1d across buckets */
 int mmdti_fds_smooth_stats(mmdti_stream_t stream, const float* stat, int nb, int D, const float* window, int ks,
                            float* out);
+/* Streaming statistics: the training steps feed per-bucket running moments, the epoch's end is one small kernel -- in place of the
+ * second forward over the training set that feeds mmdti_fds_update_stats (models/fds.py:116-155, tasks/trainer.py:288-306).  The
+ * accumulator `acc` is (nb + 2) slots of (1 + 2 D) 32-bit words, nb = bucket_num - bucket_start, 4-byte aligned, zeroed by the caller
+ * at the start of an epoch: { int32 rows | fp32 mean[D] | fp32 M2[D] } (Welford).  Slot s < nb: rows whose bin is exactly
+ * bucket_start + s; slot nb: bins < bucket_start; slot nb + 1: bins > bucket_num - 1 -- whether those fold into the end buckets is
+ * only known once the whole epoch has been seen (mmdti_fds_bins' flags).  One owner per (slot, column), no cross-workgroup float sum:
+ * the results are fixed by the row order.  Purely additive: MMDTI_ABI_VERSION does not move. */
+/* continues every (slot, column) recurrence over feats [n, D] in row order, with mmdti_fds_update_stats' update expression: one call
+ * or any split of the same rows into calls leaves bit-identical accumulators.  A slot without a row in the batch is not written;
+ * n == 0 is a no-op (models/fds.py:116-155, tasks/trainer.py:288-306). */
+int mmdti_fds_stream_accumulate(mmdti_stream_t stream, const float* feats, const int* bins, int n, int D, int bucket_start,
+                                int bucket_num, void* acc);
+/* acc_dst <- acc_dst (+) acc_src slot by slot (Chan: n = na + nb, d = mb - ma, mean = ma + d nb / n, M2 = M2a + M2b + d^2 na nb / n):
+ * the ranks' accumulators under data parallelism.  An empty side leaves the other unchanged to the bit; equal constant columns keep
+ * M2 exactly 0 (models/fds.py:116-155, tasks/trainer.py:288-306). */
+int mmdti_fds_stream_merge(mmdti_stream_t stream, void* acc_dst, const void* acc_src, int nb, int D);
+/* the epoch's end (models/fds.py:116-155, tasks/trainer.py:288-306): the below slot merges into the first bucket iff that bucket's
+ * exact count is > 0, the above slot into the last iff its exact count is > 0 and bucket_start != bucket_num - 1 (rows of a slot
+ * that does not merge are dropped); a bucket with exact count 0 is untouched; variance M2 / (cnt - 1), M2 / cnt for cnt == 1; then
+ * mmdti_fds_update_stats' EMA with `factor` and num_samples_tracked += cnt.  Does not clear acc. */
+int mmdti_fds_stream_finish(mmdti_stream_t stream, const void* acc, int D, int bucket_start, int bucket_num, float factor,
+                            float* running_mean, float* running_var, float* num_samples_tracked);
 
 /* ---- masked pooling (mm_model.py:572-576) --------------------------------------------------- */
 /* pooled[b] = (sum_{valid n} a[b,n] + sum_{valid l} t[b,l]) / (n_valid_a + n_valid_t);  a:[B,Na,D], t:[B,Nt,D] fp32,

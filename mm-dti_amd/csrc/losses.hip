@@ -565,6 +565,23 @@ __global__ __launch_bounds__(256) void fds_smooth_kernel(const float* __restrict
   }
 }
 
+// One row of a column's Welford recurrence, like ATen's var kernel: a constant column yields EXACTLY zero M2, which
+// calibrate_mean_var's `v1 == 0` test (utils/util.py:162) depends on.  Shared by the one-shot and the streaming statistics.
+__device__ __forceinline__ void fds_welford_step(int& k, float& mean, float& m2, float xv) {
+  ++k;
+  const float delta = xv - mean;
+  mean += delta / (float)k;
+  m2 += delta * (xv - mean);
+}
+
+// fds.py:141-155 for one (bucket, column): unbiased variance (population for a single row), momentum EMA
+__device__ __forceinline__ void fds_ema_store(float mean, float m2, int cnt, float factor, float* __restrict__ rmean, float* __restrict__ rvar,
+                                              long long o) {
+  const float var = cnt > 1 ? m2 / (float)(cnt - 1) : m2 / (float)cnt;
+  rmean[o] = (1.f - factor) * mean + factor * rmean[o];
+  rvar[o] = (1.f - factor) * var + factor * rvar[o];
+}
+
 // block per bucket, thread per feature column (strided)
 __global__ __launch_bounds__(256) void fds_update_kernel(const float* __restrict__ f, const int* __restrict__ bins, const int* __restrict__ flags,
                                                          int n, int D, int bs, int bn, float factor, float* __restrict__ rmean,
@@ -583,25 +600,110 @@ __global__ __launch_bounds__(256) void fds_update_kernel(const float* __restrict
   __syncthreads();
   const int cnt = s_cnt;
   if (s_exact == 0 || cnt == 0) return;  // bucket not in torch.unique(label_bin): untouched
-  // Welford, like ATen's var kernel: a constant column yields EXACTLY zero variance, which calibrate_mean_var's
-  // `v1 == 0` test (utils/util.py:162) depends on.
   for (int d = threadIdx.x; d < D; d += 256) {
     float mean = 0.f, m2 = 0.f;
     int k = 0;
     for (int i = 0; i < n; ++i) {
       if (fds_eff_bucket(bins[i], bs, bn, flags) != bucket) continue;
-      const float xv = f[(long long)i * D + d];
-      ++k;
-      const float delta = xv - mean;
-      mean += delta / (float)k;
-      m2 += delta * (xv - mean);
+      fds_welford_step(k, mean, m2, f[(long long)i * D + d]);
     }
-    const float var = cnt > 1 ? m2 / (float)(cnt - 1) : m2 / (float)cnt;
-    const long long o = (long long)blockIdx.x * D + d;
-    rmean[o] = (1.f - factor) * mean + factor * rmean[o];
-    rvar[o] = (1.f - factor) * var + factor * rvar[o];
+    fds_ema_store(mean, m2, cnt, factor, rmean, rvar, (long long)blockIdx.x * D + d);
   }
   if (threadIdx.x == 0) tracked[blockIdx.x] += (float)cnt;
+}
+
+// ---- streaming statistics (fds.py:116-155 fed by the training steps in place of the epoch pass, tasks/trainer.py:288-306)
+// Accumulator: nb + 2 slots of 1 + 2D 32-bit words -- { int32 rows | fp32 mean[D] | fp32 M2[D] }.  Slot s < nb: rows whose bin is
+// EXACTLY bs + s; slot nb: bins < bs; slot nb + 1: bins > bn - 1.  Whether the two overflow slots fold into the end buckets depends on
+// fds_eff_bucket's flags over the whole epoch, so they stay apart until fds_stream_finish_kernel.  One owner per (slot, column): no
+// cross-workgroup float sum, the result is fixed by the row order alone.
+__device__ __forceinline__ int fds_stream_slot(int b, int bs, int bn) { return b < bs ? bn - bs : (b > bn - 1 ? bn - bs + 1 : b - bs); }
+
+// Chan's pairwise merge of (nb, mb, M2b) into (na, ma, M2a).  An empty side leaves the other as it is, to the bit; equal constant
+// columns give delta == 0 and keep M2 exactly 0.
+__device__ __forceinline__ void fds_chan_merge(int na, float& ma, float& M2a, int nb, float mb, float M2b) {
+  if (nb == 0) return;
+  if (na == 0) { ma = mb; M2a = M2b; return; }
+  const float n = (float)(na + nb), delta = mb - ma;
+  ma = ma + delta * ((float)nb / n);
+  M2a = M2a + M2b + delta * delta * ((float)na * (float)nb / n);
+}
+
+// block per slot, thread per feature column (strided).  The batch's rows of the slot are listed in row order, 256 rows at a time,
+// then every column continues its recurrence over the list.
+__global__ __launch_bounds__(256) void fds_stream_accumulate_kernel(const float* __restrict__ f, const int* __restrict__ bins, int n, int D, int bs,
+                                                                    int bn, int* __restrict__ acc) {
+  const int slot = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int* cntp = acc + (long long)slot * (1 + 2 * D);
+  float* mean_p = reinterpret_cast<float*>(cntp + 1);
+  float* m2_p = mean_p + D;
+  __shared__ int s_rows[256];
+  __shared__ int s_wcnt[4];
+  const int k_in = *cntp;               // (only thread 0 writes it, after the last barrier)
+  int k0 = k_in;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + threadIdx.x;
+    const bool hit = i < n && fds_stream_slot(bins[i], bs, bn) == slot;
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) s_wcnt[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0, total = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) off += s_wcnt[w];
+      total += s_wcnt[w];
+    }
+    if (hit) s_rows[off + __popcll(m & ((1ull << lane) - 1ull))] = i;
+    __syncthreads();
+    if (total > 0) {
+      for (int d = threadIdx.x; d < D; d += 256) {
+        int k = k0;
+        float mean = mean_p[d], m2 = m2_p[d];
+        for (int j = 0; j < total; ++j) fds_welford_step(k, mean, m2, f[(long long)s_rows[j] * D + d]);
+        mean_p[d] = mean;
+        m2_p[d] = m2;
+      }
+      k0 += total;
+    }
+    __syncthreads();                    // (s_rows / s_wcnt are rewritten by the next 256 rows)
+  }
+  if (threadIdx.x == 0 && k0 != k_in) *cntp = k0;      // a slot with no row in the batch is not written
+}
+
+__global__ __launch_bounds__(256) void fds_stream_merge_kernel(int* __restrict__ dst, const int* __restrict__ src, int D) {
+  const long long o = (long long)blockIdx.x * (1 + 2 * D);
+  const int na = dst[o], nb = src[o];
+  if (nb == 0) return;
+  float* ma = reinterpret_cast<float*>(dst + o + 1);
+  const float* mb = reinterpret_cast<const float*>(src + o + 1);
+  for (int d = threadIdx.x; d < D; d += 256) {
+    float mean = ma[d], m2 = ma[D + d];
+    fds_chan_merge(na, mean, m2, nb, mb[d], mb[D + d]);
+    ma[d] = mean;
+    ma[D + d] = m2;
+  }
+  __syncthreads();                      // (every thread has read the old count)
+  if (threadIdx.x == 0) dst[o] = na + nb;
+}
+
+// block per bucket: fds_eff_bucket's membership decided from the epoch's exact counts, then fds_update_kernel's EMA
+__global__ __launch_bounds__(256) void fds_stream_finish_kernel(const int* __restrict__ acc, int D, int bs, int bn, float factor,
+                                                                float* __restrict__ rmean, float* __restrict__ rvar, float* __restrict__ tracked) {
+  const int nb = bn - bs, j = blockIdx.x, W = 1 + 2 * D;
+  const int exact = acc[(long long)j * W];
+  if (exact == 0) return;               // bucket not in torch.unique(label_bin): untouched
+  const int below = j == 0 ? acc[(long long)nb * W] : 0;                                 // first bucket: rows <=
+  const int above = (j == nb - 1 && bs != bn - 1) ? acc[(long long)(nb + 1) * W] : 0;    // last bucket: rows >=
+  const float* own = reinterpret_cast<const float*>(acc + (long long)j * W + 1);
+  const float* lo = reinterpret_cast<const float*>(acc + (long long)nb * W + 1);
+  const float* hi = reinterpret_cast<const float*>(acc + (long long)(nb + 1) * W + 1);
+  const int cnt = exact + below + above;
+  for (int d = threadIdx.x; d < D; d += 256) {
+    float mean = own[d], m2 = own[D + d];
+    if (below) fds_chan_merge(exact, mean, m2, below, lo[d], lo[D + d]);
+    if (above) fds_chan_merge(exact + below, mean, m2, above, hi[d], hi[D + d]);
+    fds_ema_store(mean, m2, cnt, factor, rmean, rvar, (long long)j * D + d);
+  }
+  if (threadIdx.x == 0) tracked[j] += (float)cnt;
 }
 
 // reflect-pad + conv1d across the bucket axis (fds.py:86-99)
@@ -1025,6 +1127,32 @@ extern "C" int mmdti_fds_update_stats(mmdti_stream_t stream, const float* feats,
 extern "C" int mmdti_fds_smooth_stats(mmdti_stream_t stream, const float* stat, int nb, int D, const float* window, int ks, float* out) {
   MMDTI_REQUIRE(stat && window && out && nb > 0 && D > 0 && ks > 0 && (ks - 1) / 2 < nb, "fds_smooth_stats: bad arguments");
   hipLaunchKernelGGL(fds_smooth_stats_kernel, dim3(cdiv((long long)nb * D, 256)), dim3(256), 0, (hipStream_t)stream, stat, nb, D, window, ks, out);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_fds_stream_accumulate(mmdti_stream_t stream, const float* feats, const int* bins, int n, int D, int bucket_start,
+                                           int bucket_num, void* acc) {
+  MMDTI_REQUIRE(acc && n >= 0 && D > 0 && D <= (1 << 20) && bucket_start >= 0 && bucket_num > bucket_start, "fds_stream_accumulate: bad arguments");
+  if (n == 0) return MMDTI_OK;
+  MMDTI_REQUIRE(feats && bins, "fds_stream_accumulate: null features / bins");
+  hipLaunchKernelGGL(fds_stream_accumulate_kernel, dim3(bucket_num - bucket_start + 2), dim3(256), 0, (hipStream_t)stream, feats, bins, n, D,
+                     bucket_start, bucket_num, static_cast<int*>(acc));
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_fds_stream_merge(mmdti_stream_t stream, void* acc_dst, const void* acc_src, int nb, int D) {
+  MMDTI_REQUIRE(acc_dst && acc_src && acc_dst != acc_src && nb > 0 && D > 0 && D <= (1 << 20), "fds_stream_merge: bad arguments");
+  hipLaunchKernelGGL(fds_stream_merge_kernel, dim3(nb + 2), dim3(256), 0, (hipStream_t)stream, static_cast<int*>(acc_dst),
+                     static_cast<const int*>(acc_src), D);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_fds_stream_finish(mmdti_stream_t stream, const void* acc, int D, int bucket_start, int bucket_num, float factor,
+                                       float* running_mean, float* running_var, float* num_samples_tracked) {
+  MMDTI_REQUIRE(acc && running_mean && running_var && num_samples_tracked && D > 0 && D <= (1 << 20) && bucket_start >= 0 &&
+                    bucket_num > bucket_start, "fds_stream_finish: bad arguments");
+  hipLaunchKernelGGL(fds_stream_finish_kernel, dim3(bucket_num - bucket_start), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const int*>(acc), D, bucket_start, bucket_num, factor, running_mean, running_var, num_samples_tracked);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

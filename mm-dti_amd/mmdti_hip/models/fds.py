@@ -9,7 +9,9 @@ gfx950 kernels; the reference does the binning in a per-sample Python list compr
 bucket.
 
 Differences by design: no hard-coded ``'cuda'`` (:84) -- buffers follow the module's device; ``raw_data`` may be a CSV
-path (as in the reference) or an array of the training targets.
+path (as in the reference) or an array of the training targets.  An addition: ``stream_reset / stream_accumulate / stream_finish``
+collect the epoch statistics from the training steps' own features (opt-in, FineTuner(fds_stats="streaming")); the state_dict keys
+stay the reference's eight.
 """
 import copy
 
@@ -125,6 +127,43 @@ class FDS(nn.Module):
         feats = features.detach().to(self.running_mean.device, torch.float32).contiguous()
         ops.fds_update_stats(feats, bins, flags, self.bucket_start, self.bucket_num, factor, self.running_mean, self.running_var,
                              self.num_samples_tracked)
+
+    # ------------------------------------------------------------------ streaming statistics (opt-in; DESIGN.md "Streaming FDS statistics")
+    # The training steps feed per-bucket running moments (stream_accumulate, one launch, no host synchronisation) and the epoch's end
+    # is one small kernel (stream_finish) -- in place of update_running_stats on the features of a second forward over the training set
+    # (tasks/trainer.py:288-306).  The accumulator is a plain attribute: not a buffer, not in state_dict(), None until the mode is used.
+    _stream_acc = None
+
+    def stream_state(self):
+        """The accumulator (ops.fds_stream_new), allocated on first use; its address then stays put (captured graphs hold it)."""
+        dev = self.running_mean.device
+        if self._stream_acc is None or self._stream_acc.device != dev:
+            self._stream_acc = ops.fds_stream_new(self.bucket_num - self.bucket_start, self.feature_dim, dev)
+        return self._stream_acc
+
+    def stream_reset(self):
+        """Start an epoch: every slot empty (in place)."""
+        self.stream_state().zero_()
+
+    def stream_accumulate(self, features, labels):
+        """Continue every bucket's running moments over the rows of one batch, in row order (enqueued; nothing is read back)."""
+        assert self.feature_dim == features.size(1), "Input feature dimension is not aligned!"
+        assert features.size(0) == labels.size(0), "Dimensions of features and labels are not aligned!"
+        if features.size(0) == 0:
+            return
+        acc = self.stream_state()
+        bins, _ = self._bins(labels)
+        feats = features.detach().to(acc.device, torch.float32).contiguous()
+        ops.fds_stream_accumulate(feats, bins, self.bucket_start, self.bucket_num, acc)
+
+    def stream_finish(self, epoch):
+        """update_running_stats on everything accumulated since stream_reset: same early return, same ``factor`` rule, the only
+        writer of running_* in the streaming mode.  The accumulator is left as it is."""
+        if epoch < float(self.epoch):
+            return
+        factor = 0.0 if epoch == self.start_update else self.momentum
+        ops.fds_stream_finish(self.stream_state(), self.bucket_start, self.bucket_num, factor, self.running_mean, self.running_var,
+                              self.num_samples_tracked)
 
     def smooth(self, features, labels, epoch):
         if epoch < self.start_smooth:

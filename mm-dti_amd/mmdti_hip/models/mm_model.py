@@ -198,6 +198,10 @@ def pair_records_of(model, src_coord, src_tokens):
 
 
 class MM_Model(nn.Module):
+    # True: training forwards of a regression + FDS model feed FDS.stream_accumulate from epoch fds_cfg.start_update on (set by
+    # FineTuner.fds_epoch_begin in the fds_stats="streaming" mode; off, forward is what it always was)
+    fds_streaming = False
+
     def __init__(self, output_dim=2, **params):
         super().__init__()
         self.cross_cfg = params.get('_cross_cfg') or crossmodal_config()
@@ -469,6 +473,13 @@ class MM_Model(nn.Module):
         if self.training and epoch >= self.fds_cfg.start_smooth and self.use_fds and self.task == 'regression':
             smoothed_features = self.FDS.smooth(smoothed_features, net_target, epoch)
             classification_feats_pooled = smoothed_features      # the reference smooths IN PLACE (:579-581): CT sees it too
+        if self.fds_streaming and self.training and not return_feature and self.use_fds and self.task == 'regression' \
+                and epoch >= self.fds_cfg.start_update:
+            # streaming FDS statistics (FineTuner(fds_stats="streaming")): this step's features -- the tensor return_feature=True
+            # returns -- feed the epoch's running moments; the epoch pass's own forwards (return_feature=True) and eval forwards do not
+            if net_target is None:
+                raise ValueError("MM_Model: fds_streaming needs net_target in every training forward (the labels decide the buckets)")
+            self.FDS.stream_accumulate(classification_feats_pooled.detach(), net_target)
 
         logits = self.classification_head(smoothed_features)
 

@@ -1180,6 +1180,50 @@ def fds_update_stats(feats, bins, flags, bucket_start, bucket_num, factor, runni
                                  float(factor), running_mean.data_ptr(), running_var.data_ptr(), tracked.data_ptr())
 
 
+def fds_stream_new(nb, D, device):
+    """A zeroed streaming-statistics accumulator: int32 [nb + 2, 1 + 2 D], per slot { rows | fp32 mean[D] | fp32 M2[D] } (the fp32 words
+    are read with fds_stream_views); slots nb / nb + 1 hold the rows below / above the bucket range (mmdti_hip.h)."""
+    return torch.zeros(nb + 2, 1 + 2 * D, device=device, dtype=torch.int32)
+
+
+def fds_stream_views(acc):
+    """-> (rows int32 [S], mean fp32 [S, D], M2 fp32 [S, D]): views of an accumulator's three fields"""
+    D = (acc.shape[1] - 1) // 2
+    fl = acc.view(F32)
+    return acc[:, 0], fl[:, 1:1 + D], fl[:, 1 + D:]
+
+
+def _chk_stream(acc, nb, D, name):
+    _chk(acc, torch.int32, name + ".acc")
+    if tuple(acc.shape) != (nb + 2, 1 + 2 * D):
+        raise MMDTIError(f"{name}: the accumulator must be [{nb + 2}, {1 + 2 * D}] (ops.fds_stream_new), got {tuple(acc.shape)}")
+
+
+def fds_stream_accumulate(feats, bins, bucket_start, bucket_num, acc):
+    n, D = feats.shape
+    _chk(feats, F32, "fds_stream_accumulate.feats")
+    _chk_stream(acc, bucket_num - bucket_start, D, "fds_stream_accumulate")
+    if _chk(bins, torch.int32, "fds_stream_accumulate.bins").numel() != n:
+        raise MMDTIError(f"fds_stream_accumulate: {bins.numel()} bins for {n} feature rows")
+    lib().mmdti_fds_stream_accumulate(_stream(), feats.data_ptr(), bins.data_ptr(), n, D, bucket_start, bucket_num, acc.data_ptr())
+
+
+def fds_stream_merge(acc_dst, acc_src):
+    nb, D = acc_dst.shape[0] - 2, (acc_dst.shape[1] - 1) // 2
+    _chk_stream(acc_dst, nb, D, "fds_stream_merge.dst")
+    _chk_stream(acc_src, nb, D, "fds_stream_merge.src")
+    lib().mmdti_fds_stream_merge(_stream(), acc_dst.data_ptr(), acc_src.data_ptr(), nb, D)
+
+
+def fds_stream_finish(acc, bucket_start, bucket_num, factor, running_mean, running_var, tracked):
+    nb, D = running_mean.shape
+    _chk_stream(acc, bucket_num - bucket_start, D, "fds_stream_finish")
+    if nb != bucket_num - bucket_start or running_var.shape != running_mean.shape or tracked.numel() != nb:
+        raise MMDTIError("fds_stream_finish: running_mean / running_var are [bucket_num - bucket_start, D], num_samples_tracked [bucket_num - bucket_start]")
+    lib().mmdti_fds_stream_finish(_stream(), acc.data_ptr(), D, bucket_start, bucket_num, float(factor), running_mean.data_ptr(),
+                                  running_var.data_ptr(), tracked.data_ptr())
+
+
 def fds_smooth_stats(stat, window):
     nb, D = stat.shape
     out = torch.empty_like(stat)

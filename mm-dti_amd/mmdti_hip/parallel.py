@@ -323,6 +323,19 @@ def gather_features(negs: "GlobalNegatives", feats: torch.Tensor, labels: torch.
     return negs.gather(feats.contiguous()), negs.gather(labels.float().view(labels.shape[0], -1).contiguous())
 
 
+def gather_fds_accumulators(acc: torch.Tensor, group=None):
+    """Streaming FDS statistics under data parallelism: every rank's accumulator (ops.fds_stream_new: [nb + 2, 1 + 2 D] 32-bit words,
+    about 0.4 MB at nb = 200, D = 512) in ONE all-gather -> the list of the ranks' accumulators in rank order, the same on every rank.
+    Merged in that order (ops.fds_stream_merge) every rank ends with bit-identical FDS buffers.  One process: [acc]."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if not _collectives_active(world):
+        return [acc]
+    acc = acc.contiguous()
+    out = torch.empty(world * acc.shape[0], acc.shape[1], device=acc.device, dtype=acc.dtype)      # (rank-major rows, as GlobalNegatives.gather)
+    dist.all_gather_into_tensor(out, acc, group=group)
+    return list(out.view(world, acc.shape[0], acc.shape[1]).unbind(0))
+
+
 def shard_batch(batch: dict, label, rank: int, world: int):
     """Contiguous split of an already-collated GLOBAL batch.  Every shard keeps the global padded lengths, which keeps
     the reference's unmasked InfoNCE mean (infonce.py:32-33) identical to the single-process value."""

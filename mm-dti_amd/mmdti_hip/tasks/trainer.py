@@ -33,7 +33,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader as TorchDataLoader
 
-from ..trainer import FineTuner
+from ..trainer import FineTuner, FDS_STATS_MODES
 from ..collate import HostCollate, device_payload, to_device, PAIR_INPUT_MODES
 
 logger = logging.getLogger("mmdti_hip")
@@ -225,6 +225,12 @@ class Trainer(object):
         self.alpha = params.get('alpha', 1)
         self.beta = params.get('beta', 0.1)
         self.fds = params.get('fds', False)
+        # where the FDS epoch statistics come from (FineTuner(fds_stats=...)): "epoch_pass", the reference's second forward over the
+        # training set (:288-306), or "streaming", the training steps' own features -- the loader is then iterated ONCE per epoch, so
+        # the shuffle stream advances half as fast and the batch order of later epochs differs from the reference's
+        self.fds_stats = params.get('fds_stats', 'epoch_pass')
+        if self.fds_stats not in FDS_STATS_MODES:
+            raise ValueError(f"Trainer: fds_stats must be one of {FDS_STATS_MODES}, got {self.fds_stats!r}")
         self.distributed = bool(params.get('distributed', False))
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
@@ -343,7 +349,7 @@ class Trainer(object):
         engine = FineTuner(model, self.task, learning_rate=self.learning_rate, adam_eps=1e-6, warmup_ratio=0.0,
                            total_steps=num_training_steps, alpha=self.alpha, beta=self.beta,
                            max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite,
-                           deterministic=self.deterministic)
+                           deterministic=self.deterministic, fds_stats=self.fds_stats)
         engine.warmup = int(num_training_steps * self.warmup_ratio)
         self._engine = engine
         task_loss = self._task_loss(loss_func)
@@ -355,6 +361,9 @@ class Trainer(object):
                 sampler.set_epoch(epoch)
             start_time = time.time()
             logged = []
+            fds_epoch = self.fds and epoch >= model.fds_cfg.start_update
+            if fds_epoch and self.fds_stats == "streaming":
+                engine.fds_epoch_begin(epoch)
             for net_input, net_target in self.device_batches(train_dataloader, feature_name):
                 out = engine.step(net_input, net_target, epoch=epoch, use_weight=use_weight, return_infonce_loss=return_infonce_loss,
                                   return_ct_loss=return_ct_loss, loss_func=task_loss)
@@ -366,7 +375,9 @@ class Trainer(object):
             steps = torch.stack(logged).cpu().numpy() if logged else np.zeros((0, 4))        # the epoch's ONE device->host sync
             skipped = int(steps[:, 4].sum()) if steps.shape[1] > 4 else 0
             steps = steps[:, :4]
-            if self.fds and epoch >= model.fds_cfg.start_update:
+            if fds_epoch and self.fds_stats == "streaming":
+                engine.fds_epoch_finish(epoch)
+            elif fds_epoch:
                 engine.fds_epoch_pass((self.decorate_batch(b, feature_name) for b in train_dataloader), epoch)
             y_preds, val_loss, metric_score = self.predict(model, valid_dataset, loss_func, activation_fn, dump_dir, fold, target_scaler,
                                                            epoch, load_model=False, feature_name=feature_name, return_infonce_loss=False)

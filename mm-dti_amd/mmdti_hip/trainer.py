@@ -60,10 +60,13 @@ def _qkv_groups(model):
     return groups
 
 
+FDS_STATS_MODES = ("epoch_pass", "streaming")
+
+
 class FineTuner:
     def __init__(self, model, task: str, learning_rate=1e-4, adam_eps=1e-6, warmup_ratio=0.03, total_steps=1000, alpha=1.0, beta=0.1,
                  max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
-                 loss_key: Optional[str] = None, deterministic: Optional[bool] = None):
+                 loss_key: Optional[str] = None, deterministic: Optional[bool] = None, fds_stats: str = "epoch_pass"):
         """deterministic: True enters the process-wide deterministic mode (ops.set_deterministic: every cross-workgroup sum into a
         parameter gradient in a fixed order, one reduction workspace per launch stream); None follows MMDTI_DETERMINISTIC; False (and
         an unset environment) touches nothing.  Sites that have no fixed-order form yet raise in the mode (DESIGN.md lists them), and so
@@ -73,7 +76,15 @@ class FineTuner:
         schedule advances.  The decision is taken on the device (no host synchronisation, captured inside graphed_step) from the
         all-reduced gradients under data parallelism, so every rank takes the same one.
         loss_key: the multilabel_classification loss table's key (models/nnmodel.py:28-32): None / 'bce' the BCE-with-logits kernel,
-        'focal' / 'ghm' the kernels of ``losses.FocalLossWithLogits()`` / ``losses.GHMCLoss(10, 0.5)`` (kept as ``self.task_loss``)."""
+        'focal' / 'ghm' the kernels of ``losses.FocalLossWithLogits()`` / ``losses.GHMCLoss(10, 0.5)`` (kept as ``self.task_loss``).
+        fds_stats: where the FDS epoch statistics come from.  "epoch_pass" (default): the reference's second forward over the training
+        set, fds_epoch_pass (tasks/trainer.py:288-306).  "streaming": the training steps' own features feed per-bucket running moments on
+        the device -- fds_epoch_begin(epoch) before an epoch's steps, fds_epoch_finish(epoch) after them, and fds_epoch_pass raises.  Each
+        batch is then seen with the weights of its own step, not with the end-of-epoch weights (DESIGN.md "Streaming FDS statistics").
+        The features are accumulated in the forward: a step that skip_nonfinite skips has still contributed its rows."""
+        if fds_stats not in FDS_STATS_MODES:
+            raise ValueError(f"FineTuner: fds_stats must be one of {FDS_STATS_MODES}, got {fds_stats!r}")
+        self.fds_stats = fds_stats
         self.model, self.task = model, task
         from . import ops
         self.deterministic = ops.deterministic_default() if deterministic is None else bool(deterministic)
@@ -165,7 +176,7 @@ class FineTuner:
             kw["return_infonce_loss"] = True
         if return_ct_loss:
             kw.update(return_ct_loss=True, use_weight=use_weight)
-        if return_ct_loss or return_infonce_loss:
+        if return_ct_loss or return_infonce_loss or getattr(model, "fds_streaming", False):
             kw["net_target"] = net_target
         out = model(**net_input, **kw)
         out = out if isinstance(out, tuple) else (out,)
@@ -235,6 +246,8 @@ class FineTuner:
         net_input = {k: v for k, v in net_input.items() if k not in HOST_FIELDS}
         key = (epoch >= getattr(getattr(self.model, "fds_cfg", None), "start_smooth", 1 << 30), bool(use_weight), tuple(sorted(kw.items())),
                tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(net_input.items())), tuple(net_target.shape), net_target.dtype)
+        if getattr(self.model, "fds_streaming", False):      # (the accumulate launch is in the graph from start_update on)
+            key += (epoch >= self.model.fds_cfg.start_update,)
         ent = self._graphs.get(key)
         if ent is None:
             ent = self._capture(net_input, net_target, epoch, use_weight, kw)
@@ -282,6 +295,9 @@ class FineTuner:
         lf = kw.get("loss_func") or self.task_loss
         loss_state = lf.device_state(dev) if hasattr(lf, "device_state") else None
         loss_saved = None if loss_state is None else loss_state.clone()
+        # ... and so is the streaming FDS accumulator the forward feeds (allocated here, before the capture; its address stays put)
+        fds_acc = self.model.FDS.stream_state() if getattr(self.model, "fds_streaming", False) else None
+        fds_saved = None if fds_acc is None else fds_acc.clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -295,6 +311,8 @@ class FineTuner:
             self.guard.copy_(saved[6])
         if loss_state is not None:
             loss_state.copy_(loss_saved)
+        if fds_acc is not None:
+            fds_acc.copy_(fds_saved)
         self.arena.refresh_shadow()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -321,6 +339,9 @@ class FineTuner:
         """Full pass over the training batches (model left in train mode as in the reference) collecting pooled features,
         then FDS.update_last_epoch_stats / update_running_stats.  Under DDP the features are all-gathered so every rank
         ends with identical buffers."""
+        if self.fds_stats == "streaming":
+            raise RuntimeError("FineTuner.fds_epoch_pass: this engine collects the FDS statistics from the training steps "
+                               "(fds_stats='streaming'): call fds_epoch_begin / fds_epoch_finish round the epoch's steps")
         model = self.model
         feats, labels = [], []
         for net_input, net_target in batches:
@@ -332,3 +353,34 @@ class FineTuner:
             f, y = gather_features(self.negs, f, y)
         model.FDS.update_last_epoch_stats(epoch)
         model.FDS.update_running_stats(f, y, epoch)
+
+    # ------------------------------------------------------------------ fds_stats="streaming"
+    def _fds_streaming(self, what):
+        if self.fds_stats != "streaming":
+            raise RuntimeError(f"FineTuner.{what}: this engine was built with fds_stats={self.fds_stats!r} (use fds_epoch_pass)")
+        if getattr(self.model, "FDS", None) is None:
+            raise RuntimeError(f"FineTuner.{what}: the model has no FDS module (regression task with fds=True)")
+        return self.model.FDS
+
+    def fds_epoch_begin(self, epoch: int):
+        """Before the steps of ``epoch``: empty accumulator, and the model's training forwards feed it (from fds_cfg.start_update on)."""
+        self._fds_streaming("fds_epoch_begin").stream_reset()
+        self.model.fds_streaming = True
+
+    @torch.no_grad()
+    def fds_epoch_finish(self, epoch: int):
+        """After the steps of ``epoch``, where fds_epoch_pass would run and in its order: update_last_epoch_stats, then the running
+        statistics from what the steps accumulated.  Under DDP the ranks' accumulators are all-gathered in one collective and merged
+        in rank order on every rank, so every rank ends with bit-identical buffers."""
+        fds = self._fds_streaming("fds_epoch_finish")
+        self.model.fds_streaming = False
+        if self.reducer is not None and self.negs.active:        # (more than one rank, or the 1-rank rehearsal of MMDTI_FORCE_DDP=1)
+            from . import ops
+            from .parallel import gather_fds_accumulators
+            acc = fds.stream_state()
+            parts = gather_fds_accumulators(acc, self.negs.group)
+            acc.zero_()
+            for part in parts:
+                ops.fds_stream_merge(acc, part)
+        fds.update_last_epoch_stats(epoch)
+        fds.stream_finish(epoch)
