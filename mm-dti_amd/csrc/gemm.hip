@@ -399,6 +399,96 @@ __device__ __forceinline__ void epilogue_colsum(const GemmArgs& a, float* lds, c
   }
 }
 
+// =====================================================================================================================
+// Pieces the kernels below share, one definition each.  They are MACROS expanded in the kernel's own scope: whatever indexes an
+// accumulator array spells the indices out as literals (a rolled loop would index acc[][] dynamically and push it to scratch), and as
+// inline functions taking the array by reference the same bodies compiled to other register allocations.  The macros name the
+// kernel's locals: a, smem, tid, lane, wave, wr, wc, acc and, where noted, more.
+
+// What a workgroup of the two 128 x 128 kernels works on.  Declares the output tile's origin (m0, n0; tn: its column tile), the batch
+// indices (zo, zi) with the operand bases A, B of that batch, and the K-split ks with its K-tile range [kt0, kt1) of the kernel's
+// KTILES -- empty for the last splits of an uneven division (uniform per block: the kernel returns).  A macro so that KTILES is
+// evaluated here, after the operand bases: as a function's argument it is evaluated first and the compiler schedules the scalar
+// prologue differently (the kernels are held to one instruction stream: profiles/gemm_shared_isa.txt).
+#define GEMM128_WORK(KTILES)                                                                       \
+  const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;                          \
+  const int wg = xcd_chunk(blockIdx.x, tiles_n * tiles_m);   /* (n-tile, m-tile) index: tiles that share an A row panel on one XCD's L2 */ \
+  const int tm = wg / tiles_n, tn = wg - tm * tiles_n;                                             \
+  const int m0 = tm * BM, n0 = tn * BN;                                                            \
+  const int z = blockIdx.z;                                                                        \
+  const int zb = z / a.splitk, ks = z - zb * a.splitk;                                             \
+  const int zo = zb / a.batch_inner, zi = zb - zo * a.batch_inner;                                 \
+  const bf16_t* __restrict__ A = a.A + zo * a.sAo + zi * a.sAi;                                    \
+  const bf16_t* __restrict__ B = a.B + zo * a.sBo + zi * a.sBi;                                    \
+  const int ktiles = (KTILES);                                                                     \
+  const int per = (ktiles + a.splitk - 1) / a.splitk;                                              \
+  const int kt0 = ks * per, kt1 = min(ktiles, kt0 + per)
+
+// One 32-deep k-step (KK = 0, 1) of a wave's 64 x 64 sub-tile of a 128 x 128 tile: four A and four B fragments, 16 MFMAs.  Operands
+// swapped (B fragment first): the accumulator then holds C^T tiles, i.e. lane = output ROW (lane&15) and the 4 registers = 4
+// consecutive output COLUMNS (4*(lane>>4)+r) -- the epilogue stores 8/16 contiguous bytes per lane straight from registers, no LDS
+// transpose.  Declares fa0..fa3 / fb0..fb3 in the scope it is expanded in; names the kernel's TA, TB, F16, BCVT.
+#define MF(I, J) acc[I][J] = mfma32<F16>(fb##J, fa##I, acc[I][J])
+#define GEMM_KK(IMGA, IMGB, KK)                                                                    \
+  const bf16x8 fa0 = load_frag<TA>(IMGA, wr * 64 + 0, KK, lane), fa1 = load_frag<TA>(IMGA, wr * 64 + 16, KK, lane), \
+               fa2 = load_frag<TA>(IMGA, wr * 64 + 32, KK, lane), fa3 = load_frag<TA>(IMGA, wr * 64 + 48, KK, lane); \
+  const bf16x8 fb0 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 0, KK, lane)), fb1 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 16, KK, lane)), \
+               fb2 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 32, KK, lane)), fb3 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 48, KK, lane)); \
+  MF(0, 0); MF(0, 1); MF(0, 2); MF(0, 3); MF(1, 0); MF(1, 1); MF(1, 2); MF(1, 3);                  \
+  MF(2, 0); MF(2, 1); MF(2, 2); MF(2, 3); MF(3, 0); MF(3, 1); MF(3, 2); MF(3, 3)
+
+// Patch pass: atomic (split-K) and unaligned outputs leave through a private 16 x 68 fp32 LDS patch per wave (sW), one 16-row
+// accumulator tile row R at a time, so that a wave instruction covers 256 contiguous bytes of one C row.  ROW: the output row of the
+// patch's first row, COL: this lane's output column.  Names l15, g4, lead.
+#define EPI_PATCH_STG(R, J) *reinterpret_cast<f32x4*>(sW + l15 * LDC_W + (J) * 16 + g4) = acc[R][J]
+#define EPI_PATCH(R, ROW, COL, COFF)                                                                 \
+  {                                                                                                  \
+    EPI_PATCH_STG(R, 0); EPI_PATCH_STG(R, 1); EPI_PATCH_STG(R, 2); EPI_PATCH_STG(R, 3);              \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
+    __builtin_amdgcn_wave_barrier();                                                                 \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                           \
+    for (int rr = 0; rr < 16; ++rr) epi_elem(a, sW[rr * LDC_W + lane], (ROW) + rr, COL, lead, COFF); \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
+    __builtin_amdgcn_wave_barrier();                                                                 \
+  }
+
+// ---- epilogue of a 128 x 128 tile; ends the kernel.  Accumulator tile (I, J) of this wave: lane -> row m0 + wr*64 + I*16 + (lane&15),
+// registers -> columns n0 + wc*64 + J*16 + 4*(lane>>4) + {0..3}.  Vector path: bias / aux / residual arrive as 8- or 16-byte loads
+// and C leaves as one 8-byte (bf16) or 16-byte (fp32) store per lane, straight from registers.  Atomic (split-K) and unaligned
+// outputs go through the patch pass.  The K-loop ends on a barrier, so the staging images may overwrite the tiles.
+// Vector path: two half-tiles of 64 rows through a [64][132] fp32 LDS image (33,792 B -- no more than the K-loop's tiles): the
+// waves of row-half h park their accumulators (16-byte LDS writes), then all 256 threads run the fused epilogue on 8 contiguous
+// columns each: every wave instruction moves full 128-byte lines of C / residual / aux.
+// Names m0, n0, zo, zi, ks.
+#define EPI128_STG(I, J) *reinterpret_cast<f32x4*>(sC + ((I) * 16 + l15) * LDC_S + wc * 64 + (J) * 16 + g4) = acc[I][J]
+#define EPI128_STG_ROW(I) EPI128_STG(I, 0); EPI128_STG(I, 1); EPI128_STG(I, 2); EPI128_STG(I, 3)
+#define EPI128_HALF(H)                                                     \
+    if (wr == (H)) { EPI128_STG_ROW(0); EPI128_STG_ROW(1); EPI128_STG_ROW(2); EPI128_STG_ROW(3); } \
+    __syncthreads();                                                       \
+    for (int it = 0; it < 4; ++it) {                                       \
+      const int chunk = tid + it * 256;                                    \
+      const int rr = chunk >> 4, cc = (chunk & 15) * 8;                    \
+      const int row = m0 + (H) * 64 + rr, col = n0 + cc;                   \
+      if (row < a.M && col < a.N) epilogue_oct(a, sC + rr * LDC_S + cc, row, col, lead, coff, a.colsum ? cs : nullptr, ebias.b0, ebias.b1); \
+    }
+#define EPI128_PATCH(I) EPI_PATCH(I, m0 + wr * 64 + (I) * 16, n0 + wc * 64 + lane, coff)
+#define GEMM128_EPILOGUE()                                                                                         \
+  const long long coff = zo * a.sCo + zi * a.sCi + a.slab * ks;      /* (slab mode: every split owns a private fp32 copy of the output) */ \
+  const bool lead = (ks == 0);                                                                                     \
+  const int g4 = (lane >> 4) * 4, l15 = lane & 15;                                                                 \
+  if (a.c_dtype != MMDTI_DT_F32_ATOMIC && a.vec_ok) {                                                              \
+    float* sC = reinterpret_cast<float*>(smem);                                                                    \
+    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                                                        \
+    const EpiBias ebias = epi_bias(a, n0 + (tid & 15) * 8, lead);                                                  \
+    EPI128_HALF(0)                                                                                                 \
+    __syncthreads();                                                                                               \
+    EPI128_HALF(1)                                                                                                 \
+    if (a.colsum) epilogue_colsum(a, sC, cs, tid, n0);                                                             \
+    return;                                                                                                        \
+  }                                                                                                                \
+  float* sW = reinterpret_cast<float*>(smem) + wave * (16 * LDC_W);                                                \
+  EPI128_PATCH(0) EPI128_PATCH(1) EPI128_PATCH(2) EPI128_PATCH(3)
+
 // BCVT: B holds fp16 and is converted to bf16 fragment by fragment (frag_h2bf) -- the weight-gradient forms, A = dy (bf16), B = a
 // saved forward activation of the fp16 forward-operand mode
 template <bool TA, bool TB, bool FAST, bool F16 = false, bool BCVT = false>
@@ -410,27 +500,7 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-
-  // XCD-aware remap of the (n-tile, m-tile) index: consecutive hardware block ids go round-robin over the 8 XCDs,
-  // so give each XCD a contiguous chunk of the tile list (bijective form, cdna guide T1).
-  const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m;
-  const int orig = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-
-  const int z = blockIdx.z;
-  const int zb = z / a.splitk, ks = z - zb * a.splitk;
-  const int zo = zb / a.batch_inner, zi = zb - zo * a.batch_inner;
-  const bf16_t* __restrict__ A = a.A + zo * a.sAo + zi * a.sAi;
-  const bf16_t* __restrict__ B = a.B + zo * a.sBo + zi * a.sBi;
-
-  // K range of this split
-  const int ktiles = (a.K + BK - 1) / BK;
-  const int per = (ktiles + a.splitk - 1) / a.splitk;
-  const int kt0 = ks * per, kt1 = min(ktiles, kt0 + per);
+  GEMM128_WORK((a.K + BK - 1) / BK);
   if (kt0 >= kt1) return;  // empty split (uniform per block): nothing to contribute
 
   f32x4 acc[4][4] = {};
@@ -460,21 +530,6 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs a) {
   store_tile<TB>(rb, smem + TILE, tid);
   __syncthreads();
 
-  // (everything that indexes acc[][] is spelled out with literal indices: a loop the optimizer declines to unroll would
-  //  turn the accumulators into a scratch array)
-// operands swapped (B fragment first): the accumulator then holds C^T tiles, i.e. lane = output ROW (lane&15) and the 4
-  // registers = 4 consecutive output COLUMNS (4*(lane>>4)+r) -- the epilogue stores 8/16 contiguous bytes per lane
-  // straight from registers, no LDS transpose.
-#define MF(I, J) acc[I][J] = mfma32<F16>(fb##J, fa##I, acc[I][J])
-#define GEMM_KK(IMGA, IMGB, KK)                                                                    \
-  {                                                                                                \
-    const bf16x8 fa0 = load_frag<TA>(IMGA, wr * 64 + 0, KK, lane), fa1 = load_frag<TA>(IMGA, wr * 64 + 16, KK, lane), \
-                 fa2 = load_frag<TA>(IMGA, wr * 64 + 32, KK, lane), fa3 = load_frag<TA>(IMGA, wr * 64 + 48, KK, lane); \
-    const bf16x8 fb0 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 0, KK, lane)), fb1 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 16, KK, lane)), \
-                 fb2 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 32, KK, lane)), fb3 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 48, KK, lane)); \
-    MF(0, 0); MF(0, 1); MF(0, 2); MF(0, 3); MF(1, 0); MF(1, 1); MF(1, 2); MF(1, 3);                \
-    MF(2, 0); MF(2, 1); MF(2, 2); MF(2, 3); MF(3, 0); MF(3, 1); MF(3, 2); MF(3, 3);                \
-  }
   for (int kt = kt0; kt < kt1; ++kt) {
     const bool more = (kt + 1 < kt1);
     // (the explicit zero on the last step keeps the staging registers defined on every path; without it hipcc demotes
@@ -486,8 +541,8 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs a) {
       ra = Stage4{z, z, z, z};
       rb = ra;
     }
-    GEMM_KK(smem, smem + TILE, 0);
-    GEMM_KK(smem, smem + TILE, 1);
+    { GEMM_KK(smem, smem + TILE, 0); }
+    { GEMM_KK(smem, smem + TILE, 1); }
     __syncthreads();  // every wave has read tile kt
     if (more) {
       store_tile<TA>(ra, smem, tid);
@@ -495,62 +550,8 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs a) {
       __syncthreads();
     }
   }
-#undef GEMM_KK
-#undef MF
 #undef GEMM_LOAD
-
-  // ---- epilogue.  Accumulator tile (I, J) of this wave: lane -> row m0 + wr*64 + I*16 + (lane&15), registers -> columns
-  // n0 + wc*64 + J*16 + 4*(lane>>4) + {0..3}.  Vector path: bias / aux / residual arrive as 8- or 16-byte loads and C
-  // leaves as one 8-byte (bf16) or 16-byte (fp32) store per lane, straight from registers.  Atomic (split-K) and
-  // unaligned outputs go through a private 16 x 68 fp32 LDS patch per wave so that a wave instruction covers 256
-  // contiguous bytes of one C row.  Literal accumulator indices throughout (a rolled loop would index acc[][]
-  // dynamically and push it to scratch).  The K-loop ends on a barrier, so the patches may overwrite the tiles.
-  const long long coff = zo * a.sCo + zi * a.sCi + a.slab * ks;      // (slab mode: every split owns a private fp32 copy of the output)
-  const bool lead = (ks == 0);
-  const int g4 = (lane >> 4) * 4, l15 = lane & 15;
-  if (a.c_dtype != MMDTI_DT_F32_ATOMIC && a.vec_ok) {
-    // two half-tiles of 64 rows through a [64][132] fp32 LDS image (33,792 B -- no more than the K-loop's tiles): the
-    // waves of row-half h park their accumulators (16-byte LDS writes), then all 256 threads run the fused epilogue on
-    // 8 contiguous columns each: every wave instruction moves full 128-byte lines of C / residual / aux.
-    float* sC = reinterpret_cast<float*>(smem);
-#define STG_Q(I, J) *reinterpret_cast<f32x4*>(sC + ((I) * 16 + l15) * LDC_S + wc * 64 + (J) * 16 + g4) = acc[I][J]
-#define STG_R(I) STG_Q(I, 0); STG_Q(I, 1); STG_Q(I, 2); STG_Q(I, 3)
-#define EPI_HALF(H)                                                        \
-    if (wr == (H)) { STG_R(0); STG_R(1); STG_R(2); STG_R(3); }             \
-    __syncthreads();                                                       \
-    for (int it = 0; it < 4; ++it) {                                       \
-      const int chunk = tid + it * 256;                                    \
-      const int r = chunk >> 4, cc = (chunk & 15) * 8;                     \
-      const int row = m0 + (H) * 64 + r, col = n0 + cc;                    \
-      if (row < a.M && col < a.N) epilogue_oct(a, sC + r * LDC_S + cc, row, col, lead, coff, a.colsum ? cs : nullptr, ebias.b0, ebias.b1); \
-    }
-    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const EpiBias ebias = epi_bias(a, n0 + (tid & 15) * 8, lead);
-    EPI_HALF(0)
-    __syncthreads();
-    EPI_HALF(1)
-    if (a.colsum) epilogue_colsum(a, sC, cs, tid, n0);
-#undef EPI_HALF
-#undef STG_R
-#undef STG_Q
-    return;
-  }
-  float* sW = reinterpret_cast<float*>(smem) + wave * (16 * LDC_W);
-#define STG_T(I, J) *reinterpret_cast<f32x4*>(sW + l15 * LDC_W + (J) * 16 + g4) = acc[I][J]
-#define EPI_PASS(I)                                                                                  \
-  {                                                                                                  \
-    STG_T(I, 0); STG_T(I, 1); STG_T(I, 2); STG_T(I, 3);                                              \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
-    __builtin_amdgcn_wave_barrier();                                                                 \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                           \
-    for (int r = 0; r < 16; ++r)                                                                     \
-      epi_elem(a, sW[r * LDC_W + lane], m0 + wr * 64 + (I) * 16 + r, n0 + wc * 64 + lane, lead, coff); \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
-    __builtin_amdgcn_wave_barrier();                                                                 \
-  }
-  EPI_PASS(0) EPI_PASS(1) EPI_PASS(2) EPI_PASS(3)
-#undef EPI_PASS
-#undef STG_T
+  GEMM128_EPILOGUE()
 }
 
 // =====================================================================================================================
@@ -656,44 +657,22 @@ __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_k
   constexpr int TILE = BM * LDT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;
-  const int nwg = tiles_n * tiles_m;
-  const int orig = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int z = blockIdx.z;
-  const int zb = z / a.splitk, ks = z - zb * a.splitk;
-  const int zo = zb / a.batch_inner, zi = zb - zo * a.batch_inner;
-  const bf16_t* __restrict__ A = a.A + zo * a.sAo + zi * a.sAi;
-  const bf16_t* __restrict__ B = a.B + zo * a.sBo + zi * a.sBi;
-  const int ktiles = a.K / BK;
-  const int per = (ktiles + a.splitk - 1) / a.splitk;
-  const int kt0 = ks * per, kt1 = min(ktiles, kt0 + per);
+  GEMM128_WORK(a.K / BK);
   if (kt0 >= kt1) return;
   f32x4 acc[4][4] = {};
   const Off4 offA = glds_offsets<TA>(a.lda, m0, a.M, tid), offB = glds_offsets<TB>(a.ldb, n0, a.N, tid);
   const long long kstepA = TA ? (long long)BK * a.lda : BK, kstepB = TB ? (long long)BK * a.ldb : BK;
-#define MF(I, J) acc[I][J] = mfma32<F16>(fb##J, fa##I, acc[I][J])
-#define GEMM_KK(IMGA, IMGB, KK)                                                                    \
-  {                                                                                                \
-    const bf16x8 fa0 = load_frag<TA>(IMGA, wr * 64 + 0, KK, lane), fa1 = load_frag<TA>(IMGA, wr * 64 + 16, KK, lane), \
-                 fa2 = load_frag<TA>(IMGA, wr * 64 + 32, KK, lane), fa3 = load_frag<TA>(IMGA, wr * 64 + 48, KK, lane); \
-    const bf16x8 fb0 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 0, KK, lane)), fb1 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 16, KK, lane)), \
-                 fb2 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 32, KK, lane)), fb3 = frag_cvt<BCVT>(load_frag<TB>(IMGB, wc * 64 + 48, KK, lane)); \
-    MF(0, 0); MF(0, 1); MF(0, 2); MF(0, 3); MF(1, 0); MF(1, 1); MF(1, 2); MF(1, 3);                \
-    MF(2, 0); MF(2, 1); MF(2, 2); MF(2, 3); MF(3, 0); MF(3, 1); MF(3, 2); MF(3, 3);                \
-    if (TA && DBUF == 1 && do_rs) {                                                                \
-      rs0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa0, rs0, 0, 0, 0);                      \
-      rs1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa1, rs1, 0, 0, 0);                      \
-      rs2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa2, rs2, 0, 0, 0);                      \
-      rs3 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa3, rs3, 0, 0, 0);                      \
-    }                                                                                              \
-  }
   const bool do_rs = TA && DBUF == 1 && a.arowsum != nullptr && tn == 0 && wc == 0;   // (double-buffered variant only: register room)
   const bf16x8 ones = ones_frag();
   f32x4 rs0 = {0.f, 0.f, 0.f, 0.f}, rs1 = rs0, rs2 = rs0, rs3 = rs0;
+  // bias gradient: the row sums of the A fragments a GEMM_KK has just multiplied (follows it in the same scope)
+#define GEMM_RS()                                                                                  \
+  if (do_rs) {                                                                                     \
+    rs0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa0, rs0, 0, 0, 0);                        \
+    rs1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa1, rs1, 0, 0, 0);                        \
+    rs2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa2, rs2, 0, 0, 0);                        \
+    rs3 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fa3, rs3, 0, 0, 0);                        \
+  }
   // LDS byte address of this wave's 1 KB slot of the A image of stage 0 (the B image 16 KB further, a stage's pair 32 KB)
   const int lds_w = lds_addr_uniform(smem) + __builtin_amdgcn_readfirstlane(wave) * 1024;
   constexpr int TB2 = TILE * 2;
@@ -707,8 +686,8 @@ __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_k
       pb += kstepB * 2;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the DMA is issued from inline assembly: the compiler does not count it)
       __syncthreads();   // the DMA'd tile is visible to every wave
-      GEMM_KK(smem, smem + TILE, 0);
-      GEMM_KK(smem, smem + TILE, 1);
+      { GEMM_KK(smem, smem + TILE, 0); }
+      { GEMM_KK(smem, smem + TILE, 1); }
       __syncthreads();   // every wave has read the tile before the next fetch overwrites it
     }
   } else if (DBUF == 2) {
@@ -733,8 +712,8 @@ __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_k
       DEEP_ISSUE(t + 3);              // -> the buffer of stage t-1
       __builtin_amdgcn_sched_barrier(0);
       const bf16_t* img = smem + (t % DEEP_STAGES) * (2 * TILE);
-      GEMM_KK(img, img + TILE, 0);
-      GEMM_KK(img, img + TILE, 1);
+      { GEMM_KK(img, img + TILE, 0); }
+      { GEMM_KK(img, img + TILE, 1); }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -757,60 +736,17 @@ __global__ __launch_bounds__(256, DBUF == 2 ? 1 : DBUF ? 2 : 4) void gemm_glds_k
       }
       __builtin_amdgcn_sched_barrier(0);
       const bf16_t* img = smem + cur * (2 * TILE);
-      GEMM_KK(img, img + TILE, 0);
-      GEMM_KK(img, img + TILE, 1);
+      { GEMM_KK(img, img + TILE, 0); GEMM_RS() }
+      { GEMM_KK(img, img + TILE, 1); GEMM_RS() }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the DMA of tile kt+1 has landed, the reads of tile kt are retired
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       cur ^= 1;
     }
   }
-#undef GEMM_KK
-#undef MF
+#undef GEMM_RS
   if (TA && DBUF == 1 && do_rs) arowsum_flush(a, rs0, rs1, rs2, rs3, m0 + wr * 64, lane);
-  const long long coff = zo * a.sCo + zi * a.sCi + a.slab * ks;      // (slab mode: every split owns a private fp32 copy of the output)
-  const bool lead = (ks == 0);
-  const int g4 = (lane >> 4) * 4, l15 = lane & 15;
-  if (a.c_dtype != MMDTI_DT_F32_ATOMIC && a.vec_ok) {
-    float* sC = reinterpret_cast<float*>(smem);
-#define STG_Q(I, J) *reinterpret_cast<f32x4*>(sC + ((I) * 16 + l15) * LDC_S + wc * 64 + (J) * 16 + g4) = acc[I][J]
-#define STG_R(I) STG_Q(I, 0); STG_Q(I, 1); STG_Q(I, 2); STG_Q(I, 3)
-#define EPI_HALF(H)                                                        \
-    if (wr == (H)) { STG_R(0); STG_R(1); STG_R(2); STG_R(3); }             \
-    __syncthreads();                                                       \
-    for (int it = 0; it < 4; ++it) {                                       \
-      const int chunk = tid + it * 256;                                    \
-      const int rr = chunk >> 4, cc = (chunk & 15) * 8;                    \
-      const int row = m0 + (H) * 64 + rr, col = n0 + cc;                   \
-      if (row < a.M && col < a.N) epilogue_oct(a, sC + rr * LDC_S + cc, row, col, lead, coff, a.colsum ? cs : nullptr, ebias.b0, ebias.b1); \
-    }
-    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const EpiBias ebias = epi_bias(a, n0 + (tid & 15) * 8, lead);
-    EPI_HALF(0)
-    __syncthreads();
-    EPI_HALF(1)
-    if (a.colsum) epilogue_colsum(a, sC, cs, tid, n0);
-#undef EPI_HALF
-#undef STG_R
-#undef STG_Q
-    return;
-  }
-  float* sW = reinterpret_cast<float*>(smem) + wave * (16 * LDC_W);
-#define STG_T(I, J) *reinterpret_cast<f32x4*>(sW + l15 * LDC_W + (J) * 16 + g4) = acc[I][J]
-#define EPI_PASS(I)                                                                                  \
-  {                                                                                                  \
-    STG_T(I, 0); STG_T(I, 1); STG_T(I, 2); STG_T(I, 3);                                              \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
-    __builtin_amdgcn_wave_barrier();                                                                 \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                           \
-    for (int rr = 0; rr < 16; ++rr)                                                                  \
-      epi_elem(a, sW[rr * LDC_W + lane], m0 + wr * 64 + (I) * 16 + rr, n0 + wc * 64 + lane, lead, coff); \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
-    __builtin_amdgcn_wave_barrier();                                                                 \
-  }
-  EPI_PASS(0) EPI_PASS(1) EPI_PASS(2) EPI_PASS(3)
-#undef EPI_PASS
-#undef STG_T
+  GEMM128_EPILOGUE()
 }
 
 // =====================================================================================================================
@@ -856,16 +792,34 @@ __device__ __forceinline__ bf16x8 small_frag(const bf16_t* img, int row0, int kk
   }
 }
 
+// One K-tile of a wave's 32 x 32 sub-tile of a 64 x 64 tile (both 64 x 64 kernels): eight fragment reads, eight MFMAs, same operand
+// order as GEMM_KK.  Declares fa<i><kk> / fb<j><kk> (16-row tile i, 16-column tile j, k half kk) in the scope it is expanded in.
+#define SMALL_KTILE(TA, TB, F16, BCVT, IMGA, IMGB)                                                                       \
+  const bf16x8 fa00 = small_frag<TA>(IMGA, wr * 32, 0, lane), fa10 = small_frag<TA>(IMGA, wr * 32 + 16, 0, lane);        \
+  const bf16x8 fb00 = frag_cvt<BCVT>(small_frag<TB>(IMGB, wc * 32, 0, lane)), fb10 = frag_cvt<BCVT>(small_frag<TB>(IMGB, wc * 32 + 16, 0, lane)); \
+  const bf16x8 fa01 = small_frag<TA>(IMGA, wr * 32, 1, lane), fa11 = small_frag<TA>(IMGA, wr * 32 + 16, 1, lane);        \
+  const bf16x8 fb01 = frag_cvt<BCVT>(small_frag<TB>(IMGB, wc * 32, 1, lane)), fb11 = frag_cvt<BCVT>(small_frag<TB>(IMGB, wc * 32 + 16, 1, lane)); \
+  acc[0][0] = mfma32<F16>(fb00, fa00, acc[0][0]); acc[0][1] = mfma32<F16>(fb10, fa00, acc[0][1]);                        \
+  acc[1][0] = mfma32<F16>(fb00, fa10, acc[1][0]); acc[1][1] = mfma32<F16>(fb10, fa10, acc[1][1]);                        \
+  acc[0][0] = mfma32<F16>(fb01, fa01, acc[0][0]); acc[0][1] = mfma32<F16>(fb11, fa01, acc[0][1]);                        \
+  acc[1][0] = mfma32<F16>(fb01, fa11, acc[1][0]); acc[1][1] = mfma32<F16>(fb11, fa11, acc[1][1])
+// the four waves park acc[2][2] in the [64][68] fp32 image SC (the one place that indexes an accumulator array from a loop: two
+// by two, always unrolled; spelled out the 64 x 64 kernels get another register assignment)
+#define SMALL_PARK(SC)                                                                             \
+  {                                                                                                \
+    const int g4 = (lane >> 4) * 4, l15 = lane & 15;                                               \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                  \
+      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                \
+        *reinterpret_cast<f32x4*>(SC + (wr * 32 + i * 16 + l15) * LDC_SM + wc * 32 + j * 16 + g4) = acc[i][j]; \
+  }
+
 template <bool TB, bool F16>
 __global__ __launch_bounds__(256, 2) void gemm_small_kernel(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int tiles_n = (a.N + SBN - 1) / SBN, tiles_m = (a.M + SBM - 1) / SBM;
-  const int nwg = tiles_n * tiles_m;
-  const int orig = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  const int wg = xcd_chunk(blockIdx.x, tiles_n * tiles_m);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int m0 = tm * SBM, n0 = tn * SBN;
   const bf16_t* __restrict__ A = a.A;
@@ -897,14 +851,7 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(GemmArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     const bf16_t* imgA = smem + (t % SM_STAGES) * (2 * SM_TILE);
     const bf16_t* imgB = imgA + SM_TILE;
-    const bf16x8 fa00 = small_frag<false>(imgA, wr * 32, 0, lane), fa10 = small_frag<false>(imgA, wr * 32 + 16, 0, lane);
-    const bf16x8 fb00 = small_frag<TB>(imgB, wc * 32, 0, lane), fb10 = small_frag<TB>(imgB, wc * 32 + 16, 0, lane);
-    const bf16x8 fa01 = small_frag<false>(imgA, wr * 32, 1, lane), fa11 = small_frag<false>(imgA, wr * 32 + 16, 1, lane);
-    const bf16x8 fb01 = small_frag<TB>(imgB, wc * 32, 1, lane), fb11 = small_frag<TB>(imgB, wc * 32 + 16, 1, lane);
-    acc[0][0] = mfma32<F16>(fb00, fa00, acc[0][0]); acc[0][1] = mfma32<F16>(fb10, fa00, acc[0][1]);
-    acc[1][0] = mfma32<F16>(fb00, fa10, acc[1][0]); acc[1][1] = mfma32<F16>(fb10, fa10, acc[1][1]);
-    acc[0][0] = mfma32<F16>(fb01, fa01, acc[0][0]); acc[0][1] = mfma32<F16>(fb11, fa01, acc[0][1]);
-    acc[1][0] = mfma32<F16>(fb01, fa11, acc[1][0]); acc[1][1] = mfma32<F16>(fb11, fa11, acc[1][1]);
+    SMALL_KTILE(false, TB, F16, false, imgA, imgB);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -912,12 +859,7 @@ __global__ __launch_bounds__(256, 2) void gemm_small_kernel(GemmArgs a) {
   __builtin_amdgcn_s_barrier();     // no DMA in flight, no read outstanding: LDS is free for the epilogue
 #undef SM_ISSUE
   float* sC = reinterpret_cast<float*>(smem);
-  const int g4 = (lane >> 4) * 4, l15 = lane & 15;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      *reinterpret_cast<f32x4*>(sC + (wr * 32 + i * 16 + l15) * LDC_SM + wc * 32 + j * 16 + g4) = acc[i][j];
+  SMALL_PARK(sC)
   const EpiBias ebias = epi_bias(a, n0 + (tid & 7) * 8, true);
   __syncthreads();
 #pragma unroll
@@ -945,10 +887,7 @@ __global__ __launch_bounds__(256, 4) void gemm_glds_tall_kernel(GemmArgs a, int 
   bf16_t* imgB = smem + BMT * LDT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + mstep - 1) / mstep;
-  const int nwg = tiles_n * tiles_m;
-  const int orig = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  const int wg = xcd_chunk(blockIdx.x, tiles_n * tiles_m);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int m0 = tm * mstep, n0 = tn * BN;
   const bf16_t* __restrict__ A = a.A;
@@ -1350,28 +1289,9 @@ __device__ __forceinline__ void big_tile(const GemmArgs& a, int tm, int tn, int 
   }
   // atomic (split-K) / unaligned outputs: a private 16 x 68 fp32 patch per wave, one row tile at a time
   float* sW = reinterpret_cast<float*>(smem) + wave * (16 * LDC_W);
-#define BSTG_T(R, C) *reinterpret_cast<f32x4*>(sW + l15 * LDC_W + (C) * 16 + g4) = acc[R][C]
-#define BIG_EPI(R)                                                                                   \
-  {                                                                                                  \
-    BSTG_T(R, 0); BSTG_T(R, 1); BSTG_T(R, 2); BSTG_T(R, 3);                                          \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
-    __builtin_amdgcn_wave_barrier();                                                                 \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                                           \
-    for (int rr = 0; rr < 16; ++rr)                                                                  \
-      epi_elem(a, sW[rr * LDC_W + lane], m0 + ((R) >> 2) * 128 + wr * 64 + ((((R) & 3) + wc) & 3) * 16 + rr, n0 + (lane >> 5) * 128 + wc * 32 + (lane & 31), lead, 0); \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                           \
-    __builtin_amdgcn_wave_barrier();                                                                 \
-  }
+#define BIG_EPI(R) EPI_PATCH(R, m0 + ((R) >> 2) * 128 + wr * 64 + ((((R) & 3) + wc) & 3) * 16, n0 + (lane >> 5) * 128 + wc * 32 + (lane & 31), 0)
   BIG_EPI(0) BIG_EPI(1) BIG_EPI(2) BIG_EPI(3) BIG_EPI(4) BIG_EPI(5) BIG_EPI(6) BIG_EPI(7)
 #undef BIG_EPI
-#undef BSTG_T
-}
-
-// XCD-aware bijective remap of a linear workgroup id (cdna guide T1): consecutive hardware ids go round-robin over the
-// 8 XCDs, so each XCD gets a contiguous chunk of the tile list
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
 
 // TAIL: K % 64 != 0 (both operands k-major) -- a kernel of its own, so that the common case carries neither its tests nor its registers
@@ -1379,7 +1299,7 @@ template <bool TA, bool TB, bool F16 = false, bool BCVT = false, bool TAIL = fal
 __global__ __launch_bounds__(512, 1) void gemm_big_kernel(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
   const int tiles_n = (a.N + BBN - 1) / BBN, tiles_m = (a.M + BBM - 1) / BBM;
-  const int wg = xcd_remap(blockIdx.x, tiles_n * tiles_m);
+  const int wg = xcd_chunk(blockIdx.x, tiles_n * tiles_m);
   const int tm = wg / tiles_n;
   big_tile<TA, TB, F16, BCVT, TAIL>(a, tm, wg - tm * tiles_n, blockIdx.z, smem);
 }
@@ -1408,7 +1328,7 @@ struct GroupArgs {
 template <bool BCVT, bool TAIL>
 __global__ __launch_bounds__(512, 1) void gemm_big_grouped_kernel(GroupArgs g) {
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-  const int wg = xcd_remap(blockIdx.x, g.ntiles);
+  const int wg = xcd_chunk(blockIdx.x, g.ntiles);
   int pi = 0;
 #pragma unroll
   for (int i = 1; i < GROUP_MAX; ++i) pi += (i < g.nprob && wg >= g.p[i].tile0) ? 1 : 0;
@@ -1441,7 +1361,7 @@ __global__ __launch_bounds__(256, STAGES == 3 ? 3 : 2) void gemm_small_dw_groupe
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const int wg = xcd_remap(blockIdx.x, g.ntiles);
+  const int wg = xcd_chunk(blockIdx.x, g.ntiles);
   int pi = 0;
 #pragma unroll
   for (int i = 1; i < GROUP_MAX; ++i) pi += (i < g.nprob && wg >= g.p[i].tile0) ? 1 : 0;
@@ -1493,14 +1413,7 @@ __global__ __launch_bounds__(256, STAGES == 3 ? 3 : 2) void gemm_small_dw_groupe
     __builtin_amdgcn_sched_barrier(0);
     const bf16_t* imgA = smem + (t2 % STAGES) * (2 * SM_TILE);
     const bf16_t* imgB = imgA + SM_TILE;
-    const bf16x8 fa00 = small_frag<true>(imgA, wr * 32, 0, lane), fa10 = small_frag<true>(imgA, wr * 32 + 16, 0, lane);
-    const bf16x8 fb00 = frag_cvt<BCVT>(small_frag<true>(imgB, wc * 32, 0, lane)), fb10 = frag_cvt<BCVT>(small_frag<true>(imgB, wc * 32 + 16, 0, lane));
-    const bf16x8 fa01 = small_frag<true>(imgA, wr * 32, 1, lane), fa11 = small_frag<true>(imgA, wr * 32 + 16, 1, lane);
-    const bf16x8 fb01 = frag_cvt<BCVT>(small_frag<true>(imgB, wc * 32, 1, lane)), fb11 = frag_cvt<BCVT>(small_frag<true>(imgB, wc * 32 + 16, 1, lane));
-    acc[0][0] = mfma32<false>(fb00, fa00, acc[0][0]); acc[0][1] = mfma32<false>(fb10, fa00, acc[0][1]);
-    acc[1][0] = mfma32<false>(fb00, fa10, acc[1][0]); acc[1][1] = mfma32<false>(fb10, fa10, acc[1][1]);
-    acc[0][0] = mfma32<false>(fb01, fa01, acc[0][0]); acc[0][1] = mfma32<false>(fb11, fa01, acc[0][1]);
-    acc[1][0] = mfma32<false>(fb01, fa11, acc[1][0]); acc[1][1] = mfma32<false>(fb11, fa11, acc[1][1]);
+    SMALL_KTILE(true, true, false, BCVT, imgA, imgB);
     if (do_rs) {
       rs0 = mfma32<false>(ones, fa00, rs0); rs1 = mfma32<false>(ones, fa10, rs1);
       rs0 = mfma32<false>(ones, fa01, rs0); rs1 = mfma32<false>(ones, fa11, rs1);
@@ -1516,12 +1429,7 @@ __global__ __launch_bounds__(256, STAGES == 3 ? 3 : 2) void gemm_small_dw_groupe
     atomicAdd(pr.arowsum + m0 + wr * 32 + 16 + lane, rs1[0]);
   }
   float* sC = reinterpret_cast<float*>(smem);
-  const int g4 = (lane >> 4) * 4, l15 = lane & 15;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      *reinterpret_cast<f32x4*>(sC + (wr * 32 + i * 16 + l15) * LDC_SM + wc * 32 + j * 16 + g4) = acc[i][j];
+  SMALL_PARK(sC)
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < 4; ++it) {      // 64 rows x 16 quads: dW += tile (this workgroup owns it)
