@@ -63,6 +63,17 @@ typedef void* mmdti_stream_t;
 
 const char* mmdti_last_error(void);
 int mmdti_abi_version(void);
+/* The kernel tables the launch plans index (mmdti_attn_plan, mmdti_gbf_plan, mmdti_pair_attn_plan): every instance a family can launch has one row, and a
+ * plan names a kernel by its row.  size_out receives the number of rows; the name of row `index` is the kernel's template-id as the
+ * source spells it ("attn_fwd_kernel<16, 10>"), null for an unknown family or a row past the end.  No GPU needed. */
+#define MMDTI_PLAN_ATTN 0
+#define MMDTI_PLAN_GBF 1
+#define MMDTI_PLAN_PAIR_ATTN_FWD 2       /* pair_attn_fwd_mfma_kernel */
+#define MMDTI_PLAN_PAIR_ATTN_BWD 3       /* pair_attn_bwd_mfma_kernel */
+#define MMDTI_PLAN_PAIR_ATTN_FWD_ELEM 4  /* pair_attn_fwd_kernel: the per-element form (N > 272, or unaligned rows / planes) */
+#define MMDTI_PLAN_PAIR_ATTN_BWD_ELEM 5  /* pair_attn_bwd_kernel */
+int mmdti_plan_table_size(int family, int* size_out);
+const char* mmdti_plan_kernel_name(int family, int index);
 /* Run-time tuning switches (A/B measurements inside one process; defaults come from the environment variable of the same
  * upper-cased name, e.g. MMDTI_GEMM_BIG).  Known names: "gemm_big" (0 off, 1 where the shape fills the chip, 2 every
  * eligible shape); "gemm_dbg" (measurement only: 1 = the large-tile GEMM skips its epilogue); "gemm_small" (1: 64 x 64 tiles for launches of
@@ -449,6 +460,22 @@ int mmdti_gbf_bias_bwd_full(mmdti_stream_t stream, const void* g, const float* d
                             long long workspace_bytes);
 /* bytes of workspace for mmdti_gbf_bias_bwd_full with E edge types (a value, not a status code) */
 int mmdti_gbf_bias_bwd_full_workspace(int E);
+/* What a pair-bias entry point would launch, without launching: the same validation, message for message, and the same plan
+ * (csrc/gbf_plan.h) -- it runs on a machine without a GPU.  entry: 0 mmdti_gbf_features_fwd, 1 mmdti_gbf_features_bwd, 2
+ * mmdti_gbf_bias_fwd, 3 mmdti_gbf_bias_bwd, 4 mmdti_gbf_bias_bwd_full; with `records` non-null, 2 and 4 are the _coords forms.
+ * deterministic: the mode the launch would find (mmdti_set_deterministic); the query does not read the process flag.  Pointers are
+ * tested for null and alignment only, and stand for groups: `operands` for every operand that needs no 16-byte alignment (null: one of
+ * them is null), `aligned` for every operand that does (feat / dfeat; w1, w2, out; u, do, du), `saved` for the forward's three saved
+ * intermediates, `records`, `tile_prefix`, `row_blocks`, `workspace` for themselves.  P is read by entries 0 and 1; B, N, ld, F, H, V,
+ * pad_idx, edge_bytes and flags by the others.  The stream's reduction workspace, which entry 1 needs in the deterministic mode, is not
+ * looked up.  plan_out receives 10 long long: the kernel's row in the MMDTI_PLAN_GBF table (mmdti_plan_kernel_name), grid x, workgroup
+ * size, dynamic LDS bytes, the MaxDynamicSharedMemorySize the kernel is raised to before its first launch (0: it never asks for more
+ * than 64 KiB), tpm (16-pair tiles per molecule; 0 for entries 0 and 1), ntiles (B * tpm; 16-pair blocks for entries 0 and 1), ltab
+ * (forward: per-edge-type tables in LDS), slab (1: partial sums go to per-workgroup slabs and a fixed-order pass adds them; 0: fp32
+ * atomics), and the grid of the gbf_slab_reduce_kernel launch that follows entry 4 with slabs (else 0). */
+int mmdti_gbf_plan(int entry, int deterministic, const void* operands, const void* aligned, const void* saved, const void* records,
+                   const int* tile_prefix, const int* row_blocks, const void* workspace, long long workspace_bytes, long long P, int B,
+                   int N, int ld, int K, int F, int H, int E, int V, int pad_idx, int edge_bytes, int flags, long long* plan_out);
 /* ---- Pair inputs from coordinates.  The two [B,N,N] planes above are functions of the atoms: the reference builds them per
  * molecule as distance_matrix(coord, coord) and tok_i * len(dictionary) + tok_j (data/conformer.py:204-212), right-pads them with 0.0
  * and the pad index, and mm_model.py:553-556 consumes them.  These entry points take the atoms instead: one 16-byte record per atom,
@@ -531,6 +558,17 @@ int mmdti_pair_attn_bwd(mmdti_stream_t stream, const void* qkv_bf16, const void*
                         int qkv_f16 /* != 0 (tiled layouts): qkv holds the fp16 q | k | v the forward multiplied; the kernel rounds them to
                         bf16 (to nearest even: the values mmdti_cast_f16_bf16 would write) on their way into LDS -- the backward's
                         products keep bf16 operands, whose range activation gradients need.  do_bf16 / dqkv_bf16 stay bf16 */);
+/* What mmdti_pair_attn_fwd (backward 0) or mmdti_pair_attn_bwd (1) would launch for the same arguments, without launching: the same
+ * validation, message for message, and the same plan (csrc/pair_attn_plan.h).  Pointers are tested for null and alignment only -- it
+ * runs on a machine without a GPU.  For the forward, s stands for bias_in, g for s_out and o_or_do_bf16 for o_bf16; dqkv_bf16 and
+ * deterministic are read for the backward only, drop_p for the forward only.  deterministic: the mode the launch would find
+ * (mmdti_set_deterministic); the query does not read the process flag.  plan_out receives 6 ints: the family (0 forward MFMA, 1
+ * backward MFMA, 2 forward per-element, 3 backward per-element: MMDTI_PLAN_PAIR_ATTN_FWD + family is its table for
+ * mmdti_plan_kernel_name), the kernel's row in that table, grid x, workgroup size, nqb (query blocks of 16; 0 for the per-element
+ * kernels) and NW (the backward MFMA kernel's wave count; else 0). */
+int mmdti_pair_attn_plan(int backward, int deterministic, const void* qkv_bf16, const void* s, const void* o_or_do_bf16, const void* g,
+                         const void* dqkv_bf16, int B, int N, int H, int ld, float drop_p, int layout, const int* key_tiles,
+                         const int* row_off, int qkv_f16, int* plan_out);
 
 /* ---- Row softmax over materialised scores (HF eager_attention_forward :158-183; BertCoAttention
  * mm_module.py:497-514) ------------------------------------------------------------------------
@@ -585,6 +623,19 @@ int mmdti_attn_long_bwd(mmdti_stream_t stream, const void* q_bf16, const void* k
                         void* dk_bf16, void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo,
                         int lddq, int lddk, float scale, float drop_p, unsigned long long seed, unsigned int site,
                         const int* q_off, const int* k_off, const int* k_cnt, int q_rows);
+
+/* What mmdti_attn_fwd / _bwd (long_entry 0) or mmdti_attn_long_fwd / _bwd (1) would launch for the same arguments, without
+ * launching: the same validation, message for message, and the same plan (csrc/attn_plan.h).  Pointers are tested for null and
+ * alignment only (pass any address with the alignment in question) -- it runs on a machine without a GPU.  ctx_or_dctx_bf16 is the
+ * forward's ctx_bf16 or the backward's dctx_bf16; drow, dq, dk, dv, lddq and lddk are read for the backward only.  The fused attention
+ * has no atomics, so the deterministic mode does not enter.  plan_out receives 13 ints: nt (16-key tiles of a score row: 10, 16, 24 or
+ * 32), lqp (queries rounded up to 32), the number of launches (1 forward; 2 backward: dQ, then dK/dV), and per launch -- the second
+ * is zero for the forward -- the kernel's row in the MMDTI_PLAN_ATTN table (mmdti_plan_kernel_name), grid x, workgroup size, dynamic
+ * LDS bytes, and the MaxDynamicSharedMemorySize the kernel is raised to before its first launch in this size class. */
+int mmdti_attn_plan(int backward, int long_entry, const void* q_bf16, const void* k_bf16, const void* v_bf16, const float* key_add,
+                    const void* ctx_or_dctx_bf16, const float* stats, const float* drow, const void* dq_bf16, const void* dk_bf16,
+                    const void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo, int lddq, int lddk,
+                    float drop_p, const int* q_off, const int* k_off, const int* k_cnt, int q_rows, int* plan_out);
 
 /* ---- GELU on bf16 (kept for un-fused call sites) ------------------------------------------- */
 int mmdti_gelu_fwd_bf16(mmdti_stream_t stream, const void* u_bf16, void* y_bf16, long long n);

@@ -23,6 +23,7 @@
 // (max, 1/sum) in fp32, and the row term sum_j dP'_ij p_ij exactly in registers (no O.dO shortcut).
 // Dropout: per-element hash of (seed, site, head, query, key) -- the same function in all three kernels.
 #include "common.h"
+#include "attn_plan.h"
 
 namespace mmdti {
 
@@ -159,14 +160,12 @@ __device__ __forceinline__ int attn_far_rows(int r) {
 //  -- except head_dim 16 with 32 tiles, which the compiler cannot hold in 256: that one instantiation runs 4 waves per workgroup,
 //  one per SIMD, and keeps its overflow in the accumulation registers instead of scratch)
 template <int HD, int NT>
-constexpr int attn_fwd_threads() { return HD == 16 && NT == 32 ? 256 : 512; }
-template <int HD, int NT>
 constexpr int attn_fwd_min_waves() {      // per SIMD: what the register budget is sized for
   if (NT <= 16) return HD == 16 ? 2 : 4;
   return HD == 16 && NT == 32 ? 1 : 2;
 }
 template <int HD, int NT>
-__global__ __launch_bounds__((attn_fwd_threads<HD, NT>()), (attn_fwd_min_waves<HD, NT>())) void attn_fwd_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+__global__ __launch_bounds__((attn_fwd_threads(HD, NT)), (attn_fwd_min_waves<HD, NT>())) void attn_fwd_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                        const bf16_t* __restrict__ v, const float* __restrict__ key_add,
                                                        bf16_t* __restrict__ ctx, float* __restrict__ stats, int heads, int Lq,
                                                        int Lk, int ldq, int ldk, int ldo, float scale, uint32_t thresh16,
@@ -541,27 +540,25 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_kv_kernel(const bf16_t* __res
 }
 
 static inline uint32_t thresh16_of(float p) { return dropout_thresh8(p); }
-// 16-key tiles of a score row (the forward / dQ kernels' NT; times 16, the key stride of the dropout counter).  Up to 256 keys: the
-// two sizes of mmdti_attn_*; 24 and 32 tiles are reached through mmdti_attn_long_* only.
-static inline int attn_nt(int Lk) { return Lk <= 160 ? 10 : Lk <= 256 ? 16 : Lk <= 384 ? 24 : 32; }
-// largest dynamic LDS any launch of mmdti_attn_* asks for: 2 x 256 rows x (64+16) bf16 + 3 x 256 floats
-constexpr size_t smem_max = (size_t)2 * 256 * 80 * 2 + 4 * 256 * 4;
-// ... and of mmdti_attn_long_*: the dK/dV kernel's Q + dO images of 512 rows x (64+8) bf16 + four 512-float row vectors = 155 648 B
-// (forward / dQ: K + V images + 512 floats of key mask = 149 504 B) of the CU's 160 KiB
-constexpr size_t smem_max_long = (size_t)2 * 512 * 72 * 2 + 4 * 512 * 4;
-constexpr int ATTN_MAX_LEN = 256, ATTN_LONG_MAX_LEN = 512;
 
-// (the attribute is raised per kernel, once per size: a process that never calls the long entry points sets what it always set)
-// (*have is a plain per-instantiation static, as the flag before it: one value for all devices, no synchronisation -- launches come from
-//  one host thread per process here; a second thread could read it before hipFuncSetAttribute has returned)
-template <typename K>
-static int attn_set_smem(K kern, size_t smem, size_t* have) {
-  if (*have >= smem) return MMDTI_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-    set_error("attn: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", smem);
-    return MMDTI_ERR_LAUNCH;
-  }
-  *have = smem;
+// every instance, at the row attn_key gives it (attn_plan.h)
+static KernelRow g_attn_kernels[ATTN_KERNELS] = {
+#define ATTN_ROWS(KIND, KERN, HD) \
+  KROW(attn_key(KIND, HD, 10), KERN<HD, 10>), KROW(attn_key(KIND, HD, 16), KERN<HD, 16>), KROW(attn_key(KIND, HD, 24), KERN<HD, 24>), \
+  KROW(attn_key(KIND, HD, 32), KERN<HD, 32>)
+    ATTN_ROWS(ATTN_FWD, attn_fwd_kernel, 16),     ATTN_ROWS(ATTN_FWD, attn_fwd_kernel, 32),     ATTN_ROWS(ATTN_FWD, attn_fwd_kernel, 64),
+    ATTN_ROWS(ATTN_BWD_Q, attn_bwd_q_kernel, 16), ATTN_ROWS(ATTN_BWD_Q, attn_bwd_q_kernel, 32), ATTN_ROWS(ATTN_BWD_Q, attn_bwd_q_kernel, 64),
+#undef ATTN_ROWS
+    KROW(attn_key(ATTN_BWD_KV, 16, 0), attn_bwd_kv_kernel<16>), KROW(attn_key(ATTN_BWD_KV, 32, 0), attn_bwd_kv_kernel<32>),
+    KROW(attn_key(ATTN_BWD_KV, 64, 0), attn_bwd_kv_kernel<64>),
+};
+const KernelRow* attn_kernel_table(int* n) { *n = ATTN_KERNELS; return g_attn_kernels; }
+
+// (the LDS opt-in is raised per kernel, once per size: a process that never calls the long entry points sets what it always set)
+static int attn_launch(const AttnLaunch& l, void** args, mmdti_stream_t stream) {
+  KernelRow& row = g_attn_kernels[l.key];
+  if (int e = ensure_dynamic_lds(row.fn, (size_t)l.lds_cap, &row.lds_have, "attn")) return e;
+  (void)hipLaunchKernel(row.fn, dim3(l.grid), dim3(l.block), args, (size_t)l.lds, (hipStream_t)stream);
   return MMDTI_OK;
 }
 
@@ -583,36 +580,51 @@ static int attn_check_varlen(const char* name, const float* key_add, const int* 
   return MMDTI_OK;
 }
 
+// What the launches and mmdti_attn_plan share: validate, plan.  Pointers are tested for null and alignment only.
 // One body for mmdti_attn_fwd (max_len 256) and mmdti_attn_long_fwd (512): up to 256 keys both launch the same instantiation with
 // the same arguments; the 24- and 32-tile instantiations exist for the long entry point only.
+static int attn_fwd_prepare(AttnPlan& plan, const char* name, int max_len, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                            const float* key_add, const void* ctx_bf16, const float* stats, int B, int heads, int Lq, int Lk, int head_dim,
+                            int ldq, int ldk, int ldo, float drop_p, const int* q_off, const int* k_off, const int* k_cnt, int q_rows) {
+  if (int e = attn_check(name, max_len, q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
+  if (int e = attn_check_varlen(name, key_add, q_off, k_off, k_cnt, q_rows)) return e;
+  MMDTI_REQUIRE(ctx_bf16 && stats && ldo >= heads * head_dim && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(ctx_bf16) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(stats) & 7) == 0, "%s: bad output arguments", name);
+  plan = attn_fwd_plan(B, heads, Lq, Lk, head_dim);
+  return MMDTI_OK;
+}
+
+static int attn_bwd_prepare(AttnPlan& plan, const char* name, int max_len, const void* q_bf16, const void* k_bf16, const void* v_bf16,
+                            const float* key_add, const void* dctx_bf16, const float* stats, const float* drow, const void* dq_bf16,
+                            const void* dk_bf16, const void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo,
+                            int lddq, int lddk, float drop_p, const int* q_off, const int* k_off, const int* k_cnt, int q_rows) {
+  if (int e = attn_check(name, max_len, q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
+  if (int e = attn_check_varlen(name, key_add, q_off, k_off, k_cnt, q_rows)) return e;
+  MMDTI_REQUIRE(dctx_bf16 && stats && drow && dq_bf16 && dk_bf16 && dv_bf16, "%s: null argument", name);
+  MMDTI_REQUIRE(ldo >= heads * head_dim && ldo % 8 == 0 && aligned16(dctx_bf16), "%s: dctx stride/alignment", name);
+  MMDTI_REQUIRE(lddq >= heads * head_dim && lddk >= heads * head_dim && lddq % 4 == 0 && lddk % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(dq_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(dk_bf16) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(dv_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
+                "%s: output stride/alignment", name);
+  plan = attn_bwd_plan(B, heads, Lq, Lk, head_dim);
+  return MMDTI_OK;
+}
+
 static int attn_fwd_launch(const char* name, int max_len, mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const void* v_bf16,
                            const float* key_add, void* ctx_bf16, float* stats, int B, int heads, int Lq, int Lk, int head_dim, int ldq,
                            int ldk, int ldo, float scale, float drop_p, unsigned long long seed, unsigned int site, const int* q_off,
                            const int* k_off, const int* k_cnt, int q_rows, int ctx_f16) {
-  if (int e = attn_check(name, max_len, q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
-  if (int e = attn_check_varlen(name, key_add, q_off, k_off, k_cnt, q_rows)) return e;
-  const AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
-  MMDTI_REQUIRE(ctx_bf16 && stats && ldo >= heads * head_dim && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(ctx_bf16) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(stats) & 7) == 0, "%s: bad output arguments", name);
-  const uint32_t th = thresh16_of(drop_p);
-  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  const int nt = attn_nt(Lk);
-  const size_t smem = (size_t)2 * nt * 16 * (head_dim + 8) * 2 + (size_t)nt * 16 * 4;
-#define ATTN_F(HD, NT)                                                                                                   \
-  do {                                                                                                                   \
-    static size_t attr_have = 65536;                                                                                     \
-    if (int e = attn_set_smem(attn_fwd_kernel<HD, NT>, NT > 16 ? smem_max_long : smem_max, &attr_have)) return e;        \
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, NT>), dim3(B * heads), dim3(attn_fwd_threads<HD, NT>()), smem, (hipStream_t)stream,                 \
-                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add, (bf16_t*)ctx_bf16,  \
-                       stats, heads, Lq, Lk, ldq, ldk, ldo, scale, th, sc, (uint64_t)seed, (uint32_t)site, vl, ctx_f16); \
-  } while (0)
-#define ATTN_F_NT(HD)                                                                                                    \
-  do {                                                                                                                   \
-    if (nt == 10) ATTN_F(HD, 10); else if (nt == 16) ATTN_F(HD, 16); else if (nt == 24) ATTN_F(HD, 24); else ATTN_F(HD, 32); \
-  } while (0)
-  if (head_dim == 64) ATTN_F_NT(64); else if (head_dim == 32) ATTN_F_NT(32); else ATTN_F_NT(16);
-#undef ATTN_F_NT
-#undef ATTN_F
+  AttnPlan plan;
+  if (int e = attn_fwd_prepare(plan, name, max_len, q_bf16, k_bf16, v_bf16, key_add, ctx_bf16, stats, B, heads, Lq, Lk, head_dim, ldq, ldk, ldo,
+                               drop_p, q_off, k_off, k_cnt, q_rows))
+    return e;
+  AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
+  uint32_t th = thresh16_of(drop_p), site32 = site;
+  float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  uint64_t seed64 = seed;
+  void* args[] = {&q_bf16, &k_bf16, &v_bf16, &key_add, &ctx_bf16, &stats, &heads, &Lq, &Lk, &ldq, &ldk, &ldo, &scale, &th, &sc, &seed64, &site32,
+                  &vl, &ctx_f16};
+  if (int e = attn_launch(plan.k[0], args, stream)) return e;
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -622,51 +634,22 @@ static int attn_bwd_launch(const char* name, int max_len, mmdti_stream_t stream,
                            void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo, int lddq, int lddk,
                            float scale, float drop_p, unsigned long long seed, unsigned int site, const int* q_off, const int* k_off,
                            const int* k_cnt, int q_rows) {
-  if (int e = attn_check(name, max_len, q_bf16, k_bf16, v_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, drop_p)) return e;
-  if (int e = attn_check_varlen(name, key_add, q_off, k_off, k_cnt, q_rows)) return e;
-  const AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
-  MMDTI_REQUIRE(dctx_bf16 && stats && drow && dq_bf16 && dk_bf16 && dv_bf16, "%s: null argument", name);
-  MMDTI_REQUIRE(ldo >= heads * head_dim && ldo % 8 == 0 && aligned16(dctx_bf16), "%s: dctx stride/alignment", name);
-  MMDTI_REQUIRE(lddq >= heads * head_dim && lddk >= heads * head_dim && lddq % 4 == 0 && lddk % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(dq_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(dk_bf16) & 7) == 0 &&
-                    (reinterpret_cast<uintptr_t>(dv_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
-                "%s: output stride/alignment", name);
-  const uint32_t th = thresh16_of(drop_p);
-  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  const int nt = attn_nt(Lk);
-  const size_t smem_q = (size_t)2 * nt * 16 * (head_dim + 8) * 2 + (size_t)nt * 16 * 4;
-  const int lqp = ((Lq + 31) / 32) * 32;
-  const size_t smem_kv = (size_t)2 * lqp * (head_dim + 8) * 2 + (size_t)4 * lqp * 4;
-  // (dQ: 4 waves up to 16 tiles; with 24 / 32 tiles the image pair leaves room for one workgroup per CU, which then brings 16 --
-  //  that form keeps no probability row and needs about 100 registers)
-#define ATTN_BQ(HD, NT)                                                                                                    \
-  do {                                                                                                                     \
-    static size_t attr_have = 65536;                                                                                       \
-    if (int e = attn_set_smem(attn_bwd_q_kernel<HD, NT>, NT > 16 ? smem_max_long : smem_max, &attr_have)) return e;        \
-    hipLaunchKernelGGL((attn_bwd_q_kernel<HD, NT>), dim3(B * heads), dim3(NT > 16 ? 1024 : 256), smem_q, (hipStream_t)stream, \
-                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add,                       \
-                       (const bf16_t*)dctx_bf16, stats, (bf16_t*)dq_bf16, drow, heads, Lq, Lk, ldq, ldk, ldo, lddq, scale, \
-                       th, sc, (uint64_t)seed, (uint32_t)site, vl);                                                        \
-  } while (0)
-#define ATTN_BQ_NT(HD)                                                                                                     \
-  do {                                                                                                                     \
-    if (nt == 10) ATTN_BQ(HD, 10); else if (nt == 16) ATTN_BQ(HD, 16); else if (nt == 24) ATTN_BQ(HD, 24); else ATTN_BQ(HD, 32); \
-  } while (0)
-#define ATTN_BKV(HD)                                                                                                       \
-  do {                                                                                                                     \
-    static size_t attr_have = 65536;                                                                                       \
-    if (int e = attn_set_smem(attn_bwd_kv_kernel<HD>, smem_kv > smem_max ? smem_max_long : smem_max, &attr_have)) return e; \
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<HD>), dim3(B * heads), dim3(512), smem_kv, (hipStream_t)stream,                 \
-                       (const bf16_t*)q_bf16, (const bf16_t*)k_bf16, (const bf16_t*)v_bf16, key_add,                       \
-                       (const bf16_t*)dctx_bf16, stats, drow, (bf16_t*)dk_bf16, (bf16_t*)dv_bf16, heads, Lq, Lk, ldq, ldk, \
-                       ldo, lddk, scale, th, sc, (uint64_t)seed, (uint32_t)site, nt * 16, vl);                             \
-  } while (0)
-  if (head_dim == 64) ATTN_BQ_NT(64); else if (head_dim == 32) ATTN_BQ_NT(32); else ATTN_BQ_NT(16);
+  AttnPlan plan;
+  if (int e = attn_bwd_prepare(plan, name, max_len, q_bf16, k_bf16, v_bf16, key_add, dctx_bf16, stats, drow, dq_bf16, dk_bf16, dv_bf16, B, heads, Lq,
+                               Lk, head_dim, ldq, ldk, ldo, lddq, lddk, drop_p, q_off, k_off, k_cnt, q_rows))
+    return e;
+  AttnVarlen vl = {q_off, k_off, k_cnt, q_rows};
+  uint32_t th = thresh16_of(drop_p), site32 = site;
+  float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  uint64_t seed64 = seed;
+  int kstride = plan.nt * 16;
+  void* args_q[] = {&q_bf16, &k_bf16, &v_bf16, &key_add, &dctx_bf16, &stats, &dq_bf16, &drow, &heads, &Lq, &Lk, &ldq, &ldk, &ldo, &lddq, &scale,
+                    &th, &sc, &seed64, &site32, &vl};
+  if (int e = attn_launch(plan.k[0], args_q, stream)) return e;
   MMDTI_LAUNCH_CHECK();
-  if (head_dim == 64) ATTN_BKV(64); else if (head_dim == 32) ATTN_BKV(32); else ATTN_BKV(16);
-#undef ATTN_BQ_NT
-#undef ATTN_BQ
-#undef ATTN_BKV
+  void* args_kv[] = {&q_bf16, &k_bf16, &v_bf16, &key_add, &dctx_bf16, &stats, &drow, &dk_bf16, &dv_bf16, &heads, &Lq, &Lk, &ldq, &ldk, &ldo, &lddk,
+                     &scale, &th, &sc, &seed64, &site32, &kstride, &vl};
+  if (int e = attn_launch(plan.k[1], args_kv, stream)) return e;
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -708,4 +691,26 @@ extern "C" int mmdti_attn_long_bwd(mmdti_stream_t stream, const void* q_bf16, co
   return attn_bwd_launch("attn_long_bwd", ATTN_LONG_MAX_LEN, stream, q_bf16, k_bf16, v_bf16, key_add, dctx_bf16, stats, drow, dq_bf16,
                          dk_bf16, dv_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, ldo, lddq, lddk, scale, drop_p, seed, site, q_off, k_off,
                          k_cnt, q_rows);
+}
+
+extern "C" int mmdti_attn_plan(int backward, int long_entry, const void* q_bf16, const void* k_bf16, const void* v_bf16, const float* key_add,
+                               const void* ctx_or_dctx_bf16, const float* stats, const float* drow, const void* dq_bf16, const void* dk_bf16,
+                               const void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo, int lddq, int lddk,
+                               float drop_p, const int* q_off, const int* k_off, const int* k_cnt, int q_rows, int* plan_out) {
+  MMDTI_REQUIRE(plan_out != nullptr, "attn_plan: null plan_out");
+  const int max_len = long_entry ? ATTN_LONG_MAX_LEN : ATTN_MAX_LEN;
+  AttnPlan plan;
+  if (backward) {
+    if (int e = attn_bwd_prepare(plan, long_entry ? "attn_long_bwd" : "attn_bwd", max_len, q_bf16, k_bf16, v_bf16, key_add, ctx_or_dctx_bf16, stats,
+                                 drow, dq_bf16, dk_bf16, dv_bf16, B, heads, Lq, Lk, head_dim, ldq, ldk, ldo, lddq, lddk, drop_p, q_off, k_off,
+                                 k_cnt, q_rows))
+      return e;
+  } else {
+    if (int e = attn_fwd_prepare(plan, long_entry ? "attn_long_fwd" : "attn_fwd", max_len, q_bf16, k_bf16, v_bf16, key_add, ctx_or_dctx_bf16, stats,
+                                 B, heads, Lq, Lk, head_dim, ldq, ldk, ldo, drop_p, q_off, k_off, k_cnt, q_rows))
+      return e;
+  }
+  static_assert(ATTN_PLAN_INTS == 13, "mmdti_hip.h documents 13 ints");
+  memcpy(plan_out, &plan, sizeof(plan));
+  return MMDTI_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <string.h>
 
 #include "../../include/mmdti_hip.h"
 #include "det.h"
@@ -50,9 +51,9 @@ static inline int det_workspace(mmdti_stream_t stream, long long need, const cha
   *ws = reinterpret_cast<float*>(slot.ws);
   return MMDTI_OK;
 }
-// a site without a fixed-order form refuses in the mode
-#define MMDTI_DET_REFUSE(site)                                                                                        \
-  MMDTI_REQUIRE(!::mmdti::det_table().on(), site ": no fixed-order form yet -- refused in the deterministic mode (its partial sums meet in atomics)")
+// a site without a fixed-order form refuses in the mode (det: det_table().on() in a launch, the caller's flag in a plan query)
+#define MMDTI_DET_REFUSE_IF(det, site) \
+  MMDTI_REQUIRE(!(det), site ": no fixed-order form yet -- refused in the deterministic mode (its partial sums meet in atomics)")
 
 // dst_k[i] += sum over the slabs s < nslab of ws[s * stride + k * n + i], k < NDST (a null dst_k is skipped).  FIXED order: sixteen
 // threads per element each add every sixteenth slab in slab order, then the sixteen partials are added 0, 1, .. 15 -- the order
@@ -97,6 +98,33 @@ static inline void det_fold(hipStream_t s, const float* ws, int nslab, long long
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- kernel tables: one row per instance -- the key its family's plan header computes, the address, and the template-id as text.  KROW
+// stringifies the tokens it takes the address of, so a name cannot point at another instance.
+struct KernelRow {
+  int key;
+  const void* fn;
+  const char* name;
+  size_t lds_have;   // MaxDynamicSharedMemorySize as last set by ensure_dynamic_lds (0: never)
+};
+#define KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define KROW(key, ...) ::mmdti::KernelRow{key, KFN(__VA_ARGS__), #__VA_ARGS__, 0}
+const KernelRow* attn_kernel_table(int* n);   // attn.hip
+const KernelRow* gbf_kernel_table(int* n);    // gbf.hip
+const KernelRow* pair_attn_kernel_row(int family, int key);   // pair_attn_bwd.hip: row `key` of a PairAttnFamily table, null past its end
+
+// > 64 KiB of dynamic LDS: opt in, once per kernel and cap (raised only if larger than what is set).  *have is a plain static of the
+// kernel's table row: one value for all devices, no synchronisation -- launches come from one host thread per process here; a second
+// thread could read it before the attribute call has returned.
+static inline int ensure_dynamic_lds(const void* fn, size_t cap, size_t* have, const char* who) {
+  if (cap <= 64 * 1024 || cap <= *have) return MMDTI_OK;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess) {
+    set_error("%s: could not raise MaxDynamicSharedMemorySize to %zu", who, cap);
+    return MMDTI_ERR_LAUNCH;
+  }
+  *have = cap;
+  return MMDTI_OK;
+}
 
 // ---- bf16 <-> f32 ----------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }

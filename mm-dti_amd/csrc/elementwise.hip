@@ -683,6 +683,27 @@ using namespace mmdti;
 extern "C" const char* mmdti_last_error(void) { return g_err; }
 extern "C" int mmdti_abi_version(void) { return MMDTI_ABI_VERSION; }
 
+// ---- the kernel tables of the planned families (each family's .hip file owns its table) ----
+static const KernelRow* plan_row(int family, int index) {
+  if (family >= MMDTI_PLAN_PAIR_ATTN_FWD && family <= MMDTI_PLAN_PAIR_ATTN_BWD_ELEM) return pair_attn_kernel_row(family - MMDTI_PLAN_PAIR_ATTN_FWD, index);
+  int n = 0;
+  const KernelRow* t = family == MMDTI_PLAN_ATTN ? attn_kernel_table(&n) : family == MMDTI_PLAN_GBF ? gbf_kernel_table(&n) : nullptr;
+  return t && index >= 0 && index < n ? &t[index] : nullptr;
+}
+extern "C" int mmdti_plan_table_size(int family, int* size_out) {
+  MMDTI_REQUIRE(size_out != nullptr, "plan_table_size: null size_out");
+  MMDTI_REQUIRE(plan_row(family, 0) != nullptr, "plan_table_size: unknown family %d", family);
+  int n = 0;
+  for (const KernelRow* r; (r = plan_row(family, n)) != nullptr; ++n)
+    MMDTI_REQUIRE(r->key == n, "plan_table_size: family %d holds key %d (%s) at row %d", family, r->key, r->name, n);   // (a plan's key IS the row)
+  *size_out = n;
+  return MMDTI_OK;
+}
+extern "C" const char* mmdti_plan_kernel_name(int family, int index) {
+  const KernelRow* r = plan_row(family, index);
+  return r ? r->name : nullptr;
+}
+
 // ---- deterministic mode: the flag and the per-stream workspace table (det.h) ----
 extern "C" int mmdti_set_deterministic(int on) {
   det_table().set_on(on != 0);

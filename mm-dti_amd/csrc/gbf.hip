@@ -8,6 +8,8 @@
 // A 256-thread block covers 16 pairs x 16 k-chunks of 8, so each thread's mu/sigma live in registers and every
 // store is a 16-byte bf16x8.
 #include "common.h"
+#include "gbf_plan.h"
+#include <initializer_list>
 
 namespace mmdti {
 
@@ -46,7 +48,6 @@ __global__ __launch_bounds__(256) void gbf_fwd_kernel(const float* __restrict__ 
 // Backward: per thread accumulates dmu/dsigma of its 8 k's over its pairs; the per-pair dL/dy is reduced over the
 // 16 k-chunk lanes and scattered into an LDS histogram over edge types (E <= 4096), flushed with one global atomic per
 // touched entry per block.
-constexpr int GBF_MAXE = 4096;
 
 __global__ __launch_bounds__(256) void gbf_bwd_kernel(const float* __restrict__ dist, const long long* __restrict__ et,
                                                       const float* __restrict__ mul, const float* __restrict__ bias,
@@ -280,8 +281,6 @@ __global__ __launch_bounds__(256) void pair_permute_bwd_kernel(const float* __re
 // row = (b*N+i)*N+j) -- same values, same bf16 rounding points as the unfused chain.
 typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
 typedef float gf32x4 __attribute__((ext_vector_type(4)));
-constexpr int GBF_K = 128, GBF_F = 128, GBF_H = 64;
-constexpr int GBF_WS = 136;  // LDS row stride (elements) of the weight images: 272-B rows, conflict-free ds_read_b128 fragments
 
 __device__ __forceinline__ gbf16x8 gbf_pack8(const float* v) {
   gbf16x8 r;
@@ -383,7 +382,6 @@ __device__ __forceinline__ gbf16x8 gbf_basis8(float y, const float* mu, const fl
 // 8 waves per workgroup, two workgroups per CU (the weight images are 52 KB); grid-stride over 16-pair tiles with the
 // NEXT tile's index math and loads (edge type, distance) issued before the current tile is computed.  ltab: the per-edge-
 // type tables sit in LDS (E <= GBF_FWD_MAXE) -- a dependent global gather would put two round trips on every tile.
-constexpr int GBF_FWD_MAXE = 4096;
 // Element types of the pair planes (see pair_attn.hip): fp32, or -- compact tiled planes -- the bias as fp16 (saturating at
 // 65504, -inf in the pad slots stays -inf) and the incoming gradient as bf16.
 __device__ __forceinline__ void gbf_put(float* p, float v) { *p = v; }
@@ -593,7 +591,6 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
 // in ONE pass over G: replaces the G re-layout, two dX GEMMs over P = 4.3 M rows and the Gaussian-backward kernel, and
 // the [P,128] dbasis tensor never exists.  Same transposed-operand scheme and pair enumeration as the forward kernel;
 // the two weight-gradient GEMMs (contraction over the 4.3 M pairs) stay on the GEMM kernel.
-constexpr int GBF_W2S = 72;   // LDS row stride of W2^T [128 f][64 h]: 144-B rows, conflict-free ds_read_b128 fragments
 
 template <bool TILED, typename GT>
 __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restrict__ gsrc, const float* __restrict__ dist,
@@ -819,14 +816,7 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
 //   phase B2:            T0 / T1 refilled with h and dO;  dW2[:, 16w..] += dO^T x h, db2;  dy -> per-edge-type histogram.
 // The [pair][feature] tiles have 288-byte rows with the feature index XOR-ed by 64 on odd 8-row groups: writes are 8/16
 // bytes per lane, the transposing reads of a half-wave hit 32 distinct bank pairs.
-constexpr int GBF_LW = 144;       // LDS row stride (elements) of W1 [128 f][144] and of the two pair tiles [128 pairs][144]
-constexpr int GBF_FULL_MAXE = 1536;   // 4 per-edge-type fp32 tables next to 126 KB of tiles in the CU's 160 KB
-// per-workgroup slab of partial gradients (fp32 elements): dW1 [F][K] | dW2 [H][F] | db1 [F] | db2 [H] | dmeans [K] | dstds [K] | dmul [E] | dbias [E]
-constexpr int GBF_SLAB_B1 = GBF_F * GBF_K + GBF_H * GBF_F, GBF_SLAB_B2 = GBF_SLAB_B1 + GBF_F, GBF_SLAB_MU = GBF_SLAB_B2 + GBF_H,
-              GBF_SLAB_SG = GBF_SLAB_MU + GBF_K, GBF_SLAB = GBF_SLAB_SG + GBF_K;
-constexpr size_t gbf_full_smem(int E) {
-  return (size_t)(GBF_F * GBF_LW + GBF_F * GBF_W2S + 2 * 128 * GBF_LW) * 2 + (size_t)(4 * GBF_K + GBF_F + 2 * 128 + 4 * E) * 4;
-}
+// (row strides GBF_LW / GBF_W2S, the per-workgroup slab layout GBF_SLAB_* and the LDS size gbf_full_smem: gbf_plan.h)
 
 typedef short gs16x4 __attribute__((ext_vector_type(4)));
 typedef short gs16x8 __attribute__((ext_vector_type(8)));
@@ -844,7 +834,6 @@ __device__ __forceinline__ gbf16x8 gbf_tr8(const bf16_t* a0, const bf16_t* a1) {
 //   * phase B2 stages the tile's (edge type, dy * d, dy) per pair, and after the barrier the thread that owns histogram bin c adds the
 //     tile's pairs of that edge type in pair order.
 // With the per-workgroup slabs (required in the mode) every sum of this kernel then has an order that depends on the grid alone.
-constexpr size_t GBF_DET_SMEM = (size_t)(8 * 128 + 3 * 128) * 4;
 // COORDS: as in the forward kernel -- fetch takes the two atoms' records, gbf_pair_rule turns them into (edge type, distance).
 template <bool TILED, typename GT, bool DET = false, bool COORDS = false>
 __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
@@ -1354,21 +1343,76 @@ __global__ __launch_bounds__(256) void pair_untile_bwd_kernel(const float* __res
 }  // namespace mmdti
 using namespace mmdti;
 
+// every instance, at the row its key gives it (gbf_plan.h)
+static KernelRow g_gbf_kernels[GBF_KERNELS] = {
+    // forward: plain, saving, from coordinates -- each row-major, tiled, compact
+    KROW(gbf_fwd_key(0, 0, 0), gbf_bias_fwd_kernel<false, false, float>), KROW(gbf_fwd_key(0, 0, 1), gbf_bias_fwd_kernel<false, true, float>),
+    KROW(gbf_fwd_key(0, 0, 2), gbf_bias_fwd_kernel<false, true, _Float16>),
+    KROW(gbf_fwd_key(1, 0, 0), gbf_bias_fwd_kernel<true, false, float>), KROW(gbf_fwd_key(1, 0, 1), gbf_bias_fwd_kernel<true, true, float>),
+    KROW(gbf_fwd_key(1, 0, 2), gbf_bias_fwd_kernel<true, true, _Float16>),
+    KROW(gbf_fwd_key(0, 1, 0), gbf_bias_fwd_kernel<false, false, float, true>), KROW(gbf_fwd_key(0, 1, 1), gbf_bias_fwd_kernel<false, true, float, true>),
+    KROW(gbf_fwd_key(0, 1, 2), gbf_bias_fwd_kernel<false, true, _Float16, true>),
+    // per-pair backward
+    KROW(gbf_bwd_key(0), gbf_bias_bwd_kernel<false, float>), KROW(gbf_bwd_key(1), gbf_bias_bwd_kernel<true, float>),
+    KROW(gbf_bwd_key(2), gbf_bias_bwd_kernel<true, __bf16>),
+    // complete backward: (deterministic, from coordinates) = (0, 0), (0, 1), (1, 0), (1, 1)
+    KROW(gbf_full_key(0, 0, 0), gbf_bias_bwd_full_kernel<false, float>), KROW(gbf_full_key(0, 0, 1), gbf_bias_bwd_full_kernel<true, float>),
+    KROW(gbf_full_key(0, 0, 2), gbf_bias_bwd_full_kernel<true, __bf16>),
+    KROW(gbf_full_key(0, 1, 0), gbf_bias_bwd_full_kernel<false, float, false, true>), KROW(gbf_full_key(0, 1, 1), gbf_bias_bwd_full_kernel<true, float, false, true>),
+    KROW(gbf_full_key(0, 1, 2), gbf_bias_bwd_full_kernel<true, __bf16, false, true>),
+    KROW(gbf_full_key(1, 0, 0), gbf_bias_bwd_full_kernel<false, float, true>), KROW(gbf_full_key(1, 0, 1), gbf_bias_bwd_full_kernel<true, float, true>),
+    KROW(gbf_full_key(1, 0, 2), gbf_bias_bwd_full_kernel<true, __bf16, true>),
+    KROW(gbf_full_key(1, 1, 0), gbf_bias_bwd_full_kernel<false, float, true, true>), KROW(gbf_full_key(1, 1, 1), gbf_bias_bwd_full_kernel<true, float, true, true>),
+    KROW(gbf_full_key(1, 1, 2), gbf_bias_bwd_full_kernel<true, __bf16, true, true>),
+    // the unfused feature kernels
+    KROW(GBF_KEY_FEATURES_FWD, gbf_fwd_kernel), KROW(GBF_KEY_FEATURES_BWD, gbf_bwd_kernel), KROW(GBF_KEY_FEATURES_BWD_DET, gbf_bwd_det_kernel),
+};
+const KernelRow* mmdti::gbf_kernel_table(int* n) { *n = GBF_KERNELS; return g_gbf_kernels; }
+
+static int gbf_launch(const GbfPlan& p, void** args, mmdti_stream_t stream, const char* who) {
+  KernelRow& row = g_gbf_kernels[p.key];
+  if (int e = ensure_dynamic_lds(row.fn, (size_t)p.lds_cap, &row.lds_have, who)) return e;
+  (void)hipLaunchKernel(row.fn, dim3((unsigned)p.grid), dim3((unsigned)p.block), args, (size_t)p.lds, (hipStream_t)stream);
+  return MMDTI_OK;
+}
+
+// the first pointer when none of them is null, else null: how a launcher hands "every required operand" to the validation it shares with
+// mmdti_gbf_plan, which tests pointers for null and alignment only
+static const void* all_of(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (!p) return nullptr;
+  return *ps.begin();
+}
+
 static int gbf_check(const char* fn, long long P, int K, int E) {
   MMDTI_REQUIRE(P > 0 && K > 0 && K % 8 == 0 && E > 0, "%s: need P>0, K%%8==0, E>0 (K=%d)", fn, K);
+  return MMDTI_OK;
+}
+
+// What mmdti_gbf_features_fwd / _bwd and mmdti_gbf_plan share: validate, plan.  `operands`: all_of the entry point's pointers.
+static int gbf_features_fwd_prepare(GbfPlan& plan, const void* operands, long long P, int K, int E, const void* feat_bf16) {
+  if (int e = gbf_check("gbf_features_fwd", P, K, E)) return e;
+  MMDTI_REQUIRE(operands && feat_bf16, "gbf_features_fwd: null pointer");
+  MMDTI_REQUIRE(aligned16(feat_bf16), "gbf_features_fwd: feat must be 16-byte aligned");
+  plan = gbf_features_fwd_plan(P);
+  return MMDTI_OK;
+}
+static int gbf_features_bwd_prepare(GbfPlan& plan, const void* operands, long long P, int K, int E, const void* dfeat_bf16, bool det) {
+  if (int e = gbf_check("gbf_features_bwd", P, K, E)) return e;
+  MMDTI_REQUIRE(operands && dfeat_bf16, "gbf_features_bwd: null pointer");
+  MMDTI_REQUIRE(aligned16(dfeat_bf16), "gbf_features_bwd: dfeat must be 16-byte aligned");
+  MMDTI_REQUIRE(!det || E <= GBF_MAXE, "gbf_features_bwd: deterministic mode keeps the mul / bias histograms in LDS (E <= %d, got %d)", GBF_MAXE, E);
+  plan = gbf_features_bwd_plan(P, E, det);
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_gbf_features_fwd(mmdti_stream_t stream, const float* dist, const long long* edge_type,
                                       const float* mul, const float* bias, const float* means, const float* stds,
                                       long long P, int K, int E, void* feat_bf16) {
-  if (int e = gbf_check("gbf_features_fwd", P, K, E)) return e;
-  MMDTI_REQUIRE(dist && edge_type && mul && bias && means && stds && feat_bf16, "gbf_features_fwd: null pointer");
-  MMDTI_REQUIRE(aligned16(feat_bf16), "gbf_features_fwd: feat must be 16-byte aligned");
-  long long blocks = (P + 15) / 16;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL(gbf_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dist, edge_type, mul,
-                     bias, means, stds, P, K, E, (bf16_t*)feat_bf16);
+  GbfPlan plan;
+  if (int e = gbf_features_fwd_prepare(plan, all_of({dist, edge_type, mul, bias, means, stds}), P, K, E, feat_bf16)) return e;
+  void* args[] = {&dist, &edge_type, &mul, &bias, &means, &stds, &P, &K, &E, &feat_bf16};
+  if (int e = gbf_launch(plan, args, stream, "gbf_features_fwd")) return e;
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -1377,19 +1421,18 @@ extern "C" int mmdti_gbf_features_bwd(mmdti_stream_t stream, const float* dist, 
                                       const float* mul, const float* bias, const float* means, const float* stds,
                                       long long P, int K, int E, const void* dfeat_bf16, float* dmul, float* dbias,
                                       float* dmeans, float* dstds) {
-  if (int e = gbf_check("gbf_features_bwd", P, K, E)) return e;
-  MMDTI_REQUIRE(dist && edge_type && mul && bias && means && stds && dfeat_bf16 && dmul && dbias && dmeans && dstds,
-                "gbf_features_bwd: null pointer");
-  MMDTI_REQUIRE(aligned16(dfeat_bf16), "gbf_features_bwd: dfeat must be 16-byte aligned");
-  if (det_table().on()) {
+  GbfPlan plan;
+  if (int e = gbf_features_bwd_prepare(plan, all_of({dist, edge_type, mul, bias, means, stds, dmul, dbias, dmeans, dstds}), P, K, E, dfeat_bf16,
+                                       det_table().on()))
+    return e;
+  if (plan.slab) {
     // the deterministic mode: per-workgroup slabs [mul | bias | means | stds] in the stream's workspace, folded in workgroup order
-    MMDTI_REQUIRE(E <= GBF_MAXE, "gbf_features_bwd: deterministic mode keeps the mul / bias histograms in LDS (E <= %d, got %d)", GBF_MAXE, E);
-    const int SL = 2 * E + 2 * K, grid = gbf_features_bwd_grid(P);
+    const int SL = 2 * E + 2 * K, grid = (int)plan.grid;
     float* slab = nullptr;
     if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_GBF_FEATURES_BWD, P, SL), "gbf_features_bwd", &slab)) return e;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gbf_bwd_det_kernel, dim3(grid), dim3(256), 2 * (size_t)E * sizeof(float), st, dist, edge_type, mul, bias, means, stds, P, K,
-                       E, (const bf16_t*)dfeat_bf16, slab);
+    void* args[] = {&dist, &edge_type, &mul, &bias, &means, &stds, &P, &K, &E, &dfeat_bf16, &slab};
+    if (int e = gbf_launch(plan, args, stream, "gbf_features_bwd")) return e;
     det_fold<1>(st, slab, grid, SL, E, DetDst<1>{{dmul}});
     det_fold<1>(st, slab + E, grid, SL, E, DetDst<1>{{dbias}});
     det_fold<1>(st, slab + 2 * E, grid, SL, K, DetDst<1>{{dmeans}});
@@ -1397,11 +1440,8 @@ extern "C" int mmdti_gbf_features_bwd(mmdti_stream_t stream, const float* dist, 
     MMDTI_LAUNCH_CHECK();
     return MMDTI_OK;
   }
-  long long blocks = (P + 15) / 16;
-  if (blocks > 256 * 8) blocks = 256 * 8;
-  const size_t smem = E <= GBF_MAXE ? 2 * (size_t)E * sizeof(float) : 0;
-  hipLaunchKernelGGL(gbf_bwd_kernel, dim3((unsigned)blocks), dim3(256), smem, (hipStream_t)stream, dist, edge_type,
-                     mul, bias, means, stds, P, K, E, (const bf16_t*)dfeat_bf16, dmul, dbias, dmeans, dstds);
+  void* args[] = {&dist, &edge_type, &mul, &bias, &means, &stds, &P, &K, &E, &dfeat_bf16, &dmul, &dbias, &dmeans, &dstds};
+  if (int e = gbf_launch(plan, args, stream, "gbf_features_bwd")) return e;
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -1435,18 +1475,17 @@ extern "C" int mmdti_pair_permute_bwd(mmdti_stream_t stream, const float* g, voi
 
 static int edge_bytes_ok(int eb) { return eb == 8 || eb == 4 || eb == 2; }
 
-// Both forms of the forward entry point: rec == nullptr, the planes (dist, edge_type); else the atom records with V and pad.
-static int gbf_bias_fwd_any(mmdti_stream_t stream, const float* dist, const void* edge_type, int edge_bytes, const float* mul,
-                            const float* bias, const float* means, const float* stds, const void* w1_bf16,
-                            const float* b1, const void* w2_bf16, const float* b2, int B, int N, int ld, int K, int F,
-                            int H, int E, void* out, void* feat_bf16, void* u_bf16, void* h_bf16, int flags,
-                            const int* tile_prefix, const int* row_blocks, const uint4* rec, int V, int pad) {
+// What both forms of the forward entry point and mmdti_gbf_plan share: validate, plan.  rec == nullptr: the planes (dist, edge_type);
+// else the atom records.  `weights`: all_of(mul, bias, means, stds, b1, b2).
+static int gbf_bias_fwd_prepare(GbfPlan& plan, const void* dist, const void* edge_type, int edge_bytes, const void* weights, const void* w1_bf16,
+                                const void* w2_bf16, int B, int N, int ld, int K, int F, int H, int E, const void* out, const void* feat_bf16,
+                                const void* u_bf16, const void* h_bf16, int flags, const void* tile_prefix, const void* row_blocks, const void* rec) {
   // bit 0: tiled pair layout; bit 1: u_bf16 receives gelu'(u) instead of u; bit 2: compact planes (out is fp16; tiled only)
-  const int tiled = flags & 1, ugrad = (flags >> 1) & 1, compact = (flags >> 2) & 1;
+  const int tiled = flags & 1, compact = (flags >> 2) & 1;
   MMDTI_REQUIRE(!compact || tiled, "gbf_bias_fwd: compact planes (flags bit 2) exist in the tiled layout only");
   MMDTI_REQUIRE(!tile_prefix || tiled, "gbf_bias_fwd: tile_prefix (ragged batches) needs the tiled pair layout");
   MMDTI_REQUIRE(!row_blocks || tile_prefix, "gbf_bias_fwd: row_blocks (packed token rows) comes with tile_prefix");
-  MMDTI_REQUIRE((rec || (dist && edge_type)) && mul && bias && means && stds && w1_bf16 && b1 && w2_bf16 && b2 && out, "gbf_bias_fwd: null argument");
+  MMDTI_REQUIRE((rec || (dist && edge_type)) && weights && w1_bf16 && w2_bf16 && out, "gbf_bias_fwd: null argument");
   MMDTI_REQUIRE(rec || edge_bytes_ok(edge_bytes), "gbf_bias_fwd: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
   MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_fwd: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
                 GBF_K, GBF_F, GBF_H, K, F, H);
@@ -1455,40 +1494,24 @@ static int gbf_bias_fwd_any(mmdti_stream_t stream, const float* dist, const void
   const bool save = feat_bf16 || u_bf16 || h_bf16;
   MMDTI_REQUIRE(!save || (feat_bf16 && u_bf16 && h_bf16 && aligned16(feat_bf16) && aligned16(u_bf16) && aligned16(h_bf16)),
                 "gbf_bias_fwd: the three saved intermediates come together, 16-byte aligned");
-  const int nb4 = (N + 3) / 4;      // tiled planes: the 4x4 blocks that hold a real pair
-  const int tpm = tiled ? nb4 * nb4 : cdiv((long long)N * ld, 16);
-  const long long ntiles = (long long)B * tpm;
-  MMDTI_REQUIRE(ntiles < (1ll << 30) && (long long)N * N < (1ll << 30), "gbf_bias_fwd: batch too large for 32-bit tile indices");
-  const int grid = (int)((ntiles + 7) / 8 < 512 ? (ntiles + 7) / 8 : 512);     // two resident workgroups per CU
-  const int ltab = E <= GBF_FWD_MAXE ? 1 : 0;
-  const size_t smem = (size_t)(GBF_F + GBF_H) * GBF_WS * 2 + (size_t)(3 * GBF_K + GBF_F + GBF_H + (ltab ? 2 * E : 0)) * 4;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const int cap = (int)((size_t)(GBF_F + GBF_H) * GBF_WS * 2 + (size_t)(3 * GBF_K + GBF_F + GBF_H + 2 * GBF_FWD_MAXE) * 4);
-    const void* fns[9] = {reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, float, true>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, false, float, true>),
-                          reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, _Float16, true>),
-                          reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, true, float>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, false, float>),
-                          reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, float>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, false, float>),
-                          reinterpret_cast<const void*>(gbf_bias_fwd_kernel<true, true, _Float16>), reinterpret_cast<const void*>(gbf_bias_fwd_kernel<false, true, _Float16>)};
-    for (int f = 0; f < 9; ++f)
-      if (hipFuncSetAttribute(fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
-        set_error("gbf_bias_fwd: hipFuncSetAttribute failed");
-        return MMDTI_ERR_LAUNCH;
-      }
-    attr_done = true;
-  }
-#define GBF_LC(SAVE, TILED, OT, COORDS)                                                                                             \
-  hipLaunchKernelGGL((gbf_bias_fwd_kernel<SAVE, TILED, OT, COORDS>), dim3(grid), dim3(512), smem, (hipStream_t)stream, dist, edge_type, edge_bytes, mul, bias, \
-                     means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, b2, (OT*)out, (bf16_t*)feat_bf16, (bf16_t*)u_bf16, \
-                     (bf16_t*)h_bf16, B, N, ld, E, tpm, ugrad, ltab, tile_prefix, row_blocks, rec, V, pad)
-#define GBF_L(SAVE, TILED, OT) GBF_LC(SAVE, TILED, OT, false)
-  if (rec) {      // (the coords form saves nothing: it exists for the configurations of the complete backward kernel)
-    if (compact) GBF_LC(false, true, _Float16, true); else if (tiled) GBF_LC(false, true, float, true); else GBF_LC(false, false, float, true);
-  } else if (compact) { if (save) GBF_L(true, true, _Float16); else GBF_L(false, true, _Float16); }
-  else if (save) { if (tiled) GBF_L(true, true, float); else GBF_L(true, false, float); }
-  else           { if (tiled) GBF_L(false, true, float); else GBF_L(false, false, float); }
-#undef GBF_L
-#undef GBF_LC
+  plan = gbf_bias_fwd_plan(B, N, ld, E, tiled, compact, save, rec != nullptr);
+  MMDTI_REQUIRE(plan.ntiles < (1ll << 30) && (long long)N * N < (1ll << 30), "gbf_bias_fwd: batch too large for 32-bit tile indices");
+  return MMDTI_OK;
+}
+
+static int gbf_bias_fwd_any(mmdti_stream_t stream, const float* dist, const void* edge_type, int edge_bytes, const float* mul,
+                            const float* bias, const float* means, const float* stds, const void* w1_bf16,
+                            const float* b1, const void* w2_bf16, const float* b2, int B, int N, int ld, int K, int F,
+                            int H, int E, void* out, void* feat_bf16, void* u_bf16, void* h_bf16, int flags,
+                            const int* tile_prefix, const int* row_blocks, const uint4* rec, int V, int pad) {
+  GbfPlan plan;
+  if (int e = gbf_bias_fwd_prepare(plan, dist, edge_type, edge_bytes, all_of({mul, bias, means, stds, b1, b2}), w1_bf16, w2_bf16, B, N, ld, K, F, H, E,
+                                   out, feat_bf16, u_bf16, h_bf16, flags, tile_prefix, row_blocks, rec))
+    return e;
+  int tpm = (int)plan.tpm, ugrad = (flags >> 1) & 1, ltab = (int)plan.ltab;
+  void* args[] = {&dist, &edge_type, &edge_bytes, &mul, &bias, &means, &stds, &w1_bf16, &b1, &w2_bf16, &b2, &out, &feat_bf16, &u_bf16, &h_bf16, &B, &N,
+                  &ld, &E, &tpm, &ugrad, &ltab, &tile_prefix, &row_blocks, &rec, &V, &pad};
+  if (int e = gbf_launch(plan, args, stream, "gbf_bias_fwd")) return e;
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -1551,45 +1574,64 @@ extern "C" int mmdti_gbf_bias_fwd_coords(mmdti_stream_t stream, const void* reco
                           nullptr, flags, tile_prefix, row_blocks, (const uint4*)records, V, pad_idx);
 }
 
-extern "C" int mmdti_gbf_bias_bwd(mmdti_stream_t stream, const void* g, const float* dist, const void* edge_type, int edge_bytes,
-                                  const float* mul, const float* bias, const float* means, const float* stds,
-                                  const void* w1_bf16, const void* w2_bf16, const void* u_bf16, int B, int N, int ld, int K,
-                                  int F, int H, int E, int flags, void* do_bf16, void* du_bf16, float* dmul, float* dbias,
-                                  float* dmeans, float* dstds) {
+// What mmdti_gbf_bias_bwd and mmdti_gbf_plan share.  `operands`: all_of the pointers that need no alignment.
+static int gbf_bias_bwd_prepare(GbfPlan& plan, const void* operands, const void* u_bf16, const void* do_bf16, const void* du_bf16, int edge_bytes,
+                                int B, int N, int ld, int K, int F, int H, int E, int flags, bool det) {
   // bit 0: tiled pair layout; bit 1: u_bf16 holds gelu'(u); bit 2: compact planes (g is bf16; tiled only)
-  const int tiled = flags & 1, ugrad = (flags >> 1) & 1, compact = (flags >> 2) & 1;
+  const int tiled = flags & 1, compact = (flags >> 2) & 1;
   MMDTI_REQUIRE(!compact || tiled, "gbf_bias_bwd: compact planes (flags bit 2) exist in the tiled layout only");
-  MMDTI_DET_REFUSE("gbf_bias_bwd (LDS float histograms of mul / bias)");
-  MMDTI_REQUIRE(g && dist && edge_type && mul && bias && means && stds && w1_bf16 && w2_bf16 && u_bf16 && do_bf16 && du_bf16 && dmul &&
-                    dbias && dmeans && dstds, "gbf_bias_bwd: null argument");
+  MMDTI_DET_REFUSE_IF(det, "gbf_bias_bwd (LDS float histograms of mul / bias)");
+  MMDTI_REQUIRE(operands && u_bf16 && do_bf16 && du_bf16, "gbf_bias_bwd: null argument");
   MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_bwd: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
                 GBF_K, GBF_F, GBF_H, K, F, H);
   MMDTI_REQUIRE(B > 0 && N > 0 && ld >= N && ld % 4 == 0 && E > 0 && E <= GBF_MAXE, "gbf_bias_bwd: bad shape (E <= %d)", GBF_MAXE);
   MMDTI_REQUIRE(edge_bytes_ok(edge_bytes), "gbf_bias_bwd: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
   MMDTI_REQUIRE(aligned16(u_bf16) && aligned16(do_bf16) && aligned16(du_bf16), "gbf_bias_bwd: 16-byte alignment required");
-  const int nb4 = (N + 3) / 4;      // tiled planes: the 4x4 blocks that hold a real pair
-  const int tpm = tiled ? nb4 * nb4 : cdiv((long long)N * ld, 16);
-  const long long ntiles = (long long)B * tpm;
-  const int grid = (int)(ntiles / 4 + 1 < 1024 ? ntiles / 4 + 1 : 1024);
-  const size_t smem = (size_t)GBF_K * GBF_WS * 2 + (size_t)GBF_F * GBF_W2S * 2 + (size_t)(3 * GBF_K + 4 * E) * 4;
-  MMDTI_REQUIRE(smem <= 96 * 1024, "gbf_bias_bwd: %d edge types do not fit the LDS tables", E);
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_kernel<true, float>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_kernel<false, float>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_kernel<true, __bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
-      set_error("gbf_bias_bwd: hipFuncSetAttribute failed");
-      return MMDTI_ERR_LAUNCH;
-    }
-    attr_done = true;
-  }
-#define GBF_B(TILED, GT)                                                                                                      \
-  hipLaunchKernelGGL((gbf_bias_bwd_kernel<TILED, GT>), dim3(grid), dim3(256), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, bias, \
-                     means, stds, (const bf16_t*)w1_bf16, (const bf16_t*)w2_bf16, (const bf16_t*)u_bf16, (bf16_t*)do_bf16,    \
-                     (bf16_t*)du_bf16, dmul, dbias, dmeans, dstds, B, N, ld, E, tpm, ugrad)
-  if (compact) GBF_B(true, __bf16); else if (tiled) GBF_B(true, float); else GBF_B(false, float);
-#undef GBF_B
+  plan = gbf_bias_bwd_plan(B, N, ld, E, tiled, compact);
+  MMDTI_REQUIRE(plan.lds <= 96 * 1024, "gbf_bias_bwd: %d edge types do not fit the LDS tables", E);
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_gbf_bias_bwd(mmdti_stream_t stream, const void* g, const float* dist, const void* edge_type, int edge_bytes,
+                                  const float* mul, const float* bias, const float* means, const float* stds,
+                                  const void* w1_bf16, const void* w2_bf16, const void* u_bf16, int B, int N, int ld, int K,
+                                  int F, int H, int E, int flags, void* do_bf16, void* du_bf16, float* dmul, float* dbias,
+                                  float* dmeans, float* dstds) {
+  GbfPlan plan;
+  if (int e = gbf_bias_bwd_prepare(plan, all_of({g, dist, edge_type, mul, bias, means, stds, w1_bf16, w2_bf16, dmul, dbias, dmeans, dstds}), u_bf16,
+                                   do_bf16, du_bf16, edge_bytes, B, N, ld, K, F, H, E, flags, det_table().on()))
+    return e;
+  int tpm = (int)plan.tpm, ugrad = (flags >> 1) & 1;
+  void* args[] = {&g, &dist, &edge_type, &edge_bytes, &mul, &bias, &means, &stds, &w1_bf16, &w2_bf16, &u_bf16, &do_bf16, &du_bf16, &dmul, &dbias,
+                  &dmeans, &dstds, &B, &N, &ld, &E, &tpm, &ugrad};
+  if (int e = gbf_launch(plan, args, stream, "gbf_bias_bwd")) return e;
   MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+
+// What both forms of the complete backward and mmdti_gbf_plan share.  `operands`: all_of g, the weights and the eight gradient outputs.
+static int gbf_bias_bwd_full_prepare(GbfPlan& plan, const void* operands, const void* dist, const void* edge_type, int edge_bytes, const void* w1_bf16,
+                                     int B, int N, int ld, int K, int F, int H, int E, int flags, const void* tile_prefix, const void* row_blocks,
+                                     const void* workspace, long long workspace_bytes, const void* rec, bool det) {
+  const int tiled = flags & 1, compact = (flags >> 2) & 1;   // bit 0: tiled pair layout; bit 2: compact planes (g is bf16; tiled only)
+  MMDTI_REQUIRE(!compact || tiled, "gbf_bias_bwd_full: compact planes (flags bit 2) exist in the tiled layout only");
+  MMDTI_REQUIRE(!tile_prefix || tiled, "gbf_bias_bwd_full: tile_prefix (ragged batches) needs the tiled pair layout");
+  MMDTI_REQUIRE(!row_blocks || tile_prefix, "gbf_bias_bwd_full: row_blocks (packed token rows) comes with tile_prefix");
+  MMDTI_REQUIRE(operands && (rec || (dist && edge_type)) && w1_bf16, "gbf_bias_bwd_full: null argument");
+  MMDTI_REQUIRE(rec || edge_bytes_ok(edge_bytes), "gbf_bias_bwd_full: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
+  MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_bwd_full: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
+                GBF_K, GBF_F, GBF_H, K, F, H);
+  MMDTI_REQUIRE(B > 0 && N > 0 && ld >= N && ld % 4 == 0 && E > 0 && E <= GBF_FULL_MAXE, "gbf_bias_bwd_full: bad shape (E <= %d)", GBF_FULL_MAXE);
+  MMDTI_REQUIRE((long long)N * ld * GBF_H < (1ll << 29) && (long long)B * N * ld / 16 < (1ll << 30), "gbf_bias_bwd_full: batch too large for 32-bit tile offsets");
+  MMDTI_REQUIRE(aligned16(w1_bf16), "gbf_bias_bwd_full: W1 must be 16-byte aligned");
+  plan = gbf_bias_bwd_full_plan(B, N, ld, E, tiled, compact, rec != nullptr, det, workspace && aligned16(workspace), workspace_bytes);
+  if (det) {
+    // the mode takes the slab form only (never the atomics of a launch without a workspace: MMDTI_GBF_SLABS=0), and its LDS staging rows
+    MMDTI_REQUIRE(plan.slab, "gbf_bias_bwd_full: deterministic mode needs the workspace of mmdti_gbf_bias_bwd_full_workspace (%lld bytes): without it the partial sums meet in atomics",
+                  plan.grid * (GBF_SLAB + 2 * (long long)E) * 4);
+    MMDTI_REQUIRE(plan.lds <= 160 * 1024, "gbf_bias_bwd_full: deterministic mode: %d edge types do not fit LDS next to the staging rows", E);
+  }
   return MMDTI_OK;
 }
 
@@ -1599,73 +1641,19 @@ static int gbf_bias_bwd_full_any(mmdti_stream_t stream, const void* g, const flo
                                  float* dw1, float* db1, float* dw2, float* db2, float* dmul, float* dbias, float* dmeans,
                                  float* dstds, const int* tile_prefix, const int* row_blocks, void* workspace, long long workspace_bytes,
                                  const uint4* rec, int V, int pad) {
-  const int tiled = flags & 1, compact = (flags >> 2) & 1;   // bit 0: tiled pair layout; bit 2: compact planes (g is bf16; tiled only)
-  MMDTI_REQUIRE(!compact || tiled, "gbf_bias_bwd_full: compact planes (flags bit 2) exist in the tiled layout only");
-  MMDTI_REQUIRE(!tile_prefix || tiled, "gbf_bias_bwd_full: tile_prefix (ragged batches) needs the tiled pair layout");
-  MMDTI_REQUIRE(!row_blocks || tile_prefix, "gbf_bias_bwd_full: row_blocks (packed token rows) comes with tile_prefix");
-  MMDTI_REQUIRE(g && (rec || (dist && edge_type)) && mul && bias && means && stds && w1_bf16 && b1 && w2_bf16 && dw1 && db1 && dw2 && db2 && dmul && dbias &&
-                    dmeans && dstds, "gbf_bias_bwd_full: null argument");
-  MMDTI_REQUIRE(rec || edge_bytes_ok(edge_bytes), "gbf_bias_bwd_full: edge types must be int64, int32 or int16 (edge_bytes=%d)", edge_bytes);
-  MMDTI_REQUIRE(K == GBF_K && F == GBF_F && H == GBF_H, "gbf_bias_bwd_full: built for %d gaussians, %d hidden, %d heads (got %d,%d,%d)",
-                GBF_K, GBF_F, GBF_H, K, F, H);
-  MMDTI_REQUIRE(B > 0 && N > 0 && ld >= N && ld % 4 == 0 && E > 0 && E <= GBF_FULL_MAXE, "gbf_bias_bwd_full: bad shape (E <= %d)", GBF_FULL_MAXE);
-  MMDTI_REQUIRE((long long)N * ld * GBF_H < (1ll << 29) && (long long)B * N * ld / 16 < (1ll << 30), "gbf_bias_bwd_full: batch too large for 32-bit tile offsets");
-  MMDTI_REQUIRE(aligned16(w1_bf16), "gbf_bias_bwd_full: W1 must be 16-byte aligned");
-  const int nb = (N + 3) / 4;
-  const int tpm = tiled ? nb * nb : cdiv((long long)N * ld, 16);
-  const long long ntiles = (long long)B * tpm;
-  const int grid = (int)((ntiles + 7) / 8 < 256 ? (ntiles + 7) / 8 : 256);
-  const bool det = det_table().on();
-  const size_t smem = gbf_full_smem(E) + (det ? GBF_DET_SMEM : 0);
-  const long long SL = GBF_SLAB + 2 * (long long)E;
-  float* slab = (workspace && aligned16(workspace) && workspace_bytes >= (long long)grid * SL * 4) ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (det) {
-    // the mode takes the slab form only (never the atomics of a launch without a workspace: MMDTI_GBF_SLABS=0), and its LDS staging rows
-    MMDTI_REQUIRE(slab != nullptr, "gbf_bias_bwd_full: deterministic mode needs the workspace of mmdti_gbf_bias_bwd_full_workspace (%lld bytes): without it the partial sums meet in atomics",
-                  (long long)grid * SL * 4);
-    MMDTI_REQUIRE(smem <= 160 * 1024, "gbf_bias_bwd_full: deterministic mode: %d edge types do not fit LDS next to the staging rows", E);
-    static bool det_attr_done = false;
-    if (!det_attr_done) {
-      const int cap = 160 * 1024;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
-        set_error("gbf_bias_bwd_full: hipFuncSetAttribute failed");
-        return MMDTI_ERR_LAUNCH;
-      }
-      det_attr_done = true;
-    }
-  }
-  static bool attr_done = false;
-  if (!attr_done) {
-    const int cap = (int)gbf_full_smem(GBF_FULL_MAXE);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, float>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<false, float>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(gbf_bias_bwd_full_kernel<true, __bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, cap) != hipSuccess) {
-      set_error("gbf_bias_bwd_full: hipFuncSetAttribute failed");
-      return MMDTI_ERR_LAUNCH;
-    }
-    attr_done = true;
-  }
-#define GBF_FX(TILED, GT, DET, COORDS)                                                                                             \
-  hipLaunchKernelGGL((gbf_bias_bwd_full_kernel<TILED, GT, DET, COORDS>), dim3(grid), dim3(512), smem, (hipStream_t)stream, (const GT*)g, dist, edge_type, edge_bytes, mul, \
-                     bias, means, stds, (const bf16_t*)w1_bf16, b1, (const bf16_t*)w2_bf16, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds, B, \
-                     N, ld, E, tpm, tile_prefix, row_blocks, slab, rec, V, pad)
-#define GBF_FL(DET, COORDS) \
-  do { if (compact) GBF_FX(true, __bf16, DET, COORDS); else if (tiled) GBF_FX(true, float, DET, COORDS); else GBF_FX(false, float, DET, COORDS); } while (0)
-  // (a workspace of at least grid slots: partial sums in per-workgroup slabs + a fixed-order reduce; else fp32 atomics)
-  if (det) { if (rec) GBF_FL(true, true); else GBF_FL(true, false); }
-  else if (rec) GBF_FL(false, true); else GBF_FL(false, false);
-#undef GBF_FL
-#undef GBF_FX
+  GbfPlan plan;
+  if (int e = gbf_bias_bwd_full_prepare(plan, all_of({g, mul, bias, means, stds, b1, w2_bf16, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds}), dist,
+                                        edge_type, edge_bytes, w1_bf16, B, N, ld, K, F, H, E, flags, tile_prefix, row_blocks, workspace,
+                                        workspace_bytes, rec, det_table().on()))
+    return e;
+  int tpm = (int)plan.tpm, grid = (int)plan.grid;
+  float* slab = plan.slab ? reinterpret_cast<float*>(workspace) : nullptr;
+  void* args[] = {&g, &dist, &edge_type, &edge_bytes, &mul, &bias, &means, &stds, &w1_bf16, &b1, &w2_bf16, &dw1, &db1, &dw2, &db2, &dmul, &dbias, &dmeans,
+                  &dstds, &B, &N, &ld, &E, &tpm, &tile_prefix, &row_blocks, &slab, &rec, &V, &pad};
+  if (int e = gbf_launch(plan, args, stream, "gbf_bias_bwd_full")) return e;
   if (slab)
-    hipLaunchKernelGGL(gbf_slab_reduce_kernel, dim3(cdiv(SL, 64)), dim3(256), 0, (hipStream_t)stream, slab, grid, E, dw1, db1, dw2, db2, dmul, dbias, dmeans, dstds);
+    hipLaunchKernelGGL(gbf_slab_reduce_kernel, dim3((unsigned)plan.reduce_grid), dim3(256), 0, (hipStream_t)stream, slab, grid, E, dw1, db1, dw2, db2, dmul,
+                       dbias, dmeans, dstds);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -1691,3 +1679,35 @@ extern "C" int mmdti_gbf_bias_bwd_full_coords(mmdti_stream_t stream, const void*
 
 /* bytes of workspace that make mmdti_gbf_bias_bwd_full reproducible (one slab per workgroup of its persistent grid, at most 256) */
 extern "C" int mmdti_gbf_bias_bwd_full_workspace(int E) { return (int)(256ll * (GBF_SLAB + 2ll * (E > 0 ? E : 0)) * 4); }
+
+extern "C" int mmdti_gbf_plan(int entry, int deterministic, const void* operands, const void* aligned, const void* saved, const void* records,
+                              const int* tile_prefix, const int* row_blocks, const void* workspace, long long workspace_bytes, long long P, int B,
+                              int N, int ld, int K, int F, int H, int E, int V, int pad_idx, int edge_bytes, int flags, long long* plan_out) {
+  MMDTI_REQUIRE(plan_out != nullptr, "gbf_plan: null plan_out");
+  const bool det = deterministic != 0;
+  GbfPlan plan;
+  int e = MMDTI_OK;
+  switch (entry) {
+    case GBF_FEATURES_FWD: e = gbf_features_fwd_prepare(plan, operands, P, K, E, aligned); break;
+    case GBF_FEATURES_BWD: e = gbf_features_bwd_prepare(plan, operands, P, K, E, aligned, det); break;
+    case GBF_BIAS_FWD:
+      if (records) e = gbf_coords_check("gbf_bias_fwd_coords", records, B, N, V, pad_idx, E);
+      if (!e)
+        e = gbf_bias_fwd_prepare(plan, records ? nullptr : operands, records ? nullptr : operands, edge_bytes, operands, aligned, aligned, B, N, ld, K, F, H, E,
+                                 aligned, records ? nullptr : saved, records ? nullptr : saved, records ? nullptr : saved, flags, tile_prefix, row_blocks,
+                                 records);
+      break;
+    case GBF_BIAS_BWD: e = gbf_bias_bwd_prepare(plan, operands, aligned, aligned, aligned, edge_bytes, B, N, ld, K, F, H, E, flags, det); break;
+    case GBF_BIAS_BWD_FULL:
+      if (records) e = gbf_coords_check("gbf_bias_bwd_full_coords", records, B, N, V, pad_idx, E);
+      if (!e)
+        e = gbf_bias_bwd_full_prepare(plan, operands, records ? nullptr : operands, records ? nullptr : operands, edge_bytes, aligned, B, N, ld, K, F, H, E,
+                                      flags, tile_prefix, row_blocks, workspace, workspace_bytes, records, det);
+      break;
+    default: MMDTI_REQUIRE(false, "gbf_plan: unknown entry %d", entry);
+  }
+  if (e) return e;
+  static_assert(GBF_PLAN_INTS == 10, "mmdti_hip.h documents 10 integers");
+  memcpy(plan_out, &plan, sizeof(plan));
+  return MMDTI_OK;
+}

@@ -1677,24 +1677,8 @@ extern "C" int mmdti_set_option(const char* name, int value) {
   return MMDTI_ERR_INVALID;
 }
 
-// > 64 KiB of dynamic LDS: opt in once per kernel
-static int ensure_dynamic_lds(const void* fn, int bytes, const char* who) {
-  static const void* done[64];
-  static int ndone = 0;
-  if (bytes <= 64 * 1024) return MMDTI_OK;
-  for (int i = 0; i < ndone; ++i)
-    if (done[i] == fn) return MMDTI_OK;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-    set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", who, (size_t)bytes);
-    return MMDTI_ERR_LAUNCH;
-  }
-  if (ndone < 64) done[ndone++] = fn;
-  return MMDTI_OK;
-}
-
 // every instance of the mmdti_gemm_bf16 families, by (family, template key); the tall kernel takes (GemmArgs, int mstep), the rest (GemmArgs)
-#define KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
-static const struct GemmKernel { int family, ta, tb, fast, f16, bcvt; const void* fn; } g_gemm_kernels[] = {
+static struct GemmKernel { int family, ta, tb, fast, f16, bcvt; const void* fn; size_t lds_have; } g_gemm_kernels[] = {
     {GEMM_REG, 0, 0, 0, 0, 0, KFN(gemm_bf16_kernel<false, false, false>)}, {GEMM_REG, 0, 0, 1, 0, 0, KFN(gemm_bf16_kernel<false, false, true>)},
     {GEMM_REG, 0, 1, 0, 0, 0, KFN(gemm_bf16_kernel<false, true, false>)},  {GEMM_REG, 0, 1, 1, 0, 0, KFN(gemm_bf16_kernel<false, true, true>)},
     {GEMM_REG, 1, 0, 0, 0, 0, KFN(gemm_bf16_kernel<true, false, false>)},  {GEMM_REG, 1, 0, 1, 0, 0, KFN(gemm_bf16_kernel<true, false, true>)},
@@ -1720,9 +1704,9 @@ static const struct GemmKernel { int family, ta, tb, fast, f16, bcvt; const void
     {GEMM_BIG, 1, 0, 0, 0, 0, KFN(gemm_big_kernel<true, false>)},           {GEMM_BIG, 1, 1, 0, 0, 0, KFN(gemm_big_kernel<true, true>)},
     {GEMM_BIG, 0, 0, 0, 1, 0, KFN(gemm_big_kernel<false, false, true>)},    {GEMM_BIG, 1, 1, 0, 0, 1, KFN(gemm_big_kernel<true, true, false, true>)},
 };
-static const void* gemm_kernel(const GemmPlan& p) {
-  for (const GemmKernel& k : g_gemm_kernels)
-    if (k.family == p.family && k.ta == p.ta && k.tb == p.tb && k.fast == p.fast && k.f16 == p.f16 && k.bcvt == p.bcvt) return k.fn;
+static GemmKernel* gemm_kernel(const GemmPlan& p) {
+  for (GemmKernel& k : g_gemm_kernels)
+    if (k.family == p.family && k.ta == p.ta && k.tb == p.tb && k.fast == p.fast && k.f16 == p.f16 && k.bcvt == p.bcvt) return &k;
   return nullptr;
 }
 
@@ -1879,9 +1863,10 @@ extern "C" int mmdti_gemm_bf16(mmdti_stream_t stream, const void* A, const void*
       }
     }
   }
-  const void* fn = gemm_kernel(plan);
-  MMDTI_REQUIRE(fn != nullptr, "gemm: no kernel instance for the planned family %d", plan.family);
-  if (int e = ensure_dynamic_lds(fn, plan.lds, "gemm")) return e;
+  GemmKernel* kern = gemm_kernel(plan);
+  MMDTI_REQUIRE(kern != nullptr, "gemm: no kernel instance for the planned family %d", plan.family);
+  const void* fn = kern->fn;
+  if (int e = ensure_dynamic_lds(fn, (size_t)plan.lds, &kern->lds_have, "gemm")) return e;
   if (plan.arowsum == AROWSUM_COLSUM_PASS)
     if (int e = mmdti_colsum_bf16(stream, A, K, M, lda, arowsum_out)) return e;
   if (plan.slabs) {
@@ -1922,10 +1907,11 @@ extern "C" int mmdti_gemm_ln_bf16(mmdti_stream_t stream, const void* A_bf16, con
   a.seed = seed; a.site = site;
   a.ln_f16 = (f16 >> 1) & 1;          // bit 0: A and W are fp16; bit 1: the 16-bit LayerNorm output is fp16
   const int rows = mmdti_gemm_ln_rows(M);
-  static const void* const kerns[2][2] = {{KFN(gemm_ln_kernel<4>), KFN(gemm_ln_kernel<4, true>)}, {KFN(gemm_ln_kernel<5>), KFN(gemm_ln_kernel<5, true>)}};
-  const void* fn = kerns[rows == 80][f16 & 1];
+  static KernelRow kerns[2][2] = {{KROW(0, gemm_ln_kernel<4>), KROW(1, gemm_ln_kernel<4, true>)}, {KROW(2, gemm_ln_kernel<5>), KROW(3, gemm_ln_kernel<5, true>)}};
+  KernelRow& kern = kerns[rows == 80][f16 & 1];
+  const void* fn = kern.fn;
   const int lds = gemm_ln_lds(rows);
-  if (int e = ensure_dynamic_lds(fn, lds, "gemm_ln")) return e;
+  if (int e = ensure_dynamic_lds(fn, (size_t)lds, &kern.lds_have, "gemm_ln")) return e;
   void* kargs[1] = {&a};
   (void)hipLaunchKernel(fn, dim3(cdiv(M, rows)), dim3(512), kargs, (size_t)lds, (hipStream_t)stream);
   MMDTI_LAUNCH_CHECK();
@@ -1948,10 +1934,10 @@ static int grouped_dw_prepare(GroupedDwPlan& plan, int nprob, const int* n_out, 
   plan = grouped_dw_plan(tiles256, tiles64, elems, rows, x_f16 != 0, gemm_options(ENTRY_GROUPED_DW));
   return MMDTI_OK;
 }
-static const void* grouped_dw_kernel(const GroupedDwPlan& p) {
-  static const void* const small_kerns[2] = {KFN(gemm_small_dw_grouped_kernel<3, false>), KFN(gemm_small_dw_grouped_kernel<3, true>)};
-  static const void* const big_kerns[2][2] = {{KFN(gemm_big_grouped_kernel<false, false>), KFN(gemm_big_grouped_kernel<false, true>)},
-                                              {KFN(gemm_big_grouped_kernel<true, false>), KFN(gemm_big_grouped_kernel<true, true>)}};
+static KernelRow& grouped_dw_kernel(const GroupedDwPlan& p) {
+  static KernelRow small_kerns[2] = {KROW(0, gemm_small_dw_grouped_kernel<3, false>), KROW(1, gemm_small_dw_grouped_kernel<3, true>)};
+  static KernelRow big_kerns[2][2] = {{KROW(0, gemm_big_grouped_kernel<false, false>), KROW(1, gemm_big_grouped_kernel<false, true>)},
+                                      {KROW(2, gemm_big_grouped_kernel<true, false>), KROW(3, gemm_big_grouped_kernel<true, true>)}};
   return p.small ? small_kerns[p.bcvt] : big_kerns[p.bcvt][p.ktail];
 }
 
@@ -1999,8 +1985,9 @@ extern "C" int mmdti_linear_dw_grouped(mmdti_stream_t stream, int nprob, const v
   }
   for (int i = nprob; i < GROUP_MAX; ++i) { g.p[i] = g.p[0]; g.p[i].tile0 = 0x7fffffff; }
   g.ntiles = tiles; g.splitk = plan.splitk; g.atomic = plan.atomic;
-  const void* fn = grouped_dw_kernel(plan);
-  if (int e = ensure_dynamic_lds(fn, plan.lds, "linear_dw_grouped")) return e;
+  KernelRow& kern = grouped_dw_kernel(plan);
+  const void* fn = kern.fn;
+  if (int e = ensure_dynamic_lds(fn, (size_t)plan.lds, &kern.lds_have, "linear_dw_grouped")) return e;
   hipStream_t s = (hipStream_t)stream;
   if (det_table().on() && !plan.small) {
     // the deterministic mode, big form: always the slab pass (the caller's workspace holds plan.splitk slabs), and the bias gradients --

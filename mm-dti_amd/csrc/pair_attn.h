@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pair_attn_plan.h"
 
 namespace mmdti {
 
@@ -172,8 +173,6 @@ __device__ __forceinline__ void pa_dispatch_kt(int ke, F&& f) {
 
 }  // namespace mmdti
 
-// key tiles of 16 the MFMA kernels are instantiated for: 17 covers the reference's crop (max_atoms = 256 -> N <= 258, data/conformer.py:53,199-204)
-#define PA_MAX_NT 17
 
 static inline int check_common(const char* fn, int B, int N, int H, int ld) {
   MMDTI_REQUIRE(B > 0 && N > 0 && H > 0, "%s: B,N,H must be positive", fn);
@@ -183,3 +182,10 @@ static inline int check_common(const char* fn, int B, int N, int H, int ld) {
   return MMDTI_OK;
 }
 
+
+namespace mmdti {
+// pair_attn.hip: the forward's two tables (PA_FWD_MFMA / PA_FWD_ELEM) and the validation + plan its launch shares with mmdti_pair_attn_plan
+const KernelRow* pair_attn_fwd_table(int family, int* n);
+int pair_attn_fwd_prepare(PairAttnPlan& plan, const void* qkv_bf16, const void* bias_in, const void* s_out, const void* o_bf16, int B, int N, int H,
+                          int ld, float drop_p, int layout, const void* key_tiles, const void* row_off, int qkv_f16);
+}  // namespace mmdti

@@ -336,10 +336,39 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
 MMDTI_DEFINE_SALT_PULL(pair_attn)
 using namespace mmdti;
 
-extern "C" int mmdti_pair_attn_fwd(mmdti_stream_t stream, const void* qkv_bf16, const void* bias_in, void* s_out,
-                                   void* o_bf16, const unsigned char* key_pad, int B, int N, int H, int ld,
-                                   float scale, float drop_p, unsigned long long seed, unsigned int site, int layout,
-                                   const int* key_tiles, int rag_store, const int* row_off, int qkv_f16) {
+
+// every MFMA instance, at the row its key gives it (pair_attn_plan.h); one argument block: the instances differ in the element type of
+// the two pair tensors only
+#define PA_FWD_COMPACT_ROW(NT)                                                                                                    \
+  KROW(pa_fwd_compact_key(NT, 0, 0), pair_attn_fwd_mfma_kernel<NT, true, true, false, _Float16>),                                 \
+  KROW(pa_fwd_compact_key(NT, 0, 1), pair_attn_fwd_mfma_kernel<NT, true, true, true, _Float16>),                                  \
+  KROW(pa_fwd_compact_key(NT, 1, 0), pair_attn_fwd_mfma_kernel<NT, true, true, false, _Float16, true>),                           \
+  KROW(pa_fwd_compact_key(NT, 1, 1), pair_attn_fwd_mfma_kernel<NT, true, true, true, _Float16, true>)
+#define PA_FWD_F32_ROW(NT)                                                                                                        \
+  KROW(pa_fwd_f32_key(pa_bucket(NT), 0, 0), pair_attn_fwd_mfma_kernel<NT, false, false, false, float>),                           \
+  KROW(pa_fwd_f32_key(pa_bucket(NT), 1, 0), pair_attn_fwd_mfma_kernel<NT, true, false, false, float>),                            \
+  KROW(pa_fwd_f32_key(pa_bucket(NT), 1, 1), pair_attn_fwd_mfma_kernel<NT, true, true, false, float>)
+static KernelRow g_pa_fwd_mfma[PA_FWD_MFMA_KERNELS] = {
+    PA_FWD_COMPACT_ROW(1),  PA_FWD_COMPACT_ROW(2),  PA_FWD_COMPACT_ROW(3),  PA_FWD_COMPACT_ROW(4),  PA_FWD_COMPACT_ROW(5),  PA_FWD_COMPACT_ROW(6),
+    PA_FWD_COMPACT_ROW(7),  PA_FWD_COMPACT_ROW(8),  PA_FWD_COMPACT_ROW(9),  PA_FWD_COMPACT_ROW(10), PA_FWD_COMPACT_ROW(11), PA_FWD_COMPACT_ROW(12),
+    PA_FWD_COMPACT_ROW(13), PA_FWD_COMPACT_ROW(14), PA_FWD_COMPACT_ROW(15), PA_FWD_COMPACT_ROW(16), PA_FWD_COMPACT_ROW(17),
+    PA_FWD_F32_ROW(5),      PA_FWD_F32_ROW(9),      PA_FWD_F32_ROW(13),     PA_FWD_F32_ROW(17),
+};
+#undef PA_FWD_COMPACT_ROW
+#undef PA_FWD_F32_ROW
+// the per-element kernels (N > 272, or rows / planes that are not 16-byte aligned): their own small family
+static KernelRow g_pa_fwd_elem[PA_FWD_ELEM_KERNELS] = {
+    KROW(pa_fwd_elem_key(1), pair_attn_fwd_kernel<1>), KROW(pa_fwd_elem_key(2), pair_attn_fwd_kernel<2>), KROW(pa_fwd_elem_key(3), pair_attn_fwd_kernel<3>),
+    KROW(pa_fwd_elem_key(4), pair_attn_fwd_kernel<4>), KROW(pa_fwd_elem_key(5), pair_attn_fwd_kernel<5>),
+};
+const KernelRow* mmdti::pair_attn_fwd_table(int family, int* n) {
+  *n = family == PA_FWD_MFMA ? PA_FWD_MFMA_KERNELS : PA_FWD_ELEM_KERNELS;
+  return family == PA_FWD_MFMA ? g_pa_fwd_mfma : g_pa_fwd_elem;
+}
+
+// What mmdti_pair_attn_fwd and mmdti_pair_attn_plan share: validate, plan.  Pointers are tested for null and alignment only.
+int mmdti::pair_attn_fwd_prepare(PairAttnPlan& plan, const void* qkv_bf16, const void* bias_in, const void* s_out, const void* o_bf16, int B, int N, int H,
+                                 int ld, float drop_p, int layout, const void* key_tiles, const void* row_off, int qkv_f16) {
   const int tiled = layout & 1, compact = (layout >> 1) & 1;   // bit 0: tiled planes; bit 1: compact planes (S fp16; tiled only)
   if (int e = check_common("pair_attn_fwd", B, N, H, ld)) return e;
   MMDTI_REQUIRE((layout & ~3) == 0 && (!compact || tiled), "pair_attn_fwd: layout must be 0 (row-major fp32), 1 (tiled fp32) or 3 (tiled, fp16 logits)");
@@ -351,56 +380,24 @@ extern "C" int mmdti_pair_attn_fwd(mmdti_stream_t stream, const void* qkv_bf16, 
   MMDTI_REQUIRE(aligned16(qkv_bf16), "pair_attn_fwd: qkv must be 16-byte aligned");
   MMDTI_REQUIRE(!tiled || (aligned16(bias_in) && aligned16(s_out)), "pair_attn_fwd: tiled pair tensors must be 16-byte aligned");
   MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "pair_attn_fwd: dropout p out of range");
-  const uint32_t th = dropout_thresh(drop_p);     // the per-element kernel (N > 272 or unaligned rows): Philox words against p * 2^32
-  const uint32_t th8 = dropout_thresh8(drop_p);   // the MFMA kernels: the shared byte generator of common.h
-  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  dim3 grid(B * H), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  // (same eligibility rule as the backward: the two MFMA kernels share one dropout-mask generator)
-  if (ld % 4 == 0 && aligned16(bias_in) && aligned16(s_out) && N <= 16 * PA_MAX_NT) {
-    const int nqb = (N + 15) / 16;
-    dim3 blk(nqb % 3 == 0 ? 192 : (nqb < 4 ? 64 * nqb : 256));
-#define PA_M(NT, TL, FL, RG, ST)                                                                                                     \
-  hipLaunchKernelGGL((pair_attn_fwd_mfma_kernel<NT, TL, FL, RG, ST>), grid, blk, 0, s, (const bf16_t*)qkv_bf16, (const ST*)bias_in, \
-                     (ST*)s_out, (bf16_t*)o_bf16, key_pad, N, H, ld, scale, th8, sc, (uint64_t)seed, (uint32_t)site, key_tiles, rag_store, row_off)
-#define PA_MT(NT)                                                                           \
-  do {                                                                                      \
-    if (!tiled) PA_M(NT, false, false, false, float);                                       \
-    else if (!compact) { if (nqb == NT) PA_M(NT, true, true, false, float); else PA_M(NT, true, false, false, float); } \
-  } while (0)
-    // The hot path (compact planes) has an instantiation for EVERY tile count: all its tiles exist, the interior ones run
-    // without predicates (FULL).  In a kernel instantiated for more tiles than N has, the surplus tiles are predicated off but
-    // still walked and no tile takes the fast path -- 25-45 % more time per real tile (N = 96 / 113 / 128 on the 9-tile kernel).
-#define PA_MH(NT, RG)                                                                                                                  \
-  hipLaunchKernelGGL((pair_attn_fwd_mfma_kernel<NT, true, true, RG, _Float16, true>), grid, blk, 0, s, (const bf16_t*)qkv_bf16,       \
-                     (const _Float16*)bias_in, (_Float16*)s_out, (bf16_t*)o_bf16, key_pad, N, H, ld, scale, th8, sc, (uint64_t)seed,  \
-                     (uint32_t)site, key_tiles, rag_store, row_off)
-#define PA_MC(NT) case NT: if (qkv_f16) { if (key_tiles) PA_MH(NT, true); else PA_MH(NT, false); } \
-                           else if (key_tiles) PA_M(NT, true, true, true, _Float16); else PA_M(NT, true, true, false, _Float16); break
-    if (compact) {
-      switch (nqb) {
-        PA_MC(1); PA_MC(2); PA_MC(3); PA_MC(4); PA_MC(5); PA_MC(6); PA_MC(7); PA_MC(8); PA_MC(9); PA_MC(10); PA_MC(11); PA_MC(12);
-        PA_MC(13); PA_MC(14); PA_MC(15); PA_MC(16); PA_MC(17);
-      }
-    } else if (nqb <= 5) PA_MT(5); else if (nqb <= 9) PA_MT(9); else if (nqb <= 13) PA_MT(13); else PA_MT(17);
-#undef PA_MC
-#undef PA_MH
-#undef PA_MT
-#undef PA_M
-    MMDTI_LAUNCH_CHECK();
-    return MMDTI_OK;
-  }
-#define PA_F(NCH)                                                                                                   \
-  hipLaunchKernelGGL((pair_attn_fwd_kernel<NCH>), grid, block, 0, s, (const bf16_t*)qkv_bf16, (const float*)bias_in, (float*)s_out, \
-                     (bf16_t*)o_bf16, key_pad, N, H, ld, scale, th, sc, (uint64_t)seed, (uint32_t)site)
-  switch ((N + 63) / 64) {
-    case 1: PA_F(1); break;
-    case 2: PA_F(2); break;
-    case 3: PA_F(3); break;
-    case 4: PA_F(4); break;
-    default: PA_F(5); break;
-  }
-#undef PA_F
+  plan = pair_attn_fwd_plan(B, N, H, ld, tiled, compact, aligned16(bias_in) && aligned16(s_out), key_tiles != nullptr, qkv_f16 != 0);
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_pair_attn_fwd(mmdti_stream_t stream, const void* qkv_bf16, const void* bias_in, void* s_out,
+                                   void* o_bf16, const unsigned char* key_pad, int B, int N, int H, int ld,
+                                   float scale, float drop_p, unsigned long long seed, unsigned int site, int layout,
+                                   const int* key_tiles, int rag_store, const int* row_off, int qkv_f16) {
+  PairAttnPlan plan;
+  if (int e = pair_attn_fwd_prepare(plan, qkv_bf16, bias_in, s_out, o_bf16, B, N, H, ld, drop_p, layout, key_tiles, row_off, qkv_f16)) return e;
+  // the per-element kernel: Philox words against p * 2^32; the MFMA kernels: the shared byte generator of common.h
+  uint32_t th = plan.family == PA_FWD_MFMA ? dropout_thresh8(drop_p) : dropout_thresh(drop_p), site32 = site;
+  float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  uint64_t seed64 = seed;
+  // (the per-element kernel's parameters are the first thirteen of the MFMA kernel's)
+  void* args[] = {&qkv_bf16, &bias_in, &s_out, &o_bf16, &key_pad, &N, &H, &ld, &scale, &th, &sc, &seed64, &site32, &key_tiles, &rag_store, &row_off};
+  const KernelRow& row = (plan.family == PA_FWD_MFMA ? g_pa_fwd_mfma : g_pa_fwd_elem)[plan.key];
+  (void)hipLaunchKernel(row.fn, dim3(plan.grid), dim3(plan.block), args, 0, (hipStream_t)stream);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

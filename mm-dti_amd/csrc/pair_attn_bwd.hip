@@ -171,10 +171,46 @@ __global__ __launch_bounds__(256) void pair_attn_bwd_kernel(const bf16_t* __rest
 MMDTI_DEFINE_SALT_PULL(pair_attn_bwd)
 using namespace mmdti;
 
-extern "C" int mmdti_pair_attn_bwd(mmdti_stream_t stream, const void* qkv_bf16, const void* s, const void* do_bf16,
-                                   void* g, void* dqkv_bf16, int B, int N, int H, int ld, float scale,
-                                   int g_in_zero, float drop_p, unsigned long long seed, unsigned int site, int layout,
-                                   const int* key_tiles, const int* row_off, int qkv_f16) {
+
+// every MFMA instance of this translation unit, at the row its key gives it (pair_attn_plan.h): the compact planes with fp32 gradients
+// (0..33) and the fp32 planes (68..87); rows 34..67 -- compact planes, bf16 gradients -- are pair_attn_bwd_g16.hip's
+static KernelRow g_pa_bwd_compact_f32[PA_BWD_COMPACT_ROWS] = {PA_BWD_COMPACT_TABLE(0, float)};
+// (per bucket: row-major on three and on four waves, tiled likewise, and the FULL form of the tile count that fills the bucket)
+#define PA_BWD_F32_ROW(NT, NWFULL)                                                                                                          \
+  KROW(pa_bwd_f32_key(pa_bucket(NT), 0, 0, 3), pair_attn_bwd_mfma_kernel<NT, false, false, 3, false, float, float>),                        \
+  KROW(pa_bwd_f32_key(pa_bucket(NT), 0, 0, 4), pair_attn_bwd_mfma_kernel<NT, false, false, 4, false, float, float>),                        \
+  KROW(pa_bwd_f32_key(pa_bucket(NT), 1, 0, 3), pair_attn_bwd_mfma_kernel<NT, true, false, 3, false, float, float>),                         \
+  KROW(pa_bwd_f32_key(pa_bucket(NT), 1, 0, 4), pair_attn_bwd_mfma_kernel<NT, true, false, 4, false, float, float>),                         \
+  KROW(pa_bwd_f32_key(pa_bucket(NT), 1, 1, NWFULL), pair_attn_bwd_mfma_kernel<NT, true, true, NWFULL, false, float, float>)
+static KernelRow g_pa_bwd_f32[20] = {PA_BWD_F32_ROW(5, 3), PA_BWD_F32_ROW(9, 3), PA_BWD_F32_ROW(13, 4), PA_BWD_F32_ROW(17, 3)};
+#undef PA_BWD_F32_ROW
+static_assert(pa_bwd_nw(5) == 3 && pa_bwd_nw(9) == 3 && pa_bwd_nw(13) == 4 && pa_bwd_nw(17) == 3, "the FULL rows above carry pa_bwd_nw of their tile count");
+static_assert(pa_bwd_nw(1) == 4 && pa_bwd_nw(2) == 4 && pa_bwd_nw(3) == 3 && pa_bwd_nw(4) == 4 && pa_bwd_nw(6) == 3 && pa_bwd_nw(7) == 4 && pa_bwd_nw(8) == 4 &&
+                  pa_bwd_nw(10) == 4 && pa_bwd_nw(11) == 4 && pa_bwd_nw(12) == 3 && pa_bwd_nw(14) == 4 && pa_bwd_nw(15) == 3 && pa_bwd_nw(16) == 3,
+              "PA_BWD_COMPACT_TABLE carries pa_bwd_nw of every tile count");
+// the per-element kernels: the plain form, then the deterministic one
+static KernelRow g_pa_bwd_elem[PA_BWD_ELEM_KERNELS] = {
+    KROW(pa_bwd_elem_key(1, 0), pair_attn_bwd_kernel<1>),       KROW(pa_bwd_elem_key(2, 0), pair_attn_bwd_kernel<2>),       KROW(pa_bwd_elem_key(3, 0), pair_attn_bwd_kernel<3>),
+    KROW(pa_bwd_elem_key(4, 0), pair_attn_bwd_kernel<4>),       KROW(pa_bwd_elem_key(5, 0), pair_attn_bwd_kernel<5>),       KROW(pa_bwd_elem_key(1, 1), pair_attn_bwd_kernel<1, true>),
+    KROW(pa_bwd_elem_key(2, 1), pair_attn_bwd_kernel<2, true>), KROW(pa_bwd_elem_key(3, 1), pair_attn_bwd_kernel<3, true>), KROW(pa_bwd_elem_key(4, 1), pair_attn_bwd_kernel<4, true>),
+    KROW(pa_bwd_elem_key(5, 1), pair_attn_bwd_kernel<5, true>),
+};
+static const KernelRow* pa_bwd_row(int family, int key) {
+  if (family == PA_BWD_ELEM) return key >= 0 && key < PA_BWD_ELEM_KERNELS ? &g_pa_bwd_elem[key] : nullptr;
+  if (key < 0 || key >= PA_BWD_MFMA_KERNELS) return nullptr;
+  return key < PA_BWD_COMPACT_ROWS ? &g_pa_bwd_compact_f32[key] : key < 2 * PA_BWD_COMPACT_ROWS ? &g_pa_bwd_compact_g16[key - PA_BWD_COMPACT_ROWS] : &g_pa_bwd_f32[key - 2 * PA_BWD_COMPACT_ROWS];
+}
+// row `key` of a pair-attention table (PairAttnFamily), null past its end
+const KernelRow* mmdti::pair_attn_kernel_row(int family, int key) {
+  if (family == PA_BWD_MFMA || family == PA_BWD_ELEM) return pa_bwd_row(family, key);
+  int n = 0;
+  const KernelRow* t = (family == PA_FWD_MFMA || family == PA_FWD_ELEM) ? pair_attn_fwd_table(family, &n) : nullptr;
+  return t && key >= 0 && key < n ? &t[key] : nullptr;
+}
+
+// What mmdti_pair_attn_bwd and mmdti_pair_attn_plan share: validate, plan.  Pointers are tested for null and alignment only.
+static int pair_attn_bwd_prepare(PairAttnPlan& plan, const void* qkv_bf16, const void* s, const void* do_bf16, const void* g, const void* dqkv_bf16, int B,
+                                 int N, int H, int ld, int layout, const void* key_tiles, const void* row_off, int qkv_f16, bool det) {
   // bit 0: tiled planes; bit 1: compact planes (s is fp16; tiled only); bit 2: g is bf16 (with bit 1 only)
   const int tiled = layout & 1, compact = (layout >> 1) & 1, g16 = (layout >> 2) & 1;
   if (int e = check_common("pair_attn_bwd", B, N, H, ld)) return e;
@@ -186,69 +222,46 @@ extern "C" int mmdti_pair_attn_bwd(mmdti_stream_t stream, const void* qkv_bf16, 
   MMDTI_REQUIRE(qkv_bf16 && s && do_bf16 && g && dqkv_bf16, "pair_attn_bwd: null pointer");
   MMDTI_REQUIRE(aligned16(qkv_bf16) && aligned16(do_bf16) && aligned16(dqkv_bf16), "pair_attn_bwd: alignment");
   MMDTI_REQUIRE(!tiled || (aligned16(s) && aligned16(g)), "pair_attn_bwd: tiled pair tensors must be 16-byte aligned");
-  const uint32_t th = dropout_thresh(drop_p);     // the per-element kernel: Philox words against p * 2^32
-  const uint32_t th8 = dropout_thresh8(drop_p);   // the MFMA kernel: the shared byte generator of common.h (as its forward)
-  const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  dim3 grid(B * H), block(256);
+  plan = pair_attn_bwd_plan(B, N, H, ld, tiled, compact, g16, aligned16(s) && aligned16(g), key_tiles != nullptr, det);
+  MMDTI_REQUIRE(plan.family == PA_BWD_MFMA || !qkv_f16,
+                "pair_attn_bwd: fp16 q | k | v are read by the MFMA kernels only (ld %% 4 == 0, N <= 272, 16-byte aligned pair tensors)");
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_pair_attn_bwd(mmdti_stream_t stream, const void* qkv_bf16, const void* s, const void* do_bf16,
+                                   void* g, void* dqkv_bf16, int B, int N, int H, int ld, float scale,
+                                   int g_in_zero, float drop_p, unsigned long long seed, unsigned int site, int layout,
+                                   const int* key_tiles, const int* row_off, int qkv_f16) {
+  PairAttnPlan plan;
+  if (int e = pair_attn_bwd_prepare(plan, qkv_bf16, s, do_bf16, g, dqkv_bf16, B, N, H, ld, layout, key_tiles, row_off, qkv_f16, det_table().on())) return e;
+  // the per-element kernel: Philox words against p * 2^32; the MFMA kernel: the shared byte generator of common.h (as its forward)
+  uint32_t th = plan.family == PA_BWD_MFMA ? dropout_thresh8(drop_p) : dropout_thresh(drop_p), site32 = site;
+  float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  uint64_t seed64 = seed;
+  const KernelRow* row = pa_bwd_row(plan.family, plan.key);
   hipStream_t st = (hipStream_t)stream;
-  if (ld % 4 == 0 && aligned16(s) && aligned16(g) && N <= 16 * PA_MAX_NT) {
-    const int nqb = (N + 15) / 16;
-    // (16 and 17 tiles: three waves and a register cap for two workgroups per CU -- with four waves the per-wave dK / dV accumulators
-    //  leave LDS for one workgroup, and 251 + 12 registers for one wave per SIMD: N = 250 / 258 took 4.2 / 3.9 ms against 2.15 at N = 240)
-    dim3 blk((nqb % 3 == 0 || nqb >= 16 || nqb == 5) ? 192 : (nqb < 4 ? 64 * nqb : 256));   // (5 blocks: 2,2,1 on three waves beats 2,1,1,1 on four)
-#define PA_MB(NT, TL, FL, NWV, RG, ST, GT)                                                                                     \
-  hipLaunchKernelGGL((pair_attn_bwd_mfma_kernel<NT, TL, FL, NWV, RG, ST, GT>), grid, blk, 0, st, (const bf16_t*)qkv_bf16,      \
-                     (const ST*)s, (const bf16_t*)do_bf16, (const GT*)g, (GT*)g, (bf16_t*)dqkv_bf16, N, H, ld, scale,           \
-                     g_in_zero, th8, sc, (uint64_t)seed, (uint32_t)site, key_tiles, row_off, qkv_f16)
-#define PA_MBW(NT, TL, FL, RG, ST, GT)                                                      \
-  do {                                                                                      \
-    if (blk.x == 192) PA_MB(NT, TL, FL, 3, RG, ST, GT); else PA_MB(NT, TL, FL, 4, RG, ST, GT); \
-  } while (0)
-#define PA_MBT(NT)                                                                          \
-  do {                                                                                      \
-    if (!tiled) PA_MBW(NT, false, false, false, float, float);                              \
-    else { if (nqb == NT) PA_MBW(NT, true, true, false, float, float); else PA_MBW(NT, true, false, false, float, float); } \
-  } while (0)
-    // (compact planes -- the hot path -- have one instantiation per tile count, for fp32 and for bf16 gradients: pair_attn_bwd_mfma.h)
-    if (compact) {
-      if (g16) pa_bwd_compact_launch_g16(nqb, grid, blk, st, qkv_bf16, s, do_bf16, g, dqkv_bf16, N, H, ld, scale, g_in_zero, th8, sc, seed, site, key_tiles, row_off, qkv_f16);
-      else pa_bwd_compact_launch<float>(nqb, grid, blk, st, qkv_bf16, s, do_bf16, g, dqkv_bf16, N, H, ld, scale, g_in_zero, th8, sc, seed, site, key_tiles, row_off, qkv_f16);
-    } else if (nqb <= 5) PA_MBT(5); else if (nqb <= 9) PA_MBT(9); else if (nqb <= 13) PA_MBT(13); else PA_MBT(17);
-#undef PA_MBW
-#undef PA_MBT
-#undef PA_MB
-    MMDTI_LAUNCH_CHECK();
-    return MMDTI_OK;
+  if (plan.family == PA_BWD_MFMA) {
+    void* args[] = {&qkv_bf16, &s, &do_bf16, &g, &g, &dqkv_bf16, &N, &H, &ld, &scale, &g_in_zero, &th, &sc, &seed64, &site32, &key_tiles, &row_off, &qkv_f16};
+    (void)hipLaunchKernel(row->fn, dim3(plan.grid), dim3(plan.block), args, 0, st);
+  } else {
+    void* args[] = {&qkv_bf16, &s, &do_bf16, &g, &dqkv_bf16, &N, &H, &ld, &scale, &g_in_zero, &th, &sc, &seed64, &site32};
+    (void)hipLaunchKernel(row->fn, dim3(plan.grid), dim3(plan.block), args, 0, st);
   }
-  MMDTI_REQUIRE(!qkv_f16, "pair_attn_bwd: fp16 q | k | v are read by the MFMA kernels only (ld %% 4 == 0, N <= 272, 16-byte aligned pair tensors)");
-#define PA_B(NCH)                                                                                                   \
-  hipLaunchKernelGGL((pair_attn_bwd_kernel<NCH>), grid, block, 0, st, (const bf16_t*)qkv_bf16, (const float*)s,    \
-                     (const bf16_t*)do_bf16, (float*)g, (bf16_t*)dqkv_bf16, N, H, ld, scale, g_in_zero, th, sc,            \
-                     (uint64_t)seed, (uint32_t)site)
-#define PA_D(NCH)                                                                                                   \
-  hipLaunchKernelGGL((pair_attn_bwd_kernel<NCH, true>), grid, block, 0, st, (const bf16_t*)qkv_bf16, (const float*)s, \
-                     (const bf16_t*)do_bf16, (float*)g, (bf16_t*)dqkv_bf16, N, H, ld, scale, g_in_zero, th, sc,            \
-                     (uint64_t)seed, (uint32_t)site)
-  if (det_table().on()) {      // the deterministic mode: the waves of a workgroup add in wave order
-    switch ((N + 63) / 64) {
-      case 1: PA_D(1); break;
-      case 2: PA_D(2); break;
-      case 3: PA_D(3); break;
-      case 4: PA_D(4); break;
-      default: PA_D(5); break;
-    }
-    MMDTI_LAUNCH_CHECK();
-    return MMDTI_OK;
-  }
-#undef PA_D
-  switch ((N + 63) / 64) {
-    case 1: PA_B(1); break;
-    case 2: PA_B(2); break;
-    case 3: PA_B(3); break;
-    case 4: PA_B(4); break;
-    default: PA_B(5); break;
-  }
-#undef PA_B
   MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_pair_attn_plan(int backward, int deterministic, const void* qkv_bf16, const void* s, const void* o_or_do_bf16, const void* g,
+                                    const void* dqkv_bf16, int B, int N, int H, int ld, float drop_p, int layout, const int* key_tiles,
+                                    const int* row_off, int qkv_f16, int* plan_out) {
+  MMDTI_REQUIRE(plan_out != nullptr, "pair_attn_plan: null plan_out");
+  PairAttnPlan plan;
+  if (backward) {
+    if (int e = pair_attn_bwd_prepare(plan, qkv_bf16, s, o_or_do_bf16, g, dqkv_bf16, B, N, H, ld, layout, key_tiles, row_off, qkv_f16, deterministic != 0)) return e;
+  } else {
+    if (int e = pair_attn_fwd_prepare(plan, qkv_bf16, s, g, o_or_do_bf16, B, N, H, ld, drop_p, layout, key_tiles, row_off, qkv_f16)) return e;
+  }
+  static_assert(PAIR_ATTN_PLAN_INTS == 6, "mmdti_hip.h documents 6 ints");
+  memcpy(plan_out, &plan, sizeof(plan));
   return MMDTI_OK;
 }

@@ -303,30 +303,18 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
 }
 
 
-// compact planes (layout 3 / 7): one FULL instantiation per tile count; key_tiles != null: the ragged (RAG) sweeps
-template <typename GT>
-static inline void pa_bwd_compact_launch(int nqb, dim3 grid, dim3 blk, hipStream_t st, const void* qkv_bf16, const void* s, const void* do_bf16,
-                                         void* g, void* dqkv_bf16, int N, int H, int ld, float scale, int g_in_zero, uint32_t th8, float sc,
-                                         unsigned long long seed, unsigned int site, const int* key_tiles, const int* row_off, int qkv_f16) {
-#define PA_MBH(NT, NWV, RG)                                                                                                   \
-  hipLaunchKernelGGL((pair_attn_bwd_mfma_kernel<NT, true, true, NWV, RG, _Float16, GT>), grid, blk, 0, st, (const bf16_t*)qkv_bf16, \
-                     (const _Float16*)s, (const bf16_t*)do_bf16, (const GT*)g, (GT*)g, (bf16_t*)dqkv_bf16, N, H, ld, scale,    \
-                     g_in_zero, th8, sc, (uint64_t)seed, (uint32_t)site, key_tiles, row_off, qkv_f16)
-#define PA_MBC(NT)                                                                                   \
-  case NT:                                                                                           \
-    if (key_tiles) PA_MBH(NT, ((NT % 3 == 0 || NT >= 16 || NT == 5) ? 3 : 4), true);                 \
-    else PA_MBH(NT, ((NT % 3 == 0 || NT >= 16 || NT == 5) ? 3 : 4), false);                          \
-    break
-  switch (nqb) {
-    PA_MBC(1); PA_MBC(2); PA_MBC(3); PA_MBC(4); PA_MBC(5); PA_MBC(6); PA_MBC(7); PA_MBC(8); PA_MBC(9); PA_MBC(10); PA_MBC(11);
-    PA_MBC(12); PA_MBC(13); PA_MBC(14); PA_MBC(15); PA_MBC(16); PA_MBC(17);
-  }
-#undef PA_MBC
-#undef PA_MBH
-}
-// the bf16-gradient build of the same launcher (pair_attn_bwd_g16.hip)
-void pa_bwd_compact_launch_g16(int nqb, dim3 grid, dim3 blk, hipStream_t st, const void* qkv_bf16, const void* s, const void* do_bf16, void* g,
-                               void* dqkv_bf16, int N, int H, int ld, float scale, int g_in_zero, uint32_t th8, float sc,
-                               unsigned long long seed, unsigned int site, const int* key_tiles, const int* row_off, int qkv_f16);
+// compact planes (layout 3 / 7): one FULL instantiation per tile count, dense and ragged (RAG), with the wave count pa_bwd_nw gives that
+// tile count -- the 34 rows a translation unit contributes to the backward's table for its gradient type GT (G16: 0 float, 1 __bf16)
+#define PA_BWD_COMPACT_ROW(G16, GT, NT, NWV)                                                                              \
+  KROW(pa_bwd_compact_key(G16, NT, 0), pair_attn_bwd_mfma_kernel<NT, true, true, NWV, false, _Float16, GT>),              \
+  KROW(pa_bwd_compact_key(G16, NT, 1), pair_attn_bwd_mfma_kernel<NT, true, true, NWV, true, _Float16, GT>)
+#define PA_BWD_COMPACT_TABLE(G16, GT)                                                                                                        \
+  PA_BWD_COMPACT_ROW(G16, GT, 1, 4), PA_BWD_COMPACT_ROW(G16, GT, 2, 4), PA_BWD_COMPACT_ROW(G16, GT, 3, 3), PA_BWD_COMPACT_ROW(G16, GT, 4, 4),    \
+  PA_BWD_COMPACT_ROW(G16, GT, 5, 3), PA_BWD_COMPACT_ROW(G16, GT, 6, 3), PA_BWD_COMPACT_ROW(G16, GT, 7, 4), PA_BWD_COMPACT_ROW(G16, GT, 8, 4),    \
+  PA_BWD_COMPACT_ROW(G16, GT, 9, 3), PA_BWD_COMPACT_ROW(G16, GT, 10, 4), PA_BWD_COMPACT_ROW(G16, GT, 11, 4), PA_BWD_COMPACT_ROW(G16, GT, 12, 3), \
+  PA_BWD_COMPACT_ROW(G16, GT, 13, 4), PA_BWD_COMPACT_ROW(G16, GT, 14, 4), PA_BWD_COMPACT_ROW(G16, GT, 15, 3), PA_BWD_COMPACT_ROW(G16, GT, 16, 3), \
+  PA_BWD_COMPACT_ROW(G16, GT, 17, 3)
+// the bf16-gradient rows (pair_attn_bwd_g16.hip)
+extern KernelRow g_pa_bwd_compact_g16[PA_BWD_COMPACT_ROWS];
 
 }  // namespace mmdti

@@ -55,8 +55,8 @@ FLT_MAX = float(torch.finfo(F32).max)
 FMIN = float(torch.finfo(F32).min)
 EPS, ETA, U16 = 2.0 ** -23, 2.0 ** -126, 2.0 ** -8
 SEED, SITE = 987654321, 3
-ATTN_NT_LINE = "static inline int attn_nt(int Lk) { return Lk <= 160 ? 10 : Lk <= 256 ? 16 : Lk <= 384 ? 24 : 32; }"
 Z_MAX = 6.0
+PTR = 0x10000          # a fake, 16-byte aligned device address: mmdti_attn_plan never dereferences one
 
 
 def attn_nt(Lk):
@@ -119,6 +119,46 @@ def case_id(c):
 
 def instances(c):
     return (f"attn_fwd_kernel<{c['hd']}, {c['nt']}>", f"attn_bwd_q_kernel<{c['hd']}, {c['nt']}>", f"attn_bwd_kv_kernel<{c['hd']}>")
+
+
+def declared_plan(hd, Lq, Lk, nb, backward):
+    """what a call is declared to launch, stated independently of csrc/attn_plan.h: (nt, lqp, [(instance, grid, workgroup size, dynamic
+    LDS bytes, LDS opt-in)]) -- one workgroup per (sequence, head); K and V (dK/dV: Q and dO) images of hd + 8 columns and one (four)
+    fp32 row vectors; the opt-in is the largest image pair of the short (256 rows) or the long (512 rows) entry points."""
+    nt, lqp = attn_nt(Lk), ((Lq + 31) // 32) * 32
+    short, long_ = 2 * 256 * 80 * 2 + 4 * 256 * 4, 2 * 512 * 72 * 2 + 4 * 512 * 4
+    img = 2 * nt * 16 * (hd + 8) * 2 + nt * 16 * 4
+    cap = long_ if nt > 16 else short
+    if not backward:
+        return nt, lqp, [(f"attn_fwd_kernel<{hd}, {nt}>", nb * HEADS, 256 if (hd, nt) == (16, 32) else 512, img, cap)]
+    kv = 2 * lqp * (hd + 8) * 2 + 4 * lqp * 4
+    return nt, lqp, [(f"attn_bwd_q_kernel<{hd}, {nt}>", nb * HEADS, 1024 if nt > 16 else 256, img, cap),
+                     (f"attn_bwd_kv_kernel<{hd}>", nb * HEADS, 512, kv, long_ if kv > short else short)]
+
+
+def library_plan(lib, backward, long_entry, hd, Lq, Lk, nb, ptr=None, ld=None, add=0, vargs=(0, 0, 0, 0), p_drop=0.0):
+    """mmdti_attn_plan's answer in the form of declared_plan.  ptr / ld: the addresses and row strides of a launch (place()); default: fake
+    aligned addresses and tight rows."""
+    import ctypes
+    D = HEADS * hd
+    ptr = ptr or {n: PTR for n in ("q", "k", "v", "ctx", "do", "dq", "dk", "dv", "stats", "drow")}
+    ld = ld or {n: D for n in ("q", "k", "ctx", "do", "dq", "dk")}
+    out = (ctypes.c_int * 13)()
+    lib.mmdti_attn_plan(int(backward), int(long_entry), ptr["q"], ptr["k"], ptr["v"], add, ptr["do"] if backward else ptr["ctx"], ptr["stats"], ptr["drow"],
+                        ptr["dq"], ptr["dk"], ptr["dv"], nb, HEADS, Lq, Lk, hd, ld["q"], ld["k"], ld["do"] if backward else ld["ctx"], ld["dq"], ld["dk"],
+                        p_drop, *vargs, out)
+    p = list(out)
+    name = lambda i: lib._dll.mmdti_plan_kernel_name(0, i).decode()
+    return p[0], p[1], [(name(p[3 + 5 * i]),) + tuple(p[4 + 5 * i:8 + 5 * i]) for i in range(p[2])]
+
+
+def assert_declared_plan(lib, c, nb, ptr=None, ld=None, add=0, vargs=(0, 0, 0, 0), p_drop=0.0, entry=None):
+    """the library plans, for the case's forward and backward, what the table declares"""
+    for backward in (False, True):
+        got = library_plan(lib, backward, (entry or c["entry"]) == "long", c["hd"], c["Lq"], c["Lk"], nb, ptr, ld, add, vargs, p_drop)
+        want = declared_plan(c["hd"], c["Lq"], c["Lk"], nb, backward)
+        assert got == want and (got[0], got[1]) == (c["nt"], c["lqp"]), (case_id(c), backward, got, want)
+        assert tuple(k[0] for k in got[2]) == (instances(c)[1:] if backward else instances(c)[:1]), (case_id(c), got)
 
 
 def runs(modes):

@@ -3,8 +3,9 @@ test_gbf_cases_cpu.py (which proves that the table reaches every kernel instance
 exact mode is exact, that an fp32 emulation of the kernels' rounding points stays inside the bounds and that six wrong emulations do
 not) and test_gbf_instances_gpu.py (which holds the kernels to the reference on the device).
 
-INSTANCES (instance(), a mirror of gbf_bias_fwd_any, mmdti_gbf_bias_bwd, gbf_bias_bwd_full_any and mmdti_gbf_features_fwd / _bwd; the
-lines it depends on are kept verbatim in SOURCE_LINES): 9 gbf_bias_fwd_kernel<SAVE, TILED, OT, COORDS>, 3 gbf_bias_bwd_kernel<TILED, GT>,
+INSTANCES (instance() and launch(), the independent statement of what each case is declared to run; test_gbf_cases_cpu.py holds the
+library's own answer, mmdti_gbf_plan, to it for every case and for a sweep of shapes; SOURCE_LINES keeps the rounding points and
+device-side rules the reference depends on verbatim): 9 gbf_bias_fwd_kernel<SAVE, TILED, OT, COORDS>, 3 gbf_bias_bwd_kernel<TILED, GT>,
 12 gbf_bias_bwd_full_kernel<TILED, GT, DET, COORDS>, gbf_fwd_kernel, gbf_bwd_kernel, gbf_bwd_det_kernel: 27.  gbf_slab_reduce_kernel
 runs behind every complete backward that is handed a workspace and is held through its outputs.
 
@@ -86,9 +87,6 @@ MODES = ("onehot", "random", "clamp")
 
 SOURCE_LINES = (
     "constexpr float GBF_A = 2.5066272160f;  // sqrt(2*3.14159) -- truncated pi exactly as mm_model.py:222-223",
-    "constexpr int GBF_MAXE = 4096;",
-    "constexpr int GBF_FWD_MAXE = 4096;",
-    "constexpr int GBF_FULL_MAXE = 1536;   // 4 per-edge-type fp32 tables next to 126 KB of tiles in the CU's 160 KB",
     "sg[i] = fabsf(stds[k0 + i]) + 1e-5f;",
     "const float sg = fabsf(stds[tid]) + 1e-5f;",
     "sCf[tid] = 1.0f / (GBF_A * sg);",
@@ -108,23 +106,6 @@ SOURCE_LINES = (
     "const float ds = stds[k] < 0.f ? -sgv : sgv;        // d|std|/dstd",
     "for (int j = 0; j < 8; ++j) gv[c * 8 + j] = valid ? gbf_get(gp + (long long)(32 * c + 8 * g + j) * plane) : 0.f;",   # an invalid lane loads nothing
     "const unsigned voff = (unsigned)(8 * g) * (unsigned)plane + (unsigned)(valid ? q : 0);",                               # ... or slot 0: pair (0, 0)
-    "const int tpm = tiled ? nb4 * nb4 : cdiv((long long)N * ld, 16);",
-    "const int grid = (int)((ntiles + 7) / 8 < 512 ? (ntiles + 7) / 8 : 512);     // two resident workgroups per CU",
-    "const int ltab = E <= GBF_FWD_MAXE ? 1 : 0;",
-    "const int grid = (int)(ntiles / 4 + 1 < 1024 ? ntiles / 4 + 1 : 1024);",
-    "const int grid = (int)((ntiles + 7) / 8 < 256 ? (ntiles + 7) / 8 : 256);",
-    "float* slab = (workspace && aligned16(workspace) && workspace_bytes >= (long long)grid * SL * 4) ? reinterpret_cast<float*>(workspace) : nullptr;",
-    "if (compact) GBF_LC(false, true, _Float16, true); else if (tiled) GBF_LC(false, true, float, true); else GBF_LC(false, false, float, true);",
-    "} else if (compact) { if (save) GBF_L(true, true, _Float16); else GBF_L(false, true, _Float16); }",
-    "else if (save) { if (tiled) GBF_L(true, true, float); else GBF_L(true, false, float); }",
-    "else           { if (tiled) GBF_L(false, true, float); else GBF_L(false, false, float); }",
-    "if (compact) GBF_B(true, __bf16); else if (tiled) GBF_B(true, float); else GBF_B(false, float);",
-    "do { if (compact) GBF_FX(true, __bf16, DET, COORDS); else if (tiled) GBF_FX(true, float, DET, COORDS); else GBF_FX(false, float, DET, COORDS); } while (0)",
-    "if (det) { if (rec) GBF_FL(true, true); else GBF_FL(true, false); }",
-    "else if (rec) GBF_FL(false, true); else GBF_FL(false, false);",
-    "if (blocks > 256 * 32) blocks = 256 * 32;",
-    "if (blocks > 256 * 8) blocks = 256 * 8;",
-    "const size_t smem = E <= GBF_MAXE ? 2 * (size_t)E * sizeof(float) : 0;",
 )
 
 
@@ -272,9 +253,63 @@ def launch(c, geo=None):
     return dict(tpm=tpm, ntiles=ntiles, grid=grid, rounds=-(-ntiles // (per * grid)))
 
 
-def acc_count(c, t=None):
-    """n of the sums over pairs: the pairs one workgroup adds up (in any order) + the partial sums that meet afterwards"""
+ENTRY = {"ffwd": 0, "fbwd": 1, "fwd": 2, "bwd": 3, "full": 4}
+PTR = 0x10000          # a fake, 16-byte aligned device address: mmdti_gbf_plan never dereferences one
+PLAN_FIELDS = ("name", "grid", "block", "lds", "lds_cap", "tpm", "ntiles", "ltab", "slab", "reduce_grid")
+
+
+def workspace_bytes(E):
+    """mmdti_gbf_bias_bwd_full_workspace: one slab per workgroup of the largest grid"""
+    return 256 * (GBF_SLAB + 2 * E) * 4
+
+
+def canonical(name):
+    """a table name with its defaulted template arguments written out, as instance() spells it"""
+    if "<" not in name:
+        return name
+    kern, args = name[:-1].split("<")
+    args = args.split(", ")
+    full = {"gbf_bias_fwd_kernel": 4, "gbf_bias_bwd_kernel": 2, "gbf_bias_bwd_full_kernel": 4}[kern]
+    return f"{kern}<{', '.join(args + ['false'] * (full - len(args)))}>"
+
+
+def library_plan(lib, c, esz=8, det=None, ws=None, operands=PTR, aligned=PTR):
+    """mmdti_gbf_plan's answer for a case (any dict with the keys of add()) -> dict of PLAN_FIELDS.  ws: workspace bytes handed to the
+    complete backward (default: what the case declares)."""
+    import ctypes
+    k, N = c["kind"], c["N"]
+    ws = (workspace_bytes(c["E"]) if c["ws"] else 0) if ws is None else ws
+    p = lambda on: PTR if on else 0
+    out = (ctypes.c_longlong * 10)()
+    lib.mmdti_gbf_plan(ENTRY[k], int(c["det"] if det is None else det), operands, aligned, p(c["save"]), p(c["coords"]), p(c["lens"] is not None), p(c["packed"]),
+                       p(ws and k == "full"), ws, c["B"] * N * N, c["B"], N, c["ld"], K, F, H, c["E"], c["V"], PAD, esz, flags(c), out)
+    v = list(out)
+    return dict(zip(PLAN_FIELDS, [canonical(lib.mmdti_plan_kernel_name(1, v[0]).decode())] + v[1:]))
+
+
+def declared_plan(c):
+    """what the case is declared to launch, from instance() and launch(): every field of the library's plan but the LDS sizes"""
+    k = c["kind"]
     L = launch(c)
+    host = L["ntiles"] if c["lens"] is None else c["B"] * L["tpm"]       # (the host does not see a ragged batch's prefix)
+    slab = int(c["det"]) if k == "fbwd" else int(bool(c["ws"])) if k == "full" else 0
+    return dict(name=instance(c), grid=L["grid"], block={"fwd": 512, "full": 512}.get(k, 256), tpm=L["tpm"], ntiles=host,
+                ltab=int(k == "fwd" and c["E"] <= GBF_FWD_MAXE), slab=slab, reduce_grid=-(-(GBF_SLAB + 2 * c["E"]) // 64) if slab and k == "full" else 0)
+
+
+def assert_declared_plan(lib, c, esz=8):
+    got, want = library_plan(lib, c, esz), declared_plan(c)
+    assert {f: got[f] for f in want} == want, (case_id(c), got, want)
+    return got
+
+
+def acc_count(c, t=None):
+    """n of the sums over pairs: the pairs one workgroup adds up (in any order) + the partial sums that meet afterwards.  The grid is the
+    library's (mmdti_gbf_plan); the rounds follow from it and the tiles the kernel enumerates."""
+    from mmdti_hip import _abi
+    grid = library_plan(_abi.lib(), c)["grid"]
+    per = {"fwd": 8, "full": 8, "bwd": 4}.get(c["kind"], 1)
+    L = dict(grid=grid, rounds=-(-launch(c)["ntiles"] // (per * grid)))
     if c["kind"] == "full":
         return 256 * L["rounds"] + L["grid"] + 8              # (128 pairs a round, twice the products with the hi + lo pair)
     if c["kind"] == "bwd":

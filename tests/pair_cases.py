@@ -4,8 +4,9 @@ with float64 autograd, that the exact modes are exact, and that an fp32 emulatio
 bounds while two wrong emulations do not) and test_pair_instances_gpu.py (which holds the kernel instances of csrc/pair_attn.hip,
 pair_attn_bwd.hip, pair_attn_bwd_mfma.h and pair_attn_bwd_g16.hip to the reference on the device).
 
-INSTANCES (instances(), a mirror of the two launchers; the source lines it depends on are kept verbatim in SOURCE_LINES and looked up
-by the CPU test).  MFMA kernels serve ld % 4 == 0, 16-byte aligned planes and N <= 272; everything else runs the per-element
+INSTANCES (instances() / blocks(): the independent statement of what each case is declared to run; the CPU test holds the library's own
+answer, mmdti_pair_attn_plan, to it for every case and for a sweep of every size, the GPU suite before every launch; SOURCE_LINES keeps
+the device-side rules it mirrors verbatim).  MFMA kernels serve ld % 4 == 0, 16-byte aligned planes and N <= 272; everything else runs the per-element
 kernels <NCH = ceil(N / 64)> (backward: x deterministic mode).  fp32 planes (layout 0 row-major, 1 tiled) run the buckets NT = 5 / 9 /
 13 / 17, tiled ones FULL when ceil(N / 16) == NT; compact planes (3: fp16 logits, 7: bf16 gradients too) have one instantiation per
 tile count, dense and ragged, the forward also for fp16 q | k | v.  The backward's NW (3 or 4 waves) follows its workgroup size.
@@ -68,43 +69,17 @@ PA_MAX_NT = 17
 SEED, SITE = 20240607, 5
 LOG2E32 = torch.tensor(1.44269504088896340736, dtype=F32)
 
-# the lines of the launchers (and of pa_kt_effective) that instances() mirrors
+# the device-side rules (pa_kt_effective, the size limit) that instances() and geometry() mirror; what the launchers choose is asked of the
+# library (library_plan)
 SOURCE_LINES = {
     "pair_attn.h": (
-        "#define PA_MAX_NT 17",
         "__host__ __device__ constexpr int pa_kt_step(int nt) { return nt <= 9 ? 1 : (nt <= 13 ? 2 : 4); }",
         "const int s = pa_kt_step(nt), k = ((kt < 1 ? 1 : kt) + s - 1) / s * s;",
         "return k >= nt ? nt : k;",
         "MMDTI_REQUIRE(N <= 320,",
     ),
-    "pair_attn.hip": (
-        "if (ld % 4 == 0 && aligned16(bias_in) && aligned16(s_out) && N <= 16 * PA_MAX_NT) {",
-        "dim3 blk(nqb % 3 == 0 ? 192 : (nqb < 4 ? 64 * nqb : 256));",
-        "else if (!compact) { if (nqb == NT) PA_M(NT, true, true, false, float); else PA_M(NT, true, false, false, float); }",
-        "#define PA_MC(NT) case NT: if (qkv_f16) { if (key_tiles) PA_MH(NT, true); else PA_MH(NT, false); } \\",
-        "else if (key_tiles) PA_M(NT, true, true, true, _Float16); else PA_M(NT, true, true, false, _Float16); break",
-        "} else if (nqb <= 5) PA_MT(5); else if (nqb <= 9) PA_MT(9); else if (nqb <= 13) PA_MT(13); else PA_MT(17);",
-        "switch ((N + 63) / 64) {",
-        "default: PA_F(5); break;",
-    ),
-    "pair_attn_bwd.hip": (
-        "if (ld % 4 == 0 && aligned16(s) && aligned16(g) && N <= 16 * PA_MAX_NT) {",
-        "dim3 blk((nqb % 3 == 0 || nqb >= 16 || nqb == 5) ? 192 : (nqb < 4 ? 64 * nqb : 256));",
-        "if (blk.x == 192) PA_MB(NT, TL, FL, 3, RG, ST, GT); else PA_MB(NT, TL, FL, 4, RG, ST, GT); \\",
-        "else { if (nqb == NT) PA_MBW(NT, true, true, false, float, float); else PA_MBW(NT, true, false, false, float, float); } \\",
-        "} else if (nqb <= 5) PA_MBT(5); else if (nqb <= 9) PA_MBT(9); else if (nqb <= 13) PA_MBT(13); else PA_MBT(17);",
-        "if (det_table().on()) {",
-        "switch ((N + 63) / 64) {",
-        "default: PA_D(5); break;",
-        "default: PA_B(5); break;",
-    ),
-    "pair_attn_bwd_mfma.h": (
-        "if (key_tiles) PA_MBH(NT, ((NT % 3 == 0 || NT >= 16 || NT == 5) ? 3 : 4), true);                 \\",
-        "else PA_MBH(NT, ((NT % 3 == 0 || NT >= 16 || NT == 5) ? 3 : 4), false);                          \\",
-        "hipLaunchKernelGGL((pair_attn_bwd_mfma_kernel<NT, true, true, NWV, RG, _Float16, GT>), grid, blk, 0, st, (const bf16_t*)qkv_bf16, \\",
-    ),
-    "pair_attn_bwd_g16.hip": ("pa_bwd_compact_launch<__bf16>(nqb,",),
 }
+PTR = 0x10000          # a fake, 16-byte aligned device address: mmdti_pair_attn_plan never dereferences one
 
 
 # ------------------------------------------------------------------------------------------------ layout arithmetic (mirrors of ops / common.h)
@@ -173,6 +148,35 @@ def instances(c):
 def blocks(c):
     """workgroup sizes of the two launches"""
     return (fwd_block(tiles(c["N"])), bwd_block(tiles(c["N"]))) if mfma(c) else (256, 256)
+
+
+def declared_plan(c, backward):
+    """what a case is declared to launch, from instances() and blocks(): (kernel, grid, workgroup size, nqb, NW)"""
+    f, b, _ = instances(c)
+    nqb = tiles(c["N"]) if mfma(c) else 0
+    nw = (3 if bwd_block(nqb) == 192 else 4) if backward and nqb else 0
+    return (b if backward else f, c["B"] * c["H"], blocks(c)[int(backward)], nqb, nw)
+
+
+def library_plan(lib, c, backward, ptr=None):
+    """mmdti_pair_attn_plan's answer in the form of declared_plan.  ptr: the addresses of a launch (qkv, s, g, o, dqkv: for the forward s is
+    bias_in, g is s_out); default: fake aligned ones, the planes 4 bytes off in a `shift` case."""
+    import ctypes
+    plane = PTR + (4 if c["shift"] else 0)
+    ptr = ptr or dict(qkv=PTR, s=plane, g=plane, o=PTR, dqkv=PTR)
+    out = (ctypes.c_int * 6)()
+    lib.mmdti_pair_attn_plan(int(backward), int(c["det"]), ptr["qkv"], ptr["s"], ptr["o"], ptr["g"], ptr["dqkv"], c["B"], c["N"], c["H"], c["ld"], 0.0,
+                             c["layout"] if backward else c["layout"] & 3, PTR if c["lens"] is not None else 0, PTR if c["packed"] else 0, int(c["f16"]), out)
+    family, key, grid, block, nqb, nw = list(out)
+    name = lib.mmdti_plan_kernel_name(2 + family, key).decode()
+    if name.startswith("pair_attn_bwd_kernel<") and "," not in name:          # (the table leaves the defaulted DET = false out)
+        name = name[:-1] + ", false>"
+    return (name, grid, block, nqb, nw)
+
+
+def assert_declared_plan(lib, c, backward, ptr=None):
+    got, want = library_plan(lib, c, backward, ptr), declared_plan(c, backward)
+    assert got == want, (case_id(c), backward, got, want)
 
 
 # ------------------------------------------------------------------------------------------------ the table

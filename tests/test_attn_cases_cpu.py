@@ -1,21 +1,86 @@
 """The case table of tests/attn_cases.py, checked without a GPU: that it reaches all 27 kernel instances of csrc/attn.hip by the rule of
-attn_nt (still verbatim in the source), through both entry points, at the edges the issue lists; that the float64 reference agrees
+attn_nt, through both entry points, at the edges the issue lists -- and that the library, asked through the launch-free query
+mmdti_attn_plan, plans for every case and for a sweep of every length what the table declares; that the float64 reference agrees
 with float64 autograd; that the exact modes are exact by construction; and that an fp32 emulation of the kernels' rounding points
 (P' and dS to bf16, the outputs to bf16 / fp16) stays inside the bounds the device results are held to -- while the same emulation
 with a softmax denominator wrong by 1 / 256 does not."""
+import ctypes
 import os
 
 import pytest
 import torch
+
+from mmdti_hip import _abi
 
 import attn_cases as A
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _table_names():
+    lib = _abi.lib()
+    n = ctypes.c_int()
+    lib.mmdti_plan_table_size(0, ctypes.byref(n))
+    names = [lib.mmdti_plan_kernel_name(0, i).decode() for i in range(n.value)]
+    assert lib.mmdti_plan_kernel_name(0, n.value) is None and lib.mmdti_plan_kernel_name(0, -1) is None
+    return names
+
+
+def test_the_library_plans_what_every_case_declares():
+    """instance names, grid, workgroup size, LDS, LDS opt-in, nt and lqp of every case, through its own entry point -- and, up to 256
+    queries and keys, through the other one"""
+    lib = _abi.lib()
+    for c in A.CASES:
+        nb = len(c["packed"][0]) if c["packed"] else A.B
+        A.assert_declared_plan(lib, c, nb)
+        if max(c["Lq"], c["Lk"]) <= 256:
+            A.assert_declared_plan(lib, c, nb, entry="long" if c["entry"] == "short" else "short")
+    names = _table_names()
+    assert len(names) == len(set(names)) == 27 and set(names) == {i for c in A.CASES for i in A.instances(c)}
+
+
+EDGES = (1, 31, 32, 33, 160, 161, 256, 257, 384, 385, 480, 481, 512)
+
+
+def test_a_sweep_of_every_length_plans_the_declared_launches_or_refuses_as_the_launcher_does():
+    """Lq = 1..512 at the edges of Lk and Lk = 1..512 at the edges of Lq, three head sizes, both entry points, forward and backward; every
+    table row is reached, and nothing outside the table is named"""
+    lib = _abi.lib()
+    seen = set()
+    pairs = sorted({(lq, lk) for lq in range(1, 513) for lk in EDGES} | {(lq, lk) for lq in EDGES for lk in range(1, 513)})
+    for hd in (16, 32, 64):
+        for long_entry in (0, 1):
+            cap = 512 if long_entry else 256
+            for backward in (0, 1):
+                who = ("attn_long_" if long_entry else "attn_") + ("bwd" if backward else "fwd")
+                for lq, lk in pairs:
+                    if max(lq, lk) > cap:
+                        with pytest.raises(_abi.MMDTIError, match=rf"{who}: at most {cap} queries / keys per head \(got {lq} / {lk}\)"):
+                            A.library_plan(lib, backward, long_entry, hd, lq, lk, 2)
+                        continue
+                    got = A.library_plan(lib, backward, long_entry, hd, lq, lk, 2)
+                    assert got == A.declared_plan(hd, lq, lk, 2, backward), (hd, long_entry, backward, lq, lk, got)
+                    seen |= {k[0] for k in got[2]}
+    assert seen == set(_table_names())
+
+
+def test_the_plan_query_validates_like_the_launch():
+    lib = _abi.lib()
+    ok = {n: A.PTR for n in ("q", "k", "v", "ctx", "do", "dq", "dk", "dv", "stats", "drow")}
+    for backward, bad, msg in ((0, dict(q=0), "attn_fwd: bad arguments"), (0, dict(k=A.PTR + 8), "attn_fwd: 16-byte alignment required"),
+                               (0, dict(ctx=A.PTR + 4), "attn_fwd: bad output arguments"), (1, dict(drow=0), "attn_bwd: null argument"),
+                               (1, dict(do=A.PTR + 8), "attn_bwd: dctx stride/alignment"), (1, dict(dv=A.PTR + 4), "attn_bwd: output stride/alignment")):
+        with pytest.raises(_abi.MMDTIError, match=msg):
+            A.library_plan(lib, backward, 0, 32, 16, 16, 2, ptr=dict(ok, **bad))
+    with pytest.raises(_abi.MMDTIError, match="head_dim must be 16, 32 or 64"):
+        A.library_plan(lib, 0, 0, 48, 16, 16, 2)
+    with pytest.raises(_abi.MMDTIError, match="come together"):
+        A.library_plan(lib, 0, 0, 32, 16, 16, 2, vargs=(A.PTR, 0, 0, 32))
+    with pytest.raises(_abi.MMDTIError, match="dropout p out of range"):
+        A.library_plan(lib, 1, 1, 32, 16, 16, 2, p_drop=1.0)
+
+
 def test_attn_nt_is_the_rule_the_table_declares():
-    src = open(os.path.join(ROOT, "mm-dti_amd", "csrc", "attn.hip")).read()
-    assert A.ATTN_NT_LINE in src
     for Lk, nt in ((1, 10), (160, 10), (161, 16), (256, 16), (257, 24), (384, 24), (385, 32), (512, 32)):
         assert A.attn_nt(Lk) == nt
     for c in A.CASES:

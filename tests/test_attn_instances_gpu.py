@@ -68,6 +68,7 @@ def _launch(c, t, p_drop=0.0, entry=None):
     nb = len(t["seqs"])
     name = {"short": "mmdti_attn", "long": "mmdti_attn_long"}[entry or c["entry"]]
     add = arenas["add"].ptr() if "add" in arenas else 0
+    A.assert_declared_plan(lib, c, nb, dict(P, stats=arenas["stats"].ptr(), drow=arenas["drow"].ptr()), ld, add, vargs, p_drop, entry or c["entry"])
     getattr(lib, name + "_fwd")(ops._stream(), P["q"], P["k"], P["v"], add, P["ctx"], arenas["stats"].ptr(), nb, A.HEADS, c["Lq"], c["Lk"], c["hd"],
                                 ld["q"], ld["k"], ld["ctx"], t["scale"], p_drop, A.SEED, A.SITE, *vargs, c["ctx_f16"])
     getattr(lib, name + "_bwd")(ops._stream(), P["q"], P["k"], P["v"], add, P["do"], arenas["stats"].ptr(), arenas["drow"].ptr(), P["dq"], P["dk"],

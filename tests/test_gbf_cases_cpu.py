@@ -1,6 +1,7 @@
-"""The case table of tests/gbf_cases.py, checked without a GPU: that its mirror of the pair-bias launchers stands on lines that are
-verbatim in csrc/gbf.hip; that the table reaches all 27 kernel instances -- the list is taken from the text of gbf.hip: the
-hipFuncSetAttribute tables, the launch macros and the plain launches -- and every runtime branch inside them; that the Python mirror
+"""The case table of tests/gbf_cases.py, checked without a GPU: that the rounding points its reference depends on are verbatim in
+csrc/gbf.hip; that the table reaches all 27 kernel instances -- the list is the library's own kernel table -- and every runtime branch
+inside them; that the library, asked through the launch-free query mmdti_gbf_plan, plans for every case and for a sweep of shapes
+what the table declares, and refuses what the launcher refuses with the launcher's message; that the Python mirror
 of tile counts, grids and prefixes agrees with ops and with values computed by hand; that the closed-form gradients of the reference
 agree with float64 autograd; that the onehot mode is exact by construction;
 that the fp32 emulation of the kernels' rounding points stays inside the bounds with |gain| < 3; and that six wrong emulations (a
@@ -8,12 +9,15 @@ dropped tile, two swapped columns of W1, the dstds sign, a halved dmul entry, pi
 
 With MMDTI_GBF_PROFILE=<path> the worst emulation ratio and |gain| per kernel family and output are merged into that JSON file under
 "emulation" (profiles/gbf_instances.json holds such a run next to the device's)."""
+import ctypes
 import json
+import math
 import os
-import re
 
 import pytest
 import torch
+
+from mmdti_hip import _abi
 
 import gbf_cases as Gc
 
@@ -36,33 +40,13 @@ def _profile():
             f.write("\n")
 
 
-DEFAULTS = {"gbf_bias_fwd_kernel": ("?", "?", "?", "false"), "gbf_bias_bwd_kernel": ("?", "?"), "gbf_bias_bwd_full_kernel": ("?", "?", "false", "false")}
-
-
-def _full(name, args):
-    args = [a.strip() for a in args]
-    d = DEFAULTS[name]
-    return f"{name}<{', '.join(args + list(d[len(args):]))}>"
-
-
-def source_instances():
-    """the instantiations gbf.hip names: in its hipFuncSetAttribute tables, and in its launch macros"""
-    attr = {_full(n, a.split(",")) for n, a in re.findall(r"reinterpret_cast<const void\*>\((gbf_bias_\w+_kernel)<([^>]*)>\)", SRC)}
-    mac = set()
-    for a in re.findall(r"GBF_LC\((\w+, \w+, \w+, \w+)\)", SRC):
-        if "SAVE" not in a:
-            mac.add(_full("gbf_bias_fwd_kernel", a.split(",")))
-    for a in re.findall(r"GBF_L\((\w+, \w+, \w+)\)", SRC):
-        if "SAVE" not in a:
-            mac.add(_full("gbf_bias_fwd_kernel", a.split(",")))
-    for a in re.findall(r"GBF_B\((\w+, \w+)\)", SRC):
-        if "TILED" not in a:
-            mac.add(_full("gbf_bias_bwd_kernel", a.split(",")))
-    fx = [a for a in re.findall(r"GBF_FX\((\w+, \w+), DET, COORDS\)", SRC) if "TILED" not in a]
-    for d, co in re.findall(r"GBF_FL\((true|false), (true|false)\)", SRC):
-        mac |= {_full("gbf_bias_bwd_full_kernel", a.split(",") + [d, co]) for a in fx}
-    plain = set(re.findall(r"hipLaunchKernelGGL\((gbf_\w+_kernel),", SRC)) - {"gbf_slab_reduce_kernel"}
-    return attr, mac, plain
+def table_names():
+    lib = _abi.lib()
+    n = ctypes.c_int()
+    lib.mmdti_plan_table_size(1, ctypes.byref(n))
+    names = [lib.mmdti_plan_kernel_name(1, i).decode() for i in range(n.value)]
+    assert lib.mmdti_plan_kernel_name(1, n.value) is None and lib.mmdti_plan_kernel_name(1, -1) is None
+    return names
 
 
 def test_the_mirrored_lines_are_verbatim_in_the_source():
@@ -71,17 +55,111 @@ def test_the_mirrored_lines_are_verbatim_in_the_source():
     assert abs(Gc.GBF_A - (2 * 3.14159) ** 0.5) < 1e-9 and Gc.GBF_SLAB == 16384 + 8192 + 128 + 64 + 256
 
 
-def test_the_table_reaches_every_instance_named_in_the_source():
-    attr, mac, plain = source_instances()
-    assert attr == mac, (attr ^ mac)
-    assert plain == {"gbf_fwd_kernel", "gbf_bwd_kernel", "gbf_bwd_det_kernel"}
-    want = attr | plain
-    assert len(want) == 27 and len([i for i in want if i.startswith("gbf_bias_fwd")]) == 9 and len([i for i in want if "full" in i]) == 12
+def test_the_table_reaches_every_instance_of_the_library():
+    names = [Gc.canonical(n) for n in table_names()]
+    want = set(names)
+    assert len(names) == len(want) == 27 and len([i for i in want if i.startswith("gbf_bias_fwd")]) == 9 and len([i for i in want if "full" in i]) == 12
+    assert len([i for i in want if i.startswith("gbf_bias_bwd_kernel")]) == 3 and {i for i in want if "<" not in i} == {"gbf_fwd_kernel", "gbf_bwd_kernel", "gbf_bwd_det_kernel"}
     got = {Gc.instance(c) for c in Gc.CASES}
     assert got == want, (got ^ want)
     assert len({Gc.case_id(c) for c in Gc.CASES}) == len(Gc.CASES)
     ids = [Gc.run_id(r) for r in Gc.runs()] + [Gc.run_id(r) for r in Gc.edge_runs()]
     assert len(set(ids)) == len(ids)
+
+
+def _plan(c, **kw):
+    return Gc.library_plan(_abi.lib(), c, **kw)
+
+
+def test_the_library_plans_what_every_case_declares():
+    """instance, workgroup size, grid, tpm, ntiles, ltab, slab use and the slab-reduce launch of every case -- and of every edge-type width"""
+    for c in Gc.CASES:
+        for esz in (8, 4, 2) if c["kind"] in ("fwd", "bwd", "full") and not c["coords"] else (8,):
+            got, want = _plan(c, esz=esz), Gc.declared_plan(c)
+            assert {f: got[f] for f in want} == want, (Gc.case_id(c), got, want)
+    full = next(c for c in Gc.CASES if c["kind"] == "full" and c["ws"] and not c["det"] and c["N"] == 130)
+    need = Gc.launch(full)["grid"] * (Gc.GBF_SLAB + 2 * full["E"]) * 4
+    assert _plan(full, ws=need)["slab"] == 1 and _plan(full, ws=need - 1)["slab"] == 0 and _plan(full, ws=need - 1)["reduce_grid"] == 0
+
+
+SWEEP_E = (1, 961, 1521, 1536, 4096, 4097, 5000)
+
+
+def _sweep_case(kind, N, layout, B, E, coords=False, save=False, det=False, ws=True):
+    V = math.isqrt(E)
+    return dict(kind=kind, N=N, layout=layout, B=B, E=E, V=V, coords=coords, save=save, ugrad=False, det=det, ws=ws, lens=None, packed=False, modes=(),
+                ld=Gc.pair_ld(N))
+
+
+def _refusal(c):
+    """the launcher's message for a combination it refuses, in the order of its checks; None: it launches"""
+    k, E = c["kind"], c["E"]
+    if k == "ffwd":
+        return None
+    if k == "fbwd":
+        return "deterministic mode keeps the mul / bias histograms in LDS" if c["det"] and E > Gc.GBF_MAXE else None
+    if c["coords"] and c["V"] ** 2 != E:
+        return r"V \* V must be the edge-table size"
+    if k == "fwd":
+        return None
+    if k == "bwd":
+        if c["det"]:
+            return "no fixed-order form yet -- refused in the deterministic mode"
+        if E > Gc.GBF_MAXE:
+            return r"gbf_bias_bwd: bad shape \(E <= 4096\)"
+        # weight images, three rows of 128 floats and four fp32 tables over the edge types in 96 KiB of LDS
+        return f"{E} edge types do not fit the LDS tables" if (128 * 136 + 128 * 72) * 2 + (3 * 128 + 4 * E) * 4 > 96 * 1024 else None
+    if E > Gc.GBF_FULL_MAXE:
+        return r"gbf_bias_bwd_full: bad shape \(E <= 1536\)"
+    return "deterministic mode needs the workspace" if c["det"] and not c["ws"] else None
+
+
+def _sweep():
+    for E in SWEEP_E:
+        for B in (1, 2, 3, 4, 8):
+            for N in range(1, 141):
+                yield _sweep_case("ffwd", N, "row", B, E)
+                for det in (False, True):
+                    yield _sweep_case("fbwd", N, "row", B, E, det=det)
+                for lay in ("row", "tiled", "compact"):
+                    for save, co in ((False, False), (True, False), (False, True)):
+                        yield _sweep_case("fwd", N, lay, B, E, coords=co, save=save)
+                    for det in (False, True):
+                        yield _sweep_case("bwd", N, lay, B, E, det=det)
+                        for co in (False, True):
+                            for ws in (True, False):
+                                yield _sweep_case("full", N, lay, B, E, coords=co, det=det, ws=ws)
+
+
+def test_a_sweep_of_shapes_plans_the_declared_launches_or_refuses_as_the_launcher_does():
+    """N = 1..140 x B x layouts x save / coords / det x E, with and without workspace: every table row is reached, nothing else is named"""
+    seen, refused = set(), set()
+    for c in _sweep():
+        msg = _refusal(c)
+        if msg:
+            refused.add(msg)
+            with pytest.raises(_abi.MMDTIError, match=msg):
+                _plan(c)
+            continue
+        got, want = _plan(c), Gc.declared_plan(c)
+        assert {f: got[f] for f in want} == want, (c, got, want)
+        seen.add(got["name"])
+    assert seen == {Gc.canonical(n) for n in table_names()} and len(refused) == 7
+
+
+def test_the_plan_query_validates_like_the_launch():
+    c = next(c for c in Gc.CASES if c["kind"] == "fwd" and c["save"] and c["layout"] == "tiled")
+    for kw, msg in ((dict(operands=0), "gbf_bias_fwd: null argument"), (dict(aligned=Gc.PTR + 8), "gbf_bias_fwd: 16-byte alignment required"),
+                    (dict(esz=3), "edge types must be int64, int32 or int16")):
+        with pytest.raises(_abi.MMDTIError, match=msg):
+            _plan(c, **kw)
+    with pytest.raises(_abi.MMDTIError, match="compact planes .* exist in the tiled layout only"):
+        _abi.lib().mmdti_gbf_plan(2, 0, Gc.PTR, Gc.PTR, 0, 0, 0, 0, 0, 0, 0, 3, 5, 8, Gc.K, Gc.F, Gc.H, 961, 31, 0, 8, 4, (ctypes.c_longlong * 10)())   # flags: compact, not tiled
+    with pytest.raises(_abi.MMDTIError, match="tile_prefix .* needs the tiled pair layout"):
+        _plan(dict(c, layout="row", lens=(5,), save=False))
+    f = next(c for c in Gc.CASES if c["kind"] == "ffwd")
+    with pytest.raises(_abi.MMDTIError, match="feat must be 16-byte aligned"):
+        _plan(f, aligned=Gc.PTR + 2)
 
 
 def test_every_instance_meets_every_size_mode_and_branch():

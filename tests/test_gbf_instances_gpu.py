@@ -187,6 +187,7 @@ def _launch(c, t, geo, ref, esz=8):
     r = Run(c, t, geo, ref, esz)
     what, kind = Gc.run_id((c, t["mode"])), c["kind"]
     st = ops._stream
+    Gc.assert_declared_plan(lib, c, esz)          # (the mode and the workspace the launch below finds are the case's: _run, and the assert on ws)
     if kind in ("ffwd", "fbwd"):
         assert esz == 8
         pm = r.params("mul", "bias", "means", "stds")

@@ -1,14 +1,18 @@
-"""The case table of tests/pair_cases.py, checked without a GPU: that its mirror of the two pair-attention launchers still stands on
-lines that are verbatim in the sources; that the table reaches all 85 forward and 98 backward kernel instances (enumerated
-independently from the template parameter ranges) and all 86 ragged bodies in each direction, every instance in every mode that
-applies to it, with and without a padding mask and with dropout at both rates; that the float64 reference agrees with float64
+"""The case table of tests/pair_cases.py, checked without a GPU: that the device-side rules it mirrors are verbatim in the sources; that
+the library, asked through the launch-free query mmdti_pair_attn_plan, plans for every case and for a sweep of every size what the
+table declares, and refuses what the launchers refuse with their message; that the table reaches all 85 forward and 98 backward
+kernel instances (enumerated independently from the template parameter ranges, and equal to the library's kernel tables) and all 86
+ragged bodies in each direction, every instance in every mode that applies to it, with and without a padding mask and with dropout at both rates; that the float64 reference agrees with float64
 autograd; that the exact modes are exact by construction; and that an fp32 emulation of the kernels' rounding points stays inside
 the bounds the device results are held to -- while the same emulation without the low parts of the hi + lo splits, or with a
 softmax denominator wrong by 1 / 256, does not."""
+import ctypes
 import os
 
 import pytest
 import torch
+
+from mmdti_hip import _abi
 
 import pair_cases as P
 
@@ -32,6 +36,76 @@ def test_the_mirrored_lines_are_verbatim_in_the_sources():
         assert torch.equal(P.geometry(c)["idx"], ops._tile_index(N, "cpu", ops.pair_ld(N)))
         for k in range(0, 19):
             assert P.pa_kt_effective(k, P.tiles(N)) == ops.pair_key_tiles_effective(k, P.tiles(N))
+
+
+def _table(families):
+    """the names of the library's kernel tables (mmdti_plan_kernel_name), the defaulted DET = false written out"""
+    lib, names = _abi.lib(), []
+    for fam in families:
+        n = ctypes.c_int()
+        lib.mmdti_plan_table_size(fam, ctypes.byref(n))
+        assert lib.mmdti_plan_kernel_name(fam, n.value) is None and lib.mmdti_plan_kernel_name(fam, -1) is None
+        names += [lib.mmdti_plan_kernel_name(fam, i).decode() for i in range(n.value)]
+    return [n[:-1] + ", false>" if n.startswith("pair_attn_bwd_kernel<") and "," not in n else n for n in names]
+
+
+def test_the_library_plans_what_every_case_declares():
+    """instance, grid, workgroup size, nqb and NW of both launches of every case; the library's tables hold the 85 + 98 instances"""
+    lib = _abi.lib()
+    for c in P.CASES:
+        for backward in (False, True):
+            P.assert_declared_plan(lib, c, backward)
+    fwd, bwd = P.all_instances()
+    tf, tb = _table((2, 4)), _table((3, 5))
+    assert len(tf) == len(set(tf)) == 85 and len(tb) == len(set(tb)) == 98 and set(tf) == fwd and set(tb) == bwd
+
+
+def _refusal(c, backward):
+    """the launcher's message for a combination it refuses, in the order of its checks; None: it launches"""
+    lay = c["layout"] if backward else c["layout"] & 3
+    tiled, compact = lay & 1, lay & 2
+    if c["lens"] is not None and not compact:
+        return "key_tiles .ragged batches. needs the compact"
+    if not backward and c["f16"] and not compact:
+        return "fp16 q . k . v .the fp16 forward-operand mode. is built for the compact tiled pair layout"
+    if tiled and (c["ld"] % 4 or c["N"] > 16 * P.PA_MAX_NT):
+        return "the tiled pair layout needs ld % 4 == 0 and N <= 272"
+    if tiled and c["shift"]:
+        return "tiled pair tensors must be 16-byte aligned"
+    if backward and c["f16"] and not P.mfma(c):
+        return "fp16 q . k . v are read by the MFMA kernels only"
+    return None
+
+
+def test_a_sweep_of_every_size_plans_the_declared_launches_or_refuses_as_the_launcher_does():
+    """N = 1..320 x layouts 0 / 1 / 3 / 7 x ragged x fp16 operands x aligned / unaligned planes x ld % 4 x deterministic, both directions:
+    every table row is reached, nothing outside the tables is named"""
+    lib = _abi.lib()
+    seen, refused = [set(), set()], set()
+    for N in range(1, 321):
+        for lay in (0, 1, 3, 7):
+            for rag in (False, True):
+                for f16 in (False, True):
+                    for shift in (False, True):
+                        for ld in (P.pair_ld(N), P.pair_ld(N) + 1):
+                            for det in (False, True):
+                                c = dict(N=N, layout=lay, B=3, H=3, ld=ld, lens=(N,) if rag else None, packed=False, f16=f16, det=det, shift=shift)
+                                for backward in (False, True):
+                                    msg = _refusal(c, backward)
+                                    if msg:
+                                        refused.add(msg)
+                                        with pytest.raises(_abi.MMDTIError, match=("pair_attn_bwd: " if backward else "pair_attn_fwd: ") + msg):
+                                            P.library_plan(lib, c, backward)
+                                        continue
+                                    got = P.library_plan(lib, c, backward)
+                                    # (the backward reads fp16 q | k | v on every MFMA instance; its instance does not depend on them)
+                                    assert got == P.declared_plan(dict(c, f16=False) if backward else c, backward), (c, backward, got)
+                                    seen[backward].add(got[0])
+    assert seen[0] == set(_table((2, 4))) and seen[1] == set(_table((3, 5))) and len(refused) == 5
+    with pytest.raises(_abi.MMDTIError, match="exceeds the supported 320 atoms"):
+        P.library_plan(lib, dict(N=321, layout=0, B=3, H=3, ld=324, lens=None, packed=False, f16=False, det=False, shift=False), False)
+    with pytest.raises(_abi.MMDTIError, match="pair_attn_bwd: alignment"):
+        P.library_plan(lib, P.CASES[0], True, ptr=dict(qkv=P.PTR, s=P.PTR, g=P.PTR, o=P.PTR + 8, dqkv=P.PTR))
 
 
 def test_the_table_reaches_every_instance_and_every_ragged_body():

@@ -105,12 +105,14 @@ class Placed:
 
 def _fwd(pl, s_in_ptr, s_out_ptr, o_ptr, kp, p, rag_store):
     c = pl.c
+    P.assert_declared_plan(_abi.lib(), c, False, dict(qkv=pl.qkv, s=s_in_ptr, g=s_out_ptr, o=o_ptr, dqkv=0))
     _abi.lib().mmdti_pair_attn_fwd(ops._stream(), pl.qkv, s_in_ptr, s_out_ptr, o_ptr, kp, c["B"], c["N"], c["H"], c["ld"], pl.t["scale"], p, P.SEED, P.SITE,
                                    c["layout"] & 3, pl.kt, int(rag_store), pl.ro, int(c["f16"]))
 
 
 def _bwd(pl, s_ptr, g_ptr, dqkv_ptr, gz, p):
     c = pl.c
+    P.assert_declared_plan(_abi.lib(), c, True, dict(qkv=pl.qkv, s=s_ptr, g=g_ptr, o=pl.do, dqkv=dqkv_ptr))
     _abi.lib().mmdti_pair_attn_bwd(ops._stream(), pl.qkv, s_ptr, pl.do, g_ptr, dqkv_ptr, c["B"], c["N"], c["H"], c["ld"], pl.t["scale"], int(gz), p, P.SEED, P.SITE,
                                    c["layout"], pl.kt, pl.ro, int(c["f16"]))
 
