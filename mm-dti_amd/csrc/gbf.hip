@@ -15,6 +15,32 @@ namespace mmdti {
 
 constexpr float GBF_A = 2.5066272160f;  // sqrt(2*3.14159) -- truncated pi exactly as mm_model.py:222-223
 
+// ---- The pieces the kernels of this file share, one definition each.  Every kernel is held to the instruction stream it had before
+// they were shared (profiles/pair_kernels_shared_isa.txt); a piece is a macro where, as a forceinline function, it changed the stream of
+// one of its kernels (the function is simplified on its own before it is inlined, and the scheduler is sensitive to what that leaves).
+// sigma of a Gaussian kernel and its normalisation 1 / (a sigma)
+__device__ __forceinline__ float gbf_sigma(float sd) { return fabsf(sd) + 1e-5f; }
+__device__ __forceinline__ float gbf_coef(float sg) { return 1.0f / (GBF_A * sg); }
+// an edge type outside the tables takes their nearest row (function form: 6 forward and 6 complete-backward instances change)
+#define GBF_CLAMP_EDGE(X, E) ((X) < 0 ? 0 : ((X) >= (E) ? (E) - 1 : (X)))
+// V summed over the 16 lanes that differ in bits 0..3 / over the 4 lanes that differ in bits 4..5 (function form: gbf_bias_bwd_kernel
+// and gbf_bwd_det_kernel change)
+// (Statement macros are one statement each -- a comma expression or a do { } while (0) -- and are written with their semicolon.)
+#define GBF_SUM16(V) ((V) += __shfl_xor((V), 1, 64), (V) += __shfl_xor((V), 2, 64), (V) += __shfl_xor((V), 4, 64), (V) += __shfl_xor((V), 8, 64))
+#define GBF_SUM4X16(V) ((V) += __shfl_xor((V), 16, 64), (V) += __shfl_xor((V), 32, 64))
+// The per-edge-type histogram HIST [2][E] (d mul | d bias) in LDS, by a workgroup of NT threads: zeroed, and added to DMUL / DBIAS with one
+// atomic per touched entry.  (function forms: gbf_bias_bwd_full_kernel, gbf_bwd_kernel and gbf_bias_bwd_kernel change)
+#define GBF_HIST_ZERO(HIST, E, TID, NT) \
+  for (int c = (TID); c < 2 * (E); c += (NT)) (HIST)[c] = 0.f
+#define GBF_HIST_FLUSH(HIST, E, TID, NT, DMUL, DBIAS)       \
+  do {                                                      \
+    for (int c = (TID); c < (E); c += (NT)) {               \
+      const float a = (HIST)[c], bb = (HIST)[(E) + c];      \
+      if (a != 0.f) atomicAdd((DMUL) + c, a);               \
+      if (bb != 0.f) atomicAdd((DBIAS) + c, bb);            \
+    }                                                       \
+  } while (0)
+
 __global__ __launch_bounds__(256) void gbf_fwd_kernel(const float* __restrict__ dist, const long long* __restrict__ et,
                                                       const float* __restrict__ mul, const float* __restrict__ bias,
                                                       const float* __restrict__ means, const float* __restrict__ stds,
@@ -26,12 +52,12 @@ __global__ __launch_bounds__(256) void gbf_fwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       mu[i] = means[k0 + i];
-      sg[i] = fabsf(stds[k0 + i]) + 1e-5f;
-      cf[i] = 1.0f / (GBF_A * sg[i]);
+      sg[i] = gbf_sigma(stds[k0 + i]);
+      cf[i] = gbf_coef(sg[i]);
     }
     for (long long p = (long long)blockIdx.x * 16 + pl; p < P; p += (long long)gridDim.x * 16) {
       long long e = et[p];
-      e = e < 0 ? 0 : (e >= E ? E - 1 : e);
+      e = GBF_CLAMP_EDGE(e, E);
       const float y = mul[e] * dist[p] + bias[e];
       uint32_t w[4];
 #pragma unroll
@@ -49,6 +75,47 @@ __global__ __launch_bounds__(256) void gbf_fwd_kernel(const float* __restrict__ 
 // 16 k-chunk lanes and scattered into an LDS histogram over edge types (E <= 4096), flushed with one global atomic per
 // touched entry per block.
 
+// The two pieces gbf_bwd_kernel and gbf_bwd_det_kernel share are macros: as forceinline functions that take the thread's arrays by
+// reference (with or without __restrict__) both kernels compile to longer instruction streams (+25 / +17 instructions), and they are held
+// to the ones they had (profiles/pair_kernels_shared_isa.txt).
+// GBF_BWD_CONSTS: declares the constants of the thread's 8 kernels k0 .. k0 + 7 (an inactive chunk, k0 >= K, divides by 1) and its zeroed
+// d means / d stds sums.  Names k0, kact, means, stds.
+#define GBF_BWD_CONSTS()                                                                                           \
+  float mu[8], sg[8], cf[8], amu[8], asg[8];                                                                       \
+  _Pragma("unroll")                                                                                                \
+  for (int i = 0; i < 8; ++i) {                                                                                    \
+    mu[i] = kact ? means[k0 + i] : 0.f;                                                                            \
+    sg[i] = kact ? gbf_sigma(stds[k0 + i]) : 1.f;                                                                  \
+    cf[i] = gbf_coef(sg[i]);                                                                                       \
+    amu[i] = asg[i] = 0.f;                                                                                         \
+  }
+// GBF_BWD_PAIR: one pair's share of the thread's 8 kernels, then the pair's dL/dy summed over its 16 lanes.  Declares dy and the pair's
+// (clamped) edge type e and distance d.  Names p, P, kact, k0, K, E, the kernel's pointers and the arrays of GBF_BWD_CONSTS.
+#define GBF_BWD_PAIR()                                                                                            \
+  float dy = 0.f;                                                                                                  \
+  long long e = 0;                                                                                                 \
+  float d = 0.f;                                                                                                   \
+  if (p < P && kact) {                                                                                             \
+    e = et[p];                                                                                                     \
+    e = GBF_CLAMP_EDGE(e, E);                                                                                      \
+    d = dist[p];                                                                                                   \
+    const float y = mul[e] * d + bias[e];                                                                          \
+    const uint4 u = *reinterpret_cast<const uint4*>(dfeat + p * K + k0);                                           \
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};                                                                    \
+    _Pragma("unroll")                                                                                              \
+    for (int i = 0; i < 8; ++i) {                                                                                  \
+      const float dv = __uint_as_float((i & 1) ? (w[i >> 1] & 0xffff0000u) : (w[i >> 1] << 16));                   \
+      const float z = (y - mu[i]) / sg[i];                                                                         \
+      const float val = __expf(-0.5f * z * z) * cf[i];                                                             \
+      const float t = dv * val;                                                                                    \
+      const float zs = z / sg[i];                                                                                  \
+      dy -= t * zs;                                                                                                \
+      amu[i] += t * zs;                                                                                            \
+      asg[i] += t * (z * zs - 1.0f / sg[i]);                                                                       \
+    }                                                                                                              \
+  }                                                                                                                \
+  GBF_SUM16(dy)
+
 __global__ __launch_bounds__(256) void gbf_bwd_kernel(const float* __restrict__ dist, const long long* __restrict__ et,
                                                       const float* __restrict__ mul, const float* __restrict__ bias,
                                                       const float* __restrict__ means, const float* __restrict__ stds,
@@ -58,50 +125,17 @@ __global__ __launch_bounds__(256) void gbf_bwd_kernel(const float* __restrict__ 
   extern __shared__ float hist[];  // [2][E] when E <= GBF_MAXE
   const bool use_hist = E <= GBF_MAXE;
   if (use_hist) {
-    for (int i = threadIdx.x; i < 2 * E; i += 256) hist[i] = 0.f;
+    GBF_HIST_ZERO(hist, E, threadIdx.x, 256);
     __syncthreads();
   }
   const int kc = threadIdx.x & 15, pl = threadIdx.x >> 4;
   for (int kb = 0; kb < K; kb += 128) {  // uniform trip count: the body shuffles across lanes
     const int k0 = kb + kc * 8;
     const bool kact = k0 < K;
-    float mu[8], sg[8], cf[8], amu[8], asg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      mu[i] = kact ? means[k0 + i] : 0.f;
-      sg[i] = kact ? fabsf(stds[k0 + i]) + 1e-5f : 1.f;
-      cf[i] = 1.0f / (GBF_A * sg[i]);
-      amu[i] = asg[i] = 0.f;
-    }
+    GBF_BWD_CONSTS();
     for (long long p0 = (long long)blockIdx.x * 16; p0 < P; p0 += (long long)gridDim.x * 16) {
       const long long p = p0 + pl;
-      float dy = 0.f;
-      long long e = 0;
-      float d = 0.f;
-      if (p < P && kact) {
-        e = et[p];
-        e = e < 0 ? 0 : (e >= E ? E - 1 : e);
-        d = dist[p];
-        const float y = mul[e] * d + bias[e];
-        const uint4 u = *reinterpret_cast<const uint4*>(dfeat + p * K + k0);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float dv = __uint_as_float((i & 1) ? (w[i >> 1] & 0xffff0000u) : (w[i >> 1] << 16));
-          const float z = (y - mu[i]) / sg[i];
-          const float val = __expf(-0.5f * z * z) * cf[i];
-          const float t = dv * val;
-          const float zs = z / sg[i];
-          dy -= t * zs;
-          amu[i] += t * zs;
-          asg[i] += t * (z * zs - 1.0f / sg[i]);
-        }
-      }
-      // reduce dy over the 16 lanes sharing this pair (lanes differ in bits 0..3)
-      dy += __shfl_xor(dy, 1, 64);
-      dy += __shfl_xor(dy, 2, 64);
-      dy += __shfl_xor(dy, 4, 64);
-      dy += __shfl_xor(dy, 8, 64);
+      GBF_BWD_PAIR();
       if (kc == 0 && p < P) {
         if (use_hist) {
           atomicAdd(&hist[e], dy * d);
@@ -117,8 +151,8 @@ __global__ __launch_bounds__(256) void gbf_bwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float a = amu[i], s = asg[i];
-      a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-      s += __shfl_xor(s, 16, 64); s += __shfl_xor(s, 32, 64);
+      GBF_SUM4X16(a);
+      GBF_SUM4X16(s);
       if ((threadIdx.x & 63) < 16 && kact) {
         atomicAdd(dmeans + k0 + i, a);
         atomicAdd(dstds + k0 + i, stds[k0 + i] < 0.f ? -s : s);  // d|std|/dstd
@@ -127,11 +161,7 @@ __global__ __launch_bounds__(256) void gbf_bwd_kernel(const float* __restrict__ 
   }
   if (use_hist) {
     __syncthreads();
-    for (int i = threadIdx.x; i < E; i += 256) {
-      const float a = hist[i], b = hist[E + i];
-      if (a != 0.f) atomicAdd(dmul + i, a);
-      if (b != 0.f) atomicAdd(dbias + i, b);
-    }
+    GBF_HIST_FLUSH(hist, E, threadIdx.x, 256, dmul, dbias);
   }
 }
 
@@ -149,48 +179,16 @@ __global__ __launch_bounds__(256) void gbf_bwd_det_kernel(const float* __restric
   __shared__ float sa[16], sb[16];
   __shared__ float red[4][16][16];   // [wave][kc][amu 0..7 | asg 0..7]
   float* const sl = slab + (long long)blockIdx.x * (2 * E + 2 * K);
-  for (int i = threadIdx.x; i < 2 * E; i += 256) hist[i] = 0.f;
+  GBF_HIST_ZERO(hist, E, threadIdx.x, 256);
   __syncthreads();
   const int kc = threadIdx.x & 15, pl = threadIdx.x >> 4, wave = threadIdx.x >> 6;
   for (int kb = 0; kb < K; kb += 128) {  // uniform trip count: the body shuffles across lanes and meets at barriers
     const int k0 = kb + kc * 8;
     const bool kact = k0 < K;
-    float mu[8], sg[8], cf[8], amu[8], asg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      mu[i] = kact ? means[k0 + i] : 0.f;
-      sg[i] = kact ? fabsf(stds[k0 + i]) + 1e-5f : 1.f;
-      cf[i] = 1.0f / (GBF_A * sg[i]);
-      amu[i] = asg[i] = 0.f;
-    }
+    GBF_BWD_CONSTS();
     for (long long p0 = (long long)blockIdx.x * 16; p0 < P; p0 += (long long)gridDim.x * 16) {
       const long long p = p0 + pl;
-      float dy = 0.f;
-      long long e = 0;
-      float d = 0.f;
-      if (p < P && kact) {
-        e = et[p];
-        e = e < 0 ? 0 : (e >= E ? E - 1 : e);
-        d = dist[p];
-        const float y = mul[e] * d + bias[e];
-        const uint4 u = *reinterpret_cast<const uint4*>(dfeat + p * K + k0);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float dv = __uint_as_float((i & 1) ? (w[i >> 1] & 0xffff0000u) : (w[i >> 1] << 16));
-          const float z = (y - mu[i]) / sg[i];
-          const float val = __expf(-0.5f * z * z) * cf[i];
-          const float t = dv * val;
-          const float zs = z / sg[i];
-          dy -= t * zs;
-          amu[i] += t * zs;
-          asg[i] += t * (z * zs - 1.0f / sg[i]);
-        }
-      }
-      dy += __shfl_xor(dy, 1, 64);
-      dy += __shfl_xor(dy, 2, 64);
-      dy += __shfl_xor(dy, 4, 64);
-      dy += __shfl_xor(dy, 8, 64);
+      GBF_BWD_PAIR();
       if (kc == 0) {
         se[pl] = p < P ? (int)e : -1;
         sa[pl] = dy * d;
@@ -210,8 +208,8 @@ __global__ __launch_bounds__(256) void gbf_bwd_det_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float a = amu[i], sv = asg[i];
-      a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-      sv += __shfl_xor(sv, 16, 64); sv += __shfl_xor(sv, 32, 64);
+      GBF_SUM4X16(a);
+      GBF_SUM4X16(sv);
       if ((threadIdx.x & 63) < 16) {
         red[wave][kc][i] = a;
         red[wave][kc][8 + i] = sv;
@@ -231,6 +229,8 @@ __global__ __launch_bounds__(256) void gbf_bwd_det_kernel(const float* __restric
   }
   for (int i = threadIdx.x; i < 2 * E; i += 256) sl[i] = hist[i];
 }
+#undef GBF_BWD_PAIR
+#undef GBF_BWD_CONSTS
 
 // [B,N,N,H] fp32 -> [B,H,N,ld] fp32.  One block per (b,i): the [N][H] slab is contiguous.
 __global__ __launch_bounds__(256) void pair_permute_fwd_kernel(const float* __restrict__ x, float* __restrict__ out,
@@ -391,6 +391,105 @@ __device__ __forceinline__ float gbf_get(const __bf16* p) {
   return __builtin_bit_cast(float, (uint32_t)(*reinterpret_cast<const unsigned short*>(p)) << 16);
 }
 
+// ---- The LDS images of the three fused kernels, staged by a workgroup of NT threads.
+// W1[f][k] in rows of `ws` elements, 16 bytes per step
+template <int NT>
+__device__ __forceinline__ void gbf_stage_w1(bf16_t* sW1, const bf16_t* W1, int ws) {
+  for (int c = threadIdx.x; c < GBF_F * (GBF_K / 8); c += NT) {
+    const int row = c >> 4, col = (c & 15) * 8;
+    *reinterpret_cast<uint4*>(sW1 + row * ws + col) = *reinterpret_cast<const uint4*>(W1 + row * GBF_K + col);
+  }
+}
+// W2^T[f][h] in rows of GBF_W2S, and the per-edge-type affine of the Gaussian layer (function forms: every instance that uses them changes)
+#define GBF_STAGE_W2T(SW2T, W2, TID, NT)                    \
+  do {                                                      \
+    for (int c = (TID); c < GBF_H * GBF_F; c += (NT)) {     \
+      const int h = c >> 7, f = c & 127;                    \
+      (SW2T)[f * GBF_W2S + h] = (W2)[c];                    \
+    }                                                       \
+  } while (0)
+#define GBF_STAGE_TABLES(SMUL, SBIA, MUL, BIAS, E, TID, NT) \
+  do {                                                      \
+    for (int c = (TID); c < (E); c += (NT)) {               \
+      (SMUL)[c] = (MUL)[c];                                 \
+      (SBIA)[c] = (BIAS)[c];                                \
+    }                                                       \
+  } while (0)
+// ---- Pieces of their per-pair arithmetic.
+// an accumulator quad times four packed bf16 values
+__device__ __forceinline__ gf32x4 gbf_mul4(gf32x4 acc, uint2 pk) {
+  acc[0] *= __uint_as_float(pk.x << 16);
+  acc[1] *= __uint_as_float(pk.x & 0xffff0000u);
+  acc[2] *= __uint_as_float(pk.y << 16);
+  acc[3] *= __uint_as_float(pk.y & 0xffff0000u);
+  return acc;
+}
+// two accumulator quads (feature halves hf = 0, 1) as one K = 32 operand: slots 8g + 4hf + e
+__device__ __forceinline__ gbf16x8 gbf_pack8(gf32x4 a, gf32x4 b) {
+  float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return gbf_pack8(v);
+}
+
+// ---- The pair-tile decode of the fetch lambdas of gbf_bias_fwd_kernel and gbf_bias_bwd_full_kernel (gbf_bias_bwd_kernel enumerates the row
+// block slowest, has no ragged form and stays out).  Pair tiles of 16.  Row-major planes: 16 consecutive q = i*ld + j (64 contiguous bytes
+// of every head plane).  Tiled planes (the blocked rows of common.h, 16x16 tiles in MFMA accumulator order -- the layout the pair-attention
+// kernels stream): a 4x4 (query, key) block, again 64 contiguous bytes.  Ragged batches (tile_prefix, tiled planes only): molecule b covers
+// its first tile_prefix[b+1] - tile_prefix[b] tiles -- column block slowest, so these are exactly the blocks of its first key tiles.
+// Macros: as three forceinline functions (walk: b_run, b, tq by reference; block decode: returns a struct; load: outputs by reference) 18 of
+// the two kernels' 21 instances compiled to other instruction streams.
+// GBF_TILE_MOLECULE: tile -> (molecule b, tile tq inside it); b_run walks tile_prefix (fetch is called with increasing tiles).
+#define GBF_TILE_MOLECULE()                                                       \
+  do {                                                                            \
+    if (rag) {                                                                    \
+      while (b_run + 1 < B && tile >= tile_prefix[b_run + 1]) ++b_run;            \
+      b = b_run;                                                                  \
+      tq = tile - tile_prefix[b];                                                 \
+    } else {                                                                      \
+      b = (int)((unsigned)tile / (unsigned)tpm);                                  \
+      tq = tile - b * tpm;                                                        \
+    }                                                                             \
+  } while (0)
+// GBF_TILE_PAIR: lane i's pair (ii, jj) of tile tq and its slot q; declares ii, jj, inplane (a row past N has no slot: row 0's is taken) and
+// past (the whole block lies past N, for every lane alike; none is enumerated), assigns q.  NBLK: 4-row blocks of a molecule.  (The forward's
+// statement order; the complete backward ignores inplane and past.)  Tiled: query block fastest -- inside a 16x16 tile the 64-byte segments
+// of rb & 3 = 0..3 are consecutive, so a workgroup's eight waves write, and the backward reads, whole 128-byte lines.  Packed token rows
+// (row_blocks): only the first row_blocks[b] 4-row blocks of molecule b, up to its representative pad row, are produced.
+#define GBF_TILE_PAIR(NBLK)                                                       \
+  int ii, jj;                                                                     \
+  [[maybe_unused]] bool inplane = true, past = false;                             \
+  if (TILED) {                                                                    \
+    const int rbk = (rag && row_blocks) ? row_blocks[b] : (NBLK);                 \
+    const int cb = (int)((unsigned)tq / (unsigned)rbk), rb = tq - cb * rbk;       \
+    past = 4 * rb >= N || 4 * cb >= N;                                            \
+    ii = 4 * rb + (i >> 2);                                                       \
+    jj = 4 * cb + (i & 3);                                                        \
+    inplane = ii < N;                                                             \
+    q = (int)pair_off(N, inplane ? ii : 0, jj);                                   \
+  } else {                                                                        \
+    q = tq * 16 + i;                                                              \
+    ii = (int)((unsigned)q / (unsigned)ld);                                       \
+    jj = q - ii * ld;                                                             \
+    inplane = q < plane;                                                          \
+  }
+// GBF_PAIR_LOAD: what a lane fetches for its pair -- the two atoms' records (COORDS) or (edge type, distance) at offset PL (gbf_plane_off,
+// evaluated behind the molecule's base) of the molecule's planes: a scalar base + 32-bit lane offsets (host: N*N and 64*plane fit 31 bits).
+// A pad lane reads atom 0 / pair (0, 0) of its molecule.
+__device__ __forceinline__ unsigned gbf_plane_off(bool valid, int ii, int jj, int N) { return (unsigned)((valid ? ii : 0) * N + (valid ? jj : 0)); }
+#define GBF_PAIR_LOAD(PL)                                                         \
+  do {                                                                            \
+    if constexpr (COORDS) {                                                       \
+      const uint4* mr = rec + (long long)b * N;                                   \
+      ai = mr[valid ? ii : 0];                                                    \
+      aj = mr[valid ? jj : 0];                                                    \
+    } else {                                                                      \
+      const long long mol = (long long)b * N * N;                                 \
+      const unsigned po = (PL);                                                   \
+      const int e32 = gbf_edge(et, mol, po, esz);                                 \
+      e = GBF_CLAMP_EDGE(e32, E);                                                 \
+      d = (dist + mol)[po];                                                       \
+    }                                                                             \
+  } while (0)
+
 // COORDS: the pair's (edge type, distance) comes from the two atoms' records (gbf_pair_rule) instead of the two planes; only fetch differs.
 template <bool SAVE, bool TILED, typename OT, bool COORDS = false>
 __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __restrict__ dist, const void* __restrict__ et, int esz,
@@ -415,88 +514,43 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
   float* sMul = sB2 + GBF_H;                                // [E], [E] when ltab
   float* sBia = sMul + E;
   const int tid = threadIdx.x, lane = tid & 63;
-  for (int c = tid; c < GBF_F * (GBF_K / 8); c += 512) {
-    const int row = c >> 4, col = (c & 15) * 8;
-    *reinterpret_cast<uint4*>(sW1 + row * GBF_WS + col) = *reinterpret_cast<const uint4*>(W1 + row * GBF_K + col);
-  }
+  gbf_stage_w1<512>(sW1, W1, GBF_WS);
   for (int c = tid; c < GBF_H * 32; c += 512) {  // 8-byte pieces: slot 32u+8g+4hf.. <- feature 32u+16hf+4g..
     const int row = c >> 5, pc = c & 31, u = pc >> 3, g = (pc >> 1) & 3, hf = pc & 1;
     *reinterpret_cast<uint2*>(sW2 + row * GBF_WS + 32 * u + 8 * g + 4 * hf) =
         *reinterpret_cast<const uint2*>(W2 + row * GBF_F + 32 * u + 16 * hf + 4 * g);
   }
   if (tid < GBF_K) {
-    const float sg = fabsf(stds[tid]) + 1e-5f;
+    const float sg = gbf_sigma(stds[tid]);
     sMu[tid] = means[tid];
     sIq[tid] = GBF_SQ / sg;
-    sCf[tid] = 1.0f / (GBF_A * sg);
+    sCf[tid] = gbf_coef(sg);
     sB1[tid] = b1[tid];
     if (tid < GBF_H) sB2[tid] = b2[tid];
   }
-  if (ltab)
-    for (int c = tid; c < E; c += 512) {
-      sMul[c] = mul[c];
-      sBia[c] = bias[c];
-    }
+  if (ltab) GBF_STAGE_TABLES(sMul, sBia, mul, bias, E, tid, 512);
   __syncthreads();
   const int g = lane >> 4, i = lane & 15;
-  // Ragged batches (tile_prefix, tiled planes only): molecule b covers its first tile_prefix[b+1] - tile_prefix[b] tiles -- with
-  // the column block slowest in a molecule's tile order these are exactly the blocks of its first key tiles; the all-padding
-  // key tiles behind them are never read by the ragged pair-attention kernels and are not written.
+  // (pair tiles, ragged batches and packed rows: GBF_TILE_MOLECULE / GBF_TILE_PAIR.  The all-padding key tiles behind a ragged
+  //  molecule's prefix are never read by the ragged pair-attention kernels and are not written.)
   const bool rag = TILED && tile_prefix != nullptr;
   const int ntiles = rag ? tile_prefix[B] : B * tpm;
   const int nwaves = (int)gridDim.x * 8;
-  int b_run = 0;   // (fetch is called with increasing tiles: the molecule index only moves forward)
-  // Pair tiles of 16.  Row-major planes: 16 consecutive q = i*ld + j (64 contiguous bytes of every head plane).  Tiled
-  // planes (the blocked rows of common.h, 16x16 tiles in MFMA accumulator order -- the layout the pair-attention kernels
-  // stream): a 4x4 (query, key) block, which is again 64 contiguous bytes.  The blocks that hold a real pair cover every slot
-  // of the plane; the pad keys N .. N4-1 of a real query receive -inf (the attention kernels then need no masking of pad keys).
+  int b_run = 0;
+  // The blocks that hold a real pair cover every slot of a tiled plane; the pad keys N .. N4-1 of a real query receive -inf (the
+  // attention kernels then need no masking of pad keys).
   const int nblk = (N + 3) >> 2;
   const long long plane = TILED ? pair_plane(N) : (long long)N * ld;
   // flags: bit 0 valid pair, bit 1 slot inside the plane, bit 2 whole block past N
   auto fetch = [&](int tile, int& b, int& q, int& flags, unsigned& pl, int& e, float& d, uint4& ai, uint4& aj) {
     tile = __builtin_amdgcn_readfirstlane(tile < ntiles ? tile : ntiles - 1);
     int tq;
-    if (rag) {
-      while (b_run + 1 < B && tile >= tile_prefix[b_run + 1]) ++b_run;
-      b = b_run;
-      tq = tile - tile_prefix[b];
-    } else {
-      b = (int)((unsigned)tile / (unsigned)tpm);
-      tq = tile - b * tpm;
-    }
-    int ii, jj;
-    bool inplane = true, past = false;
-    if (TILED) {
-      // (query block fastest: inside a 16x16 tile the 64-byte segments of rb & 3 = 0..3 are consecutive in memory, so the
-      //  eight waves of a workgroup write -- and the backward reads -- whole 128-byte lines together)
-      // packed token rows (row_blocks): molecule b's queries stop at its representative pad row -- only its first row_blocks[b]
-      // 4-row blocks are produced (the pair-attention kernels read no query row past it)
-      const int rbk = (rag && row_blocks) ? row_blocks[b] : nblk;
-      const int cb = (int)((unsigned)tq / (unsigned)rbk), rb = tq - cb * rbk;
-      past = 4 * rb >= N || 4 * cb >= N;   // (the same for every lane of the wave; no such block is enumerated: nothing is stored for it)
-      ii = 4 * rb + (i >> 2);
-      jj = 4 * cb + (i & 3);
-      inplane = ii < N;                    // (a row past N has no slot)
-      q = (int)pair_off(N, inplane ? ii : 0, jj);
-    } else {
-      q = tq * 16 + i;
-      ii = (int)((unsigned)q / (unsigned)ld);
-      jj = q - ii * ld;
-      inplane = q < plane;
-    }
+    GBF_TILE_MOLECULE();
+    GBF_TILE_PAIR(nblk);
     const bool valid = ii < N && jj < N;
     flags = (valid ? 1 : 0) | (inplane ? 2 : 0) | (past ? 4 : 0);
-    pl = (unsigned)((valid ? ii : 0) * N + (valid ? jj : 0));
-    if constexpr (COORDS) {       // (a pad lane reads atom 0 of its molecule, as it reads pair (0, 0) of the planes)
-      const uint4* mr = rec + (long long)b * N;
-      ai = mr[valid ? ii : 0];
-      aj = mr[valid ? jj : 0];
-    } else {
-      const long long mol = (long long)b * N * N;
-      const int e32 = gbf_edge(et, mol, pl, esz);
-      e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
-      d = (dist + mol)[pl];
-    }
+    pl = gbf_plane_off(valid, ii, jj, N);
+    GBF_PAIR_LOAD(pl);
   };
   int b, q, flags, e = 0, n_b, n_q, n_flags, n_e = 0;
   unsigned pl, n_pl;
@@ -507,7 +561,7 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
   for (; tile < ntiles; tile += nwaves) {
     if constexpr (COORDS) {       // the records arrived an iteration ago: reduce them to (e, d) before the next pair's eight registers go live
       gbf_pair_rule(ai, aj, V, pad, e, d);
-      e = e < 0 ? 0 : (e >= E ? E - 1 : e);
+      e = GBF_CLAMP_EDGE(e, E);
     }
     fetch(tile + nwaves, n_b, n_q, n_flags, n_pl, n_e, n_d, n_ai, n_aj);
     const bool valid = flags & 1, inplane = flags & 2, past = flags & 4;
@@ -558,8 +612,7 @@ __global__ __launch_bounds__(512, 2) void gbf_bias_fwd_kernel(const float* __res
         hv[hf] = acc;
         __builtin_amdgcn_sched_barrier(0);  // keep the unrolled tiles in order: hoisted weight fragments would eat the register file
       }
-      float v[8] = {hv[0][0], hv[0][1], hv[0][2], hv[0][3], hv[1][0], hv[1][1], hv[1][2], hv[1][3]};
-      hB[u] = gbf_pack8(v);
+      hB[u] = gbf_pack8(hv[0], hv[1]);
     }
     // bias^T = W2 . hidden^T (+ b2): accumulator rows = heads 16*ht + 4g + r, column = pair
 #pragma unroll
@@ -612,27 +665,21 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
   float* sMul = hist + 2 * E;                            // [E] mul, [E] bias (the per-pair affine of the Gaussian layer)
   float* sBia = sMul + E;
   const int tid = threadIdx.x, lane = tid & 63;
-  for (int c = tid; c < E; c += 256) {
-    sMul[c] = mul[c];
-    sBia[c] = bias[c];
-  }
+  GBF_STAGE_TABLES(sMul, sBia, mul, bias, E, tid, 256);
   // W1^T with the feature (contraction) axis in k-slot order: slot 32u+8g+4hf+e <- feature 32u+16hf+4g+e
   for (int c = tid; c < GBF_K * GBF_F; c += 256) {
     const int f = c >> 7, k = c & 127;                   // coalesced read of W1[f][k]
     const int u = f >> 5, hf = (f >> 4) & 1, g = (f >> 2) & 3, e = f & 3;
     sW1T[k * GBF_WS + 32 * u + 8 * g + 4 * hf + e] = W1[c];
   }
-  for (int c = tid; c < GBF_H * GBF_F; c += 256) {
-    const int h = c >> 7, f = c & 127;
-    sW2T[f * GBF_W2S + h] = W2[c];
-  }
+  GBF_STAGE_W2T(sW2T, W2, tid, 256);
   if (tid < GBF_K) {
-    const float sg = fabsf(stds[tid]) + 1e-5f;
+    const float sg = gbf_sigma(stds[tid]);
     sMu[tid] = means[tid];
     sIs[tid] = 1.0f / sg;
-    sCf[tid] = 1.0f / (GBF_A * sg);
+    sCf[tid] = gbf_coef(sg);
   }
-  for (int c = tid; c < 2 * E; c += 256) hist[c] = 0.f;
+  GBF_HIST_ZERO(hist, E, tid, 256);
   __syncthreads();
   const int g = lane >> 4, i = lane & 15;
   const long long ntiles = (long long)B * tpm;
@@ -671,7 +718,7 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
     valid = ii < N && jj < N;
     p = ((long long)b * N + (valid ? ii : 0)) * N + (valid ? jj : 0);
     const int e32 = gbf_edge(et, p, esz);
-    e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
+    e = GBF_CLAMP_EDGE(e32, E);
     d = dist[p];
     const GT* gp = gsrc + (long long)b * GBF_H * plane + (valid ? q : 0);
 #pragma unroll
@@ -718,10 +765,7 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
         }
         const uint2 up = upre[ft];
         if (ugrad) {   // (the forward saved gelu' itself)
-          acc[0] *= __uint_as_float(up.x << 16);
-          acc[1] *= __uint_as_float(up.x & 0xffff0000u);
-          acc[2] *= __uint_as_float(up.y << 16);
-          acc[3] *= __uint_as_float(up.y & 0xffff0000u);
+          acc = gbf_mul4(acc, up);
         } else {
           acc[0] *= gelu_erf_grad(__uint_as_float(up.x << 16));
           acc[1] *= gelu_erf_grad(__uint_as_float(up.x & 0xffff0000u));
@@ -732,8 +776,7 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
         dv[hf] = acc;
         __builtin_amdgcn_sched_barrier(0);
       }
-      float v[8] = {dv[0][0], dv[0][1], dv[0][2], dv[0][3], dv[1][0], dv[1][1], dv[1][2], dv[1][3]};
-      uB[u] = gbf_pack8(v);
+      uB[u] = gbf_pack8(dv[0], dv[1]);
     }
     // dbasis^T = W1^T . du^T: rows = Gaussian kernels 16*kt + 4g + r; Gaussian backward on the accumulator layout
     float dy = 0.f;
@@ -761,8 +804,7 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    dy += __shfl_xor(dy, 16, 64);
-    dy += __shfl_xor(dy, 32, 64);
+    GBF_SUM4X16(dy);
     if (g == 0 && valid) {
       atomicAdd(&hist[e], dy * d);
       atomicAdd(&hist[E + e], dy);
@@ -780,8 +822,8 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float a = amu[kt][r], sgv = asg[kt][r];
-      a += __shfl_xor(a, 1, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 4, 64); a += __shfl_xor(a, 8, 64);
-      sgv += __shfl_xor(sgv, 1, 64); sgv += __shfl_xor(sgv, 2, 64); sgv += __shfl_xor(sgv, 4, 64); sgv += __shfl_xor(sgv, 8, 64);
+      GBF_SUM16(a);
+      GBF_SUM16(sgv);
       if (i == 0) {
         const int k = 16 * kt + 4 * g + r;
         atomicAdd(dmeans + k, a);
@@ -789,11 +831,7 @@ __global__ __launch_bounds__(256, 2) void gbf_bias_bwd_kernel(const GT* __restri
       }
     }
   __syncthreads();
-  for (int c = tid; c < E; c += 256) {
-    const float a = hist[c], bb = hist[E + c];
-    if (a != 0.f) atomicAdd(dmul + c, a);
-    if (bb != 0.f) atomicAdd(dbias + c, bb);
-  }
+  GBF_HIST_FLUSH(hist, E, tid, 256, dmul, dbias);
 }
 
 // =====================================================================================================================
@@ -834,7 +872,7 @@ __device__ __forceinline__ gbf16x8 gbf_tr8(const bf16_t* a0, const bf16_t* a1) {
 //   * phase B2 stages the tile's (edge type, dy * d, dy) per pair, and after the barrier the thread that owns histogram bin c adds the
 //     tile's pairs of that edge type in pair order.
 // With the per-workgroup slabs (required in the mode) every sum of this kernel then has an order that depends on the grid alone.
-// COORDS: as in the forward kernel -- fetch takes the two atoms' records, gbf_pair_rule turns them into (edge type, distance).
+// COORDS: as in gbf_bias_fwd_kernel (GBF_PAIR_LOAD) -- fetch takes the two atoms' records, gbf_pair_rule turns them into (edge type, distance).
 template <bool TILED, typename GT, bool DET = false, bool COORDS = false>
 __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     const GT* __restrict__ gsrc, const float* __restrict__ dist, const void* __restrict__ et, int esz, const float* __restrict__ mul,
@@ -863,28 +901,19 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
   float* sHa = reinterpret_cast<float*>(sHe + 128);
   float* sHb = sHa + 128;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int c = tid; c < E; c += 512) {
-    sMul[c] = mul[c];
-    sBia[c] = bias[c];
-  }
-  for (int c = tid; c < GBF_F * (GBF_K / 8); c += 512) {
-    const int row = c >> 4, col = (c & 15) * 8;
-    *reinterpret_cast<uint4*>(sW1 + row * GBF_LW + col) = *reinterpret_cast<const uint4*>(W1 + row * GBF_K + col);
-  }
-  for (int c = tid; c < GBF_H * GBF_F; c += 512) {
-    const int h = c >> 7, f = c & 127;
-    sW2T[f * GBF_W2S + h] = W2[c];
-  }
+  GBF_STAGE_TABLES(sMul, sBia, mul, bias, E, tid, 512);
+  gbf_stage_w1<512>(sW1, W1, GBF_LW);
+  GBF_STAGE_W2T(sW2T, W2, tid, 512);
   if (tid < GBF_K) {
-    const float sg = fabsf(stds[tid]) + 1e-5f;
+    const float sg = gbf_sigma(stds[tid]);
     sMu[tid] = means[tid];
     sIs[tid] = 1.0f / sg;
-    sCf[tid] = 1.0f / (GBF_A * sg);
+    sCf[tid] = gbf_coef(sg);
     sIq[tid] = GBF_SQ / sg;
     sB1[tid] = b1[tid];
     sDy[tid] = 0.f;
   }
-  for (int c = tid; c < 2 * E; c += 512) hist[c] = 0.f;
+  GBF_HIST_ZERO(hist, E, tid, 512);
   __syncthreads();
   const int g = lane >> 4, i = lane & 15;
   const int ploc = 16 * wave + i;                                 // this lane's row in the pair tiles
@@ -915,7 +944,7 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
   unsigned o_gconst = o_f32 + (unsigned)(8 * g) * 4;             // Gaussian constants of kernels 32c + 8g + 0..7 (phase A)
   unsigned o_b1row = o_f32 + (unsigned)(4 * GBF_K + 4 * g) * 4;
   unsigned o_kconst = o_f32 + (unsigned)(16 * wave + 4 * g) * 4; // phase B1's Gaussian constants: kernels k = 16*wave + 4g + r
-  // (ragged batches: tile_prefix as in the forward kernel -- here a molecule's tiles are its 4x4 blocks of REAL pairs, column
+  // (ragged batches: tile_prefix as in GBF_TILE_MOLECULE -- here a molecule's tiles are its 4x4 blocks of REAL pairs, column
   //  block slowest, so a prefix of them covers its first key tiles; the gradient is zero, and never written, behind them)
   const bool rag = TILED && tile_prefix != nullptr;
   const int ntiles = rag ? tile_prefix[B] : B * tpm;
@@ -938,39 +967,11 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     act = tile < ntiles;
     tile = act ? tile : ntiles - 1;
     int b, tq;
-    if (rag) {
-      while (b_run + 1 < B && tile >= tile_prefix[b_run + 1]) ++b_run;
-      b = b_run;
-      tq = tile - tile_prefix[b];
-    } else {
-      b = (int)((unsigned)tile / (unsigned)tpm);
-      tq = tile - b * tpm;
-    }
-    int q, ii, jj;
-    if (TILED) {
-      const int rbk = (rag && row_blocks) ? row_blocks[b] : nb;               // (packed token rows: see the forward kernel)
-      const int cb = (int)((unsigned)tq / (unsigned)rbk), rb = tq - cb * rbk;   // query block fastest: see the forward kernel
-      ii = 4 * rb + (i >> 2);
-      jj = 4 * cb + (i & 3);
-      q = (int)pair_off(N, ii < N ? ii : 0, jj);
-    } else {
-      q = tq * 16 + i;
-      ii = (int)((unsigned)q / (unsigned)ld);
-      jj = q - ii * ld;
-    }
+    GBF_TILE_MOLECULE();
+    int q;
+    GBF_TILE_PAIR(nb);
     valid = act && ii < N && jj < N;
-    // scalar base of the molecule + 32-bit lane offsets (host: N*N and 64*plane fit 31 bits)
-    if constexpr (COORDS) {
-      const uint4* mr = rec + (long long)b * N;
-      ai = mr[valid ? ii : 0];
-      aj = mr[valid ? jj : 0];
-    } else {
-      const long long mol = (long long)b * N * N;
-      const unsigned pl = (unsigned)((valid ? ii : 0) * N + (valid ? jj : 0));
-      const int e32 = gbf_edge(et, mol, pl, esz);
-      e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);
-      d = (dist + mol)[pl];
-    }
+    GBF_PAIR_LOAD(gbf_plane_off(valid, ii, jj, N));
     const GT* mb = gsrc + (long long)b * GBF_H * plane;
     const unsigned voff = (unsigned)(8 * g) * (unsigned)plane + (unsigned)(valid ? q : 0);
 #pragma unroll
@@ -998,9 +999,9 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     const float* gconst = reinterpret_cast<const float*>(gbf_smem + o_gconst);
     const float* b1row = reinterpret_cast<const float*>(gbf_smem + o_b1row);
     const float* kconst = reinterpret_cast<const float*>(gbf_smem + o_kconst);
-    if constexpr (COORDS) {       // (before the next fetch, as in the forward kernel)
+    if constexpr (COORDS) {       // (before the next fetch, as in gbf_bias_fwd_kernel: the records become (e, d) before the next pair's go live)
       gbf_pair_rule(ai, aj, V, pad, e, d);
-      e = e < 0 ? 0 : (e >= E ? E - 1 : e);
+      e = GBF_CLAMP_EDGE(e, E);
     }
     fetch(tile + stride, n_act, n_valid, n_d, n_e, n_gv, n_ai, n_aj);
     // ------------------------------------------------------------------------------------------------ phase A
@@ -1053,23 +1054,17 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
             ua = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, fB[c], ua, 0, 0, 0);
           }
           ua += *reinterpret_cast<const gf32x4*>(b1row + 16 * ft);
-          {
-            f32x2_t y0, g0, y1, g1;
-            gelu_erf_both2(f32x2_t{ua[0], ua[1]}, y0, g0);
-            gelu_erf_both2(f32x2_t{ua[2], ua[3]}, y1, g1);
-            hv[hf] = gf32x4{y0[0], y0[1], y1[0], y1[1]};
-            // gelu' passes through bf16 exactly where the unfused chain's saved tensor did
-            const uint2 gb = gbf_pack4(gf32x4{g0[0], g0[1], g1[0], g1[1]});
-            acc[0] *= __uint_as_float(gb.x << 16);
-            acc[1] *= __uint_as_float(gb.x & 0xffff0000u);
-            acc[2] *= __uint_as_float(gb.y << 16);
-            acc[3] *= __uint_as_float(gb.y & 0xffff0000u);
-          }
+          f32x2_t y0, g0, y1, g1;
+          gelu_erf_both2(f32x2_t{ua[0], ua[1]}, y0, g0);
+          gelu_erf_both2(f32x2_t{ua[2], ua[3]}, y1, g1);
+          hv[hf] = gf32x4{y0[0], y0[1], y1[0], y1[1]};
+          // gelu' passes through bf16 exactly where the unfused chain's saved tensor did
+          const uint2 gb = gbf_pack4(gf32x4{g0[0], g0[1], g1[0], g1[1]});
+          acc = gbf_mul4(acc, gb);
           *reinterpret_cast<uint2*>(GBF_SWZ(r1lo, r1hi, 16 * ft) + 4 * g) = gbf_pack4(acc);
           __builtin_amdgcn_sched_barrier(0);
         }
-        float w[8] = {hv[0][0], hv[0][1], hv[0][2], hv[0][3], hv[1][0], hv[1][1], hv[1][2], hv[1][3]};
-        hB[u] = gbf_pack8(w);      // slots 8g' + 4hf + e <-> features 32u + 16hf + 4g + e
+        hB[u] = gbf_pack8(hv[0], hv[1]);      // slots 8g' + 4hf + e <-> features 32u + 16hf + 4g + e
       }
     } else {                       // tile past the end: its rows of the pair tiles contribute nothing
       const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
@@ -1133,8 +1128,7 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
         GBF_G2(2, acc[2], acc[3])
 #undef GBF_G2
         float dy = dy2[0] + dy2[1];
-        dy += __shfl_xor(dy, 16, 64);
-        dy += __shfl_xor(dy, 32, 64);
+        GBF_SUM4X16(dy);
         if (g == 0) {
           if constexpr (DET) sDyW[128 * wave + 16 * j + i] = dy;
           else atomicAdd(&sDy[16 * j + i], dy);
@@ -1252,8 +1246,8 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     float a = amu[r], sgv = asg[r];
-    a += __shfl_xor(a, 1, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 4, 64); a += __shfl_xor(a, 8, 64);
-    sgv += __shfl_xor(sgv, 1, 64); sgv += __shfl_xor(sgv, 2, 64); sgv += __shfl_xor(sgv, 4, 64); sgv += __shfl_xor(sgv, 8, 64);
+    GBF_SUM16(a);
+    GBF_SUM16(sgv);
     if (i == 0) {
       const int k = 16 * wave + 4 * g + r;
       const float ds = stds[k] < 0.f ? -sgv : sgv;        // d|std|/dstd
@@ -1262,6 +1256,8 @@ __global__ __launch_bounds__(512, 1) void gbf_bias_bwd_full_kernel(
     }
   }
   __syncthreads();
+  // (GBF_HIST_FLUSH with the slab test inside its loop.  Hoisted -- if (sl) copy loop, else GBF_HIST_FLUSH -- all 12 instances of this kernel
+  //  compile to 15 to 59 more instructions, and they are held to the stream they had.)
   for (int c = tid; c < E; c += 512) {
     const float a = hist[c], bb = hist[E + c];
     if (sl) { sl[GBF_SLAB + c] = a; sl[GBF_SLAB + E + c] = bb; }

@@ -171,6 +171,133 @@ __device__ __forceinline__ void pa_dispatch_kt(int ke, F&& f) {
   }
 }
 
+// ---- The pieces pair_attn_fwd_mfma_kernel (pair_attn.hip) and pair_attn_bwd_mfma_kernel (pair_attn_bwd_mfma.h) share, one definition
+// each.  Both kernels are held to the instruction streams they had before the pieces were shared (profiles/pair_kernels_shared_isa.txt).
+// The pieces that declare or name the state of a kernel body are macros: that state lives in the captures of the kernels' body lambdas.
+
+// Workgroup prologue.  Declares bh / b / h (the 64 heads of a token share 128-byte q / k / v lines, 8 heads per line: xcd_chunk keeps a
+// molecule's heads on one XCD), D / D3, tid / lane / wave / nwaves, nKB, kt (wave-uniform: one molecule per workgroup; rounded up to a
+// count the sweeps are unrolled for) and the token rows of molecule b: row0 / rows / base.
+// PACKED token rows (RAG only, row_off != null): molecule b owns rows [row_off[b], row_off[b+1]) of qkv / o / key_pad -- its real
+// tokens followed by at most ONE representative pad row (every pad row of a molecule is the same row at dropout 0: zeroed
+// input, constant bias row, same keys) -- instead of rows [b*N, (b+1)*N).  Pair planes stay indexed by position.
+// Names the kernel's RAG, NT, qkv, N, H, key_tiles, row_off.
+#define PA_WG_PROLOGUE()                                                                                                   \
+  const int bh = xcd_chunk(blockIdx.x, gridDim.x), b = bh / H, h = bh - b * H;                                             \
+  const int D = H * HD, D3 = 3 * D;                                                                                        \
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;                                 \
+  const int nKB = (N + 15) >> 4;                                                                                           \
+  const int kt = RAG ? pa_kt_effective(min(__builtin_amdgcn_readfirstlane(key_tiles[b]), nKB), NT) : NT;                   \
+  const bool packed = RAG && row_off != nullptr;                                                                           \
+  const int row0 = packed ? __builtin_amdgcn_readfirstlane(row_off[b]) : b * N;                                            \
+  const int rows = packed ? __builtin_amdgcn_readfirstlane(row_off[b + 1]) - row0 : N;                                     \
+  const bf16_t* base = qkv + (long long)row0 * D3 + h * HD
+
+// Layouts (TILED): row-major [N][ld] planes, or the blocked-row planes of common.h whose 16x16 tiles are stored in accumulator
+// order -- a wave's access to a tile is then one contiguous KiB at a compile-time offset from the query block's base,
+// and, because every pad slot of a tiled S holds -inf (written by mmdti_gbf_bias_fwd, preserved by every S store) and every pad slot
+// of a tiled G holds 0, interior tiles need no predicate and no pad masking at all.  Only the last query block (EDGE) and the last
+// key tile keep per-lane predicates.  FULL: nKB == NT, so "last tile" is a compile-time index.
+// PA_LAST_TILE: declares nlast, colok and the dropout key rk of the (molecule, head) plane (common.h).  Names nKB, g, N, seed, site, bh.
+#define PA_LAST_TILE()                                 \
+  const int nlast = nKB - 1;                           \
+  const bool colok = 4 * g < N - 16 * nlast;           \
+  const Rng24 rk = rng24_key(seed, site, (uint32_t)bh)
+// Query-block addressing of a body (query block qb, EDGE), in three parts so that each kernel keeps the order of its statements (moving the
+// kernels' own loads and pointers across them changes the schedule).  PA_QROW declares qi, this query row's drop threshold t8, qvalid and
+// rowoff (row-major: the lane's 4 keys of tile t start at rowoff + 16t + 4g; also the dropout counter base); PA_QTILE vr and tbase;
+// PA_TILE_STEP TSTEP and goff.
+// (tiled planes, common.h "blocked rows": the block of 16 queries starts at 16 qb N4, a lane's 4 keys of tile t sit at
+//  vr (16 t + 4 g) + 4 c16 -- 256 t + 4 lane in a complete block; lanes past the last query of an incomplete block point at query 0,
+//  key groups past N4 -- N <= 12 only -- at group 0: whatever a predicate-off lane reads lies inside the plane)
+// Names qb, c16, g, thresh, rk, rows, bh, N, ld.
+#define PA_QROW()                                                                                                          \
+  const int qi = qb * 16 + c16;                                                                                            \
+  const uint32_t t8 = thresh ? rng24_row_t8(rk, (uint32_t)qi, thresh) : 0u;                                                \
+  const bool qvalid = EDGE ? qi < rows : true;                                                                             \
+  const long long rowoff = ((long long)bh * N + (qvalid ? qi : 0)) * ld
+#define PA_QTILE()                                                                                                         \
+  const int vr = EDGE ? min(16, N - qb * 16) : 16;                                                                         \
+  const long long tbase = (long long)bh * pair_plane(N) + (long long)qb * 16 * pair_n4(N) + ((4 * g < pair_n4(N) ? g : 0) * vr + (qvalid ? c16 : 0)) * 4
+#define PA_TILE_STEP()                                                                                                     \
+  const int TSTEP = TILED ? (EDGE ? vr * 16 : 256) : 16;                                                                   \
+  const int goff = TILED ? 0 : 4 * g
+// the predicate of this lane's 4 keys of tile T, and "interior tile of a complete query block: no predicate" (FULL only: as a
+// wave-uniform run-time branch it doubles the unrolled code and the NT = 13 backward fell out of the instruction cache, 1.2 -> 3.3 ms).
+// Name TILED, FULL, EDGE, NT, qvalid, g, N, nlast, colok.
+#define PA_PRED(T) (!TILED ? (qvalid && (T) * 16 + 4 * g < N) \
+                           : (qvalid && (FULL ? ((T) < NT - 1 || colok) : ((T) < nlast || ((T) == nlast && colok)))))
+#define PA_FAST(T) (TILED && !EDGE && (FULL ? (T) < NT - 1 : false))
+// (Statement macros are one statement each -- a comma expression or a do { } while (0) -- and are written with their semicolon.)
+// DST = the lane's 4 values of tile T of the plane at PTR: a non-temporal load on the fast path, else predicated -- a lane whose
+// predicate is off reads the first 16 bytes at PTR (always inside the tensor) and takes FILL.  PA_LOAD4_IF: only where COND (uniform:
+// the backward's "there is an incoming gradient") holds, FILL elsewhere.  Names TSTEP, goff.
+// (PA_LOAD4_: AND_COND is "&& (COND)", or nothing where COND is true -- "PA_PRED(T) && (true)" gives the non-FULL tiled instances of both
+//  kernels other instruction streams, and "(COND) ? PA_PRED(T) : false" every backward instance.)
+#define PA_LOAD4_(DST, PTR, T, FILL, COND, AND_COND)                             \
+  do {                                                                           \
+    if (PA_FAST(T)) {                                                            \
+      const f32x4 ld4 = pa_load4_nt((PTR) + ((COND) ? (T) * TSTEP + goff : 0));  \
+      DST = (COND) ? ld4 : f32x4{FILL, FILL, FILL, FILL};                        \
+    } else {                                                                     \
+      const bool pr = PA_PRED(T) AND_COND;                                       \
+      const f32x4 ld4 = pa_load4((PTR) + (pr ? (T) * TSTEP + goff : 0));         \
+      DST = pr ? ld4 : f32x4{FILL, FILL, FILL, FILL};                            \
+    }                                                                            \
+  } while (0)
+#define PA_LOAD4(DST, PTR, T, FILL) PA_LOAD4_(DST, PTR, T, FILL, true, )
+#define PA_LOAD4_IF(DST, PTR, T, FILL, COND) PA_LOAD4_(DST, PTR, T, FILL, COND, && (COND))
+// ... and the store of V to them
+#define PA_STORE4(PTR, T, V)                                                     \
+  do {                                                                           \
+    if (PA_FAST(T)) {                                                            \
+      pa_store4_nt((PTR) + (T) * TSTEP + goff, V);                               \
+    } else if (PA_PRED(T)) {                                                     \
+      pa_store4_nt((PTR) + (T) * TSTEP + goff, V);                               \
+    }                                                                            \
+  } while (0)
+// Row softmax of the KT quads X[t] a lane holds of its query's row.  PA_ROW_MAX finishes the row max M over the lane groups;
+// PA_ROW_EXP2 declares mneg and lsum, replaces X by exp(X - M) as exp2(X * log2(e) - M * log2(e)) -- one FMA + v_exp_f32 per element,
+// the same in both directions -- and sums the row.  (What an all -inf row does to M and what becomes of 1 / lsum is the kernels' own.)
+#define PA_ROW_MAX(M) ((M) = fmaxf((M), __shfl_xor((M), 16, 64)), (M) = fmaxf((M), __shfl_xor((M), 32, 64)))
+#define PA_ROW_EXP2(X, M)                                                        \
+  const float mneg = -M * PA_LOG2E;                                              \
+  float lsum = 0.f;                                                              \
+  _Pragma("unroll")                                                              \
+  for (int t = 0; t < KT; ++t) {                                                 \
+    {                                                                            \
+      _Pragma("unroll")                                                          \
+      for (int r = 0; r < 4; ++r) {                                              \
+        const float e = __builtin_amdgcn_exp2f(fmaf(X[t][r], PA_LOG2E, mneg));   \
+        X[t][r] = e;                                                             \
+        lsum += e;                                                               \
+      }                                                                          \
+    }                                                                            \
+  }                                                                              \
+  lsum += __shfl_xor(lsum, 16, 64);                                              \
+  lsum += __shfl_xor(lsum, 32, 64)
+// the dropout word of the lane's 4 keys of tile T (the counter: the element's index in the row-major plane).  Names rk, qi, ld, g.
+#define PA_DROP_WORD(T) rng24_word(rk, ((uint32_t)qi * (uint32_t)ld + (T) * 16 + 4 * g) >> 2)
+// what a wave has written to its LDS patches is visible to its other lanes
+__device__ __forceinline__ void pa_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// The kernels' tail: every wave takes query blocks wave, wave + nwaves, .. (packed: the pad rows past the representative one are not
+// computed), a complete block of a tiled plane without the EDGE predicates; ragged kernels branch once into the body unrolled for kt.
+// Names body, packed, rows, nKB, wave, nwaves, kt.
+#define PA_RUN_QUERY_BLOCKS()                                                    \
+  const int nQB = packed ? (rows + 15) >> 4 : nKB;                               \
+  auto run = [&](auto kt_c) {                                                    \
+    for (int qb = wave; qb < nQB; qb += nwaves) {                                \
+      if (TILED && qb * 16 + 16 <= rows) body(qb, std::false_type{}, kt_c);      \
+      else body(qb, std::true_type{}, kt_c);                                     \
+    }                                                                            \
+  };                                                                             \
+  if constexpr (RAG) pa_dispatch_kt<NT, NT>(kt, run);                            \
+  else run(std::integral_constant<int, NT>{})
+
 }  // namespace mmdti
 
 

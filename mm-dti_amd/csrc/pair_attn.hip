@@ -133,20 +133,7 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
   __shared__ __attribute__((aligned(16))) bf16_t sK[NP * 8];
   __shared__ __attribute__((aligned(16))) bf16_t sVT[8 * KSTR];
   __shared__ __attribute__((aligned(16))) float sM[NP];
-  // (the 64 heads of a token share 128-byte q / k / v lines, 8 heads per line: keep a molecule's heads on one XCD)
-  const int bh = xcd_chunk(blockIdx.x, gridDim.x), b = bh / H, h = bh - b * H;
-  const int D = H * HD, D3 = 3 * D;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-  const int nKB = (N + 15) >> 4;
-  // (wave-uniform: one molecule per workgroup; rounded up to a count the sweeps are unrolled for)
-  const int kt = RAG ? pa_kt_effective(min(__builtin_amdgcn_readfirstlane(key_tiles[b]), nKB), NT) : NT;
-  // PACKED token rows (RAG only, row_off != null): molecule b owns rows [row_off[b], row_off[b+1]) of qkv / o / key_pad -- its real
-  // tokens followed by at most ONE representative pad row (every pad row of a molecule is the same row at dropout 0: zeroed
-  // input, constant bias row, same keys) -- instead of rows [b*N, (b+1)*N).  Pair planes stay indexed by position.
-  const bool packed = RAG && row_off != nullptr;
-  const int row0 = packed ? __builtin_amdgcn_readfirstlane(row_off[b]) : b * N;
-  const int rows = packed ? __builtin_amdgcn_readfirstlane(row_off[b + 1]) - row0 : N;
-  const bf16_t* base = qkv + (long long)row0 * D3 + h * HD;
+  PA_WG_PROLOGUE();   // (pair_attn.h, as every PA_ piece below)
   for (int t = tid; t < NP; t += blockDim.x) {
     uint4 q = make_uint4(0u, 0u, 0u, 0u), kk = q, vv = q;
     float msk = 1.f;
@@ -167,40 +154,19 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
   __syncthreads();
   const int g = lane >> 4, c16 = lane & 15;
   const float NEG_INF = -INFINITY;
-  // Layouts (TILED): row-major [N][ld] planes, or the blocked-row planes of common.h whose 16x16 tiles are stored in accumulator
-  // order -- a wave's access to a tile is then one contiguous KiB at a compile-time offset from the query block's base,
-  // and, because every pad slot of a tiled tensor holds -inf (written by mmdti_gbf_bias_fwd, preserved by every S
-  // store), interior tiles need no predicate and no pad masking at all.  Only the last query block (EDGE) and the last
-  // key tile keep per-lane predicates.  FULL: nKB == NT, so "last tile" is a compile-time index.
-  const int nlast = nKB - 1;
-  const bool colok = 4 * g < N - 16 * nlast;
-  const Rng24 rk = rng24_key(seed, site, (uint32_t)bh);     // dropout: the (molecule, head) plane's key (common.h)
+  PA_LAST_TILE();
   auto body = [&](int qb, auto edge_c, auto kt_c) {
     constexpr bool EDGE = decltype(edge_c)::value;
     constexpr int KT = decltype(kt_c)::value;   // key tiles this molecule's sweeps cover (NT unless RAG)
-    const int qi = qb * 16 + c16;
-    const uint32_t t8 = thresh ? rng24_row_t8(rk, (uint32_t)qi, thresh) : 0u;   // this query row's drop threshold
-    const bool qvalid = EDGE ? qi < rows : true;
-    const long long rowoff = ((long long)bh * N + (qvalid ? qi : 0)) * ld;   // (also the dropout counter base)
+    PA_QROW();
     const pa_s16x4 zero4 = {0, 0, 0, 0};
     // B of S^T = K.Q^T : Q[query c16][d = 4g..4g+3] (k = d: lane groups 2, 3 carry zeros)
     const pa_s16x4 qv = g < 2 ? *reinterpret_cast<const pa_s16x4*>(sQ + (qb * 16 + c16) * 8 + 4 * g) : zero4;
-    // (tiled planes, common.h "blocked rows": the block of 16 queries starts at 16 qb N4, a lane's 4 keys of tile t sit at
-    //  vr (16 t + 4 g) + 4 c16 -- 256 t + 4 lane in a complete block; lanes past the last query of an incomplete block point at query 0,
-    //  key groups past N4 -- N <= 12 only -- at group 0: whatever a predicate-off lane reads lies inside the plane)
-    const int vr = EDGE ? min(16, N - qb * 16) : 16;
-    const long long tbase = (long long)bh * pair_plane(N) + (long long)qb * 16 * pair_n4(N) + ((4 * g < pair_n4(N) ? g : 0) * vr + (qvalid ? c16 : 0)) * 4;
-    // (row-major: the lane's 4 keys of tile t start at rowoff + 16t + 4g; a lane whose predicate is off reads the row's
-    //  first 16 bytes instead -- always inside the tensor, unlike "tile 0 + 4g" when ld < 16)
+    PA_QTILE();
+    // (a lane whose predicate is off reads the row's first 16 bytes -- always inside the tensor, unlike "tile 0 + 4g" when ld < 16)
     const ST* bin = bias_in + (TILED ? tbase : rowoff);
     ST* sout = s_out + (TILED ? tbase : rowoff);
-    const int TSTEP = TILED ? (EDGE ? vr * 16 : 256) : 16;
-    const int goff = TILED ? 0 : 4 * g;
-#define PA_PRED(T) (!TILED ? (qvalid && (T) * 16 + 4 * g < N) \
-                           : (qvalid && (FULL ? ((T) < NT - 1 || colok) : ((T) < nlast || ((T) == nlast && colok)))))
-    // interior tiles of a complete query block: no predicate (FULL only: as a wave-uniform run-time branch it doubles the unrolled
-    // code and the NT = 13 backward fell out of the instruction cache, 1.2 -> 3.3 ms)
-#define PA_FAST(T) (TILED && !EDGE && (FULL ? (T) < NT - 1 : false))
+    PA_TILE_STEP();
     // Phase 1: request every bias tile of this query block (the NT 16-byte loads are issued back to back and stay in
     // flight together).  Slots that are not loaded: -inf (pad keys), or 0 in a pad ROW (keeps that row's softmax finite;
     // nothing of it is stored).
@@ -208,24 +174,14 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
     f32x4 S[KT];
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
-      if (PA_FAST(t)) {
-        S[t] = pa_load4_nt(bin + t * TSTEP + goff);
-      } else {
-        const bool pr = PA_PRED(t);
-        const f32x4 ld4 = pa_load4(bin + (pr ? t * TSTEP + goff : 0));
-        S[t] = pr ? ld4 : f32x4{fillv, fillv, fillv, fillv};
-      }
+      PA_LOAD4(S[t], bin, t, fillv);
     }
     float m = NEG_INF;
     if (RAG && rag_store) {   // the all-padding tiles past KT: -inf (the last layer: its S goes back to the caller)
       const f32x4 ninf = {NEG_INF, NEG_INF, NEG_INF, NEG_INF};
 #pragma unroll
       for (int t = KT; t < NT; ++t) {
-        if (PA_FAST(t)) {
-          pa_store4_nt(sout + t * TSTEP + goff, ninf);
-        } else if (PA_PRED(t)) {
-          pa_store4_nt(sout + t * TSTEP + goff, ninf);
-        }
+        PA_STORE4(sout, t, ninf);
       }
     }
 #pragma unroll
@@ -245,34 +201,14 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
         }
         typename std::conditional<sizeof(ST) == 2, pa_f16x4, f32x4>::type cs;
         c = pa_round4(cs, c);   // (compact: the fp16 value that is stored is also the one this layer's softmax sees)
-        if (PA_FAST(t)) {
-          pa_store4_nt(sout + t * TSTEP + goff, cs);
-        } else if (PA_PRED(t)) {
-          pa_store4_nt(sout + t * TSTEP + goff, cs);
-        }
+        PA_STORE4(sout, t, cs);
         S[t] = c;
         m = fmaxf(fmaxf(m, c[0]), c[1]);   // (two v_max3_f32)
         m = fmaxf(fmaxf(m, c[2]), c[3]);
       }
     }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    // exp(S - m) as exp2(S * log2(e) - m * log2(e)): one FMA + v_exp_f32 per element (the backward recomputes it the same way)
-    const float mneg = -m * PA_LOG2E;
-    float lsum = 0.f;
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = __builtin_amdgcn_exp2f(fmaf(S[t][r], PA_LOG2E, mneg));
-          S[t][r] = e;
-          lsum += e;
-        }
-      }
-    }
-    lsum += __shfl_xor(lsum, 16, 64);
-    lsum += __shfl_xor(lsum, 32, 64);
+    PA_ROW_MAX(m);
+    PA_ROW_EXP2(S, m);
     const float inv = dscale / lsum;   // (dropout's 1 / (1 - p) folded in: dscale == 1 without dropout)
     f32x4 oacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -280,7 +216,7 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
       {
         f32x4 p = S[t] * inv;
         if (thresh) {
-          const uint32_t kw = rng24_word(rk, ((uint32_t)qi * (uint32_t)ld + t * 16 + 4 * g) >> 2);
+          const uint32_t kw = PA_DROP_WORD(t);
 #pragma unroll
           for (int r = 0; r < 4; ++r) p[r] = rng24_kept(kw, r, t8) ? p[r] : 0.f;
         }
@@ -304,18 +240,8 @@ __global__ __launch_bounds__(256, NT > 9 ? 2 : 4) void pair_attn_fwd_mfma_kernel
       }
       *reinterpret_cast<uint2*>(o + ((long long)row0 + qi) * D + h * HD + 4 * g) = pk;
     }
-#undef PA_PRED
-#undef PA_FAST
   };
-  const int nQB = packed ? (rows + 15) >> 4 : nKB;   // (packed: the pad rows past the representative one are not computed)
-  auto run = [&](auto kt_c) {
-    for (int qb = wave; qb < nQB; qb += nwaves) {
-      if (TILED && qb * 16 + 16 <= rows) body(qb, std::false_type{}, kt_c);
-      else body(qb, std::true_type{}, kt_c);
-    }
-  };
-  if constexpr (RAG) pa_dispatch_kt<NT, NT>(kt, run);
-  else run(std::integral_constant<int, NT>{});
+  PA_RUN_QUERY_BLOCKS();
 }
 
 // =====================================================================================================================

@@ -7,7 +7,7 @@
 
 namespace mmdti {
 
-// RAG: see the forward kernel.  Skipped key tiles contribute nothing (P = 0, G = 0) and their G is NOT written: the caller
+// RAG: see pair_attn_fwd_mfma_kernel (pair_attn.hip).  Skipped key tiles contribute nothing (P = 0, G = 0) and their G is NOT written: the caller
 // hands in a zero-initialised G when the batch is ragged.
 template <int NT, bool TILED, bool FULL, int NW, bool RAG, typename ST, typename GT>
 __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) : 3) void pair_attn_bwd_mfma_kernel(const bf16_t* __restrict__ qkv, const ST* __restrict__ s_in,
@@ -34,17 +34,7 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
   // parts: with two patches instead of four the workgroup stays under 40 KB -> four per CU); the 8-byte slot s of row q
   // sits at slot s ^ (2 * (q >> 3)), which makes both the row writes and the transposing reads conflict-free
   __shared__ __attribute__((aligned(16))) bf16_t patch[NW][2][256];
-  // (the 64 heads of a token share 128-byte q / k / v lines, 8 heads per line: keep a molecule's heads on one XCD)
-  const int bh = xcd_chunk(blockIdx.x, gridDim.x), b = bh / H, h = bh - b * H;
-  const int D = H * HD, D3 = 3 * D;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-  const int nKB = (N + 15) >> 4;
-  const int kt = RAG ? pa_kt_effective(min(__builtin_amdgcn_readfirstlane(key_tiles[b]), nKB), NT) : NT;   // (see the forward kernel)
-  // (packed token rows: see the forward kernel)
-  const bool packed = RAG && row_off != nullptr;
-  const int row0 = packed ? __builtin_amdgcn_readfirstlane(row_off[b]) : b * N;
-  const int rows = packed ? __builtin_amdgcn_readfirstlane(row_off[b + 1]) - row0 : N;
-  const bf16_t* base = qkv + (long long)row0 * D3 + h * HD;
+  PA_WG_PROLOGUE();   // (pair_attn.h, as every PA_ piece below)
   for (int t = tid; t < NP + 2; t += blockDim.x) {
     uint4 q = make_uint4(0u, 0u, 0u, 0u), kk = q, vv = q, dd = q;
     if (t < rows) {
@@ -76,28 +66,16 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
   const int pwr = c16 * 16 + ((g ^ ((c16 >> 3) << 1)) << 2);
   const int prd = (4 * g + (c16 >> 2)) * 16 + (((c16 & 3) ^ ((g >> 1) << 1)) << 2);
   const pa_s16x4 zero4 = {0, 0, 0, 0};
-  // (layouts, TILED / FULL / EDGE: see the forward kernel.  In a tiled S every pad slot is -inf and in a tiled G every pad
-  //  slot is 0 -- both are preserved by the stores below --, so interior tiles run without predicates or pad masking.)
-  const int nlast = nKB - 1;
-  const bool colok = 4 * g < N - 16 * nlast;
-  const Rng24 rk = rng24_key(seed, site, (uint32_t)bh);     // dropout: the (molecule, head) plane's key (common.h)
+  PA_LAST_TILE();   // (the pad slots of a tiled S, -inf, and of a tiled G, 0, are preserved by the stores below)
   auto body = [&](int qb, auto edge_c, auto kt_c) {
     constexpr bool EDGE = decltype(edge_c)::value;
     constexpr int KT = decltype(kt_c)::value;   // key tiles this molecule's sweeps cover (NT unless RAG)
-    const int qi = qb * 16 + c16;
-    const uint32_t t8 = thresh ? rng24_row_t8(rk, (uint32_t)qi, thresh) : 0u;   // this query row's drop threshold
-    const bool qvalid = EDGE ? qi < rows : true;
-    const long long rowoff = ((long long)bh * N + (qvalid ? qi : 0)) * ld;   // (also the dropout counter base)
-    const int vr = EDGE ? min(16, N - qb * 16) : 16;       // (tiled planes: the blocked rows of common.h, see the forward kernel)
-    const long long tbase = (long long)bh * pair_plane(N) + (long long)qb * 16 * pair_n4(N) + ((4 * g < pair_n4(N) ? g : 0) * vr + (qvalid ? c16 : 0)) * 4;
+    PA_QROW();
+    PA_QTILE();
     const ST* sin_p = s_in + (TILED ? tbase : rowoff);     // (predicate-off lanes read the row's first 16 bytes: in bounds)
     const GT* gin_p = gin + (TILED ? tbase : rowoff);
     GT* gout_p = gout + (TILED ? tbase : rowoff);
-    const int TSTEP = TILED ? (EDGE ? vr * 16 : 256) : 16;
-    const int goff = TILED ? 0 : 4 * g;
-#define PA_PRED(T) (!TILED ? (qvalid && (T) * 16 + 4 * g < N) \
-                           : (qvalid && (FULL ? ((T) < NT - 1 || colok) : ((T) < nlast || ((T) == nlast && colok)))))
-#define PA_FAST(T) (TILED && !EDGE && (FULL ? (T) < NT - 1 : false))
+    PA_TILE_STEP();
     // operands of this query block that do not depend on the key tile:
     //   dob : B of dP^T = V.dO^T          -> dO[query c16][d = 4g..4g+3]   (k = d: lane groups 2, 3 carry zeros)
     //   bD  : B of dV  += Pd^T.dO         -> dO[queries 4g..4g+3][d = c16] (transposing read; columns d >= 8 are unused)
@@ -114,13 +92,7 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
       {
         const int kcol = t * 16 + 4 * g;
         f32x4 c;
-        if (PA_FAST(t)) {
-          c = pa_load4_nt(sin_p + t * TSTEP + goff);
-        } else {
-          const bool inrow = PA_PRED(t);
-          const f32x4 ld4 = pa_load4(sin_p + (inrow ? t * TSTEP + goff : 0));
-          c = inrow ? ld4 : f32x4{NEG_INF, NEG_INF, NEG_INF, NEG_INF};
-        }
+        PA_LOAD4(c, sin_p, t, NEG_INF);
         if (!TILED) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) c[r] = (kcol + r < N) ? c[r] : NEG_INF;   // pad columns of the row are not data
@@ -130,24 +102,9 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
         m = fmaxf(fmaxf(m, c[2]), c[3]);
       }
     }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    PA_ROW_MAX(m);
     if (m == NEG_INF) m = 0.f;   // rows beyond N: everything is -inf, keep the arithmetic finite
-    const float mneg = -m * PA_LOG2E;   // (same exponential as the forward: exp2(S * log2(e) - m * log2(e)))
-    float lsum = 0.f;
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-      {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float e = __builtin_amdgcn_exp2f(fmaf(P[t][r], PA_LOG2E, mneg));
-          P[t][r] = e;
-          lsum += e;
-        }
-      }
-    }
-    lsum += __shfl_xor(lsum, 16, 64);
-    lsum += __shfl_xor(lsum, 32, 64);
+    PA_ROW_EXP2(P, m);
     const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
     // dropped elements are remembered in the SIGN of P (P >= 0): |P| feeds the softmax gradient, P > 0 selects dropout(P)
     float dl = 0.f;
@@ -160,7 +117,7 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
         dp = PA_MFMA16(va, dob, dp);
         f32x4 pr = P[t] * inv;
         if (thresh) {
-          const uint32_t kw = rng24_word(rk, ((uint32_t)qi * (uint32_t)ld + t * 16 + 4 * g) >> 2);
+          const uint32_t kw = PA_DROP_WORD(t);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const bool kp = rng24_kept(kw, r, t8);
@@ -182,13 +139,9 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
     // fewer at the 168 cap -- no spills), pinned in place by scheduling barriers
     constexpr int PA_LA = 3;
     auto load_gin = [&](int t) -> f32x4 {
-      if (PA_FAST(t)) {
-        const f32x4 ld4 = pa_load4_nt(gin_p + (g_in_zero ? 0 : t * TSTEP + goff));
-        return g_in_zero ? f32x4{0.f, 0.f, 0.f, 0.f} : ld4;
-      }
-      const bool inrow = PA_PRED(t) && !g_in_zero;
-      const f32x4 ld4 = pa_load4(gin_p + (inrow ? t * TSTEP + goff : 0));
-      return inrow ? ld4 : f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 gq;
+      PA_LOAD4_IF(gq, gin_p, t, 0.f, !g_in_zero);
+      return gq;
     };
     f32x4 Gq[PA_LA];
 #pragma unroll
@@ -212,11 +165,7 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
         for (int r = 0; r < 4; ++r) G[r] = (kcol + r < N) ? G[r] : 0.f;
       }
       if (EDGE && !qvalid) G = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (PA_FAST(t)) {
-        pa_store4_nt(gout_p + t * TSTEP + goff, G);
-      } else if (PA_PRED(t)) {
-        pa_store4_nt(gout_p + t * TSTEP + goff, G);
-      }
+      PA_STORE4(gout_p, t, G);
       f32x4 Pd;
 #pragma unroll
       for (int r = 0; r < 4; ++r) Pd[r] = P[t][r] > 0.f ? P[t][r] * dscale : 0.f;   // dscale == 1 without dropout
@@ -231,19 +180,13 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
       const pa_s16x4 ka = *reinterpret_cast<const pa_s16x4*>(sKT + (c16 & 7) * KSTR + t * 16 + 4 * g);
       dq = PA_MFMA16(ka, Gh, dq);
       dq = PA_MFMA16(ka, Gl, dq);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      pa_wave_sync();
       const pa_s16x4 aPh = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_lds_s16x4*)(pw + prd));
       const pa_s16x4 aGh = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_lds_s16x4*)(pw + 256 + prd));
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();   // (LDS operations of a wave complete in order: the low parts land after the reads above)
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      pa_wave_sync();   // (LDS operations of a wave complete in order: the low parts land after the reads above)
       *reinterpret_cast<pa_s16x4*>(pw + pwr) = Pl;
       *reinterpret_cast<pa_s16x4*>(pw + 256 + pwr) = Gl;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      pa_wave_sync();
       const pa_s16x4 aPl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_lds_s16x4*)(pw + prd));
       const pa_s16x4 aGl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_lds_s16x4*)(pw + 256 + prd));
       // dK / dV of key tile t: accumulator column = d (lanes c16 < 8), rows = keys 16t + 4g + r; the running sums of
@@ -259,9 +202,7 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
         *reinterpret_cast<f32x4*>(accK) = dKt;
         *reinterpret_cast<f32x4*>(accV) = dVt;
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();   // the next tile overwrites the patches
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      pa_wave_sync();   // the next tile overwrites the patches
     }
     // dQ^T accumulator: column = query, rows d = 4g + r (valid for g < 2)
     if (qvalid && g < 2) {
@@ -270,18 +211,8 @@ __global__ __launch_bounds__(64 * NW, NT > 9 ? ((NT >= 16 && NW == 3) ? 2 : 1) :
       pk.y = (uint32_t)f2bf(dq[2] * scale) | ((uint32_t)f2bf(dq[3] * scale) << 16);
       *reinterpret_cast<uint2*>(dqkv + ((long long)row0 + qi) * D3 + h * HD + 4 * g) = pk;
     }
-#undef PA_PRED
-#undef PA_FAST
   };
-  const int nQB = packed ? (rows + 15) >> 4 : nKB;
-  auto run = [&](auto kt_c) {
-    for (int qb = wave; qb < nQB; qb += nwaves) {
-      if (TILED && qb * 16 + 16 <= rows) body(qb, std::false_type{}, kt_c);
-      else body(qb, std::true_type{}, kt_c);
-    }
-  };
-  if constexpr (RAG) pa_dispatch_kt<NT, NT>(kt, run);
-  else run(std::integral_constant<int, NT>{});
+  PA_RUN_QUERY_BLOCKS();
   __syncthreads();
   for (int key = tid; key < rows; key += blockDim.x) {   // (packed: the representative pad row is no key -- its sums are the zeros they started as)
     const int t = key >> 4, kg = (key & 15) >> 2, r = key & 3;

@@ -36,12 +36,12 @@ MODES
 
 REFERENCE (chain(), float64; emulate() is the same function in fp32 -- one statement of the arithmetic, two precisions; without its
 rounding points it agrees with float64 autograd of sum(out G) to 1e-11, test_gbf_cases_cpu.py):
-    y = mul[e] d + bias[e]    val = exp(-z^2 / 2) / (a sigma), z = (y - mu) / sigma, sigma = |std| + 1e-5    basis = bf16(val)   [gbf.hip:380, 41]
-    u = W1 basis + b1         h = bf16(gelu(u)) [:564, :559]          out = W2 h + b2  (compact: min(., 65504) as fp16 [:390])
-    saved: feat = basis, u = bf16(u) or bf16(gelu'(u)) [:555, :553], h
-    dO = bf16(G) in the per-pair kernel [:705]; the complete kernel carries fp32 G as a bf16 hi + lo pair [:1029-1036] (bf16 G: exact)
-    du = bf16((dO W2) gp) [:734, :1079], gp = u_in | gelu'(u_in) (per-pair) or bf16(gelu'(u)) of the recomputed fp32 u (complete [:1073])
-    dW1 = du^T basis, db1 = sum du, dW2 = dO^T h, db2 = sum dO           dbasis = du W1 -- bf16 in the per-pair kernel only [:756; :1128 stays fp32]
+    y = mul[e] d + bias[e]    val = exp(-z^2 / 2) / (a sigma), z = (y - mu) / sigma, sigma = |std| + 1e-5    basis = bf16(val)   [gbf.hip:379, 67]
+    u = W1 basis + b1         h = bf16(gelu(u)) [:615, :611]          out = W2 h + b2  (compact: min(., 65504) as fp16 [:388])
+    saved: feat = basis, u = bf16(u) or bf16(gelu'(u)) [:607, :605], h
+    dO = bf16(G) in the per-pair kernel [:749]; the complete kernel carries fp32 G as a bf16 hi + lo pair [:1019-1026] (bf16 G: exact)
+    du = bf16((dO W2) gp) [:775, :1064], gp = u_in | gelu'(u_in) (per-pair) or bf16(gelu'(u)) of the recomputed fp32 u (complete [:1062])
+    dW1 = du^T basis, db1 = sum du, dW2 = dO^T h, db2 = sum dO           dbasis = du W1 -- bf16 in the per-pair kernel only [:796; :1112 stays fp32]
     t = dbasis val (val unrounded), zs = z / sigma: dy = -sum_k t zs, dmeans = sum_p t zs, dstds = sign(std) sum_p t (z zs - 1 / sigma),
     dmul[e] = sum dy d, dbias[e] = sum dy.        The gradient buffers start at FILL and are accumulated into.
 
@@ -87,13 +87,11 @@ MODES = ("onehot", "random", "clamp")
 
 SOURCE_LINES = (
     "constexpr float GBF_A = 2.5066272160f;  // sqrt(2*3.14159) -- truncated pi exactly as mm_model.py:222-223",
-    "sg[i] = fabsf(stds[k0 + i]) + 1e-5f;",
-    "const float sg = fabsf(stds[tid]) + 1e-5f;",
-    "sCf[tid] = 1.0f / (GBF_A * sg);",
-    "e = e < 0 ? 0 : (e >= E ? E - 1 : e);",
-    "e = e32 < 0 ? 0 : (e32 >= E ? E - 1 : e32);",
+    "__device__ __forceinline__ float gbf_sigma(float sd) { return fabsf(sd) + 1e-5f; }",          # the one definition of sigma ...
+    "__device__ __forceinline__ float gbf_coef(float sg) { return 1.0f / (GBF_A * sg); }",         # ... of 1 / (a sigma) ...
+    "#define GBF_CLAMP_EDGE(X, E) ((X) < 0 ? 0 : ((X) >= (E) ? (E) - 1 : (X)))",                    # ... and of the edge clamp
     "return gbf_pack8(v);",                                                           # the basis leaves gbf_basis8 as bf16
-    "hB[u] = gbf_pack8(v);",                                                          # h before the second product
+    "hB[u] = gbf_pack8(hv[0], hv[1]);",                                               # h before the second product
     "if (SAVE && valid) *reinterpret_cast<uint2*>(u_out + p * GBF_F + 16 * ft + 4 * g) = gbf_pack4(acc);",
     "oB[c] = gbf_pack8(gv + 8 * c);",                                                 # per-pair: dO = bf16(G)
     "for (int j = 0; j < 16; ++j) lo[j] = gv[j] - (float)oB[j >> 3][j & 7];",           # complete: hi + lo

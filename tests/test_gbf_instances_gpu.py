@@ -5,8 +5,8 @@ tests/test_gbf_cases_cpu.py proves on the CPU that the table reaches every insta
 emulation of the kernels' rounding points, and not for six wrong ones.
 
 dist, the edge types, the atom records, G and the saved u are cut from NaN-filled (integers: poisoned) arenas -- G holds NaN in every slot
-that no computed pair owns: an invalid lane of the per-pair backward loads nothing (gbf.hip:683), one of the complete backward loads slot
-0 of the plane, which is pair (0, 0) (gbf.hip:986) -- ; the out planes, the saved tensors, do / du and the eight gradient buffers (filled
+that no computed pair owns: an invalid lane of the per-pair backward loads nothing (gbf.hip:727), one of the complete backward loads slot
+0 of the plane, which is pair (0, 0) (gbf.hip:976) -- ; the out planes, the saved tensors, do / du and the eight gradient buffers (filled
 with gbf_cases.FILL: the kernels accumulate) from sentinel-filled ones.  After every launch: no output holds a NaN, every slot the contract
 says is written holds no sentinel, the pad columns [N, ld) of row-major planes are exactly 0 and the pad keys of tiled planes exactly -inf,
 the blocks behind a ragged molecule's tile prefix and the rows of its pairs there still hold the sentinel, and no sentinel outside a view
