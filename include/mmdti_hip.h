@@ -827,6 +827,22 @@ int mmdti_adam_step_masked(mmdti_stream_t stream, float* p, const float* g, floa
                            float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* grad_scale_dev,
                            const float* step_state_dev, void* p_f16 /* nullable */, const float* guard /* nullable */,
                            const unsigned char* skip);
+/* Parameter groups in the fused pass (tasks/trainer.py:160,270-282: the reference's one Adam(lr, eps) with its clip, extended by what
+ * torch.optim's parameter groups give): mmdti_adam_step_masked (guard and skip nullable, same meaning, same sources of lr and of the
+ * bias corrections) where element i belongs to group gid = group[i / 8] and is updated with the learning rate lr * table_dev[2 gid]
+ * and the weight decay wd = table_dev[2 gid + 1]; there is no by-value weight decay.  Two decay forms:
+ *   decoupled == 0 (torch.optim.Adam):   g' = g * scale + wd * p; the moments and the update see g'
+ *   decoupled != 0 (torch.optim.AdamW):  p *= 1 - lr_i * wd before the update; the moments see g * scale alone
+ * group: one byte per 8 elements, (n + 7) / 8 bytes (the arena's parameters start at multiples of 8 elements); table_dev: fp32
+ * [ngroups][2] on the device, 1 <= ngroups <= 256.  Group ids are NOT checked on the host: the kernel clamps an id >= ngroups to
+ * ngroups - 1.  A scale of 0 is legal: the group's m and v advance (torch with lr = 0) while p and both shadows are not written and
+ * keep their bits.  With a scale of 1 and one weight decay the coupled form reproduces the three entry points above to the bit.
+ * p, g, m, v and the shadows are 16-byte aligned; n == 0 launches nothing.  Purely additive: MMDTI_ABI_VERSION does not move. */
+int mmdti_adam_step_grouped(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                            float lr, float beta1, float beta2, float eps, int step, const float* grad_scale_dev,
+                            const float* step_state_dev, void* p_f16 /* nullable */, const float* guard /* nullable */,
+                            const unsigned char* skip /* nullable */, const unsigned char* group, const float* table_dev, int ngroups,
+                            int decoupled);
 /* HOST function: table_host[2(t-1)], [2(t-1)+1] = 1-beta1^t, sqrt(1-beta2^t) for t = 1 .. steps, exactly as mmdti_adam_step computes
  * them from its by-value step. */
 int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host);

@@ -662,6 +662,118 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// One element of the grouped pass.  Every rounding point is spelt (no contraction left to the backend) as the backend forms adam_kernel's
+// statements: gi = fma(wd, p, g gs); m = fma(b1, m, (1 - b1) gi); v = fma(b2, v, ((1 - b2) gi) gi); p - ((lr / bc1) m) / denom.  With
+// lr_scale == 1 and one weight decay the coupled form therefore EQUALS adam_kernel to the bit (tests/test_adam_group_instances_gpu.py).
+// DECOUPLED (torch.optim.AdamW): p *= 1 - lr_i wd_i first -- three roundings of their own -- and the moments see g alone.
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_group_elem(float& pi, float g, float& mi, float& vi, float gs, float lr_i, float wd_i, float step_size,
+                                                float b1, float b2, float ob1, float ob2, float eps, float bc2_sqrt) {
+#pragma clang fp contract(off)
+  float gi = g * gs;
+  if constexpr (DECOUPLED) {
+    const float lw = lr_i * wd_i;
+    const float keep = 1.f - lw;
+    pi = pi * keep;
+  } else {
+    if (wd_i != 0.f) gi = __builtin_fmaf(wd_i, pi, gi);
+  }
+  const float mg = ob1 * gi;
+  mi = __builtin_fmaf(b1, mi, mg);
+  const float vg = ob2 * gi;
+  const float vgg = vg * gi;
+  vi = __builtin_fmaf(b2, vi, vgg);
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  const float num = step_size * mi;
+  pi = pi - num / denom;
+}
+
+// The Adam pass with parameter groups: group[i / 8] names the group of element i (arena offsets are multiples of 8: a block of 8 never
+// straddles two parameters; an id >= ngroups counts as ngroups - 1), table[2 gid] = the group's learning-rate scale, table[2 gid + 1] its
+// weight decay -- coupled (added to the gradient, torch.optim.Adam) or DECOUPLED (torch.optim.AdamW).  One thread per block of 8: one byte
+// and two table words (<= 2 KB, cached), then p, g, m, v as two 16-byte vectors each and each 16-bit shadow as one 16-byte store; the
+// ragged last block goes element by element.  GUARD / MASK as in adam_kernel.  lr_scale == 0: m and v advance (torch with lr = 0), p and
+// both shadows are not stored at all -- they keep their bits.
+template <bool GUARD, bool MASK, bool DECOUPLED>
+__global__ __launch_bounds__(256) void adam_group_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, bf16_t* __restrict__ pb, bf16_t* __restrict__ ph, long long n, float lr,
+                                                         float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                                         const float* __restrict__ gscale, const float* __restrict__ state,
+                                                         const float* __restrict__ guard, const unsigned char* __restrict__ skip,
+                                                         const unsigned char* __restrict__ group, const float* __restrict__ table, int ngroups) {
+  if constexpr (GUARD) {
+    if (guard[NF_FLAG] != 0.f) return;
+  }
+  const float gs = gscale ? *gscale : 1.0f;
+  if (state) {
+    lr = state[1];
+    bc1 = state[2];
+    bc2_sqrt = state[3];
+  }
+  if constexpr (GUARD) {
+    bc1 = guard[NF_BC1];
+    bc2_sqrt = guard[NF_BC2];
+  }
+  const float ob1 = 1.f - b1, ob2 = 1.f - b2;
+  const long long nblk = (n + 7) >> 3;
+  for (long long blk = (long long)blockIdx.x * 256 + threadIdx.x; blk < nblk; blk += (long long)gridDim.x * 256) {
+    if constexpr (MASK) {
+      if (skip[blk]) continue;
+    }
+    const int gid = min((int)group[blk], ngroups - 1);
+    const float s = table[2 * gid], wd_i = table[2 * gid + 1];
+    const float lr_i = lr * s;
+    const float step_size = lr_i / bc1;
+    const long long i0 = blk << 3;
+    if (i0 + 8 <= n) {
+      float pe[8], ge[8], me[8], ve[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 p4 = reinterpret_cast<const float4*>(p + i0)[h], g4 = reinterpret_cast<const float4*>(g + i0)[h];
+        const float4 m4 = reinterpret_cast<const float4*>(m + i0)[h], v4 = reinterpret_cast<const float4*>(v + i0)[h];
+        pe[4 * h] = p4.x; pe[4 * h + 1] = p4.y; pe[4 * h + 2] = p4.z; pe[4 * h + 3] = p4.w;
+        ge[4 * h] = g4.x; ge[4 * h + 1] = g4.y; ge[4 * h + 2] = g4.z; ge[4 * h + 3] = g4.w;
+        me[4 * h] = m4.x; me[4 * h + 1] = m4.y; me[4 * h + 2] = m4.z; me[4 * h + 3] = m4.w;
+        ve[4 * h] = v4.x; ve[4 * h + 1] = v4.y; ve[4 * h + 2] = v4.z; ve[4 * h + 3] = v4.w;
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        adam_group_elem<DECOUPLED>(pe[e], ge[e], me[e], ve[e], gs, lr_i, wd_i, step_size, b1, b2, ob1, ob2, eps, bc2_sqrt);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        reinterpret_cast<float4*>(m + i0)[h] = make_float4(me[4 * h], me[4 * h + 1], me[4 * h + 2], me[4 * h + 3]);
+        reinterpret_cast<float4*>(v + i0)[h] = make_float4(ve[4 * h], ve[4 * h + 1], ve[4 * h + 2], ve[4 * h + 3]);
+      }
+      if (s != 0.f) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          reinterpret_cast<float4*>(p + i0)[h] = make_float4(pe[4 * h], pe[4 * h + 1], pe[4 * h + 2], pe[4 * h + 3]);
+        if (pb) {
+          uint32_t w[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) w[k] = (uint32_t)f2bf(pe[2 * k]) | ((uint32_t)f2bf(pe[2 * k + 1]) << 16);
+          *reinterpret_cast<uint4*>(pb + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        if (ph)
+          *reinterpret_cast<uint4*>(ph + i0) =
+              make_uint4(f2h_sat2(pe[0], pe[1]), f2h_sat2(pe[2], pe[3]), f2h_sat2(pe[4], pe[5]), f2h_sat2(pe[6], pe[7]));
+      }
+    } else {
+      for (long long i = i0; i < n; ++i) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        adam_group_elem<DECOUPLED>(pi, g[i], mi, vi, gs, lr_i, wd_i, step_size, b1, b2, ob1, ob2, eps, bc2_sqrt);
+        m[i] = mi;
+        v[i] = vi;
+        if (s != 0.f) {
+          p[i] = pi;
+          if (pb) pb[i] = f2bf(pi);
+          if (ph) ph[i] = f2h_sat(pi);
+        }
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- hardware probe: ds_read_b64_tr_b16 semantics
 __global__ __launch_bounds__(64) void probe_tr_kernel(int stride, unsigned short* out) {
   __shared__ __attribute__((aligned(16))) unsigned short img[64 * 64];
@@ -1024,6 +1136,46 @@ extern "C" int mmdti_adam_step_masked(mmdti_stream_t stream, float* p, const flo
                        (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev, step_state_dev,
                        nullptr, skip);
   }
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+template <bool DECOUPLED>
+static void adam_group_launch(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr,
+                              float beta1, float beta2, float eps, int step, const float* grad_scale_dev, const float* step_state_dev,
+                              void* p_f16, const float* guard, const unsigned char* skip, const unsigned char* group, const float* table_dev,
+                              int ngroups) {
+  float bc1 = 1.f, bc2s = 1.f;
+  if (!guard) adam_bias_host(beta1, beta2, step, &bc1, &bc2s);
+#define ADAM_GROUP(G, M)                                                                                                                     \
+  hipLaunchKernelGGL((adam_group_kernel<G, M, DECOUPLED>), dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,       \
+                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, bc1, bc2s, grad_scale_dev, step_state_dev, guard, skip, group, \
+                     table_dev, ngroups)
+  if (guard) {
+    if (skip) ADAM_GROUP(true, true); else ADAM_GROUP(true, false);
+  } else {
+    if (skip) ADAM_GROUP(false, true); else ADAM_GROUP(false, false);
+  }
+#undef ADAM_GROUP
+}
+
+extern "C" int mmdti_adam_step_grouped(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                                       float lr, float beta1, float beta2, float eps, int step, const float* grad_scale_dev,
+                                       const float* step_state_dev, void* p_f16, const float* guard, const unsigned char* skip,
+                                       const unsigned char* group, const float* table_dev, int ngroups, int decoupled) {
+  MMDTI_REQUIRE(p && g && m && v && group && table_dev, "adam_step_grouped: null pointer");
+  MMDTI_REQUIRE(ngroups >= 1 && ngroups <= 256, "adam_step_grouped: ngroups must be 1 .. 256");
+  MMDTI_REQUIRE(n >= 0, "adam_step_grouped: negative n");
+  MMDTI_REQUIRE(guard || step >= 1 || step_state_dev, "adam_step_grouped: no source of bias corrections (guard, step >= 1 or step state)");
+  MMDTI_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(p_bf16) && aligned16(p_f16),
+                "adam_step_grouped: 16-byte alignment required");
+  if (n == 0) return MMDTI_OK;
+  if (decoupled)
+    adam_group_launch<true>(stream, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, step, grad_scale_dev, step_state_dev, p_f16, guard, skip,
+                            group, table_dev, ngroups);
+  else
+    adam_group_launch<false>(stream, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, step, grad_scale_dev, step_state_dev, p_f16, guard, skip,
+                             group, table_dev, ngroups);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

@@ -85,3 +85,14 @@ def arena_skip_mask(flags: Sequence[bool], offsets: Sequence[int], sizes: Sequen
             assert o % align == 0
             m[o // align:(o + n + align - 1) // align] = 1
     return m
+
+
+def arena_group_ids(indices: Sequence[int], offsets: Sequence[int], sizes: Sequence[int], numel: int, align: int = 8):
+    """The per-`align`-element group ids of the grouped Adam pass (ops.adam_step_grouped), on the host as a uint8 tensor of
+    (numel + align - 1) // align ids.  indices / offsets / sizes: per arena parameter (offsets are multiples of `align`); the padding
+    slots behind a parameter, its last ragged block included, take their owner's id."""
+    ids = torch.zeros((numel + align - 1) // align, dtype=torch.uint8)
+    for g, o, n in zip(indices, offsets, sizes):
+        assert o % align == 0 and 0 <= int(g) < 256
+        ids[o // align:(o + n + align - 1) // align] = int(g)
+    return ids

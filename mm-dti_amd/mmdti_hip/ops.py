@@ -1388,6 +1388,24 @@ def adam_step_masked(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, st
                                  _p(p_f16), _p(guard), skip.data_ptr())
 
 
+def adam_step_grouped(p, g, m, v, p_bf16, lr, beta1, beta2, eps, step, group, table, decoupled=False, skip=None, guard=None, grad_scale=None,
+                      step_state=None, p_f16=None):
+    """adam_step_masked (skip and guard both optional) with parameter groups: element i is updated with lr * table[group[i // 8], 0] and the
+    weight decay table[group[i // 8], 1] -- added to the gradient (torch.optim.Adam) or, decoupled, as p *= 1 - lr_i * wd (torch.optim.AdamW).
+    group: uint8 device tensor, one id per 8 elements; table: fp32 [ngroups, 2] device tensor, ngroups <= 256.  A scale of 0 leaves the
+    group's p and shadows to the bit while m and v advance."""
+    assert group.dtype == torch.uint8 and group.is_contiguous() and group.numel() >= (p.numel() + 7) // 8, "adam_step_grouped.group"
+    _chk(table, F32, "adam_step_grouped.table")
+    assert table.dim() == 2 and table.shape[1] == 2, "adam_step_grouped.table is [ngroups, 2]"
+    if skip is not None:
+        assert skip.dtype == torch.uint8 and skip.is_contiguous() and skip.numel() >= (p.numel() + 7) // 8, "adam_step_grouped.skip"
+    if guard is not None:
+        _chk(guard, F32, "adam_step_grouped.guard")
+    lib().mmdti_adam_step_grouped(_stream(), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), p.numel(), float(lr),
+                                  float(beta1), float(beta2), float(eps), int(step), _p(grad_scale), _p(step_state), _p(p_f16), _p(guard),
+                                  _p(skip), group.data_ptr(), table.data_ptr(), table.shape[0], int(bool(decoupled)))
+
+
 def adam_bias_table(beta1, beta2, steps, device):
     """fp32 [steps, 2] device table of (1-beta1^t, sqrt(1-beta2^t)) for t = 1 .. steps, computed on the host exactly as adam_step does
     from its by-value step; enqueued from pinned memory (no synchronisation)."""

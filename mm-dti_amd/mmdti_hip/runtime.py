@@ -67,6 +67,21 @@ class ParamArena:
         # parameters frozen after the arena was built (requires_grad cleared): their elements are skipped by the Adam pass
         self.skip_mask: Optional[torch.Tensor] = None
         self._flags = (True,) * len(self.params)
+        # parameter groups (set_groups): per block of 8 elements a group id, per group (lr_scale, weight_decay) -- both on the device
+        self.group_ids: Optional[torch.Tensor] = None
+        self.group_table: Optional[torch.Tensor] = None
+        self.decoupled = False
+
+    def set_groups(self, ids: torch.Tensor, table: torch.Tensor, decoupled: bool = False):
+        """Switch the Adam pass to ops.adam_step_grouped.  ids: host uint8, one group id per block of 8 elements
+        (freeze.arena_group_ids); table: host fp32 [ngroups, 2] of (lr_scale, weight_decay).  Both are uploaded ONCE: their device
+        addresses never move afterwards (a captured graph reads them; later changes are copies into group_table)."""
+        assert ids.dtype == torch.uint8 and ids.numel() == (self.numel + _ALIGN - 1) // _ALIGN, "set_groups: one id per block of 8 elements"
+        assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] == 2 and 1 <= table.shape[0] <= 256, "set_groups: table is fp32 [ngroups <= 256, 2]"
+        assert self.group_ids is None, "set_groups: the groups are set once (change a row with a copy into group_table)"
+        self.group_ids = ops.upload(ids.contiguous(), self.data.device)
+        self.group_table = ops.upload(table.contiguous(), self.data.device)
+        self.decoupled = bool(decoupled)
 
     def sync_trainable(self) -> bool:
         """Re-read requires_grad of the arena's parameters; rebuild the Adam skip mask when it changed.  -> True on a change.  (A
@@ -186,7 +201,11 @@ class ParamArena:
         # (the Adam pass writes BOTH 16-bit shadows -- bf16 for the backward GEMMs, fp16 for the forward ones -- through raw pointers:
         #  a captured graph's replays keep them fresh too; the fp16 one exists once a forward GEMM has asked for it)
         p_f16 = self.shadow16 if self._epoch16 == self._epoch else None
-        if self.skip_mask is not None:
+        if self.group_ids is not None:
+            # (parameter groups: the table holds every group's weight decay; the by-value one is the default group's row)
+            ops.adam_step_grouped(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, self.step_count,
+                                  self.group_ids, self.group_table, self.decoupled, self.skip_mask, guard, scale, step_state, p_f16=p_f16)
+        elif self.skip_mask is not None:
             ops.adam_step_masked(self.data, self.grad, self.adam_m, self.adam_v, self.shadow, lr, betas[0], betas[1], eps, weight_decay,
                                  self.step_count, self.skip_mask, guard, scale, step_state, p_f16=p_f16)
         elif guard is None:

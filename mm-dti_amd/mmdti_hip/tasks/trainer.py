@@ -232,6 +232,13 @@ class Trainer(object):
         if self.fds_stats not in FDS_STATS_MODES:
             raise ValueError(f"Trainer: fds_stats must be one of {FDS_STATS_MODES}, got {self.fds_stats!r}")
         self.distributed = bool(params.get('distributed', False))
+        # parameter groups of the fused Adam pass (not reference parameters; the defaults are the reference's one Adam(lr, eps=1e-6)):
+        # weight_decay, coupled or decoupled (AdamW); param_groups, a list of param_groups.ParamGroup; layer_decay, the shorthand for
+        # param_groups.layerwise_decay(model, layer_decay), appended behind the given groups
+        self.weight_decay = float(params.get('weight_decay', 0.0))
+        self.decoupled_weight_decay = bool(params.get('decoupled_weight_decay', False))
+        self.param_groups = params.get('param_groups', None)
+        self.layer_decay = params.get('layer_decay', None)
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
@@ -346,10 +353,19 @@ class Trainer(object):
         train_dataloader, sampler = self.train_loader(model, train_dataset, feature_name)
         min_val_loss, max_score, wait = float("inf"), float("-inf"), 0
         num_training_steps = len(train_dataloader) * self.max_epochs
+        groups = self.param_groups
+        if self.layer_decay is not None:
+            from ..param_groups import layerwise_decay
+            groups = list(groups or ()) + layerwise_decay(model, float(self.layer_decay))
         engine = FineTuner(model, self.task, learning_rate=self.learning_rate, adam_eps=1e-6, warmup_ratio=0.0,
                            total_steps=num_training_steps, alpha=self.alpha, beta=self.beta,
                            max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite,
-                           deterministic=self.deterministic, fds_stats=self.fds_stats)
+                           deterministic=self.deterministic, fds_stats=self.fds_stats, weight_decay=self.weight_decay,
+                           decoupled_weight_decay=self.decoupled_weight_decay, param_groups=groups)
+        if engine.param_groups is not None or self.weight_decay:
+            for name, count, elements, scale, wd in engine.param_group_summary():
+                logger.info('param group {}: {} parameters, {} elements, lr_scale {:g}, weight_decay {:g}{}'.format(
+                    name, count, elements, scale, wd, ' (decoupled)' if self.decoupled_weight_decay else ''))
         engine.warmup = int(num_training_steps * self.warmup_ratio)
         self._engine = engine
         task_loss = self._task_loss(loss_func)

@@ -16,6 +16,7 @@ AMP branch :274), same per-epoch FDS statistics pass (:288-306).  What changes i
 from __future__ import annotations
 
 import logging
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -66,7 +67,8 @@ FDS_STATS_MODES = ("epoch_pass", "streaming")
 class FineTuner:
     def __init__(self, model, task: str, learning_rate=1e-4, adam_eps=1e-6, warmup_ratio=0.03, total_steps=1000, alpha=1.0, beta=0.1,
                  max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
-                 loss_key: Optional[str] = None, deterministic: Optional[bool] = None, fds_stats: str = "epoch_pass"):
+                 loss_key: Optional[str] = None, deterministic: Optional[bool] = None, fds_stats: str = "epoch_pass",
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False, param_groups=None):
         """deterministic: True enters the process-wide deterministic mode (ops.set_deterministic: every cross-workgroup sum into a
         parameter gradient in a fixed order, one reduction workspace per launch stream); None follows MMDTI_DETERMINISTIC; False (and
         an unset environment) touches nothing.  Sites that have no fixed-order form yet raise in the mode (DESIGN.md lists them), and so
@@ -81,7 +83,13 @@ class FineTuner:
         set, fds_epoch_pass (tasks/trainer.py:288-306).  "streaming": the training steps' own features feed per-bucket running moments on
         the device -- fds_epoch_begin(epoch) before an epoch's steps, fds_epoch_finish(epoch) after them, and fds_epoch_pass raises.  Each
         batch is then seen with the weights of its own step, not with the end-of-epoch weights (DESIGN.md "Streaming FDS statistics").
-        The features are accumulated in the forward: a step that skip_nonfinite skips has still contributed its rows."""
+        The features are accumulated in the forward: a step that skip_nonfinite skips has still contributed its rows.
+        weight_decay: Adam's weight decay (default 0, the reference's), added to the gradient as torch.optim.Adam does -- or, with
+        decoupled_weight_decay=True, applied as p *= 1 - lr * wd (torch.optim.AdamW).  param_groups: a list of
+        param_groups.ParamGroup (first match wins; unmatched parameters keep scale 1 and `weight_decay`), e.g.
+        ``no_decay(model) + layerwise_decay(model, 0.8)``: each group's learning-rate scale and weight decay live in a small device table
+        that the fused clip + Adam + shadow pass reads per block of 8 elements (DESIGN.md "Parameter groups"); set_group changes a row
+        without a synchronisation or a re-capture.  Without groups and with coupled decay the pass is the ungrouped one."""
         if fds_stats not in FDS_STATS_MODES:
             raise ValueError(f"FineTuner: fds_stats must be one of {FDS_STATS_MODES}, got {fds_stats!r}")
         self.fds_stats = fds_stats
@@ -99,6 +107,13 @@ class FineTuner:
         self.arena = ParamArena(model.parameters(), adjacent=_qkv_groups(model))
         self._outside = [p for p in model.parameters() if id(p) not in self.arena.offsets]
         self._warned_unfrozen = False
+        self.weight_decay = float(weight_decay)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.param_groups = None                         # the resolved ParamGroup list ([]: the default group alone), None: ungrouped pass
+        if param_groups is not None or self.decoupled_weight_decay:
+            self._set_param_groups(list(param_groups or ()))
+        elif not (math.isfinite(self.weight_decay) and self.weight_decay >= 0.0):
+            raise ValueError(f"FineTuner: weight_decay must be finite and >= 0, got {weight_decay!r}")
         self.skip_nonfinite = bool(skip_nonfinite)
         self.last_optimizer_outputs = (None, None)       # (skipped, grad_norm) of the latest optimizer_step
         self.guard = new_nonfinite_guard(self.arena.data.device) if self.skip_nonfinite else None
@@ -139,6 +154,56 @@ class FineTuner:
             self.task_loss = from_key(loss_key)
         else:
             self.task_loss = None
+
+    # ------------------------------------------------------------------ parameter groups
+    def _set_param_groups(self, groups):
+        """Resolve the groups against the model, spread the indices over the arena's blocks of 8 and hand ids and table to the arena."""
+        from .freeze import arena_group_ids
+        from .param_groups import group_names, resolve
+        index, table = resolve(self.model, groups, self.weight_decay)
+        of = {id(p): g for (_, p), g in zip(self.model.named_parameters(), index)}
+        a = self.arena
+        per_param = [of[id(p)] for p in a.params]
+        ids = arena_group_ids(per_param, [a.offsets[id(p)] for p in a.params], [p.numel() for p in a.params], a.numel)
+        a.set_groups(ids, torch.tensor(table, dtype=torch.float32), self.decoupled_weight_decay)
+        self.param_groups, self._group_names, self._group_table, self._group_of = groups, group_names(groups), table, per_param
+
+    def set_group(self, index_or_name, lr_scale: Optional[float] = None, weight_decay: Optional[float] = None):
+        """Change a group's learning-rate scale and / or weight decay: one small copy into the device table, enqueued on the current
+        stream -- no synchronisation.  The next step honours it, and so does the next replay of every graph already captured (the
+        table's address does not move; nothing is re-captured).  lr_scale = 0 freezes the group's parameters and shadows to the bit
+        while its moments keep following the gradients; raising it again is gradual unfreezing.  index_or_name: the table row (0: the
+        default group, j + 1: param_groups[j]) or the group's name (param_group_summary lists them)."""
+        if self.param_groups is None:
+            raise RuntimeError("FineTuner.set_group: this engine was built without parameter groups (pass param_groups=[...])")
+        if isinstance(index_or_name, str):
+            if index_or_name not in self._group_names:
+                raise KeyError(f"FineTuner.set_group: no group named {index_or_name!r} (groups: {self._group_names})")
+            i = self._group_names.index(index_or_name)
+        else:
+            i = int(index_or_name)
+            if not 0 <= i < len(self._group_table):
+                raise IndexError(f"FineTuner.set_group: group {i} out of range (0 .. {len(self._group_table) - 1})")
+        row = list(self._group_table[i])
+        for k, x, what in ((0, lr_scale, "lr_scale"), (1, weight_decay, "weight_decay")):
+            if x is not None:
+                if not (math.isfinite(float(x)) and float(x) >= 0.0):
+                    raise ValueError(f"FineTuner.set_group: {what} must be finite and >= 0, got {x!r}")
+                row[k] = float(x)
+        self._group_table[i] = row
+        from . import ops
+        self.arena.group_table[i].copy_(ops.upload(torch.tensor(row, dtype=torch.float32), self.arena.data.device), non_blocking=True)
+
+    def param_group_summary(self):
+        """-> [(name, parameters, elements, lr_scale, weight_decay)], one row per group, over the parameters the optimizer holds."""
+        params = self.arena.params
+        if self.param_groups is None:
+            return [("default", len(params), sum(p.numel() for p in params), 1.0, self.weight_decay)]
+        rows = []
+        for g, (name, (s, wd)) in enumerate(zip(self._group_names, self._group_table)):
+            mine = [p for p, gid in zip(params, self._group_of) if gid == g]
+            rows.append((name, len(mine), sum(p.numel() for p in mine), s, wd))
+        return rows
 
     # ------------------------------------------------------------------
     def _sync_trainable(self):
@@ -208,7 +273,7 @@ class FineTuner:
         -> (skipped, grad_norm) device scalars, each None when this engine does not compute it (see StepOutput).  They are also kept
         as ``last_optimizer_outputs``, which is where step() reads them: callers may wrap this method and drop its return value."""
         lr = linear_warmup_lr(self.lr, self.sched_step, self.warmup, self.total_steps)
-        norm, skipped = self.arena.adam_step(lr, eps=self.eps, max_norm=self.max_norm, guard=self.guard)
+        norm, skipped = self.arena.adam_step(lr, eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm, guard=self.guard)
         self.sched_step += 1
         self.last_optimizer_outputs = (skipped, norm)
         return skipped, norm
@@ -270,7 +335,8 @@ class FineTuner:
         from . import ops
         ops.step_state_advance(self._state, self._salt, self.lr, self.warmup, self.total_steps)
         out = self.forward_backward(net_input, net_target, epoch, use_weight, **kw)
-        out.grad_norm, out.skipped = self.arena.adam_step(0.0, eps=self.eps, max_norm=self.max_norm, step_state=self._state, guard=self.guard)
+        out.grad_norm, out.skipped = self.arena.adam_step(0.0, eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm,
+                                                          step_state=self._state, guard=self.guard)
         self.arena.step_count -= 1                   # (the host-side counter is advanced by graphed_step, once per replay)
         return out
 
