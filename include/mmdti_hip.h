@@ -847,6 +847,22 @@ int mmdti_adam_step_grouped(mmdti_stream_t stream, float* p, const float* g, flo
  * them from its by-value step. */
 int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host);
 
+/* ---- weight averaging: an exponential moving average of the parameter arena (an engine feature; the reference has none) ---- */
+/* ema[i] <- fma(w, p[i] - ema[i], ema[i]) for i < n: two roundings, the difference and the fma.  w = 1 - d in fp32 with d = decay, or,
+ * warmup != 0, d = min(decay, (1 + t) / (10 + t)).  t = the optimizer steps applied so far, this one included, from exactly one source:
+ *   guard non-null (the state of mmdti_sumsq_check_f32, already advanced by this step's check): a set skip flag returns before anything is
+ *     read or written -- a skipped step leaves the average alone -- else t = the guard's count of steps taken;
+ *   else step_state non-null (mmdti_step_state_advance): t = state[0];
+ *   else t = step by value, >= 1.
+ * Launch it right after the Adam pass of the step, on the same stream.  0 < decay < 1; p and ema are two buffers, 16-byte aligned;
+ * n == 0 launches nothing.  Purely additive: MMDTI_ABI_VERSION does not move. */
+int mmdti_ema_update(mmdti_stream_t stream, const float* p, float* ema, long long n, float decay, int warmup, int step,
+                     const float* guard /* nullable */, const float* step_state /* nullable */);
+/* One pass that exchanges p[i] and ema[i] bit for bit and writes the bf16 shadow -- and the fp16 one when given -- of the new p[i] with the
+ * roundings of the Adam pass: both shadows are valid when the kernel ends, without a temporary and without cast passes.  Twice is the
+ * identity.  p, ema and the shadows are 16-byte aligned; n == 0 launches nothing.  Purely additive: MMDTI_ABI_VERSION does not move. */
+int mmdti_ema_swap(mmdti_stream_t stream, float* p, float* ema, void* p_bf16, void* p_f16 /* nullable */, long long n);
+
 /* ---- hardware probes used by the test-suite ------------------------------------------------- */
 /* out[64*4] <- what ds_read_b64_tr_b16 returns to each lane for an LDS image holding element index == value */
 int mmdti_probe_tr_read(mmdti_stream_t stream, int row_stride_elems, unsigned short* out);

@@ -774,6 +774,72 @@ __global__ __launch_bounds__(256) void adam_group_kernel(float* __restrict__ p, 
   }
 }
 
+// ---------------------------------------------------------------- weight averaging (EMA of the parameter arena)
+// ema <- ema + w (p - ema), w = 1 - d, d = decay or -- warm-up -- min(decay, (1 + t) / (10 + t)); t = the optimizer steps applied so far,
+// this one included.  Its ONE source: the guard (a set flag leaves before anything is read or written: a skipped step leaves the average
+// alone; else NF_T, which the check kernel has already advanced), else the step state's counter, else the by-value step.  Two roundings per
+// element, both spelt: the difference, then the fma.  A kernel of its own, not a fifth axis of the Adam templates (DESIGN.md "Weight
+// averaging (EMA)").  One thread per 16-byte vector, grid-stride; the n % 4 tail element by element.
+__global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ p, float* __restrict__ ema, long long n, float decay, int warmup,
+                                                         float t, const float* __restrict__ guard, const float* __restrict__ state) {
+  if (guard) {
+    if (guard[NF_FLAG] != 0.f) return;
+    t = guard[NF_T];
+  } else if (state) {
+    t = state[0];
+  }
+  const float d = warmup ? fminf(decay, (1.f + t) / (10.f + t)) : decay;
+  const float w = 1.f - d;
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  const long long nvec = n >> 2;
+  for (long long k = tid; k < nvec; k += stride) {
+    const float4 p4 = reinterpret_cast<const float4*>(p)[k];
+    float4 e4 = reinterpret_cast<const float4*>(ema)[k];
+    e4.x = __fmaf_rn(w, __fsub_rn(p4.x, e4.x), e4.x);
+    e4.y = __fmaf_rn(w, __fsub_rn(p4.y, e4.y), e4.y);
+    e4.z = __fmaf_rn(w, __fsub_rn(p4.z, e4.z), e4.z);
+    e4.w = __fmaf_rn(w, __fsub_rn(p4.w, e4.w), e4.w);
+    reinterpret_cast<float4*>(ema)[k] = e4;
+  }
+  for (long long i = (nvec << 2) + tid; i < n; i += stride) {
+    const float e = ema[i];
+    ema[i] = __fmaf_rn(w, __fsub_rn(p[i], e), e);
+  }
+}
+
+// p <-> ema as bit patterns, and both 16-bit shadows of the NEW p with the Adam pass's own roundings (f2bf, f2h_sat): the shadows are
+// valid when the kernel ends.  One thread per block of 8 elements (two 16-byte vectors of p and of ema, one 16-byte store per shadow),
+// grid-stride; the n % 8 tail element by element.
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ ema, bf16_t* __restrict__ pb,
+                                                       bf16_t* __restrict__ ph, long long n) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  const long long nblk = n >> 3;
+  for (long long blk = tid; blk < nblk; blk += stride) {
+    const long long i0 = blk << 3;
+    uint4* pv = reinterpret_cast<uint4*>(p + i0);
+    uint4* ev = reinterpret_cast<uint4*>(ema + i0);
+    const uint4 p0 = pv[0], p1 = pv[1], e0 = ev[0], e1 = ev[1];
+    pv[0] = e0; pv[1] = e1;
+    ev[0] = p0; ev[1] = p1;
+    const float x[8] = {__uint_as_float(e0.x), __uint_as_float(e0.y), __uint_as_float(e0.z), __uint_as_float(e0.w),
+                        __uint_as_float(e1.x), __uint_as_float(e1.y), __uint_as_float(e1.z), __uint_as_float(e1.w)};
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = (uint32_t)f2bf(x[2 * k]) | ((uint32_t)f2bf(x[2 * k + 1]) << 16);
+    *reinterpret_cast<uint4*>(pb + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+    if (ph)
+      *reinterpret_cast<uint4*>(ph + i0) = make_uint4(f2h_sat2(x[0], x[1]), f2h_sat2(x[2], x[3]), f2h_sat2(x[4], x[5]), f2h_sat2(x[6], x[7]));
+  }
+  for (long long i = (nblk << 3) + tid; i < n; i += stride) {
+    const uint32_t a = reinterpret_cast<uint32_t*>(p)[i], b = reinterpret_cast<uint32_t*>(ema)[i];
+    reinterpret_cast<uint32_t*>(p)[i] = b;
+    reinterpret_cast<uint32_t*>(ema)[i] = a;
+    const float x = __uint_as_float(b);
+    pb[i] = f2bf(x);
+    if (ph) ph[i] = f2h_sat(x);
+  }
+}
+
 // ---------------------------------------------------------------- hardware probe: ds_read_b64_tr_b16 semantics
 __global__ __launch_bounds__(64) void probe_tr_kernel(int stride, unsigned short* out) {
   __shared__ __attribute__((aligned(16))) unsigned short img[64 * 64];
@@ -1183,6 +1249,30 @@ extern "C" int mmdti_adam_step_grouped(mmdti_stream_t stream, float* p, const fl
 extern "C" int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host) {
   MMDTI_REQUIRE(table_host && steps >= 1, "adam_bias_table: bad arguments");
   for (int t = 1; t <= steps; ++t) adam_bias_host(beta1, beta2, t, &table_host[2 * (t - 1)], &table_host[2 * (t - 1) + 1]);
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_ema_update(mmdti_stream_t stream, const float* p, float* ema, long long n, float decay, int warmup, int step,
+                                const float* guard, const float* step_state) {
+  MMDTI_REQUIRE(p && ema && p != ema, "ema_update: p and ema are two non-null buffers");
+  MMDTI_REQUIRE(n >= 0, "ema_update: negative n");
+  MMDTI_REQUIRE(decay > 0.f && decay < 1.f, "ema_update: decay must lie in (0, 1)");
+  MMDTI_REQUIRE(guard || step_state || step >= 1, "ema_update: no source of t (guard, step state or step >= 1)");
+  MMDTI_REQUIRE(aligned16(p) && aligned16(ema), "ema_update: 16-byte alignment required");
+  if (n == 0) return MMDTI_OK;
+  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, ema, n, decay, warmup, (float)step,
+                     guard, step_state);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_ema_swap(mmdti_stream_t stream, float* p, float* ema, void* p_bf16, void* p_f16, long long n) {
+  MMDTI_REQUIRE(p && ema && p != ema && p_bf16, "ema_swap: p, ema (two buffers) and p_bf16 must be given");
+  MMDTI_REQUIRE(n >= 0, "ema_swap: negative n");
+  MMDTI_REQUIRE(aligned16(p) && aligned16(ema) && aligned16(p_bf16) && aligned16(p_f16), "ema_swap: 16-byte alignment required");
+  if (n == 0) return MMDTI_OK;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, p, ema, (bf16_t*)p_bf16, (bf16_t*)p_f16, n);
+  MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 

@@ -1414,6 +1414,31 @@ def adam_bias_table(beta1, beta2, steps, device):
     return host.to(device, non_blocking=True)
 
 
+def ema_update(p, ema, decay, warmup=True, step=0, guard=None, step_state=None):
+    """ema <- ema + w (p - ema) in one pass, w = 1 - decay or, warmup, 1 - min(decay, (1 + t) / (10 + t)).  t, the optimizer steps applied
+    including this one, has ONE source: guard (a set skip flag leaves ema untouched; else its count of steps taken), else step_state
+    (its counter), else the by-value step >= 1.  Call it right after the Adam launch of the step."""
+    _chk(p, F32, "ema_update.p"); _chk(ema, F32, "ema_update.ema")
+    assert ema.numel() == p.numel(), "ema_update: ema has the size of p"
+    if guard is not None:
+        _chk(guard, F32, "ema_update.guard")
+        assert guard.numel() >= 5
+    if step_state is not None:
+        _chk(step_state, F32, "ema_update.step_state")
+    lib().mmdti_ema_update(_stream(), p.data_ptr(), ema.data_ptr(), p.numel(), float(decay), int(bool(warmup)), int(step), _p(guard),
+                           _p(step_state))
+
+
+def ema_swap(p, ema, p_bf16, p_f16=None):
+    """Exchange p and ema bit for bit and write the bf16 shadow (and the fp16 one when given) of the new p, in one pass."""
+    _chk(p, F32, "ema_swap.p"); _chk(ema, F32, "ema_swap.ema"); _chk(p_bf16, BF16, "ema_swap.p_bf16")
+    assert ema.numel() == p.numel() and p_bf16.numel() == p.numel(), "ema_swap: ema and the shadows have the size of p"
+    if p_f16 is not None:
+        _chk(p_f16, F16, "ema_swap.p_f16")
+        assert p_f16.numel() == p.numel()
+    lib().mmdti_ema_swap(_stream(), p.data_ptr(), ema.data_ptr(), p_bf16.data_ptr(), _p(p_f16), p.numel())
+
+
 def step_state_advance(state, salt, base_lr, warmup, total, beta1=0.9, beta2=0.999):
     """state [4] fp32, salt [2] int64 (device): advance the optimizer-step counter, this step's learning rate / bias
     corrections and the dropout salt, then publish the salt to every kernel library."""

@@ -63,6 +63,7 @@ class ParamArena:
         self.refresh_shadow()
         self.adam_m: Optional[torch.Tensor] = None
         self.adam_v: Optional[torch.Tensor] = None
+        self.ema: Optional[torch.Tensor] = None           # the parameters' moving average (enable_ema), fp32 like `data`
         self.step_count = 0
         # parameters frozen after the arena was built (requires_grad cleared): their elements are skipped by the Adam pass
         self.skip_mask: Optional[torch.Tensor] = None
@@ -218,6 +219,30 @@ class ParamArena:
         if self.shadow16 is not None and self._epoch16 == self._epoch - 1:
             self._epoch16 = self._epoch
         return norm, skipped
+
+    # ------------------------------------------------------------------ weight averaging (DESIGN.md "Weight averaging (EMA)")
+    def enable_ema(self):
+        """Allocate the average: an fp32 buffer like ``data``, initialised as a copy of it."""
+        if self.ema is None:
+            self.ema = self.data.clone()
+
+    def ema_step(self, decay, warmup=True, guard=None, step_state=None):
+        """One launch, right after adam_step and with its choice of the source of t: the guard's count of steps actually taken (a skipped
+        step leaves the average alone), else the step state's counter, else this arena's step_count by value."""
+        assert self.ema is not None, "ema_step: enable_ema() first"
+        ops.ema_update(self.data, self.ema, decay, warmup, self.step_count, guard, step_state)
+
+    def swap_average(self):
+        """Exchange ``data`` and ``ema`` in one pass that also writes the bf16 shadow and -- once it exists -- the fp16 one from the new
+        ``data``.  As in adam_step the kernel writes through raw pointers, so the bookkeeping follows here: every parameter's shadow
+        slice is fresh at its current version (a pending in-place edit was part of what the pass read), and so is the fp16 shadow."""
+        assert self.ema is not None, "swap_average: enable_ema() first"
+        ops.ema_swap(self.data, self.ema, self.shadow, self.shadow16)
+        for p in self.params:
+            self._version[id(p)] = p._version
+        self._epoch += 1
+        if self.shadow16 is not None:
+            self._epoch16 = self._epoch
 
     def _bias_table(self, betas):
         """Device table of the host's bias corrections for t = 1 .. >= step_count (the guard's t never exceeds the steps enqueued):

@@ -25,6 +25,7 @@ There is no CPU path: ``use_cuda=False`` raises.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 import logging
@@ -33,7 +34,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader as TorchDataLoader
 
-from ..trainer import FineTuner, FDS_STATS_MODES
+from ..trainer import FineTuner, FDS_STATS_MODES, check_ema_decay
 from ..collate import HostCollate, device_payload, to_device, PAIR_INPUT_MODES
 
 logger = logging.getLogger("mmdti_hip")
@@ -239,6 +240,10 @@ class Trainer(object):
         self.decoupled_weight_decay = bool(params.get('decoupled_weight_decay', False))
         self.param_groups = params.get('param_groups', None)
         self.layer_decay = params.get('layer_decay', None)
+        # weight averaging (FineTuner(ema_decay=..., ema_warmup=...); not a reference parameter, off by default): when set, every epoch's
+        # validation, the early-stop decision and the checkpoint see the moving average of the parameters, not the last step's weights
+        self.ema_decay = check_ema_decay(params.get('ema_decay', None), "Trainer")
+        self.ema_warmup = bool(params.get('ema_warmup', True))
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
@@ -361,7 +366,11 @@ class Trainer(object):
                            total_steps=num_training_steps, alpha=self.alpha, beta=self.beta,
                            max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite,
                            deterministic=self.deterministic, fds_stats=self.fds_stats, weight_decay=self.weight_decay,
-                           decoupled_weight_decay=self.decoupled_weight_decay, param_groups=groups)
+                           decoupled_weight_decay=self.decoupled_weight_decay, param_groups=groups, ema_decay=self.ema_decay,
+                           ema_warmup=self.ema_warmup)
+        if self.ema_decay is not None:
+            logger.info('weight averaging: EMA decay {:g}{}; validation and checkpoints use the averaged weights'.format(
+                self.ema_decay, ' with warm-up min(decay, (1 + t) / (10 + t))' if self.ema_warmup else ''))
         if engine.param_groups is not None or self.weight_decay:
             for name, count, elements, scale, wd in engine.param_group_summary():
                 logger.info('param group {}: {} parameters, {} elements, lr_scale {:g}, weight_decay {:g}{}'.format(
@@ -395,18 +404,21 @@ class Trainer(object):
                 engine.fds_epoch_finish(epoch)
             elif fds_epoch:
                 engine.fds_epoch_pass((self.decorate_batch(b, feature_name) for b in train_dataloader), epoch)
-            y_preds, val_loss, metric_score = self.predict(model, valid_dataset, loss_func, activation_fn, dump_dir, fold, target_scaler,
-                                                           epoch, load_model=False, feature_name=feature_name, return_infonce_loss=False)
-            total_val_loss = float(np.mean(val_loss))
-            _metric, _score = next(iter(metric_score.items()))
-            self.history.append(dict(epoch=epoch, steps=steps, val_loss=total_val_loss, metric=_metric, score=_score, skipped=skipped))
-            if steps.size:
-                logger.info('Epoch [{}/{}] train_loss: {:.4f}, train_m_loss: {:.4f}, train_infonce_loss: {:.4f}, train_ct_loss: {:.4f}, '
-                            'val_loss: {:.4f}, val_{}: {:.4f}, {:.1f}s'.format(epoch + 1, self.max_epochs, *steps.mean(0), total_val_loss,
-                                                                                _metric, _score, time.time() - start_time)
-                            + (', skipped steps: {}'.format(skipped) if self.skip_nonfinite else ''))
-            is_early_stop, min_val_loss, wait, max_score = self._early_stop_choice(
-                wait, total_val_loss, min_val_loss, metric_score, max_score, model, dump_dir, fold, self.patience, epoch)
+            # weight averaging: validation, the early-stop decision and the checkpoint it writes see the averaged weights (the FDS pass
+            # above ran on the raw ones); the block's exit puts the raw weights back, bit for bit, for the next epoch's steps
+            with (engine.averaged() if self.ema_decay is not None else contextlib.nullcontext()):
+                y_preds, val_loss, metric_score = self.predict(model, valid_dataset, loss_func, activation_fn, dump_dir, fold, target_scaler,
+                                                               epoch, load_model=False, feature_name=feature_name, return_infonce_loss=False)
+                total_val_loss = float(np.mean(val_loss))
+                _metric, _score = next(iter(metric_score.items()))
+                self.history.append(dict(epoch=epoch, steps=steps, val_loss=total_val_loss, metric=_metric, score=_score, skipped=skipped))
+                if steps.size:
+                    logger.info('Epoch [{}/{}] train_loss: {:.4f}, train_m_loss: {:.4f}, train_infonce_loss: {:.4f}, train_ct_loss: {:.4f}, '
+                                'val_loss: {:.4f}, val_{}: {:.4f}, {:.1f}s'.format(epoch + 1, self.max_epochs, *steps.mean(0), total_val_loss,
+                                                                                    _metric, _score, time.time() - start_time)
+                                + (', skipped steps: {}'.format(skipped) if self.skip_nonfinite else ''))
+                is_early_stop, min_val_loss, wait, max_score = self._early_stop_choice(
+                    wait, total_val_loss, min_val_loss, metric_score, max_score, model, dump_dir, fold, self.patience, epoch)
             if is_early_stop:
                 break
         self._checkpoint_barrier()          # rank 0's last write is complete before any rank reads the file

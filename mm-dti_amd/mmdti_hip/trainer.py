@@ -11,10 +11,13 @@ AMP branch :274), same per-epoch FDS statistics pass (:288-306).  What changes i
     fetched by the caller when it wants them (the reference does four ``float(t.data)`` syncs per step, :195-197,238);
   * optional data parallelism (``parallel.py``): global InfoNCE negatives + bucketed gradient all-reduce over RCCL;
   * ``skip_nonfinite``: the other half of the reference's GradScaler (:268-282) -- an optimizer step whose gradients hold an inf or
-    NaN is skipped (parameters and Adam state untouched, the schedule advances), decided on the device.
+    NaN is skipped (parameters and Adam state untouched, the schedule advances), decided on the device;
+  * ``ema_decay``: an exponential moving average of the parameters, one launch after the Adam pass; ``averaged()`` puts it into the
+    model for validation and checkpoints (not in the reference, off by default).
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 import os
@@ -64,11 +67,37 @@ def _qkv_groups(model):
 FDS_STATS_MODES = ("epoch_pass", "streaming")
 
 
+def check_ema_decay(ema_decay, who="FineTuner"):
+    """None (weight averaging off) or a finite decay with 0 < decay < 1 as a float; anything else is a ValueError.  Needs no device."""
+    if ema_decay is None:
+        return None
+    try:
+        d = float(ema_decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: ema_decay must be None or a number in (0, 1), got {ema_decay!r}") from None
+    if not (math.isfinite(d) and 0.0 < d < 1.0):
+        raise ValueError(f"{who}: ema_decay must be finite with 0 < ema_decay < 1, got {ema_decay!r}")
+    return d
+
+
+def ema_decay_at(t, decay, warmup=True):
+    """The decay the averaging kernel applies at applied optimizer step t (1, 2, ...), in its own fp32 arithmetic:
+    min(decay, (1 + t) / (10 + t)) with warmup, else decay.  -> numpy.float32; the kernel's weight is float32(1) - it."""
+    import numpy as np
+    f = np.float32
+    d = f(decay)
+    if warmup:
+        tt = f(t)
+        d = min(d, (f(1) + tt) / (f(10) + tt))
+    return f(d)
+
+
 class FineTuner:
     def __init__(self, model, task: str, learning_rate=1e-4, adam_eps=1e-6, warmup_ratio=0.03, total_steps=1000, alpha=1.0, beta=0.1,
                  max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
                  loss_key: Optional[str] = None, deterministic: Optional[bool] = None, fds_stats: str = "epoch_pass",
-                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False, param_groups=None):
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False, param_groups=None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         """deterministic: True enters the process-wide deterministic mode (ops.set_deterministic: every cross-workgroup sum into a
         parameter gradient in a fixed order, one reduction workspace per launch stream); None follows MMDTI_DETERMINISTIC; False (and
         an unset environment) touches nothing.  Sites that have no fixed-order form yet raise in the mode (DESIGN.md lists them), and so
@@ -89,7 +118,14 @@ class FineTuner:
         param_groups.ParamGroup (first match wins; unmatched parameters keep scale 1 and `weight_decay`), e.g.
         ``no_decay(model) + layerwise_decay(model, 0.8)``: each group's learning-rate scale and weight decay live in a small device table
         that the fused clip + Adam + shadow pass reads per block of 8 elements (DESIGN.md "Parameter groups"); set_group changes a row
-        without a synchronisation or a re-capture.  Without groups and with coupled decay the pass is the ungrouped one."""
+        without a synchronisation or a re-capture.  Without groups and with coupled decay the pass is the ungrouped one.
+        ema_decay: None (default: no buffer, no launch) or 0 < decay < 1 -- an exponential moving average of the arena's parameters,
+        ``arena.ema``, updated by one launch right after every applied Adam pass (eager and captured; a step the guard skips leaves it
+        alone): ema += (1 - d)(p - ema), d = decay or, with ema_warmup (default), min(decay, (1 + t) / (10 + t)) for the t-th applied
+        step (ema_decay_at).  ``with engine.averaged():`` puts the average into the model -- parameters, state dict and both 16-bit
+        shadows -- for validation and checkpoints, and takes it out again to the bit (DESIGN.md "Weight averaging (EMA)")."""
+        self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
+        self._averaged = False
         if fds_stats not in FDS_STATS_MODES:
             raise ValueError(f"FineTuner: fds_stats must be one of {FDS_STATS_MODES}, got {fds_stats!r}")
         self.fds_stats = fds_stats
@@ -138,6 +174,10 @@ class FineTuner:
             # gradient buckets leave during backward (MMDTI_NO_REDUCE_OVERLAP=1: all of them after it)
             if os.environ.get("MMDTI_NO_REDUCE_OVERLAP") != "1":
                 add_grad_ready_hook(self, self.reducer.on_grads_ready)
+        if self.ema_decay is not None:
+            # (after the broadcast: the average starts as a copy of the parameters every replica starts from; the update is elementwise on
+            #  bit-identical replicas, so it needs no collective)
+            self.arena.enable_ema()
         # built-in task-loss kernels (models/nnmodel.py:24-34): MSE, cross-entropy, and the multilabel table's three entries -- BCE-with-
         # logits ('bce', and the default here), focal and GHM by `loss_key`; every other task / loss (MAE-with-NaN ...) runs as the
         # callable the caller passes as `loss_func`
@@ -204,6 +244,29 @@ class FineTuner:
             mine = [p for p, gid in zip(params, self._group_of) if gid == g]
             rows.append((name, len(mine), sum(p.numel() for p in mine), s, wd))
         return rows
+
+    # ------------------------------------------------------------------ weight averaging
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside the block the model holds the averaged weights: the arena's parameters, hence ``state_dict()``, and both 16-bit shadows
+        the GEMMs read (one swap launch on entry, one on exit; afterwards parameters and shadows are what they were, bit for bit).
+        Validate and checkpoint inside it.  Only the arena's parameters are averaged: parameters frozen when the engine was built and
+        buffers (the FDS statistics) are the model's own.  step, graphed_step, optimizer_step and a nested averaged() raise inside."""
+        if self.ema_decay is None:
+            raise RuntimeError("FineTuner.averaged: this engine was built without weight averaging (pass ema_decay=...)")
+        self._not_averaged("averaged")
+        self.arena.swap_average()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._averaged = False
+            self.arena.swap_average()
+
+    def _not_averaged(self, what):
+        if self._averaged:
+            raise RuntimeError(f"FineTuner.{what}: not inside averaged() -- the model holds the averaged weights, the raw ones sit in the "
+                               "average's buffer until the block ends")
 
     # ------------------------------------------------------------------
     def _sync_trainable(self):
@@ -272,8 +335,11 @@ class FineTuner:
         """Clip + Adam with this step's learning rate; the schedule advances (also on a step the guard skips).
         -> (skipped, grad_norm) device scalars, each None when this engine does not compute it (see StepOutput).  They are also kept
         as ``last_optimizer_outputs``, which is where step() reads them: callers may wrap this method and drop its return value."""
+        self._not_averaged("optimizer_step")
         lr = linear_warmup_lr(self.lr, self.sched_step, self.warmup, self.total_steps)
         norm, skipped = self.arena.adam_step(lr, eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm, guard=self.guard)
+        if self.ema_decay is not None:
+            self.arena.ema_step(self.ema_decay, self.ema_warmup, guard=self.guard)
         self.sched_step += 1
         self.last_optimizer_outputs = (skipped, norm)
         return skipped, norm
@@ -297,6 +363,7 @@ class FineTuner:
         Adam's bias corrections and the dropout salt (ops.step_state_advance is the first node of the graph); the inputs
         are copied into the graph's static buffers before each replay.  Returned tensors are the graph's static outputs --
         read them before the next call.  Not available under data parallelism (collectives are left out of graphs here)."""
+        self._not_averaged("graphed_step")
         if self.reducer is not None:
             raise RuntimeError("graphed_step: not supported with distributed=True (use step())")
         from . import ops
@@ -337,7 +404,9 @@ class FineTuner:
         out = self.forward_backward(net_input, net_target, epoch, use_weight, **kw)
         out.grad_norm, out.skipped = self.arena.adam_step(0.0, eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm,
                                                           step_state=self._state, guard=self.guard)
-        self.arena.step_count -= 1                   # (the host-side counter is advanced by graphed_step, once per replay)
+        if self.ema_decay is not None:
+            self.arena.ema_step(self.ema_decay, self.ema_warmup, guard=self.guard, step_state=self._state)
+        self.arena.step_count -= 1                  # (the host-side counter is advanced by graphed_step, once per replay)
         return out
 
     def _capture(self, net_input, net_target, epoch, use_weight, kw):
@@ -356,7 +425,8 @@ class FineTuner:
         # warm-up on a side stream (lazy stream / buffer creation must not happen inside the capture), with a throw-away copy of
         # the state this step mutates
         saved = (self.arena.data.clone(), self.arena.adam_m.clone(), self.arena.adam_v.clone(), self._state.clone(), self._salt.clone(),
-                 self.arena.step_count, None if self.guard is None else self.guard.clone())
+                 self.arena.step_count, None if self.guard is None else self.guard.clone(),
+                 None if self.arena.ema is None else self.arena.ema.clone())
         # a task loss with device state of its own (losses.GHMCLoss: the bin counts every call averages into) is part of that state
         lf = kw.get("loss_func") or self.task_loss
         loss_state = lf.device_state(dev) if hasattr(lf, "device_state") else None
@@ -375,6 +445,8 @@ class FineTuner:
         self.arena.step_count = saved[5]
         if self.guard is not None:
             self.guard.copy_(saved[6])
+        if saved[7] is not None:
+            self.arena.ema.copy_(saved[7])
         if loss_state is not None:
             loss_state.copy_(loss_saved)
         if fds_acc is not None:
@@ -387,6 +459,7 @@ class FineTuner:
         return static_in, static_tgt, graph, out
 
     def step(self, net_input: dict, net_target: torch.Tensor, epoch: int = 0, use_weight: bool = False, **kw) -> StepOutput:
+        self._not_averaged("step")
         if getattr(self, "_salted", False):
             # graph replays left their dropout salt in the kernel libraries: an eager step draws its masks from the by-value
             # (seed, site) pairs alone, as every other engine in the process expects (enqueued, no synchronisation)
