@@ -63,7 +63,7 @@ typedef void* mmdti_stream_t;
 
 const char* mmdti_last_error(void);
 int mmdti_abi_version(void);
-/* The kernel tables the launch plans index (mmdti_attn_plan, mmdti_gbf_plan, mmdti_pair_attn_plan): every instance a family can launch has one row, and a
+/* The kernel tables the launch plans index (mmdti_attn_plan, mmdti_gbf_plan, mmdti_pair_attn_plan, mmdti_row_plan, mmdti_stream_plan): every instance a family can launch has one row, and a
  * plan names a kernel by its row.  size_out receives the number of rows; the name of row `index` is the kernel's template-id as the
  * source spells it ("attn_fwd_kernel<16, 10>"), null for an unknown family or a row past the end.  No GPU needed. */
 #define MMDTI_PLAN_ATTN 0
@@ -72,6 +72,8 @@ int mmdti_abi_version(void);
 #define MMDTI_PLAN_PAIR_ATTN_BWD 3       /* pair_attn_bwd_mfma_kernel */
 #define MMDTI_PLAN_PAIR_ATTN_FWD_ELEM 4  /* pair_attn_fwd_kernel: the per-element form (N > 272, or unaligned rows / planes) */
 #define MMDTI_PLAN_PAIR_ATTN_BWD_ELEM 5  /* pair_attn_bwd_kernel */
+#define MMDTI_PLAN_ROW 6                 /* LayerNorm and row softmax (mmdti_row_plan): 26 rows */
+#define MMDTI_PLAN_STREAM 7              /* casts, dropout, axpy, GELU, column sum, sum of squares, Adam, EMA, step state (mmdti_stream_plan): 29 rows */
 int mmdti_plan_table_size(int family, int* size_out);
 const char* mmdti_plan_kernel_name(int family, int index);
 /* Run-time tuning switches (A/B measurements inside one process; defaults come from the environment variable of the same
@@ -862,6 +864,63 @@ int mmdti_ema_update(mmdti_stream_t stream, const float* p, float* ema, long lon
  * roundings of the Adam pass: both shadows are valid when the kernel ends, without a temporary and without cast passes.  Twice is the
  * identity.  p, ema and the shadows are 16-byte aligned; n == 0 launches nothing.  Purely additive: MMDTI_ABI_VERSION does not move. */
 int mmdti_ema_swap(mmdti_stream_t stream, float* p, float* ema, void* p_bf16, void* p_f16 /* nullable */, long long n);
+
+/* ---- Launch plans of the row kernels and of the streaming, reduction and optimizer kernels, without launching.  Each query runs the
+ * validation of the entry point it stands for, message for message, and returns the plan that entry would launch (csrc/row_plan.h,
+ * csrc/stream_plan.h).  No GPU needed.  ptrs is a HOST array of the entry's addresses in the order listed below; they are tested for
+ * null and alignment only (pass any address with the alignment in question).  deterministic: the mode the launch would find
+ * (mmdti_set_deterministic); the queries do not read the process flag, and the stream's reduction workspace is not looked up.
+ * plan_out receives long long words: the number of launches (0: the entry returns without one, n == 0 where it admits that), then for
+ * each of two launches -- the second is zero when there is one -- the kernel's row in the family's table (mmdti_plan_kernel_name;
+ * -1: det_fold_kernel, the fixed-order fold queued behind a slab kernel), grid x, grid y, workgroup size, dynamic LDS bytes; then the
+ * family's derived numbers.
+ *
+ * mmdti_row_plan, table MMDTI_PLAN_ROW, 13 words: ... nv (the instance's NV), rows per wave (LayerNorm backward; else 0).
+ *   MMDTI_ROW_LAYERNORM_FWD  ptrs = x, gamma, beta, y_f32, y_bf16;  rows, D, drop_p
+ *   MMDTI_ROW_LAYERNORM_BWD  ptrs = dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dx_bf16, dx_colsum;  rows, D, dy_dtype, drop_p, drop2_p,
+ *                            deterministic (two launches: ln_bwd_slab_kernel, then the fold)
+ *   MMDTI_ROW_SOFTMAX_FWD    ptrs = s, p_bf16, pd_bf16;  B, heads, Lq, Lk, ld, drop_p
+ *   MMDTI_ROW_SOFTMAX_BWD    ptrs = p_bf16, dp, ds_bf16;  B, heads, Lq, Lk, ld, drop_p */
+#define MMDTI_ROW_LAYERNORM_FWD 0
+#define MMDTI_ROW_LAYERNORM_BWD 1
+#define MMDTI_ROW_SOFTMAX_FWD 2
+#define MMDTI_ROW_SOFTMAX_BWD 3
+int mmdti_row_plan(int entry, int deterministic, const void* const* ptrs, int rows_or_B, int heads, int Lq, int Lk, int D_or_ld, int dy_dtype,
+                   float drop_p, float drop2_p, long long* plan_out);
+/* mmdti_stream_plan, table MMDTI_PLAN_STREAM, 12 words: ... the sum of squares' workgroups = partials (0 in its atomic form and elsewhere).
+ *   MMDTI_STREAM_CAST_F32_BF16, _CAST_F32_F16   ptrs = x, y;  n, f = drop_p
+ *   MMDTI_STREAM_CAST_F16_BF16                  ptrs = x_f16, y_bf16;  a = rows, b = cols, c = ldx
+ *   MMDTI_STREAM_CAST_BF16_F32, _AXPY_F32, _GELU_FWD_BF16   ptrs = x (u), y;  n
+ *   MMDTI_STREAM_DROPOUT_F32                    ptrs = x, y;  n, f = drop_p
+ *   MMDTI_STREAM_COLSUM_BF16                    ptrs = x_bf16, out;  a = rows, b = cols, c = ld, deterministic (two launches: slab kernel, fold)
+ *   MMDTI_STREAM_SUMSQ_F32                      ptrs = g, out, ws;  n, a = ws_floats, deterministic (refused without the ws form)
+ *   MMDTI_STREAM_SUMSQ_CHECK_F32                ptrs = g, out, ws, bias_table;  n, a = ws_floats, b = table_steps
+ *   MMDTI_STREAM_ADAM_STEP                      ptrs = p, g, m, v, step_state_dev;  n, a = step
+ *   MMDTI_STREAM_ADAM_STEP_GUARDED              ptrs = p, g, m, v, guard;  n
+ *   MMDTI_STREAM_ADAM_STEP_MASKED               ptrs = p, g, m, v, step_state_dev, guard, skip;  n, a = step
+ *   MMDTI_STREAM_ADAM_STEP_GROUPED              ptrs = p, g, m, v, p_bf16, p_f16, step_state_dev, guard, skip, group, table_dev;  n, a = step,
+ *                                               b = ngroups, c = decoupled
+ *   MMDTI_STREAM_EMA_UPDATE                     ptrs = p, ema, guard, step_state;  n, a = step, f = decay
+ *   MMDTI_STREAM_EMA_SWAP                       ptrs = p, ema, p_bf16, p_f16;  n
+ *   MMDTI_STREAM_STEP_STATE_ADVANCE             ptrs = state, salt;  a = warmup_steps, b = total_steps */
+#define MMDTI_STREAM_CAST_F32_BF16 0
+#define MMDTI_STREAM_CAST_F32_F16 1
+#define MMDTI_STREAM_CAST_F16_BF16 2
+#define MMDTI_STREAM_CAST_BF16_F32 3
+#define MMDTI_STREAM_DROPOUT_F32 4
+#define MMDTI_STREAM_AXPY_F32 5
+#define MMDTI_STREAM_GELU_FWD_BF16 6
+#define MMDTI_STREAM_COLSUM_BF16 7
+#define MMDTI_STREAM_SUMSQ_F32 8
+#define MMDTI_STREAM_SUMSQ_CHECK_F32 9
+#define MMDTI_STREAM_ADAM_STEP 10
+#define MMDTI_STREAM_ADAM_STEP_GUARDED 11
+#define MMDTI_STREAM_ADAM_STEP_MASKED 12
+#define MMDTI_STREAM_ADAM_STEP_GROUPED 13
+#define MMDTI_STREAM_EMA_UPDATE 14
+#define MMDTI_STREAM_EMA_SWAP 15
+#define MMDTI_STREAM_STEP_STATE_ADVANCE 16
+int mmdti_stream_plan(int entry, int deterministic, const void* const* ptrs, long long n, int a, int b, int c, float f, long long* plan_out);
 
 /* ---- hardware probes used by the test-suite ------------------------------------------------- */
 /* out[64*4] <- what ds_read_b64_tr_b16 returns to each lane for an LDS image holding element index == value */

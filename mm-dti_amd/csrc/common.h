@@ -93,7 +93,8 @@ __global__ __launch_bounds__(1024) void det_fold_kernel(const float* __restrict_
 }
 template <int NDST>
 static inline void det_fold(hipStream_t s, const float* ws, int nslab, long long stride, int n, DetDst<NDST> d) {
-  hipLaunchKernelGGL((det_fold_kernel<NDST>), dim3((n + 63) / 64, NDST), dim3(1024), 0, s, ws, nslab, stride, n, d);
+  const PlanLaunch k = det_fold_launch(n, NDST);   // (what a plan with a slab kernel names as its second launch)
+  hipLaunchKernelGGL((det_fold_kernel<NDST>), dim3(k.gx, k.gy), dim3(k.block), 0, s, ws, nslab, stride, n, d);
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -112,6 +113,28 @@ struct KernelRow {
 const KernelRow* attn_kernel_table(int* n);   // attn.hip
 const KernelRow* gbf_kernel_table(int* n);    // gbf.hip
 const KernelRow* pair_attn_kernel_row(int family, int key);   // pair_attn_bwd.hip: row `key` of a PairAttnFamily table, null past its end
+const KernelRow* ln_kernel_table(int* n);     // layernorm.hip: rows 0..19 of MMDTI_PLAN_ROW (elementwise.hip holds the softmax rows behind them)
+// layernorm.hip: the validation and plan its two launchers and mmdti_row_plan (elementwise.hip) share
+int ln_fwd_prepare(RowPlan& plan, const float* x, const float* gamma, const float* beta, int rows, int D, const float* y_f32,
+                   const void* y_bf16, float drop_p);
+int ln_bwd_prepare(RowPlan& plan, bool det, const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
+                   const float* rstd, int rows, int D, const float* dx, const float* dgamma, const float* dbeta, float drop_p,
+                   const void* dx_bf16, float drop2_p, const float* dx_colsum);
+
+// Launch a table's row (the one the plan's key names) with the plan's geometry.  `like` is any instance of the kernel template the row belongs to: each
+// argument is converted to that signature's parameter type before its address goes into the argument array, so the compiler checks
+// the list as it does for a direct launch (count and types; a mismatch does not compile).
+template <typename... P>
+static inline void launch_typed(const void* fn, const PlanLaunch& k, hipStream_t s, P... a) {
+  void* argv[] = {static_cast<void*>(&a)...};
+  (void)hipLaunchKernel(fn, dim3((unsigned)k.gx, (unsigned)k.gy), dim3((unsigned)k.block), argv, (size_t)k.lds, s);
+}
+template <typename... P, typename... A>
+static inline void launch_row(void (*like)(P...), const KernelRow& row, const PlanLaunch& k, hipStream_t s, A... args) {
+  (void)like;
+  static_assert(sizeof...(P) == sizeof...(A), "launch_row: one argument per kernel parameter");
+  launch_typed<P...>(row.fn, k, s, args...);
+}
 
 // > 64 KiB of dynamic LDS: opt in, once per kernel and cap (raised only if larger than what is set).  *have is a plain static of the
 // kernel's table row: one value for all devices, no synchronisation -- launches come from one host thread per process here; a second

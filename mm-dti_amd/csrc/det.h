@@ -9,6 +9,8 @@
 #include <mutex>
 #include <vector>
 
+#include "stream_plan.h"
+
 namespace mmdti {
 
 struct DetSlot {
@@ -59,20 +61,9 @@ inline DetTable& det_table() {
   return t;
 }
 
-// ---- launch geometry the workspace sizes follow from (the launchers use the same functions) ----
+// ---- launch geometry the workspace sizes follow from (the launchers use the same functions: ln_bwd_grid of row_plan.h, colsum_grid_y
+// of stream_plan.h) ----
 static inline int det_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-// LayerNorm backward: float4 columns per lane, rows per wave, workgroups (4 waves each)
-static inline int ln_nv(int D) { return (D / 4 + 63) / 64; }
-static inline int ln_bwd_rows_per_wave(int rows, int D) {
-  const int min_rpw = 4, r = det_cdiv(rows, 4 * (ln_nv(D) <= 2 ? 3 : 2) * 256);
-  return r > min_rpw ? r : min_rpw;
-}
-static inline int ln_bwd_grid(int rows, int D) { return det_cdiv(rows, 4 * ln_bwd_rows_per_wave(rows, D)); }
-// column sum: row groups (grid.y)
-static inline int colsum_grid_y(int rows) {
-  const int gy = det_cdiv(rows, 8 * 8);
-  return gy > 1024 ? 1024 : gy;
-}
 
 // unfused pair-bias feature backward in the mode: workgroups (16 pairs per iteration each)
 static inline int gbf_features_bwd_grid(long long P) {

@@ -15,13 +15,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-static inline int grid_for(long long n, int per_block) {
-  long long b = (n + per_block - 1) / per_block;
-  if (b > 256 * 16) b = 256 * 16;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 // ---------------------------------------------------------------- casts / dropout / axpy
 __device__ __forceinline__ bf16_t f2h16(float f) { return f2h_sat(f); }
 
@@ -503,8 +496,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 }
 // The reproducible form (a workspace is given): 16-byte loads, one partial per workgroup, and the partials folded in a FIXED order by
 // sumsq_fold_kernel -- the gradient norm, and with it the clip coefficient of every Adam step, is the same to the bit from run to run
-// (the atomic form above differs in the last bit, and a training trajectory with it).
-constexpr int SUMSQ_WGS = 2048;
+// (the atomic form above differs in the last bit, and a training trajectory with it).  At most SUMSQ_WGS partials (stream_plan.h).
 // CHECK: the same pass also counts the non-finite gradient elements (the found-inf test of GradScaler.unscale_) -- one per-workgroup count
 // next to each partial.  Inf / NaN is told by the exponent bits, which no fast-math flag can fold away (a `x != x` test can vanish).  The
 // float arithmetic is the same statement sequence in both instantiations: the sum is the same to the bit with or without the check.
@@ -861,11 +853,35 @@ using namespace mmdti;
 extern "C" const char* mmdti_last_error(void) { return g_err; }
 extern "C" int mmdti_abi_version(void) { return MMDTI_ABI_VERSION; }
 
+// ---- this file's own tables: the softmax rows of MMDTI_PLAN_ROW (sm_key, row_plan.h: they follow layernorm.hip's twenty) and
+// MMDTI_PLAN_STREAM (StreamKey, stream_plan.h) ----
+static KernelRow g_softmax_kernels[ROW_KERNELS - ROW_LN_KERNELS] = {
+    KROW(sm_key(0, 1), softmax_fwd_kernel<1>), KROW(sm_key(0, 2), softmax_fwd_kernel<2>), KROW(sm_key(0, 4), softmax_fwd_kernel<4>),
+    KROW(sm_key(1, 1), softmax_bwd_kernel<1>), KROW(sm_key(1, 2), softmax_bwd_kernel<2>), KROW(sm_key(1, 4), softmax_bwd_kernel<4>),
+};
+static KernelRow g_stream_kernels[STREAM_KERNELS] = {
+    KROW(SK_CAST_F32_BF16, cast_f32_bf16_kernel<false>), KROW(SK_CAST_F32_BF16 + 1, cast_f32_bf16_kernel<true>),
+    KROW(SK_CAST_F16_BF16, cast_f16_bf16_kernel), KROW(SK_CAST_BF16_F32, cast_bf16_f32_kernel), KROW(SK_DROPOUT, dropout_f32_kernel),
+    KROW(SK_AXPY, axpy_kernel), KROW(SK_GELU, gelu_bf16_kernel), KROW(SK_COLSUM, colsum_bf16_kernel), KROW(SK_COLSUM_SLAB, colsum_bf16_slab_kernel),
+    KROW(SK_SUMSQ, sumsq_kernel), KROW(sumsq_part_key(0), sumsq_part_kernel<false>), KROW(sumsq_fold_key(0), sumsq_fold_kernel<false>),
+    KROW(sumsq_part_key(1), sumsq_part_kernel<true>), KROW(sumsq_fold_key(1), sumsq_fold_kernel<true>),
+    KROW(SK_ADAM, adam_kernel<false, false>), KROW(SK_ADAM + 1, adam_kernel<true, false>), KROW(SK_ADAM + 2, adam_kernel<false, true>),
+    KROW(SK_ADAM + 3, adam_kernel<true, true>), KROW(SK_STEP_STATE, step_state_advance_kernel),
+    KROW(SK_ADAM_GROUP, adam_group_kernel<false, false, false>), KROW(SK_ADAM_GROUP + 1, adam_group_kernel<false, false, true>),
+    KROW(SK_ADAM_GROUP + 2, adam_group_kernel<false, true, false>), KROW(SK_ADAM_GROUP + 3, adam_group_kernel<false, true, true>),
+    KROW(SK_ADAM_GROUP + 4, adam_group_kernel<true, false, false>), KROW(SK_ADAM_GROUP + 5, adam_group_kernel<true, false, true>),
+    KROW(SK_ADAM_GROUP + 6, adam_group_kernel<true, true, false>), KROW(SK_ADAM_GROUP + 7, adam_group_kernel<true, true, true>),
+    KROW(SK_EMA_UPDATE, ema_update_kernel), KROW(SK_EMA_SWAP, ema_swap_kernel),
+};
+
 // ---- the kernel tables of the planned families (each family's .hip file owns its table) ----
 static const KernelRow* plan_row(int family, int index) {
   if (family >= MMDTI_PLAN_PAIR_ATTN_FWD && family <= MMDTI_PLAN_PAIR_ATTN_BWD_ELEM) return pair_attn_kernel_row(family - MMDTI_PLAN_PAIR_ATTN_FWD, index);
+  if (family == MMDTI_PLAN_ROW && index >= ROW_LN_KERNELS) return index < ROW_KERNELS ? &g_softmax_kernels[index - ROW_LN_KERNELS] : nullptr;
   int n = 0;
-  const KernelRow* t = family == MMDTI_PLAN_ATTN ? attn_kernel_table(&n) : family == MMDTI_PLAN_GBF ? gbf_kernel_table(&n) : nullptr;
+  const KernelRow* t = family == MMDTI_PLAN_ATTN ? attn_kernel_table(&n) : family == MMDTI_PLAN_GBF ? gbf_kernel_table(&n)
+                       : family == MMDTI_PLAN_ROW ? ln_kernel_table(&n) : nullptr;
+  if (family == MMDTI_PLAN_STREAM) t = g_stream_kernels, n = STREAM_KERNELS;
   return t && index >= 0 && index < n ? &t[index] : nullptr;
 }
 extern "C" int mmdti_plan_table_size(int family, int* size_out) {
@@ -906,94 +922,135 @@ static void adam_bias_host(float beta1, float beta2, int step, float* bc1, float
   *bc2_sqrt = sqrtf(1.f - powf(beta2, (float)step));
 }
 
-#define DROP_SETUP(name)                                                                  \
-  MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, name ": dropout p out of range");          \
-  const uint32_t th = dropout_thresh(drop_p);                                             \
+#define DROP_REQUIRE(name) MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, name ": dropout p out of range")
+#define DROP_SETUP()                           \
+  const uint32_t th = dropout_thresh(drop_p);  \
   const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f
+#define STREAM_ROW(plan, i) g_stream_kernels[(plan).k[i].key], (plan).k[i], (hipStream_t)stream
+
+// ---- What each launcher and mmdti_stream_plan share: validate, plan (stream_plan.h).  Pointers are tested for null and alignment only. ----
+static int cast_f32_bf16_prepare(StreamPlan& plan, const float* x, const void* y_bf16, long long n, float drop_p) {
+  MMDTI_REQUIRE(x && y_bf16 && n > 0, "cast_f32_bf16: bad arguments");
+  MMDTI_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(y_bf16) & 7) == 0, "cast_f32_bf16: alignment");
+  DROP_REQUIRE("cast_f32_bf16");
+  plan = cast_f32_16_plan(n, false);
+  return MMDTI_OK;
+}
+static int cast_f32_f16_prepare(StreamPlan& plan, const float* x, const void* y_f16, long long n, float drop_p) {
+  MMDTI_REQUIRE(x && y_f16 && n > 0, "cast_f32_f16: bad arguments");
+  MMDTI_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(y_f16) & 7) == 0, "cast_f32_f16: alignment");
+  DROP_REQUIRE("cast_f32_f16");
+  plan = cast_f32_16_plan(n, true);
+  return MMDTI_OK;
+}
+static int cast_f16_bf16_prepare(StreamPlan& plan, const void* x_f16, int rows, int cols, int ldx, const void* y_bf16) {
+  MMDTI_REQUIRE(x_f16 && y_bf16 && rows > 0 && cols > 0 && cols % 8 == 0 && ldx >= cols && ldx % 8 == 0, "cast_f16_bf16: bad arguments (cols %% 8, ldx %% 8)");
+  MMDTI_REQUIRE(aligned16(x_f16) && aligned16(y_bf16), "cast_f16_bf16: 16-byte alignment required");
+  plan = cast_f16_bf16_plan(rows, cols);
+  return MMDTI_OK;
+}
+static int cast_bf16_f32_prepare(StreamPlan& plan, const void* x_bf16, const float* y, long long n) {
+  MMDTI_REQUIRE(x_bf16 && y && n > 0, "cast_bf16_f32: bad arguments");
+  plan = stream_plan(SK_CAST_BF16_F32, n, 256);
+  return MMDTI_OK;
+}
+static int dropout_f32_prepare(StreamPlan& plan, const float* x, const float* y, long long n, float drop_p) {
+  MMDTI_REQUIRE(x && y && n > 0, "dropout_f32: bad arguments");
+  DROP_REQUIRE("dropout_f32");
+  plan = stream_plan(SK_DROPOUT, n, 256);
+  return MMDTI_OK;
+}
+static int axpy_f32_prepare(StreamPlan& plan, const float* x, const float* y, long long n) {
+  MMDTI_REQUIRE(x && y && n > 0, "axpy_f32: bad arguments");
+  plan = stream_plan(SK_AXPY, n, 256);
+  return MMDTI_OK;
+}
+static int gelu_fwd_bf16_prepare(StreamPlan& plan, const void* u_bf16, const void* y_bf16, long long n) {
+  MMDTI_REQUIRE(u_bf16 && y_bf16 && n > 0, "gelu_fwd_bf16: bad arguments");
+  plan = stream_plan(SK_GELU, n, 256);
+  return MMDTI_OK;
+}
+// det: the mode the launch finds (det_table().on()); the stream's workspace is looked up by the launch alone
+static int colsum_bf16_prepare(StreamPlan& plan, bool det, const void* x_bf16, int rows, int cols, int ld, const float* out) {
+  MMDTI_REQUIRE(x_bf16 && out && rows > 0 && cols > 0 && ld >= cols, "colsum_bf16: bad arguments");
+  MMDTI_REQUIRE(ld % 8 == 0 && aligned16(x_bf16), "colsum_bf16: ld%%8 and 16-byte alignment required");
+  plan = colsum_plan(rows, cols, det);
+  return MMDTI_OK;
+}
+
+// (both fp32 -> 16-bit casts: one signature, the plan's key tells them apart)
+static int cast_f32_16_launch(const StreamPlan& plan, mmdti_stream_t stream, const float* x, void* y16, long long n, float drop_p,
+                              unsigned long long seed, unsigned int site) {
+  DROP_SETUP();
+  launch_row(cast_f32_bf16_kernel<false>, STREAM_ROW(plan, 0), x, (bf16_t*)y16, n / 4, n, th, sc, (uint64_t)seed, (uint32_t)site);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
 
 extern "C" int mmdti_cast_f32_bf16(mmdti_stream_t stream, const float* x, void* y_bf16, long long n, float drop_p,
                                    unsigned long long seed, unsigned int site) {
-  MMDTI_REQUIRE(x && y_bf16 && n > 0, "cast_f32_bf16: bad arguments");
-  MMDTI_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(y_bf16) & 7) == 0, "cast_f32_bf16: alignment");
-  DROP_SETUP("cast_f32_bf16");
-  hipLaunchKernelGGL(cast_f32_bf16_kernel<false>, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     (bf16_t*)y_bf16, n / 4, n, th, sc, (uint64_t)seed, (uint32_t)site);
-  MMDTI_LAUNCH_CHECK();
-  return MMDTI_OK;
+  StreamPlan plan;
+  if (int e = cast_f32_bf16_prepare(plan, x, y_bf16, n, drop_p)) return e;
+  return cast_f32_16_launch(plan, stream, x, y_bf16, n, drop_p, seed, site);
 }
 
 extern "C" int mmdti_cast_f32_f16(mmdti_stream_t stream, const float* x, void* y_f16, long long n, float drop_p,
                                   unsigned long long seed, unsigned int site) {
-  MMDTI_REQUIRE(x && y_f16 && n > 0, "cast_f32_f16: bad arguments");
-  MMDTI_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(y_f16) & 7) == 0, "cast_f32_f16: alignment");
-  DROP_SETUP("cast_f32_f16");
-  hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     (bf16_t*)y_f16, n / 4, n, th, sc, (uint64_t)seed, (uint32_t)site);
-  MMDTI_LAUNCH_CHECK();
-  return MMDTI_OK;
+  StreamPlan plan;
+  if (int e = cast_f32_f16_prepare(plan, x, y_f16, n, drop_p)) return e;
+  return cast_f32_16_launch(plan, stream, x, y_f16, n, drop_p, seed, site);
 }
 
 extern "C" int mmdti_cast_f16_bf16(mmdti_stream_t stream, const void* x_f16, int rows, int cols, int ldx, void* y_bf16) {
-  MMDTI_REQUIRE(x_f16 && y_bf16 && rows > 0 && cols > 0 && cols % 8 == 0 && ldx >= cols && ldx % 8 == 0, "cast_f16_bf16: bad arguments (cols %% 8, ldx %% 8)");
-  MMDTI_REQUIRE(aligned16(x_f16) && aligned16(y_bf16), "cast_f16_bf16: 16-byte alignment required");
-  const long long n8 = (long long)rows * (cols / 8);
-  hipLaunchKernelGGL(cast_f16_bf16_kernel, dim3(grid_for(n8, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x_f16, cols / 8, ldx,
-                     (bf16_t*)y_bf16, n8);
+  StreamPlan plan;
+  if (int e = cast_f16_bf16_prepare(plan, x_f16, rows, cols, ldx, y_bf16)) return e;
+  launch_row(cast_f16_bf16_kernel, STREAM_ROW(plan, 0), (const bf16_t*)x_f16, cols / 8, ldx, (bf16_t*)y_bf16, (long long)rows * (cols / 8));
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_cast_bf16_f32(mmdti_stream_t stream, const void* x_bf16, float* y, long long n) {
-  MMDTI_REQUIRE(x_bf16 && y && n > 0, "cast_bf16_f32: bad arguments");
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x_bf16, y, n);
+  StreamPlan plan;
+  if (int e = cast_bf16_f32_prepare(plan, x_bf16, y, n)) return e;
+  launch_row(cast_bf16_f32_kernel, STREAM_ROW(plan, 0), (const bf16_t*)x_bf16, y, n);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_dropout_f32(mmdti_stream_t stream, const float* x, float* y, long long n, float drop_p,
                                  unsigned long long seed, unsigned int site) {
-  MMDTI_REQUIRE(x && y && n > 0, "dropout_f32: bad arguments");
-  DROP_SETUP("dropout_f32");
-  hipLaunchKernelGGL(dropout_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, th, sc,
-                     (uint64_t)seed, (uint32_t)site);
+  StreamPlan plan;
+  if (int e = dropout_f32_prepare(plan, x, y, n, drop_p)) return e;
+  DROP_SETUP();
+  launch_row(dropout_f32_kernel, STREAM_ROW(plan, 0), x, y, n, th, sc, (uint64_t)seed, (uint32_t)site);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_axpy_f32(mmdti_stream_t stream, const float* x, float* y, long long n, float a) {
-  MMDTI_REQUIRE(x && y && n > 0, "axpy_f32: bad arguments");
-  hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, a);
+  StreamPlan plan;
+  if (int e = axpy_f32_prepare(plan, x, y, n)) return e;
+  launch_row(axpy_kernel, STREAM_ROW(plan, 0), x, y, n, a);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_gelu_fwd_bf16(mmdti_stream_t stream, const void* u_bf16, void* y_bf16, long long n) {
-  MMDTI_REQUIRE(u_bf16 && y_bf16 && n > 0, "gelu_fwd_bf16: bad arguments");
-  hipLaunchKernelGGL(gelu_bf16_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)u_bf16, (bf16_t*)y_bf16, n);
+  StreamPlan plan;
+  if (int e = gelu_fwd_bf16_prepare(plan, u_bf16, y_bf16, n)) return e;
+  launch_row(gelu_bf16_kernel, STREAM_ROW(plan, 0), (const bf16_t*)u_bf16, (bf16_t*)y_bf16, n);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_colsum_bf16(mmdti_stream_t stream, const void* x_bf16, int rows, int cols, int ld, float* out) {
-  MMDTI_REQUIRE(x_bf16 && out && rows > 0 && cols > 0 && ld >= cols, "colsum_bf16: bad arguments");
-  MMDTI_REQUIRE(ld % 8 == 0 && aligned16(x_bf16), "colsum_bf16: ld%%8 and 16-byte alignment required");
-  // 8 rows per thread (two rounds of four 16-byte loads): enough workgroups to fill 256 CUs several times over --
-  // the reduction is latency-bound at one workgroup per CU
-  const int gy = colsum_grid_y(rows);
-  if (det_table().on()) {
-    // the deterministic mode: one row of the stream's workspace per row group, folded in row-group order (never atomics)
-    float* slab = nullptr;
-    if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_COLSUM, rows, cols), "colsum_bf16", &slab)) return e;
-    hipLaunchKernelGGL(colsum_bf16_slab_kernel, dim3(cdiv(cols, 256), gy), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x_bf16, rows,
-                       cols, ld, slab);
-    det_fold<1>((hipStream_t)stream, slab, gy, cols, cols, DetDst<1>{{out}});
-    MMDTI_LAUNCH_CHECK();
-    return MMDTI_OK;
-  }
-  hipLaunchKernelGGL(colsum_bf16_kernel, dim3(cdiv(cols, 256), gy), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x_bf16, rows, cols, ld, out);
+  StreamPlan plan;
+  if (int e = colsum_bf16_prepare(plan, det_table().on(), x_bf16, rows, cols, ld, out)) return e;
+  float* dst = out;
+  if (plan.nlaunch == 2)   // the deterministic mode: the sums go to the stream's workspace first
+    if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_COLSUM, rows, cols), "colsum_bf16", &dst)) return e;
+  launch_row(colsum_bf16_kernel, STREAM_ROW(plan, 0), (const bf16_t*)x_bf16, rows, cols, ld, dst);
+  if (plan.nlaunch == 2) det_fold<1>((hipStream_t)stream, dst, (int)plan.k[0].gy, cols, cols, DetDst<1>{{out}});
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -1053,22 +1110,34 @@ extern "C" int mmdti_roberta_position_ids(mmdti_stream_t stream, const long long
   return MMDTI_OK;
 }
 
-extern "C" int mmdti_softmax_fwd(mmdti_stream_t stream, const float* s, const float* key_add, void* p_bf16,
-                                 void* pd_bf16, int B, int heads, int Lq, int Lk, int ld, float drop_p,
-                                 unsigned long long seed, unsigned int site) {
+static int softmax_fwd_prepare(RowPlan& plan, const float* s, const void* p_bf16, const void* pd_bf16, int B, int heads, int Lq, int Lk, int ld,
+                               float drop_p) {
   MMDTI_REQUIRE(s && p_bf16 && pd_bf16 && B > 0 && heads > 0 && Lq > 0 && Lk > 0, "softmax_fwd: bad arguments");
   MMDTI_REQUIRE(ld >= Lk && ld <= 1024 && ld % 8 == 0, "softmax_fwd: need Lk <= ld <= 1024, ld %% 8 == 0");
   MMDTI_REQUIRE(aligned16(s) && aligned16(p_bf16) && aligned16(pd_bf16), "softmax_fwd: 16-byte alignment required");
-  DROP_SETUP("softmax_fwd");
+  DROP_REQUIRE("softmax_fwd");
   MMDTI_REQUIRE(drop_p == 0.f || pd_bf16 != p_bf16, "softmax_fwd: dropout needs a separate pd buffer");
-  const long long rows = (long long)B * heads * Lq;
-  dim3 grid(cdiv(rows, 4)), block(256);
-#define SM_F(NV)                                                                                                   \
-  hipLaunchKernelGGL((softmax_fwd_kernel<NV>), grid, block, 0, (hipStream_t)stream, s, key_add, (bf16_t*)p_bf16,  \
-                     (bf16_t*)pd_bf16, rows, heads, Lq, Lk, ld, th, sc, (uint64_t)seed, (uint32_t)site)
-  const int nv = (ld + 255) / 256;
-  if (nv <= 1) SM_F(1); else if (nv <= 2) SM_F(2); else SM_F(4);
-#undef SM_F
+  plan = softmax_plan(false, (long long)B * heads * Lq, ld);
+  return MMDTI_OK;
+}
+static int softmax_bwd_prepare(RowPlan& plan, const void* p_bf16, const float* dp, const void* ds_bf16, int B, int heads, int Lq, int Lk, int ld,
+                               float drop_p) {
+  MMDTI_REQUIRE(p_bf16 && dp && ds_bf16 && B > 0 && heads > 0 && Lq > 0 && Lk > 0, "softmax_bwd: bad arguments");
+  MMDTI_REQUIRE(ld >= Lk && ld <= 1024 && ld % 8 == 0, "softmax_bwd: need Lk <= ld <= 1024, ld %% 8 == 0");
+  MMDTI_REQUIRE(aligned16(dp) && aligned16(p_bf16) && aligned16(ds_bf16), "softmax_bwd: 16-byte alignment required");
+  DROP_REQUIRE("softmax_bwd");
+  plan = softmax_plan(true, (long long)B * heads * Lq, ld);
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_softmax_fwd(mmdti_stream_t stream, const float* s, const float* key_add, void* p_bf16,
+                                 void* pd_bf16, int B, int heads, int Lq, int Lk, int ld, float drop_p,
+                                 unsigned long long seed, unsigned int site) {
+  RowPlan plan;
+  if (int e = softmax_fwd_prepare(plan, s, p_bf16, pd_bf16, B, heads, Lq, Lk, ld, drop_p)) return e;
+  DROP_SETUP();
+  launch_row(softmax_fwd_kernel<1>, g_softmax_kernels[plan.k[0].key - ROW_LN_KERNELS], plan.k[0], (hipStream_t)stream, s, key_add, (bf16_t*)p_bf16,
+             (bf16_t*)pd_bf16, (long long)B * heads * Lq, heads, Lq, Lk, ld, th, sc, (uint64_t)seed, (uint32_t)site);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -1076,19 +1145,32 @@ extern "C" int mmdti_softmax_fwd(mmdti_stream_t stream, const float* s, const fl
 extern "C" int mmdti_softmax_bwd(mmdti_stream_t stream, const void* p_bf16, const float* dp, void* ds_bf16, int B,
                                  int heads, int Lq, int Lk, int ld, float scale, float drop_p,
                                  unsigned long long seed, unsigned int site) {
-  MMDTI_REQUIRE(p_bf16 && dp && ds_bf16 && B > 0 && heads > 0 && Lq > 0 && Lk > 0, "softmax_bwd: bad arguments");
-  MMDTI_REQUIRE(ld >= Lk && ld <= 1024 && ld % 8 == 0, "softmax_bwd: need Lk <= ld <= 1024, ld %% 8 == 0");
-  MMDTI_REQUIRE(aligned16(dp) && aligned16(p_bf16) && aligned16(ds_bf16), "softmax_bwd: 16-byte alignment required");
-  DROP_SETUP("softmax_bwd");
-  const long long rows = (long long)B * heads * Lq;
-  dim3 grid(cdiv(rows, 4)), block(256);
-#define SM_B(NV)                                                                                              \
-  hipLaunchKernelGGL((softmax_bwd_kernel<NV>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)p_bf16, dp, \
-                     (bf16_t*)ds_bf16, rows, Lk, ld, scale, th, sc, (uint64_t)seed, (uint32_t)site)
-  const int nv = (ld + 255) / 256;
-  if (nv <= 1) SM_B(1); else if (nv <= 2) SM_B(2); else SM_B(4);
-#undef SM_B
+  RowPlan plan;
+  if (int e = softmax_bwd_prepare(plan, p_bf16, dp, ds_bf16, B, heads, Lq, Lk, ld, drop_p)) return e;
+  DROP_SETUP();
+  launch_row(softmax_bwd_kernel<1>, g_softmax_kernels[plan.k[0].key - ROW_LN_KERNELS], plan.k[0], (hipStream_t)stream, (const bf16_t*)p_bf16, dp,
+             (bf16_t*)ds_bf16, (long long)B * heads * Lq, Lk, ld, scale, th, sc, (uint64_t)seed, (uint32_t)site);
   MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+// The plan a LayerNorm or row-softmax entry would launch, without launching (include/mmdti_hip.h documents ptrs and plan_out)
+extern "C" int mmdti_row_plan(int entry, int deterministic, const void* const* ptrs, int rows_or_B, int heads, int Lq, int Lk, int D_or_ld,
+                              int dy_dtype, float drop_p, float drop2_p, long long* plan_out) {
+  MMDTI_REQUIRE(plan_out != nullptr && ptrs != nullptr, "row_plan: null plan_out or ptrs");
+  MMDTI_REQUIRE(entry >= MMDTI_ROW_LAYERNORM_FWD && entry <= MMDTI_ROW_SOFTMAX_BWD, "row_plan: unknown entry %d", entry);
+  auto f = [&](int i) { return static_cast<const float*>(ptrs[i]); };
+  RowPlan plan;
+  int e;
+  if (entry == MMDTI_ROW_LAYERNORM_FWD) e = ln_fwd_prepare(plan, f(0), f(1), f(2), rows_or_B, D_or_ld, f(3), ptrs[4], drop_p);
+  else if (entry == MMDTI_ROW_LAYERNORM_BWD)
+    e = ln_bwd_prepare(plan, deterministic != 0, ptrs[0], dy_dtype, f(1), f(2), f(3), f(4), rows_or_B, D_or_ld, f(5), f(6), f(7), drop_p, ptrs[8],
+                       drop2_p, f(9));
+  else if (entry == MMDTI_ROW_SOFTMAX_FWD) e = softmax_fwd_prepare(plan, f(0), ptrs[1], ptrs[2], rows_or_B, heads, Lq, Lk, D_or_ld, drop_p);
+  else e = softmax_bwd_prepare(plan, ptrs[0], f(1), ptrs[2], rows_or_B, heads, Lq, Lk, D_or_ld, drop_p);
+  if (e) return e;
+  static_assert(ROW_PLAN_INTS == 13, "mmdti_hip.h documents 13 long long");
+  memcpy(plan_out, &plan, sizeof(plan));
   return MMDTI_OK;
 }
 
@@ -1133,117 +1215,141 @@ extern "C" int mmdti_masked_pool_packed_bwd(mmdti_stream_t stream, const float* 
   return MMDTI_OK;
 }
 
-extern "C" int mmdti_sumsq_f32(mmdti_stream_t stream, const float* g, long long n, float* out, float* ws, int ws_floats) {
+// det: the mode the launch finds (det_table().on())
+static int sumsq_f32_prepare(StreamPlan& plan, bool det, const float* g, long long n, const float* out, const float* ws, int ws_floats) {
   MMDTI_REQUIRE(g && out && n > 0, "sumsq_f32: bad arguments");
-  if (ws && ws_floats >= 1 && aligned16(g)) {
-    const int wgs = (int)min((long long)min(ws_floats, SUMSQ_WGS), (n / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(sumsq_part_kernel<false>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g, n, ws, nullptr);
-    hipLaunchKernelGGL(sumsq_fold_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, wgs, out, nullptr, nullptr, nullptr, 0,
-                       0.f, 0.f);
-  } else {
-    MMDTI_REQUIRE(!det_table().on(), "sumsq_f32: deterministic mode needs the ws form (16-byte aligned g, ws_floats >= 1): without it the partials meet in an atomic");
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, g, n, out);
-  }
-  MMDTI_LAUNCH_CHECK();
+  const bool parts = ws && ws_floats >= 1 && aligned16(g);
+  if (!parts)
+    MMDTI_REQUIRE(!det, "sumsq_f32: deterministic mode needs the ws form (16-byte aligned g, ws_floats >= 1): without it the partials meet in an atomic");
+  plan = sumsq_plan(n, parts ? ws_floats : 0, false);
   return MMDTI_OK;
 }
+static int sumsq_check_f32_prepare(StreamPlan& plan, const float* g, long long n, const float* out, const float* ws, int ws_floats,
+                                   const float* bias_table, int table_steps) {
+  MMDTI_REQUIRE(g && out && ws && n > 0 && ws_floats >= 2, "sumsq_check_f32: bad arguments");
+  MMDTI_REQUIRE(aligned16(g), "sumsq_check_f32: 16-byte alignment required");
+  MMDTI_REQUIRE(!bias_table || table_steps >= 1, "sumsq_check_f32: empty bias-correction table");
+  plan = sumsq_plan(n, ws_floats / 2, true);   // the workgroup count of mmdti_sumsq_f32 with ws_floats / 2 partials
+  return MMDTI_OK;
+}
+// partials, then the fixed-order fold: both instantiations, the plan's keys tell them apart
+static void sumsq_parts_launch(const StreamPlan& plan, mmdti_stream_t stream, const float* g, long long n, float* ws, unsigned* cnt, float* out,
+                               float* guard, const float* bias_table, int table_steps, float beta1, float beta2) {
+  launch_row(sumsq_part_kernel<false>, STREAM_ROW(plan, 0), g, n, ws, cnt);
+  launch_row(sumsq_fold_kernel<false>, STREAM_ROW(plan, 1), ws, (int)plan.wgs, out, cnt, guard, bias_table, table_steps, beta1, beta2);
+}
 
-extern "C" int mmdti_adam_step(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16,
-                               long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                               int step, const float* grad_scale_dev, const float* step_state_dev, void* p_f16) {
-  MMDTI_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_state_dev), "adam_step: bad arguments");
-  float bc1, bc2s;
-  adam_bias_host(beta1, beta2, step, &bc1, &bc2s);
-  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev, step_state_dev, nullptr);
+extern "C" int mmdti_sumsq_f32(mmdti_stream_t stream, const float* g, long long n, float* out, float* ws, int ws_floats) {
+  StreamPlan plan;
+  if (int e = sumsq_f32_prepare(plan, det_table().on(), g, n, out, ws, ws_floats)) return e;
+  if (plan.nlaunch == 2) sumsq_parts_launch(plan, stream, g, n, ws, nullptr, out, nullptr, nullptr, 0, 0.f, 0.f);
+  else launch_row(sumsq_kernel, STREAM_ROW(plan, 0), g, n, out);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_sumsq_check_f32(mmdti_stream_t stream, const float* g, long long n, float* out, float* ws, int ws_floats, float* guard,
                                      const float* bias_table, int table_steps, float beta1, float beta2) {
-  MMDTI_REQUIRE(g && out && ws && n > 0 && ws_floats >= 2, "sumsq_check_f32: bad arguments");
-  MMDTI_REQUIRE(aligned16(g), "sumsq_check_f32: 16-byte alignment required");
-  MMDTI_REQUIRE(!bias_table || table_steps >= 1, "sumsq_check_f32: empty bias-correction table");
-  // the workgroup count of mmdti_sumsq_f32 with ws_floats / 2 partials: the same partials, so the same sum to the bit
-  const int wgs = (int)min((long long)min(ws_floats / 2, SUMSQ_WGS), (n / 4 + 255) / 256 + 1);
-  unsigned* cnt = reinterpret_cast<unsigned*>(ws + wgs);
-  hipLaunchKernelGGL(sumsq_part_kernel<true>, dim3(wgs), dim3(256), 0, (hipStream_t)stream, g, n, ws, cnt);
-  hipLaunchKernelGGL(sumsq_fold_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, wgs, out, cnt, guard, bias_table,
-                     table_steps, beta1, beta2);
+  StreamPlan plan;
+  if (int e = sumsq_check_f32_prepare(plan, g, n, out, ws, ws_floats, bias_table, table_steps)) return e;
+  sumsq_parts_launch(plan, stream, g, n, ws, reinterpret_cast<unsigned*>(ws + plan.wgs), out, guard, bias_table, table_steps, beta1, beta2);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
-extern "C" int mmdti_adam_step_guarded(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
-                                       float lr, float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev,
-                                       const float* step_state_dev, void* p_f16, const float* guard) {
-  MMDTI_REQUIRE(p && g && m && v && n > 0 && guard, "adam_step_guarded: bad arguments");
-  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale_dev, step_state_dev,
-                     guard);
-  MMDTI_LAUNCH_CHECK();
-  return MMDTI_OK;
-}
-
-extern "C" int mmdti_adam_step_masked(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
-                                      float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                                      const float* grad_scale_dev, const float* step_state_dev, void* p_f16, const float* guard,
-                                      const unsigned char* skip) {
-  MMDTI_REQUIRE(p && g && m && v && n > 0 && skip && (guard || step >= 1 || step_state_dev), "adam_step_masked: bad arguments");
-  if (guard) {
-    hipLaunchKernelGGL((adam_kernel<true, true>), dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale_dev, step_state_dev,
-                       guard, skip);
-  } else {
-    float bc1, bc2s;
-    adam_bias_host(beta1, beta2, step, &bc1, &bc2s);
-    hipLaunchKernelGGL((adam_kernel<false, true>), dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale_dev, step_state_dev,
-                       nullptr, skip);
-  }
-  MMDTI_LAUNCH_CHECK();
-  return MMDTI_OK;
-}
-
-template <bool DECOUPLED>
-static void adam_group_launch(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr,
-                              float beta1, float beta2, float eps, int step, const float* grad_scale_dev, const float* step_state_dev,
-                              void* p_f16, const float* guard, const unsigned char* skip, const unsigned char* group, const float* table_dev,
-                              int ngroups) {
+// ---- the Adam pass: four entry points, each with its own argument rules, over one launcher ----
+struct AdamArgs {
+  float* p; const float* g; float* m; float* v; void* p_bf16; void* p_f16;
+  long long n;
+  float lr, beta1, beta2, eps, weight_decay;
+  int step;
+  const float *grad_scale_dev, *step_state_dev, *guard;
+  const unsigned char* skip;
+  const unsigned char* group; const float* table_dev; int ngroups;   // mmdti_adam_step_grouped alone
+};
+// Host bias corrections (by value, from `step`) only when no guard is given: a guarded kernel reads the guard's
+static int adam_launch(const StreamPlan& plan, mmdti_stream_t stream, const AdamArgs& a) {
+  if (plan.nlaunch == 0) return MMDTI_OK;
   float bc1 = 1.f, bc2s = 1.f;
-  if (!guard) adam_bias_host(beta1, beta2, step, &bc1, &bc2s);
-#define ADAM_GROUP(G, M)                                                                                                                     \
-  hipLaunchKernelGGL((adam_group_kernel<G, M, DECOUPLED>), dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,       \
-                     (bf16_t*)p_bf16, (bf16_t*)p_f16, n, lr, beta1, beta2, eps, bc1, bc2s, grad_scale_dev, step_state_dev, guard, skip, group, \
-                     table_dev, ngroups)
-  if (guard) {
-    if (skip) ADAM_GROUP(true, true); else ADAM_GROUP(true, false);
-  } else {
-    if (skip) ADAM_GROUP(false, true); else ADAM_GROUP(false, false);
-  }
-#undef ADAM_GROUP
+  if (!a.guard) adam_bias_host(a.beta1, a.beta2, a.step, &bc1, &bc2s);
+  if (a.group)
+    launch_row(adam_group_kernel<false, false, false>, STREAM_ROW(plan, 0), a.p, a.g, a.m, a.v, (bf16_t*)a.p_bf16, (bf16_t*)a.p_f16, a.n, a.lr, a.beta1,
+               a.beta2, a.eps, bc1, bc2s, a.grad_scale_dev, a.step_state_dev, a.guard, a.skip, a.group, a.table_dev, a.ngroups);
+  else
+    launch_row(adam_kernel<false, false>, STREAM_ROW(plan, 0), a.p, a.g, a.m, a.v, (bf16_t*)a.p_bf16, (bf16_t*)a.p_f16, a.n, a.lr, a.beta1, a.beta2,
+               a.eps, a.weight_decay, bc1, bc2s, a.grad_scale_dev, a.step_state_dev, a.guard, a.skip);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
 }
 
-extern "C" int mmdti_adam_step_grouped(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
-                                       float lr, float beta1, float beta2, float eps, int step, const float* grad_scale_dev,
-                                       const float* step_state_dev, void* p_f16, const float* guard, const unsigned char* skip,
-                                       const unsigned char* group, const float* table_dev, int ngroups, int decoupled) {
+static int adam_step_prepare(StreamPlan& plan, const float* p, const float* g, const float* m, const float* v, long long n, int step,
+                             const float* step_state_dev) {
+  MMDTI_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_state_dev), "adam_step: bad arguments");
+  plan = adam_plan(ADAM_STEP, n, false, false, false);
+  return MMDTI_OK;
+}
+static int adam_step_guarded_prepare(StreamPlan& plan, const float* p, const float* g, const float* m, const float* v, long long n,
+                                     const float* guard) {
+  MMDTI_REQUIRE(p && g && m && v && n > 0 && guard, "adam_step_guarded: bad arguments");
+  plan = adam_plan(ADAM_STEP_GUARDED, n, true, false, false);
+  return MMDTI_OK;
+}
+static int adam_step_masked_prepare(StreamPlan& plan, const float* p, const float* g, const float* m, const float* v, long long n, int step,
+                                    const float* step_state_dev, const float* guard, const unsigned char* skip) {
+  MMDTI_REQUIRE(p && g && m && v && n > 0 && skip && (guard || step >= 1 || step_state_dev), "adam_step_masked: bad arguments");
+  plan = adam_plan(ADAM_STEP_MASKED, n, guard != nullptr, true, false);
+  return MMDTI_OK;
+}
+static int adam_step_grouped_prepare(StreamPlan& plan, const float* p, const float* g, const float* m, const float* v, const void* p_bf16,
+                                     long long n, int step, const float* step_state_dev, const void* p_f16, const float* guard,
+                                     const unsigned char* skip, const unsigned char* group, const float* table_dev, int ngroups, int decoupled) {
   MMDTI_REQUIRE(p && g && m && v && group && table_dev, "adam_step_grouped: null pointer");
   MMDTI_REQUIRE(ngroups >= 1 && ngroups <= 256, "adam_step_grouped: ngroups must be 1 .. 256");
   MMDTI_REQUIRE(n >= 0, "adam_step_grouped: negative n");
   MMDTI_REQUIRE(guard || step >= 1 || step_state_dev, "adam_step_grouped: no source of bias corrections (guard, step >= 1 or step state)");
   MMDTI_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(p_bf16) && aligned16(p_f16),
                 "adam_step_grouped: 16-byte alignment required");
-  if (n == 0) return MMDTI_OK;
-  if (decoupled)
-    adam_group_launch<true>(stream, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, step, grad_scale_dev, step_state_dev, p_f16, guard, skip,
-                            group, table_dev, ngroups);
-  else
-    adam_group_launch<false>(stream, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, step, grad_scale_dev, step_state_dev, p_f16, guard, skip,
-                             group, table_dev, ngroups);
-  MMDTI_LAUNCH_CHECK();
+  plan = adam_plan(ADAM_STEP_GROUPED, n, guard != nullptr, skip != nullptr, decoupled != 0);
   return MMDTI_OK;
+}
+
+extern "C" int mmdti_adam_step(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16,
+                               long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               int step, const float* grad_scale_dev, const float* step_state_dev, void* p_f16) {
+  StreamPlan plan;
+  if (int e = adam_step_prepare(plan, p, g, m, v, n, step, step_state_dev)) return e;
+  return adam_launch(plan, stream, AdamArgs{p, g, m, v, p_bf16, p_f16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, step_state_dev,
+                                            nullptr, nullptr, nullptr, nullptr, 0});
+}
+
+extern "C" int mmdti_adam_step_guarded(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, const float* grad_scale_dev,
+                                       const float* step_state_dev, void* p_f16, const float* guard) {
+  StreamPlan plan;
+  if (int e = adam_step_guarded_prepare(plan, p, g, m, v, n, guard)) return e;
+  return adam_launch(plan, stream, AdamArgs{p, g, m, v, p_bf16, p_f16, n, lr, beta1, beta2, eps, weight_decay, 0, grad_scale_dev, step_state_dev,
+                                            guard, nullptr, nullptr, nullptr, 0});
+}
+
+extern "C" int mmdti_adam_step_masked(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                      const float* grad_scale_dev, const float* step_state_dev, void* p_f16, const float* guard,
+                                      const unsigned char* skip) {
+  StreamPlan plan;
+  if (int e = adam_step_masked_prepare(plan, p, g, m, v, n, step, step_state_dev, guard, skip)) return e;
+  return adam_launch(plan, stream, AdamArgs{p, g, m, v, p_bf16, p_f16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale_dev, step_state_dev,
+                                            guard, skip, nullptr, nullptr, 0});
+}
+
+extern "C" int mmdti_adam_step_grouped(mmdti_stream_t stream, float* p, const float* g, float* m, float* v, void* p_bf16, long long n,
+                                       float lr, float beta1, float beta2, float eps, int step, const float* grad_scale_dev,
+                                       const float* step_state_dev, void* p_f16, const float* guard, const unsigned char* skip,
+                                       const unsigned char* group, const float* table_dev, int ngroups, int decoupled) {
+  StreamPlan plan;
+  if (int e = adam_step_grouped_prepare(plan, p, g, m, v, p_bf16, n, step, step_state_dev, p_f16, guard, skip, group, table_dev, ngroups, decoupled))
+    return e;
+  return adam_launch(plan, stream, AdamArgs{p, g, m, v, p_bf16, p_f16, n, lr, beta1, beta2, eps, 0.f, step, grad_scale_dev, step_state_dev, guard, skip,
+                                            group, table_dev, ngroups});
 }
 
 extern "C" int mmdti_adam_bias_table(float beta1, float beta2, int steps, float* table_host) {
@@ -1252,36 +1358,93 @@ extern "C" int mmdti_adam_bias_table(float beta1, float beta2, int steps, float*
   return MMDTI_OK;
 }
 
-extern "C" int mmdti_ema_update(mmdti_stream_t stream, const float* p, float* ema, long long n, float decay, int warmup, int step,
-                                const float* guard, const float* step_state) {
+static int ema_update_prepare(StreamPlan& plan, const float* p, const float* ema, long long n, float decay, int step, const float* guard,
+                              const float* step_state) {
   MMDTI_REQUIRE(p && ema && p != ema, "ema_update: p and ema are two non-null buffers");
   MMDTI_REQUIRE(n >= 0, "ema_update: negative n");
   MMDTI_REQUIRE(decay > 0.f && decay < 1.f, "ema_update: decay must lie in (0, 1)");
   MMDTI_REQUIRE(guard || step_state || step >= 1, "ema_update: no source of t (guard, step state or step >= 1)");
   MMDTI_REQUIRE(aligned16(p) && aligned16(ema), "ema_update: 16-byte alignment required");
-  if (n == 0) return MMDTI_OK;
-  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, ema, n, decay, warmup, (float)step,
-                     guard, step_state);
+  plan = ema_plan(false, n);
+  return MMDTI_OK;
+}
+static int ema_swap_prepare(StreamPlan& plan, const float* p, const float* ema, const void* p_bf16, const void* p_f16, long long n) {
+  MMDTI_REQUIRE(p && ema && p != ema && p_bf16, "ema_swap: p, ema (two buffers) and p_bf16 must be given");
+  MMDTI_REQUIRE(n >= 0, "ema_swap: negative n");
+  MMDTI_REQUIRE(aligned16(p) && aligned16(ema) && aligned16(p_bf16) && aligned16(p_f16), "ema_swap: 16-byte alignment required");
+  plan = ema_plan(true, n);
+  return MMDTI_OK;
+}
+static int step_state_advance_prepare(StreamPlan& plan, const float* state, const unsigned long long* salt, int warmup_steps, int total_steps) {
+  MMDTI_REQUIRE(state && salt, "step_state_advance: null pointer");
+  MMDTI_REQUIRE(total_steps > 0 && warmup_steps >= 0, "step_state_advance: bad schedule");
+  plan = step_state_plan();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_ema_update(mmdti_stream_t stream, const float* p, float* ema, long long n, float decay, int warmup, int step,
+                                const float* guard, const float* step_state) {
+  StreamPlan plan;
+  if (int e = ema_update_prepare(plan, p, ema, n, decay, step, guard, step_state)) return e;
+  if (plan.nlaunch == 0) return MMDTI_OK;
+  launch_row(ema_update_kernel, STREAM_ROW(plan, 0), p, ema, n, decay, warmup, (float)step, guard, step_state);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_ema_swap(mmdti_stream_t stream, float* p, float* ema, void* p_bf16, void* p_f16, long long n) {
-  MMDTI_REQUIRE(p && ema && p != ema && p_bf16, "ema_swap: p, ema (two buffers) and p_bf16 must be given");
-  MMDTI_REQUIRE(n >= 0, "ema_swap: negative n");
-  MMDTI_REQUIRE(aligned16(p) && aligned16(ema) && aligned16(p_bf16) && aligned16(p_f16), "ema_swap: 16-byte alignment required");
-  if (n == 0) return MMDTI_OK;
-  hipLaunchKernelGGL(ema_swap_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, p, ema, (bf16_t*)p_bf16, (bf16_t*)p_f16, n);
+  StreamPlan plan;
+  if (int e = ema_swap_prepare(plan, p, ema, p_bf16, p_f16, n)) return e;
+  if (plan.nlaunch == 0) return MMDTI_OK;
+  launch_row(ema_swap_kernel, STREAM_ROW(plan, 0), p, ema, (bf16_t*)p_bf16, (bf16_t*)p_f16, n);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
 
 extern "C" int mmdti_step_state_advance(mmdti_stream_t stream, float* state, unsigned long long* salt, float base_lr, int warmup_steps,
                                         int total_steps, float beta1, float beta2) {
-  MMDTI_REQUIRE(state && salt, "step_state_advance: null pointer");
-  MMDTI_REQUIRE(total_steps > 0 && warmup_steps >= 0, "step_state_advance: bad schedule");
-  hipLaunchKernelGGL(step_state_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, salt, base_lr, warmup_steps, total_steps, beta1, beta2);
+  StreamPlan plan;
+  if (int e = step_state_advance_prepare(plan, state, salt, warmup_steps, total_steps)) return e;
+  launch_row(step_state_advance_kernel, STREAM_ROW(plan, 0), state, salt, base_lr, warmup_steps, total_steps, beta1, beta2);
   MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+// The plan a stream, reduction or optimizer entry would launch, without launching (include/mmdti_hip.h documents the entries, what
+// each reads of ptrs, n, a, b, c and f, and plan_out)
+extern "C" int mmdti_stream_plan(int entry, int deterministic, const void* const* ptrs, long long n, int a, int b, int c, float f,
+                                 long long* plan_out) {
+  MMDTI_REQUIRE(plan_out != nullptr && ptrs != nullptr, "stream_plan: null plan_out or ptrs");
+  auto F = [&](int i) { return static_cast<const float*>(ptrs[i]); };
+  auto U8 = [&](int i) { return static_cast<const unsigned char*>(ptrs[i]); };
+  const bool det = deterministic != 0;
+  StreamPlan plan;
+  int e;
+  switch (entry) {
+    case MMDTI_STREAM_CAST_F32_BF16: e = cast_f32_bf16_prepare(plan, F(0), ptrs[1], n, f); break;
+    case MMDTI_STREAM_CAST_F32_F16: e = cast_f32_f16_prepare(plan, F(0), ptrs[1], n, f); break;
+    case MMDTI_STREAM_CAST_F16_BF16: e = cast_f16_bf16_prepare(plan, ptrs[0], a, b, c, ptrs[1]); break;
+    case MMDTI_STREAM_CAST_BF16_F32: e = cast_bf16_f32_prepare(plan, ptrs[0], F(1), n); break;
+    case MMDTI_STREAM_DROPOUT_F32: e = dropout_f32_prepare(plan, F(0), F(1), n, f); break;
+    case MMDTI_STREAM_AXPY_F32: e = axpy_f32_prepare(plan, F(0), F(1), n); break;
+    case MMDTI_STREAM_GELU_FWD_BF16: e = gelu_fwd_bf16_prepare(plan, ptrs[0], ptrs[1], n); break;
+    case MMDTI_STREAM_COLSUM_BF16: e = colsum_bf16_prepare(plan, det, ptrs[0], a, b, c, F(1)); break;
+    case MMDTI_STREAM_SUMSQ_F32: e = sumsq_f32_prepare(plan, det, F(0), n, F(1), F(2), a); break;
+    case MMDTI_STREAM_SUMSQ_CHECK_F32: e = sumsq_check_f32_prepare(plan, F(0), n, F(1), F(2), a, F(3), b); break;
+    case MMDTI_STREAM_ADAM_STEP: e = adam_step_prepare(plan, F(0), F(1), F(2), F(3), n, a, F(4)); break;
+    case MMDTI_STREAM_ADAM_STEP_GUARDED: e = adam_step_guarded_prepare(plan, F(0), F(1), F(2), F(3), n, F(4)); break;
+    case MMDTI_STREAM_ADAM_STEP_MASKED: e = adam_step_masked_prepare(plan, F(0), F(1), F(2), F(3), n, a, F(4), F(5), U8(6)); break;
+    case MMDTI_STREAM_ADAM_STEP_GROUPED:
+      e = adam_step_grouped_prepare(plan, F(0), F(1), F(2), F(3), ptrs[4], n, a, F(6), ptrs[5], F(7), U8(8), U8(9), F(10), b, c);
+      break;
+    case MMDTI_STREAM_EMA_UPDATE: e = ema_update_prepare(plan, F(0), F(1), n, f, a, F(2), F(3)); break;
+    case MMDTI_STREAM_EMA_SWAP: e = ema_swap_prepare(plan, F(0), F(1), ptrs[2], ptrs[3], n); break;
+    case MMDTI_STREAM_STEP_STATE_ADVANCE: e = step_state_advance_prepare(plan, F(0), static_cast<const unsigned long long*>(ptrs[1]), a, b); break;
+    default: MMDTI_REQUIRE(false, "stream_plan: unknown entry %d", entry);
+  }
+  if (e) return e;
+  static_assert(STREAM_PLAN_INTS == 12, "mmdti_hip.h documents 12 long long");
+  memcpy(plan_out, &plan, sizeof(plan));
   return MMDTI_OK;
 }
 

@@ -75,7 +75,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 
 // Backward.  Each block handles ROWS_PER_BLOCK rows (4 waves x 8 rows); dgamma/dbeta partials are kept per lane in
 // registers over the wave's rows, combined across the 4 waves in LDS and added to global with one atomic per column.
-constexpr int LN_BWD_MIN_ROWS_PER_WAVE = 4;
 
 // SLAB (the deterministic mode): the workgroup's three [D] partials go to its own slot of `slab` ([workgroups][3][D], plain stores)
 // and det_fold_kernel, queued directly behind, adds the slots in workgroup order into dgamma / dbeta / dx_colsum -- no atomics.
@@ -257,28 +256,57 @@ __global__ __launch_bounds__(256) void ln_bwd_slab_kernel(LN_BWD_PARAMS, float* 
 MMDTI_DEFINE_SALT_PULL(layernorm)
 using namespace mmdti;
 
-extern "C" int mmdti_layernorm_fwd(mmdti_stream_t stream, const float* x, const float* gamma, const float* beta,
-                                   float eps, int rows, int D, float* y_f32, void* y_bf16, float* mean, float* rstd,
-                                   const unsigned char* row_zero, float drop_p, unsigned long long seed,
-                                   unsigned int site, int y16_f16) {
+namespace mmdti {
+
+// ---- rows 0..19 of the MMDTI_PLAN_ROW table, indexed by ln_fwd_key / ln_bwd_key (row_plan.h) ----
+#define LN_BWD_ROWS(slab, kernel, nv)                                                        \
+  KROW(ln_bwd_key(slab, nv, 0), kernel<nv, false>), KROW(ln_bwd_key(slab, nv, 1), kernel<nv, true>)
+static KernelRow g_ln_kernels[ROW_LN_KERNELS] = {
+    KROW(ln_fwd_key(1), ln_fwd_kernel<1>), KROW(ln_fwd_key(2), ln_fwd_kernel<2>), KROW(ln_fwd_key(4), ln_fwd_kernel<4>), KROW(ln_fwd_key(8), ln_fwd_kernel<8>),
+    LN_BWD_ROWS(0, ln_bwd_kernel, 1), LN_BWD_ROWS(0, ln_bwd_kernel, 2), LN_BWD_ROWS(0, ln_bwd_kernel, 4), LN_BWD_ROWS(0, ln_bwd_kernel, 8),
+    LN_BWD_ROWS(1, ln_bwd_slab_kernel, 1), LN_BWD_ROWS(1, ln_bwd_slab_kernel, 2), LN_BWD_ROWS(1, ln_bwd_slab_kernel, 4), LN_BWD_ROWS(1, ln_bwd_slab_kernel, 8),
+};
+#undef LN_BWD_ROWS
+const KernelRow* ln_kernel_table(int* n) { *n = ROW_LN_KERNELS; return g_ln_kernels; }
+
+// What the launches and mmdti_row_plan share: validate, plan.  Pointers are tested for null and alignment only.
+int ln_fwd_prepare(RowPlan& plan, const float* x, const float* gamma, const float* beta, int rows, int D, const float* y_f32,
+                   const void* y_bf16, float drop_p) {
   MMDTI_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "layernorm_fwd: need rows>0, D%%4==0, D<=2048 (D=%d)", D);
   MMDTI_REQUIRE(x && gamma && beta && (y_f32 || y_bf16), "layernorm_fwd: null pointer");
   MMDTI_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta), "layernorm_fwd: 16-byte alignment required");
   MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "layernorm_fwd: dropout p out of range");
+  plan = ln_fwd_plan(rows, D);
+  return MMDTI_OK;
+}
+
+// det: the mode the launch finds (det_table().on()); the stream's workspace is looked up by the launch alone
+int ln_bwd_prepare(RowPlan& plan, bool det, const void* dy, int dy_dtype, const float* x, const float* gamma, const float* mean,
+                   const float* rstd, int rows, int D, const float* dx, const float* dgamma, const float* dbeta, float drop_p,
+                   const void* dx_bf16, float drop2_p, const float* dx_colsum) {
+  MMDTI_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "layernorm_bwd: need rows>0, D%%4==0, D<=2048 (D=%d)", D);
+  MMDTI_REQUIRE(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
+  MMDTI_REQUIRE(dy_dtype == MMDTI_DT_F32 || dy_dtype == MMDTI_DT_BF16, "layernorm_bwd: bad dy dtype");
+  MMDTI_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(dx) && aligned16(dy), "layernorm_bwd: alignment");
+  MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f && drop2_p >= 0.f && drop2_p < 1.f, "layernorm_bwd: dropout p out of range");
+  MMDTI_REQUIRE(!dx_bf16 || (reinterpret_cast<uintptr_t>(dx_bf16) & 7) == 0, "layernorm_bwd: dx_bf16 alignment");
+  MMDTI_REQUIRE(!dx_colsum || dx_bf16, "layernorm_bwd: dx_colsum sums the bf16 copy, which was not requested");
+  plan = ln_bwd_plan(rows, D, dy_dtype == MMDTI_DT_BF16, det && (dgamma || dbeta || dx_colsum));
+  return MMDTI_OK;
+}
+
+}  // namespace mmdti
+
+extern "C" int mmdti_layernorm_fwd(mmdti_stream_t stream, const float* x, const float* gamma, const float* beta,
+                                   float eps, int rows, int D, float* y_f32, void* y_bf16, float* mean, float* rstd,
+                                   const unsigned char* row_zero, float drop_p, unsigned long long seed,
+                                   unsigned int site, int y16_f16) {
+  RowPlan plan;
+  if (int e = ln_fwd_prepare(plan, x, gamma, beta, rows, D, y_f32, y_bf16, drop_p)) return e;
   const uint32_t th = dropout_thresh(drop_p);
   const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  dim3 grid(cdiv(rows, 4)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define LN_F(NV)                                                                                                    \
-  hipLaunchKernelGGL((ln_fwd_kernel<NV>), grid, block, 0, s, x, gamma, beta, eps, rows, D, y_f32, (bf16_t*)y_bf16, \
-                     mean, rstd, row_zero, th, sc, (uint64_t)seed, (uint32_t)site, y16_f16)
-  switch (ln_nv(D)) {
-    case 1: LN_F(1); break;
-    case 2: LN_F(2); break;
-    case 3: case 4: LN_F(4); break;
-    default: LN_F(8); break;
-  }
-#undef LN_F
+  launch_row(ln_fwd_kernel<1>, g_ln_kernels[plan.k[0].key], plan.k[0], (hipStream_t)stream, x, gamma, beta, eps, rows, D, y_f32, (bf16_t*)y_bf16, mean, rstd,
+             row_zero, th, sc, (uint64_t)seed, (uint32_t)site, y16_f16);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }
@@ -288,54 +316,28 @@ extern "C" int mmdti_layernorm_bwd(mmdti_stream_t stream, const void* dy, int dy
                                    const float* dres, float* dx, float* dgamma, float* dbeta,
                                    const unsigned char* row_zero, float drop_p, unsigned long long seed,
                                    unsigned int site, void* dx_bf16, float drop2_p, unsigned int site2, float* dx_colsum) {
-  MMDTI_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048, "layernorm_bwd: need rows>0, D%%4==0, D<=2048 (D=%d)", D);
-  MMDTI_REQUIRE(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
-  MMDTI_REQUIRE(dy_dtype == MMDTI_DT_F32 || dy_dtype == MMDTI_DT_BF16, "layernorm_bwd: bad dy dtype");
-  MMDTI_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(dx) && aligned16(dy), "layernorm_bwd: alignment");
-  MMDTI_REQUIRE(drop_p >= 0.f && drop_p < 1.f && drop2_p >= 0.f && drop2_p < 1.f, "layernorm_bwd: dropout p out of range");
-  MMDTI_REQUIRE(!dx_bf16 || (reinterpret_cast<uintptr_t>(dx_bf16) & 7) == 0, "layernorm_bwd: dx_bf16 alignment");
+  RowPlan plan;
+  if (int e = ln_bwd_prepare(plan, det_table().on(), dy, dy_dtype, x, gamma, mean, rstd, rows, D, dx, dgamma, dbeta, drop_p, dx_bf16, drop2_p,
+                             dx_colsum))
+    return e;
   const uint32_t th = dropout_thresh(drop_p);
   const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
   const uint32_t th2 = dropout_thresh(drop2_p);
   const float sc2 = drop2_p > 0.f ? 1.f / (1.f - drop2_p) : 1.f;
-  // rows per wave: enough that the whole grid is resident at once (3 workgroups of 4 waves per CU at this kernel's
-  // register count, 2 for the wide-row variants) -- no second, partly filled round, and fewer dgamma / dbeta atomics
-  const int rpw = ln_bwd_rows_per_wave(rows, D);
-  static_assert(LN_BWD_MIN_ROWS_PER_WAVE == 4, "det.h states the same floor");
-  dim3 grid(ln_bwd_grid(rows, D)), block(256);
-  MMDTI_REQUIRE(!dx_colsum || dx_bf16, "layernorm_bwd: dx_colsum sums the bf16 copy, which was not requested");
-  const size_t smem = 12 * (size_t)D * sizeof(float);
+  const int rpw = (int)plan.rpw;
   hipStream_t s = (hipStream_t)stream;
-  if (det_table().on() && (dgamma || dbeta || dx_colsum)) {
+  if (plan.nlaunch == 2) {
     // the deterministic mode: per-workgroup slabs in the stream's workspace, folded in workgroup order (never atomics)
     float* slab = nullptr;
     if (int e = det_workspace(stream, det_workspace_bytes(MMDTI_DET_LAYERNORM_BWD, rows, D), "layernorm_bwd", &slab)) return e;
-#define LN_S(NV, BF)                                                                                                        \
-  hipLaunchKernelGGL((ln_bwd_slab_kernel<NV, BF>), grid, block, smem, s, dy, dy_add, x, gamma, mean, rstd, rows, D, dres, dx,   \
-                     dgamma, dbeta, row_zero, th, sc, (uint64_t)seed, (uint32_t)site, (bf16_t*)dx_bf16, th2, sc2, (uint32_t)site2, dx_colsum, rpw, slab)
-    const bool bf16 = dy_dtype == MMDTI_DT_BF16;
-    switch (ln_nv(D)) {
-      case 1: if (bf16) LN_S(1, true); else LN_S(1, false); break;
-      case 2: if (bf16) LN_S(2, true); else LN_S(2, false); break;
-      case 3: case 4: if (bf16) LN_S(4, true); else LN_S(4, false); break;
-      default: if (bf16) LN_S(8, true); else LN_S(8, false); break;
-    }
-#undef LN_S
-    det_fold<3>(s, slab, (int)grid.x, 3ll * D, D, DetDst<3>{{dgamma, dbeta, dx_colsum}});
+    launch_row(ln_bwd_slab_kernel<1, false>, g_ln_kernels[plan.k[0].key], plan.k[0], s, dy, dy_add, x, gamma, mean, rstd, rows, D, dres, dx, dgamma, dbeta, row_zero,
+               th, sc, (uint64_t)seed, (uint32_t)site, (bf16_t*)dx_bf16, th2, sc2, (uint32_t)site2, dx_colsum, rpw, slab);
+    det_fold<3>(s, slab, (int)plan.k[0].gx, 3ll * D, D, DetDst<3>{{dgamma, dbeta, dx_colsum}});
     MMDTI_LAUNCH_CHECK();
     return MMDTI_OK;
   }
-#define LN_B(NV, BF)                                                                                               \
-  hipLaunchKernelGGL((ln_bwd_kernel<NV, BF>), grid, block, smem, s, dy, dy_add, x, gamma, mean, rstd, rows, D, dres, dx,  \
-                     dgamma, dbeta, row_zero, th, sc, (uint64_t)seed, (uint32_t)site, (bf16_t*)dx_bf16, th2, sc2, (uint32_t)site2, dx_colsum, rpw)
-  const bool bf = dy_dtype == MMDTI_DT_BF16;
-  switch (ln_nv(D)) {
-    case 1: if (bf) LN_B(1, true); else LN_B(1, false); break;
-    case 2: if (bf) LN_B(2, true); else LN_B(2, false); break;
-    case 3: case 4: if (bf) LN_B(4, true); else LN_B(4, false); break;
-    default: if (bf) LN_B(8, true); else LN_B(8, false); break;
-  }
-#undef LN_B
+  launch_row(ln_bwd_kernel<1, false>, g_ln_kernels[plan.k[0].key], plan.k[0], s, dy, dy_add, x, gamma, mean, rstd, rows, D, dres, dx, dgamma, dbeta, row_zero, th, sc,
+             (uint64_t)seed, (uint32_t)site, (bf16_t*)dx_bf16, th2, sc2, (uint32_t)site2, dx_colsum, rpw);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

@@ -84,6 +84,23 @@ def rounds(c):
     return -(-items // (g * per))
 
 
+def library_plan(lib, c):
+    """mmdti_stream_plan's answer for mmdti_adam_step_grouped with the addresses the case gives (stream_cases.stream_plan)"""
+    on = lambda x: S.PTR if x else 0
+    ptrs = [S.PTR] * 4 + [on("bf16" in c["shadows"]), on("f16" in c["shadows"]), on(c["state"]), on(c["guard"]), on(c["mask"]), S.PTR, S.PTR]
+    return S.stream_plan(lib, "adam_step_grouped", ptrs, c["n"], a=7 if c["state"] or c["guard"] else 1, b=len(table_of(c)), c=int(c["decoupled"]))
+
+
+def declared_plan(c):
+    return dict(launches=S.flat(instance(c)[0], launch(c)[0]), wgs=0)
+
+
+def assert_declared_plan(lib, c):
+    got, want = library_plan(lib, c), declared_plan(c)
+    assert got == want, (case_id(c), got, want)
+    return got
+
+
 def table_of(c):
     return ((1.0, c["wd1"]),) if c["layout"] == "one" else TABLE4
 

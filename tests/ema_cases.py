@@ -26,6 +26,44 @@ NF_T, NF_SKIPPED, NF_FLAG = 0, 1, 2
 SENT32 = -7.0e-33                       # guard value round every device buffer of the instance tests (no input takes it)
 
 
+ALL_KERNELS = ("ema_update_kernel", "ema_swap_kernel")
+CAP = 4096
+
+
+def grid_for(n, per):
+    return max(1, min(CAP, -(-n // per)))
+
+
+def instance(swap):
+    return ALL_KERNELS[int(bool(swap))]
+
+
+def launch(swap, n):
+    """(workgroups, elements per workgroup and round): the update takes one 16-byte vector per thread, the swap one block of 8"""
+    per = 256 * 8 if swap else 256 * 4
+    return grid_for(n, per), per
+
+
+def library_plan(lib, swap, n, source="value", with_f16=True):
+    """mmdti_stream_plan's answer for mmdti_ema_update (t from `source`) or mmdti_ema_swap (stream_cases.stream_plan)"""
+    import stream_cases as S
+    if swap:
+        return S.stream_plan(lib, "ema_swap", [S.PTR, S.PTR + 0x1000, S.PTR, S.PTR if with_f16 else 0], n)
+    ptrs = [S.PTR, S.PTR + 0x1000, S.PTR if source == "guard" else 0, S.PTR if source in ("guard", "state") else 0]
+    return S.stream_plan(lib, "ema_update", ptrs, n, a=1 if source == "value" else 7, f=0.9)
+
+
+def declared_plan(swap, n):
+    """one launch; none for an empty arena"""
+    return dict(launches=[(instance(swap), launch(swap, n)[0], 1, 256, 0)] if n else [], wgs=0)
+
+
+def assert_declared_plan(lib, swap, n, **kw):
+    got, want = library_plan(lib, swap, n, **kw), declared_plan(swap, n)
+    assert got == want, (swap, n, kw, got, want)
+    return got
+
+
 def update_cases():
     """one row per launch: every size x decay x warm-up x t x source of t"""
     return [dict(n=n, decay=d, warmup=w, t=t, source=s) for n in SIZES for s in SOURCES for d in DECAYS for w in WARMUPS for t in STEPS]

@@ -4,7 +4,8 @@ the exact modes are exact, that the fp32 emulation stays inside the bounds and t
 test_row_instances_gpu.py (which holds the kernels of csrc/layernorm.hip and the softmax kernels of csrc/elementwise.hip to the
 reference on the device).  Dropout masks come from dropout_rule.py, never from a kernel's output.
 
-INSTANCES (instance(c), an independent statement of the two launchers' dispatch; SOURCE_LINES keeps their lines verbatim):
+INSTANCES (instance(c) and launch(c): an independent statement of the launchers' dispatch and geometry, held against the library's own
+answer, mmdti_row_plan, by assert_declared_plan; SOURCE_LINES keeps the rounding points verbatim):
 ln_fwd_kernel<NV> NV in 1, 2, 4, 8; ln_bwd_kernel<NV, DY_BF16> and ln_bwd_slab_kernel<NV, DY_BF16> (16); softmax_fwd_kernel<NV> and
 softmax_bwd_kernel<NV>, NV in 1, 2, 4: 26.  det_fold_kernel runs behind every slab case and is held through dgamma, dbeta and colsum.
     LayerNorm  nv = ceil(D / 256), 3 -> 4, 5..7 -> 8;   softmax  nv = ceil(ld / 256), 3 -> 4
@@ -69,15 +70,6 @@ FMIN = float(torch.finfo(F32).min)
 
 SOURCE_LINES = {
     "layernorm.hip": (
-        "switch (ln_nv(D)) {",
-        "case 3: case 4: LN_F(4); break;",
-        "default: LN_F(8); break;",
-        "case 3: case 4: if (bf) LN_B(4, true); else LN_B(4, false); break;",
-        "default: if (bf) LN_B(8, true); else LN_B(8, false); break;",
-        "case 3: case 4: if (bf16) LN_S(4, true); else LN_S(4, false); break;",
-        "if (det_table().on() && (dgamma || dbeta || dx_colsum)) {",
-        "const int rpw = ln_bwd_rows_per_wave(rows, D);",
-        "dim3 grid(ln_bwd_grid(rows, D)), block(256);",
         "const float mean = wave_sum(s) / (float)D;",
         "const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);",
         "const float sc = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;",
@@ -89,15 +81,7 @@ SOURCE_LINES = {
         "if (dx_colsum) {   // sums the ROUNDED values: exactly what a column-sum pass over dx_bf16 would add up",
         "if (cur.zero) d[0] = d[1] = d[2] = d[3] = 0.f;",
     ),
-    "det.h": (
-        "static inline int ln_nv(int D) { return (D / 4 + 63) / 64; }",
-        "const int min_rpw = 4, r = det_cdiv(rows, 4 * (ln_nv(D) <= 2 ? 3 : 2) * 256);",
-        "static inline int ln_bwd_grid(int rows, int D) { return det_cdiv(rows, 4 * ln_bwd_rows_per_wave(rows, D)); }",
-    ),
     "elementwise.hip": (
-        "const int nv = (ld + 255) / 256;",
-        "if (nv <= 1) SM_F(1); else if (nv <= 2) SM_F(2); else SM_F(4);",
-        "if (nv <= 1) SM_B(1); else if (nv <= 2) SM_B(2); else SM_B(4);",
         "v[c][e] = (j + e < Lk) ? tv[e] + (ka ? ka[j + e] : 0.f) : -INFINITY;",
         "v[c][e] = __expf(v[c][e] - m);   // exp(-inf) = 0 in the pad columns",
         "const float inv = 1.0f / wave_sum(sum);",
@@ -188,6 +172,78 @@ def instance(c):
 
 ALL_INSTANCES = ([f"ln_fwd_kernel<{n}>" for n in (1, 2, 4, 8)] + [f"ln_bwd{s}_kernel<{n}, {b}>" for s in ("", "_slab") for n in (1, 2, 4, 8) for b in ("false", "true")]
                  + [f"softmax_{d}_kernel<{n}>" for d in ("fwd", "bwd") for n in (1, 2, 4)])
+
+def launch(c, det=None):
+    """the launches of the case: [(kernel, grid x, grid y, workgroup size, dynamic LDS bytes)] -- one wave per row, four rows per workgroup;
+    the LayerNorm backward keeps [3][4 waves][D] floats in LDS and, in its slab form, is followed by the fold over D columns x 3 sums"""
+    k = c["kind"]
+    if k == "ln_fwd":
+        return [(instance(c), -(-c["rows"] // 4), 1, 256, 0)]
+    if k == "ln_bwd":
+        name = instance(dict(c, det=c["det"] if det is None else det))
+        first = [(name, ln_grid(c["rows"], c["D"]), 1, 256, 12 * c["D"] * 4)]
+        return first + ([("det_fold_kernel", -(-c["D"] // 64), 3, 1024, 0)] if "_slab_" in name else [])
+    return [(instance(c), -(-sm_rows(c) // 4), 1, 256, 0)]
+
+
+# ------------------------------------------------------------------------------------------------ the library's answer (mmdti_row_plan)
+PLAN_FAMILY = 6                      # MMDTI_PLAN_ROW
+ENTRY = {"ln_fwd": 0, "ln_bwd": 1, "sm_fwd": 2, "sm_bwd": 3}
+PTR = 0x7F0000001000                 # an address with every alignment; the queries test pointers for null and alignment only
+
+
+def kernel_name(lib, family, row):
+    return "det_fold_kernel" if row == -1 else lib.mmdti_plan_kernel_name(family, row).decode()
+
+
+def read_plan(lib, family, words, derived):
+    """the queries' word array -> dict(launches=[(kernel, grid x, grid y, workgroup size, LDS bytes)], **derived numbers)"""
+    v = list(words)
+    n = v[0]
+    assert all(x == 0 for x in v[1 + 5 * n:11]), v                      # the launches a plan does not make are zero
+    launches = [(kernel_name(lib, family, v[1 + 5 * i]),) + tuple(v[2 + 5 * i:6 + 5 * i]) for i in range(n)]
+    return dict(launches=launches, **dict(zip(derived, v[11:])))
+
+
+def row_plan(lib, kind, ptrs, rows_or_B, heads, Lq, Lk, D_or_ld, det=False, dybf=False, p=0.0, p2=0.0):
+    """one call of mmdti_row_plan: ptrs in the entry's order (include/mmdti_hip.h)"""
+    import ctypes
+    out = (ctypes.c_longlong * 13)()
+    arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+    lib.mmdti_row_plan(ENTRY[kind], int(det), arr, rows_or_B, heads, Lq, Lk, D_or_ld, 1 if dybf else 0, p, p2, out)
+    return read_plan(lib, PLAN_FAMILY, out, ("nv", "rpw"))
+
+
+def case_ptrs(c):
+    """the addresses the case hands to its entry point, null where the case gives none"""
+    on = lambda x: PTR if x else 0
+    if c["kind"] == "ln_fwd":
+        return [PTR, PTR, PTR, on(c["outs"] in ("both", "y32")), on(c["outs"] in ("both", "y16"))]
+    if c["kind"] == "ln_bwd":
+        copy = c["copy"]
+        return [PTR] * 6 + [on(not c["nullg"]), on(not c["nullg"]), on(copy is not None), on(copy is not None and copy[1])]
+    return [PTR, PTR, PTR + 0x1000]
+
+
+def library_plan(lib, c, det=None):
+    k = c["kind"]
+    if k.startswith("ln"):
+        p2 = c["copy"][0] if k == "ln_bwd" and c["copy"] is not None else 0.0
+        return row_plan(lib, k, case_ptrs(c), c["rows"], 0, 0, 0, c["D"], det=c.get("det", False) if det is None else det, dybf=c.get("dybf", False), p=c["p"], p2=p2)
+    return row_plan(lib, k, case_ptrs(c), c["B"], c["heads"], c["Lq"], c["Lk"], c["ld"], p=c["p"])
+
+
+def declared_plan(c, det=None):
+    """what the case is declared to launch, from instance() and launch(): every field of the library's plan"""
+    k = c["kind"]
+    return dict(launches=launch(c, det), nv=sm_nv(c["ld"]) if k.startswith("sm") else ln_nv(c["D"]), rpw=ln_rpw(c["rows"], c["D"]) if k == "ln_bwd" else 0)
+
+
+def assert_declared_plan(lib, c):
+    got, want = library_plan(lib, c), declared_plan(c)
+    assert got == want, (case_id(c), got, want)
+    return got
+
 
 # ------------------------------------------------------------------------------------------------ the table
 CASES = []

@@ -36,7 +36,7 @@ import torch
 import dropout_rule as DR
 from attn_cases import Z_MAX, gain  # noqa: F401
 from gemm_cases import F64, GELU_G_MEASURED, SENT16, SENT32, gelu64, worst_ratio  # noqa: F401
-from row_cases import Bufs, round16, ulp16  # noqa: F401
+from row_cases import PTR, Bufs, read_plan, round16, ulp16  # noqa: F401
 
 BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 U = 2.0 ** -24
@@ -50,19 +50,6 @@ SUMSQ_WGS = 2048
 NF_T, NF_SKIPPED, NF_FLAG, NF_BC1, NF_BC2 = range(5)
 
 SOURCE_LINES = (
-    "if (b > 256 * 16) b = 256 * 16;",
-    "hipLaunchKernelGGL(cast_f32_bf16_kernel<false>, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, x,",
-    "hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, x,",
-    "hipLaunchKernelGGL(cast_f16_bf16_kernel, dim3(grid_for(n8, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x_f16, cols / 8, ldx,",
-    "hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,",
-    "hipLaunchKernelGGL(dropout_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, th, sc,",
-    "hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, a);",
-    "hipLaunchKernelGGL(gelu_bf16_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,",
-    "hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,",
-    "hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, g, n, out);",
-    "const int wgs = (int)min((long long)min(ws_floats, SUMSQ_WGS), (n / 4 + 255) / 256 + 1);",
-    "const int wgs = (int)min((long long)min(ws_floats / 2, SUMSQ_WGS), (n / 4 + 255) / 256 + 1);",
-    "constexpr int SUMSQ_WGS = 2048;",
     "if (thresh) o = dropout_keep(seed, site, (uint64_t)i, thresh) ? o * dscale : 0.f;",
     "Rand4 r = philox4(seed, site, (uint64_t)i);",
     "y[i] = f2bf(gelu_erf(bf2f(u[i])));",
@@ -84,7 +71,7 @@ SOURCE_LINES = (
     "st[1] = base_lr * lam;",
     "unsigned long long x = *salt + 0x9E3779B97F4A7C15ull;       // splitmix64: a fresh, well-mixed word per step",
 )
-DET_LINES = ("const int gy = det_cdiv(rows, 8 * 8);", "return gy > 1024 ? 1024 : gy;")
+PLAN_LINES = ("constexpr int SUMSQ_WGS = 2048;",)           # (csrc/stream_plan.h: the constant this file restates)
 
 ALL_KERNELS = ("cast_f32_bf16_kernel<false>", "cast_f32_bf16_kernel<true>", "cast_f16_bf16_kernel", "cast_bf16_f32_kernel", "dropout_f32_kernel", "axpy_kernel",
                "gelu_bf16_kernel", "colsum_bf16_kernel", "colsum_bf16_slab_kernel", "sumsq_kernel", "sumsq_part_kernel<false>", "sumsq_fold_kernel<false>",
@@ -212,6 +199,83 @@ def colsum_gy(rows):
 def colsum_depth(rows):
     gy = colsum_gy(rows)
     return -(-rows // (gy * 8)) + 8 + gy
+
+
+# ------------------------------------------------------------------------------------------------ the library's answer (mmdti_stream_plan)
+PLAN_FAMILY = 7                      # MMDTI_PLAN_STREAM
+ENTRY = {name: i for i, name in enumerate(("cast_f32_bf16", "cast_f32_f16", "cast_f16_bf16", "cast_bf16_f32", "dropout_f32", "axpy_f32", "gelu_fwd_bf16", "colsum_bf16",
+                                           "sumsq_f32", "sumsq_check_f32", "adam_step", "adam_step_guarded", "adam_step_masked", "adam_step_grouped", "ema_update",
+                                           "ema_swap", "step_state_advance"))}
+FLAT_ENTRY = {"cast_b32": "cast_bf16_f32", "dropout": "dropout_f32", "axpy": "axpy_f32", "gelu": "gelu_fwd_bf16"}
+
+
+def stream_plan(lib, entry, ptrs, n=0, a=0, b=0, c=0, f=0.0, det=False):
+    """one call of mmdti_stream_plan: ptrs in the entry's order (include/mmdti_hip.h) -> dict(launches, wgs)"""
+    import ctypes
+    out = (ctypes.c_longlong * 12)()
+    lib.mmdti_stream_plan(ENTRY[entry], int(det), (ctypes.c_void_p * len(ptrs))(*ptrs), n, a, b, c, f, out)
+    return read_plan(lib, PLAN_FAMILY, out, ("wgs",))
+
+
+def flat(name, grid):
+    return [(name, grid, 1, 256, 0)]
+
+
+def adam_entry(c):
+    """(entry, ptrs): the entry point the case goes through and the addresses it gives -- p, g, m, v, then the entry's optional ones"""
+    on = lambda x: PTR if x else 0
+    if c["mask"]:
+        return "adam_step_masked", [PTR] * 4 + [on(c["state"]), on(c["guard"]), PTR]
+    if c["guard"]:
+        return "adam_step_guarded", [PTR] * 5
+    return "adam_step", [PTR] * 4 + [on(c["state"])]
+
+
+def library_plan(lib, c, det=None):
+    k = c["kind"]
+    det = c.get("det", False) if det is None else det
+    if k == "cast":
+        return stream_plan(lib, "cast_f32_f16" if c["f16"] else "cast_f32_bf16", [PTR, PTR], c["n"], f=c["p"])
+    if k == "cast_hb":
+        return stream_plan(lib, "cast_f16_bf16", [PTR, PTR], a=c["rows"], b=c["cols"], c=c["ldx"])
+    if k in FLAT_ENTRY:
+        return stream_plan(lib, FLAT_ENTRY[k], [PTR, PTR], c["n"], f=c.get("p", 0.0))
+    if k == "colsum":
+        return stream_plan(lib, "colsum_bf16", [PTR, PTR], a=c["rows"], b=c["cols"], c=c["ld"], det=det)
+    if k == "sumsq":
+        if c["form"] in ("atomic", "part"):
+            return stream_plan(lib, "sumsq_f32", [PTR, PTR, PTR if c["form"] == "part" else 0], c["n"], a=c["ws"] if c["form"] == "part" else 0, det=det)
+        table = c["form"] == "guard_table"
+        return stream_plan(lib, "sumsq_check_f32", [PTR, PTR, PTR, PTR if table else 0], c["n"], a=c["ws"], b=3 if table else 0)
+    if k == "adam":
+        entry, ptrs = adam_entry(c)
+        return stream_plan(lib, entry, ptrs, c["n"], a=7 if c["state"] or c["guard"] else 1)
+    assert k == "step"
+    return stream_plan(lib, "step_state_advance", [PTR, PTR], a=c["warmup"], b=c["total"])
+
+
+def declared_plan(c, det=None):
+    """what the case is declared to launch, from instance() and launch(): every field of the library's plan"""
+    k, names = c["kind"], instance(c)
+    det = c.get("det", False) if det is None else det
+    wgs = 0
+    if k == "colsum":
+        name = "colsum_bf16_slab_kernel" if det else "colsum_bf16_kernel"
+        launches = [(name, -(-c["cols"] // 256), colsum_gy(c["rows"]), 256, 0)] + ([("det_fold_kernel", -(-c["cols"] // 64), 1, 1024, 0)] if det else [])
+    elif k == "sumsq" and c["form"] != "atomic":
+        wgs = sumsq_wgs(c)
+        launches = flat(names[0], wgs) + flat(names[1], 1)
+    elif k == "step":
+        launches = [(names[0], 1, 1, 1, 0)]
+    else:
+        launches = flat(names[0], launch(c)[0])
+    return dict(launches=launches, wgs=wgs)
+
+
+def assert_declared_plan(lib, c):
+    got, want = library_plan(lib, c), declared_plan(c)
+    assert got == want, (case_id(c), got, want)
+    return got
 
 
 def case_id(c):

@@ -1,7 +1,7 @@
 """The case table of tests/adam_group_cases.py, checked without a GPU: it reaches all eight adam_group_kernel<GUARD, MASK, DECOUPLED>
 instantiations, every size, every group layout, the scales 0, 1, 0.37 and the decays 0, 0.01, and stream_cases.ADAM_OPTS' options (clip
-scale, step state, shadows, zero data) in each; the large size passes the 4096-workgroup cap once with a ragged tail; the entry point is
-declared with the arguments the device test passes; the fp32 emulation stays inside every bound with |gain| <= 6; and four wrong
+scale, step state, shadows, zero data) in each; the large size passes the 4096-workgroup cap once with a ragged tail; the declared instance
+and grid of every case are the library's own plan (mmdti_stream_plan); the entry point is declared with the arguments the device test passes; the fp32 emulation stays inside every bound with |gain| <= 6; and four wrong
 emulations -- coupled and decoupled decay swapped, the group id read at i >> 2, decoupled decay without lr_i, the table's columns
 swapped -- leave the bounds."""
 import os
@@ -59,8 +59,21 @@ def test_the_large_size_crosses_the_grid_cap_once_with_a_tail():
         else:
             assert g == 1 and G.rounds(c) == 1
     src = open(os.path.join(ROOT, "mm-dti_amd", "csrc", "elementwise.hip")).read()
-    assert "hipLaunchKernelGGL((adam_group_kernel<G, M, DECOUPLED>), dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, p, g, m, v," in src
-    assert "const int gid = min((int)group[blk], ngroups - 1);" in src and "if (b > 256 * 16) b = 256 * 16;" in src
+    assert "const int gid = min((int)group[blk], ngroups - 1);" in src
+
+
+def test_the_declared_plan_is_the_librarys_for_every_case():
+    """instance() and launch() against mmdti_stream_plan, called as the device test calls mmdti_adam_step_grouped: the eight rows are
+    reached, each by the (guard, skip, decoupled) the case gives, with the grid launch() states"""
+    lib = _abi.lib()
+    reached = set()
+    for c in G.CASES:
+        got = G.assert_declared_plan(lib, c)
+        assert len(got["launches"]) == 1 and got["launches"][0][1] == (4096 if c["n"] == G.BIGG else 1)
+        reached.add(got["launches"][0][0])
+    assert reached == set(G.ALL_KERNELS)
+    with pytest.raises(_abi.MMDTIError, match="adam_step_grouped: ngroups must be 1 .. 256"):
+        S.stream_plan(lib, "adam_step_grouped", [S.PTR] * 11, 8, a=1, b=0)
 
 
 def test_the_entry_point_is_declared_as_the_device_test_calls_it():

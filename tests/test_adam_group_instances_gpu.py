@@ -80,6 +80,7 @@ def _launch(c, t):
 @pytest.mark.parametrize("c", G.CASES, ids=G.case_id)
 def test_instance(c):
     t, ref = G.prepared(c["i"])
+    G.assert_declared_plan(_abi.lib(), c)          # (host only: the launches below are the ones the case declares)
     got = _launch(c, t)
     res = G.evaluate(c, ref, got)
     assert set(res) == set(ref)

@@ -1,6 +1,7 @@
 """Weight averaging without a GPU: the two entry points are declared and exported and the ABI constant has not moved; ema_decay_at is the
 kernel's fp32 schedule; the float64 reference of tests/ema_cases.py obeys the closed form of the recurrence; the case table reaches every
-size, decay, warm-up setting, step and source of t; and tasks.Trainer refuses a bad ema_decay at construction."""
+size, decay, warm-up setting, step and source of t; the declared instance and grid of both kernels are the library's own plan
+(mmdti_stream_plan) at every size of the table and on both sides of the grid cap; and tasks.Trainer refuses a bad ema_decay at construction."""
 import ctypes
 import math
 
@@ -26,6 +27,28 @@ def test_header_and_library_export_both_symbols_and_the_abi_constant_stays():
     src = open(_abi.HEADER).read()
     doc = src[src.index("weight averaging"):src.index("int mmdti_ema_swap(")]
     assert doc.count("Purely additive: MMDTI_ABI_VERSION does not move") == 2
+
+
+def test_the_declared_plan_is_the_librarys_for_both_kernels():
+    """instance() and launch() of ema_cases.py against mmdti_stream_plan, called as ops.ema_update / ops.ema_swap call the entry points:
+    every size of the table with t from each source, the sizes round the 4096-workgroup cap (1024 elements a workgroup for the update,
+    2048 for the swap), an empty arena (no launch), and the launchers' own refusals"""
+    lib = _abi.lib()
+    for n in E.SIZES + (0,):
+        for source in E.SOURCES:
+            got = E.assert_declared_plan(lib, False, n, source=source)
+            assert n == 0 or got["launches"][0][:2] == ("ema_update_kernel", -(-n // 1024))
+        for with_f16 in (True, False):
+            got = E.assert_declared_plan(lib, True, n, with_f16=with_f16)
+            assert n == 0 or got["launches"][0][:2] == ("ema_swap_kernel", -(-n // 2048))
+    for swap, per in ((False, 1024), (True, 2048)):
+        for n in (E.CAP * per - 1, E.CAP * per, E.CAP * per + 1, 3 * E.CAP * per + 7):
+            assert E.assert_declared_plan(lib, swap, n)["launches"][0][1] == min(E.CAP, -(-n // per))
+    import stream_cases as S
+    with pytest.raises(_abi.MMDTIError, match="ema_update: no source of t"):
+        S.stream_plan(lib, "ema_update", [S.PTR, S.PTR + 64, 0, 0], 8, a=0, f=0.9)
+    with pytest.raises(_abi.MMDTIError, match="ema_swap: 16-byte alignment required"):
+        S.stream_plan(lib, "ema_swap", [S.PTR, S.PTR + 64, S.PTR + 2, 0], 8)
 
 
 def test_ema_decay_at_is_the_fp32_schedule_and_never_decreases():

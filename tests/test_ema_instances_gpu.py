@@ -53,6 +53,7 @@ def _t_args(source, t):
 @pytest.mark.parametrize("n", E.SIZES)
 def test_update_instance(n, source):
     p, e0 = E.make_inputs(n, 1)
+    E.assert_declared_plan(_abi.lib(), False, n, source=source)          # (host only: the launches below are the declared ones)
     P = Guarded(p)
     worst = 0.0
     for c in (c for c in E.update_cases() if c["n"] == n and c["source"] == source):
@@ -134,6 +135,7 @@ def test_swap_instance(n, with_f16):
     p, e = E.make_inputs(n, 3)
     if n >= 1023:                              # bit patterns a float move must not touch, and values past the fp16 range
         p[9], e[10], p[n - 2], e[n - 3] = float("nan"), float("inf"), -0.0, 1e5
+    E.assert_declared_plan(_abi.lib(), True, n, with_f16=with_f16)
     P, A = Guarded(p), Guarded(e)
     B, H = Guarded(n=n, dtype=BF16), Guarded(n=n, dtype=F16)
     sent16 = _bits(H.view).clone()

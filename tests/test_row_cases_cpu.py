@@ -1,7 +1,8 @@
-"""The case table of tests/row_cases.py and the keep rule of tests/dropout_rule.py, checked without a GPU: the dispatch lines and rounding
-points the reference depends on are verbatim in the sources; the table reaches all 26 LayerNorm / softmax instances and every instance
-sees every option; the grid statement of the LayerNorm backward is the library's (ops.det_workspace_bytes), for every case and a sweep of
-shapes; the exact modes are exact in the fp32 emulation; the emulation stays inside every bound with |gain| <= 6; and nine wrong
+"""The case table of tests/row_cases.py and the keep rule of tests/dropout_rule.py, checked without a GPU: the rounding points the
+reference depends on are verbatim in the sources; the table reaches all 26 LayerNorm / softmax instances, which are exactly the rows of
+the library's MMDTI_PLAN_ROW table, and every instance sees every option; the declared dispatch and geometry are the library's
+(mmdti_row_plan) for every case and over sweeps of every D and ld, and the query refuses what the launchers refuse, in their words; the
+grid statement of the LayerNorm backward is also the one the workspace size follows (ops.det_workspace_bytes); the exact modes are exact in the fp32 emulation; the emulation stays inside every bound with |gain| <= 6; and nine wrong
 emulations (one-pass variance, eps outside the root, unbiased variance, row_zero before the statistics, dgamma from the un-dropped dy,
 column sums before rounding, softmax over ld, dl before the dropout of dp, the mask indexed by row x Lk + key) leave them.
 
@@ -9,12 +10,14 @@ With MMDTI_ROW_PROFILE=<path> the worst emulation ratio and |gain| per instance 
 "emulation" (profiles/row_instances.json holds such a run next to the device's)."""
 import json
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from mmdti_hip import ops
+from mmdti_hip import _abi, ops
 
 import dropout_rule as DR
 import row_cases as R
@@ -125,6 +128,103 @@ def test_every_instance_sees_every_option():
     rpw = {R.ln_nv(c["D"]) <= 2: R.ln_rpw(c["rows"], c["D"]) for c in R.CASES if c["kind"] == "ln_bwd" and c["rows"] > 8000}
     assert rpw == {True: 5, False: 5}                      # rows_per_wave > 4, once per register class
     assert {(c["Lk"], c["ld"]) for c in R.CASES if c["kind"] == "sm_fwd"} == set(R.SM_SHAPES)
+
+
+def test_the_plan_table_is_the_instance_list():
+    """26 rows, in the order of ALL_INSTANCES, and every row is reached by a case of the table through the library's own plan"""
+    lib = _abi.lib()
+    import ctypes
+    n = ctypes.c_int()
+    lib.mmdti_plan_table_size(R.PLAN_FAMILY, ctypes.byref(n))
+    names = [lib.mmdti_plan_kernel_name(R.PLAN_FAMILY, i).decode() for i in range(n.value)]
+    assert names == R.ALL_INSTANCES and lib.mmdti_plan_kernel_name(R.PLAN_FAMILY, n.value) is None
+    reached = {R.library_plan(lib, c)["launches"][0][0] for c in R.CASES}
+    assert reached == set(names), reached ^ set(names)
+
+
+@pytest.mark.parametrize("kind", ("ln_fwd", "ln_bwd", "sm_fwd", "sm_bwd"))
+def test_the_declared_plan_is_the_librarys_for_every_case(kind):
+    lib = _abi.lib()
+    n = 0
+    for c in R.CASES:
+        if c["kind"] == kind:
+            got = R.assert_declared_plan(lib, c)
+            assert len(got["launches"]) == (2 if "_slab_" in R.instance(c) else 1)
+            n += 1
+    assert n >= 36
+
+
+SWEEP_ROWS = (1, 3, 4, 5, 17, 3071, 3072, 3073, 8197, 12293, 65536)
+
+
+def test_the_declared_plan_is_the_librarys_over_every_width():
+    """every D in 4 .. 2048 and every ld in 8 .. 1024 against rows on both sides of a workgroup, of a resident grid (3072 = 4 x 3 x 256
+    waves, 2 x 256 workgroups of the wide rows) and far past it; the backward in both dy types, in and out of the deterministic mode,
+    with and without a sum to fold"""
+    lib = _abi.lib()
+    for D in range(4, 2049, 4):
+        for rows in SWEEP_ROWS:
+            c = dict(kind="ln_fwd", rows=rows, D=D, outs="both", p=0.0)
+            assert R.library_plan(lib, c) == R.declared_plan(c), (rows, D)
+            for dybf, det, nullg in ((False, False, False), (True, False, True), (False, True, False), (True, True, False), (True, True, True)):
+                c = dict(kind="ln_bwd", rows=rows, D=D, dybf=dybf, det=det, nullg=nullg, copy=None, p=0.0)
+                got = R.library_plan(lib, c)
+                assert got == R.declared_plan(c), (rows, D, dybf, det, nullg)
+                assert len(got["launches"]) == (2 if det and not nullg else 1)
+    for ld in range(8, 1025, 8):
+        for B, heads, Lq in ((1, 1, 1), (1, 1, 5), (2, 3, 7), (64, 8, 128)):
+            for k in ("sm_fwd", "sm_bwd"):
+                c = dict(kind=k, B=B, heads=heads, Lq=Lq, Lk=ld - (ld // 3) % 8, ld=ld, p=0.0)
+                assert R.library_plan(lib, c) == R.declared_plan(c), (k, ld, B)
+    # the slab form needs one sum to fold: each of the three alone brings it
+    for ptr in (6, 7, 9):
+        ptrs = [R.PTR] * 6 + [0, 0, R.PTR, 0]
+        ptrs[ptr] = R.PTR
+        assert [l[0] for l in R.row_plan(lib, "ln_bwd", ptrs, 37, 0, 0, 0, 516, det=True)["launches"]] == ["ln_bwd_slab_kernel<4, false>", "det_fold_kernel"]
+        assert [l[0] for l in R.row_plan(lib, "ln_bwd", ptrs, 37, 0, 0, 0, 516, det=False)["launches"]] == ["ln_bwd_kernel<4, false>"]
+
+
+def test_the_query_refuses_in_the_launchers_words():
+    lib, P = _abi.lib(), R.PTR
+    cases = (("layernorm_fwd: need rows>0, D%4==0, D<=2048 \\(D=2052\\)", "ln_fwd", [P] * 5, (3, 0, 0, 0, 2052), {}),
+             ("layernorm_fwd: need rows>0", "ln_fwd", [P] * 5, (0, 0, 0, 0, 64), {}),
+             ("layernorm_fwd: null pointer", "ln_fwd", [P, P, P, 0, 0], (3, 0, 0, 0, 64), {}),
+             ("layernorm_fwd: 16-byte alignment required", "ln_fwd", [P, P + 8, P, P, P], (3, 0, 0, 0, 64), {}),
+             ("layernorm_fwd: dropout p out of range", "ln_fwd", [P] * 5, (3, 0, 0, 0, 64), dict(p=1.0)),
+             ("layernorm_bwd: need rows>0, D%4==0, D<=2048 \\(D=6\\)", "ln_bwd", [P] * 10, (3, 0, 0, 0, 6), {}),
+             ("layernorm_bwd: null pointer", "ln_bwd", [P, P, P, 0] + [P] * 6, (3, 0, 0, 0, 64), {}),
+             ("layernorm_bwd: alignment", "ln_bwd", [P + 4] + [P] * 9, (3, 0, 0, 0, 64), {}),
+             ("layernorm_bwd: dropout p out of range", "ln_bwd", [P] * 10, (3, 0, 0, 0, 64), dict(p2=-0.5)),
+             ("layernorm_bwd: dx_bf16 alignment", "ln_bwd", [P] * 8 + [P + 4, P], (3, 0, 0, 0, 64), {}),
+             ("layernorm_bwd: dx_colsum sums the bf16 copy, which was not requested", "ln_bwd", [P] * 8 + [0, P], (3, 0, 0, 0, 64), {}),
+             ("softmax_fwd: bad arguments", "sm_fwd", [P, P, P], (1, 0, 4, 8, 8), {}),
+             ("softmax_fwd: need Lk <= ld <= 1024, ld % 8 == 0", "sm_fwd", [P, P, P], (1, 2, 4, 1030, 1032), {}),
+             ("softmax_fwd: need Lk <= ld", "sm_fwd", [P, P, P], (1, 2, 4, 9, 8), {}),
+             ("softmax_fwd: 16-byte alignment required", "sm_fwd", [P, P + 8, P], (1, 2, 4, 8, 8), {}),
+             ("softmax_fwd: dropout needs a separate pd buffer", "sm_fwd", [P, P, P], (1, 2, 4, 8, 8), dict(p=0.1)),
+             ("softmax_bwd: bad arguments", "sm_bwd", [P, 0, P], (1, 2, 4, 8, 8), {}),
+             ("softmax_bwd: need Lk <= ld <= 1024, ld % 8 == 0", "sm_bwd", [P, P, P], (1, 2, 4, 8, 12), {}),
+             ("softmax_bwd: dropout p out of range", "sm_bwd", [P, P, P], (1, 2, 4, 8, 8), dict(p=1.5)))
+    for msg, kind, ptrs, shape, kw in cases:
+        with pytest.raises(_abi.MMDTIError, match=msg):
+            R.row_plan(lib, kind, ptrs, *shape, **kw)
+    import ctypes
+    with pytest.raises(_abi.MMDTIError, match="layernorm_bwd: bad dy dtype"):
+        lib.mmdti_row_plan(1, 0, (ctypes.c_void_p * 10)(*[P] * 10), 3, 0, 0, 0, 64, 7, 0.0, 0.0, (ctypes.c_longlong * 13)())
+    with pytest.raises(_abi.MMDTIError, match="row_plan: unknown entry 4"):
+        lib.mmdti_row_plan(4, 0, (ctypes.c_void_p * 10)(*[P] * 10), 3, 0, 0, 0, 64, 0, 0.0, 0.0, (ctypes.c_longlong * 13)())
+
+
+def test_both_plan_headers_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/plan_sweep_main.cpp: a stand-alone program over csrc/row_plan.h and csrc/stream_plan.h (every width, sizes up to INT_MAX rows
+    and 2^40 elements, every key), built with -fsanitize=address,undefined.  Nothing loaded into Python is sanitized."""
+    cxx = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc"))
+    assert cxx, "no hipcc (the compiler the library itself is built with)"
+    exe = str(tmp_path / "plan_sweep_main")
+    subprocess.run([cxx, "-x", "c++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    os.path.join(ROOT, "tests", "plan_sweep_main.cpp"), "-o", exe], check=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.stdout[-600:], r.stderr[-600:])
 
 
 def test_the_grid_statement_is_the_librarys():

@@ -137,6 +137,7 @@ def _check(c, t, ref, got, record=True):
 @pytest.mark.parametrize("c", R.CASES, ids=R.case_id)
 def test_instance(c):
     t, ref = R.prepared(c["i"])
+    R.assert_declared_plan(_abi.lib(), c)          # (host only: the launch below is the one the case declares)
     got = LAUNCH[c["kind"]](c, t)
     res = _check(c, t, ref, got)
     k = c["kind"]

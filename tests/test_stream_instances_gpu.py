@@ -219,6 +219,7 @@ LAUNCH = {"cast": _launch_cast, "dropout": _launch_dropout, "cast_hb": _launch_c
 @pytest.mark.parametrize("c", [c for c in S.CASES if c["kind"] != "step"], ids=S.case_id)
 def test_instance(c):
     t, ref = S.prepared(c["i"])
+    S.assert_declared_plan(_abi.lib(), c)          # (host only: the launches below are the ones the case declares)
     got = LAUNCH[c["kind"]](c, t)
     res = S.evaluate(c, ref, got)
     _record(c, res)
@@ -254,6 +255,7 @@ def test_step_state_advance():
     on MI355X: the largest |got - ref| / bound is 0.32, below 0.5)"""
     c = next(c for c in S.CASES if c["kind"] == "step")
     lib = _abi.lib()
+    S.assert_declared_plan(lib, c)
     state = torch.zeros(4, dtype=F32, device=DEV)
     salt = torch.zeros(2, dtype=torch.int64, device=DEV)
     x, worst = 0, 0.0
