@@ -660,6 +660,24 @@ int mmdti_seq_mean_packed_fwd(mmdti_stream_t stream, const void* x_bf16, int B, 
  * [rows] int32, the sequence each packed row belongs to; f / aux_mode as in mmdti_seq_mean_bwd. */
 int mmdti_seq_mean_packed_bwd(mmdti_stream_t stream, const float* dout, int rows, int S, int D, int ld, const int* row_off,
                               const int* n_real, const int* row_seq, void* dx_bf16, const void* aux_bf16, int ld_aux, int aux_mode);
+/* The mean over the REAL positions of every sequence -- where models/infonce.py:32-33 averages over all positions, padding included,
+ * this divides the sum over the real positions by their number (InfoNCE(pool="real")): no padded row is read.  One entry point for
+ * both layouts; exactly one of mask / row_off is non-null, anything else is MMDTI_ERR_INVALID before a launch.
+ *   mask    [B,S] uint8, non-zero = real (any pattern, not only prefixes): x is [B*S, ld] bf16, masked rows may hold anything;
+ *   row_off [B+1] int32: x is packed rows without pad rows, sequence b owns rows [row_off[b], row_off[b+1]), all of them real.
+ * out [B,D] fp32.  A sequence with no real position gives a zero row.  D % 8 == 0, ld % 8 == 0 and a 16-byte aligned x take 16-byte
+ * loads (D <= 4096), anything else a scalar kernel.  Both forms walk a sequence's positions in the same order and skip a masked row by
+ * predicate, so a right-padded batch pools to the same bits in either layout.  No atomics: the sum has one order. */
+int mmdti_seq_mean_real_fwd(mmdti_stream_t stream, const void* x_bf16, int B, int S, int D, int ld, const unsigned char* mask,
+                            const int* row_off, float* out);
+/* Its backward (the adjoint of the mean over real positions, not of infonce.py:32-33's mean over all S):
+ *   dx[row] = bf16(dout[b] / count_b * f(aux[row]))   for a real row, f / aux_mode as in mmdti_seq_mean_bwd;
+ *   dx[row] = 0 exactly                               for a masked row (its aux is not read), and in the pad columns D..ld.
+ * rows: B*S with mask; the packed row count with row_off, and then row_seq [rows] int32 names each row's sequence (unread with mask).
+ * An aux factor needs ld % 8 == 0, ld_aux % 8 == 0, ld_aux >= ld and 16-byte aligned dx / aux (MMDTI_ERR_INVALID otherwise); without
+ * one, rows that are not 8-column aligned take a scalar kernel.  Purely additive: MMDTI_ABI_VERSION does not move. */
+int mmdti_seq_mean_real_bwd(mmdti_stream_t stream, const float* dout, int rows, int B, int S, int D, int ld, const unsigned char* mask,
+                            const int* row_off, const int* row_seq, void* dx_bf16, const void* aux_bf16, int ld_aux, int aux_mode);
 /* F.normalize(x, dim=-1) (infonce.py:104-105; contrastive.py:22-23) */
 int mmdti_l2norm_fwd(mmdti_stream_t stream, const float* x, int B, int D, int ldx, float* xhat, float* inv_norm);
 int mmdti_l2norm_bwd(mmdti_stream_t stream, const float* dxhat, const float* xhat, const float* inv_norm, int B,

@@ -145,6 +145,153 @@ __global__ __launch_bounds__(256) void seq_mean_packed_bwd_kernel(const float* _
   *reinterpret_cast<uint4*>(dx + row * ld + c8) = o;
 }
 
+// ---------------------------------------------------------------- mean over the real positions (InfoNCE(pool="real"))
+// Departs from infonce.py:32-33 (which averages over every position, padding included): sum over the real positions / their number.
+// One code path for both layouts -- mask [B,S] over padded rows, or row_off over pad-free packed rows -- with the positions walked in
+// the same order and a masked row SKIPPED (never multiplied by 0: it may hold anything), so a right-padded batch pools to the same
+// bits either way.  An empty sequence gives zeros.
+__global__ __launch_bounds__(256) void seq_mean_real_fwd_kernel(const bf16_t* __restrict__ x, int S, int D, int ld, const unsigned char* __restrict__ mask,
+                                                                const int* __restrict__ row_off, float* __restrict__ out) {
+  const int b = blockIdx.x;
+  const long long r0 = row_off ? (long long)row_off[b] : (long long)b * S;
+  const int rows = row_off ? row_off[b + 1] - row_off[b] : S;
+  const unsigned char* m = mask ? mask + (long long)b * S : nullptr;
+  for (int d = threadIdx.x; d < D; d += 256) {
+    float s = 0.f;
+    int n = 0;
+    for (int i = 0; i < rows; ++i) {
+      if (m && !m[i]) continue;
+      s += bf2f(x[(r0 + i) * ld + d]);
+      ++n;
+    }
+    out[(long long)b * D + d] = n > 0 ? s / (float)n : 0.f;
+  }
+}
+// Wide rows: the shape of seq_mean_fwd_vec_kernel -- one workgroup per (sequence, 64-column slice), 32 row phases x 8 pieces of 8
+// columns, the phases folded through LDS in a fixed order; position r of a sequence is phase r % 32 in both layouts.
+__global__ __launch_bounds__(256) void seq_mean_real_fwd_vec_kernel(const bf16_t* __restrict__ x, int S, int D, int ld,
+                                                                    const unsigned char* __restrict__ mask, const int* __restrict__ row_off,
+                                                                    float* __restrict__ out) {
+  __shared__ float red[32][65];
+  __shared__ int cnt[32];
+  const int b = blockIdx.x, c0 = blockIdx.y * 64;
+  const int piece = threadIdx.x & 7, phase = threadIdx.x >> 3;
+  const long long r0 = row_off ? (long long)row_off[b] : (long long)b * S;
+  const int rows = row_off ? row_off[b + 1] - row_off[b] : S;
+  const unsigned char* m = mask ? mask + (long long)b * S : nullptr;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int col = c0 + piece * 8;
+  int n = 0;
+  for (int r = phase; r < rows; r += 32) {
+    if (m && !m[r]) continue;
+    ++n;
+    if (col < D) {
+      const uint4 u = *reinterpret_cast<const uint4*>(x + (r0 + r) * ld + col);
+      const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[2 * e] += __uint_as_float(w4[e] << 16);
+        acc[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u);
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) red[phase][piece * 8 + e] = acc[e];
+  if (piece == 0) cnt[phase] = n;
+  __syncthreads();
+  if (threadIdx.x < 64 && c0 + threadIdx.x < D) {
+    float t = 0.f;
+    int c = 0;
+#pragma unroll
+    for (int ph = 0; ph < 32; ++ph) {
+      t += red[ph][threadIdx.x];
+      c += cnt[ph];
+    }
+    out[(long long)b * D + c0 + threadIdx.x] = c > 0 ? t / (float)c : 0.f;
+  }
+}
+// dx[row, d] = bf16(dout[b, d] / count_b * f(aux[row, d])), f as in seq_mean_bwd_vec_kernel; a masked row and the pad columns D..ld
+// are exact zeros (the row's aux is not read: the zero keeps padded rows out of the weight gradient that consumes dx).
+__device__ __forceinline__ void seq_mean_real_store8(const float* __restrict__ dout, int b, int D, int ld, int c8, long long row, bool real, float inv,
+                                                     const bf16_t* __restrict__ aux, int ld_aux, int aux_mode, bf16_t* __restrict__ dx) {
+  uint4 o = make_uint4(0u, 0u, 0u, 0u);
+  if (real) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (c8 + e < D) ? dout[(long long)b * D + c8 + e] * inv : 0.f;
+    if (aux_mode) {
+      const uint4 u = *reinterpret_cast<const uint4*>(aux + row * ld_aux + c8);
+      const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float a = __uint_as_float((e & 1) ? (w4[e >> 1] & 0xffff0000u) : (w4[e >> 1] << 16));
+        v[e] = (c8 + e < D) ? v[e] * (aux_mode == 1 ? a : gelu_erf_grad(a)) : 0.f;
+      }
+    }
+    o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+    o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+    o.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
+    o.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
+  }
+  *reinterpret_cast<uint4*>(dx + row * ld + c8) = o;
+}
+// padded rows: one workgroup per (sequence, 32-position slab); it counts the sequence's real positions itself (integers below 2^24
+// summed as floats: exact), so nothing is handed over from the forward
+__global__ __launch_bounds__(256) void seq_mean_real_bwd_mask_kernel(const float* __restrict__ dout, int S, int D, int ld,
+                                                                     const unsigned char* __restrict__ mask, const bf16_t* __restrict__ aux, int ld_aux,
+                                                                     int aux_mode, bf16_t* __restrict__ dx) {
+  __shared__ float red[4];
+  const int b = blockIdx.x, s0 = blockIdx.y * 32;
+  const unsigned char* m = mask + (long long)b * S;
+  float c = 0.f;
+  for (int i = threadIdx.x; i < S; i += 256) c += m[i] ? 1.f : 0.f;
+  const float cntf = block_sum(c, red);
+  const float inv = cntf > 0.f ? 1.0f / cntf : 0.f;
+  const int cpr = ld >> 3;
+  const int nrow = min(32, S - s0);
+  for (int t = threadIdx.x; t < nrow * cpr; t += 256) {
+    const int rr = t / cpr;
+    const int c8 = (t - rr * cpr) * 8;
+    seq_mean_real_store8(dout, b, D, ld, c8, (long long)b * S + s0 + rr, m[s0 + rr] != 0, inv, aux, ld_aux, aux_mode, dx);
+  }
+}
+// pad-free packed rows: every row is real, its sequence's count is its row range
+__global__ __launch_bounds__(256) void seq_mean_real_bwd_packed_kernel(const float* __restrict__ dout, int D, int ld, const int* __restrict__ row_off,
+                                                                       const int* __restrict__ row_seq, const bf16_t* __restrict__ aux, int ld_aux,
+                                                                       int aux_mode, bf16_t* __restrict__ dx, long long rows) {
+  const int cpr = ld >> 3;
+  const long long chunk = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long row = chunk / cpr;
+  if (row >= rows) return;
+  const int c8 = (int)(chunk - row * cpr) * 8;
+  const int b = row_seq[row];
+  const float inv = 1.0f / (float)(row_off[b + 1] - row_off[b]);
+  seq_mean_real_store8(dout, b, D, ld, c8, row, true, inv, aux, ld_aux, aux_mode, dx);
+}
+// rows that are not 8-column aligned (no aux factor): one workgroup per row, either layout
+__global__ __launch_bounds__(256) void seq_mean_real_bwd_kernel(const float* __restrict__ dout, int S, int D, int ld, const unsigned char* __restrict__ mask,
+                                                                const int* __restrict__ row_off, const int* __restrict__ row_seq,
+                                                                bf16_t* __restrict__ dx) {
+  __shared__ float red[4];
+  const long long row = blockIdx.x;
+  int b;
+  float cntf;
+  bool real = true;
+  if (mask) {
+    b = (int)(row / S);
+    const unsigned char* m = mask + (long long)b * S;
+    float c = 0.f;
+    for (int i = threadIdx.x; i < S; i += 256) c += m[i] ? 1.f : 0.f;
+    cntf = block_sum(c, red);
+    real = m[row - (long long)b * S] != 0;
+  } else {
+    b = row_seq[row];
+    cntf = (float)(row_off[b + 1] - row_off[b]);
+  }
+  const float inv = cntf > 0.f ? 1.0f / cntf : 0.f;
+  for (int d = threadIdx.x; d < ld; d += 256) dx[row * ld + d] = f2bf(real && d < D ? dout[(long long)b * D + d] * inv : 0.f);
+}
+
 // ---------------------------------------------------------------- F.normalize (eps 1e-12)
 __global__ __launch_bounds__(64) void l2norm_fwd_kernel(const float* __restrict__ x, int D, int ldx, float* __restrict__ xh, float* __restrict__ invn) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -1029,6 +1176,42 @@ extern "C" int mmdti_seq_mean_packed_bwd(mmdti_stream_t stream, const float* dou
   const long long chunks = (long long)rows * (ld / 8);
   hipLaunchKernelGGL(seq_mean_packed_bwd_kernel, dim3((unsigned)cdiv(chunks, 256)), dim3(256), 0, (hipStream_t)stream, dout, S, D, ld, row_off,
                      n_real, row_seq, (const bf16_t*)aux_bf16, ld_aux, aux_mode, (bf16_t*)dx_bf16, (long long)rows);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_seq_mean_real_fwd(mmdti_stream_t stream, const void* x_bf16, int B, int S, int D, int ld, const unsigned char* mask,
+                                       const int* row_off, float* out) {
+  MMDTI_REQUIRE(x_bf16 && out && B > 0 && S > 0 && S < (1 << 24) && D > 0 && ld >= D, "seq_mean_real_fwd: bad arguments");
+  MMDTI_REQUIRE((mask != nullptr) != (row_off != nullptr), "seq_mean_real_fwd: exactly one of mask (padded rows) / row_off (packed rows) is given");
+  if (D % 8 == 0 && ld % 8 == 0 && D <= 4096 && aligned16(x_bf16)) {
+    hipLaunchKernelGGL(seq_mean_real_fwd_vec_kernel, dim3(B, cdiv(D, 64)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x_bf16, S, D, ld, mask, row_off,
+                       out);
+  } else {
+    hipLaunchKernelGGL(seq_mean_real_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x_bf16, S, D, ld, mask, row_off, out);
+  }
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_seq_mean_real_bwd(mmdti_stream_t stream, const float* dout, int rows, int B, int S, int D, int ld, const unsigned char* mask,
+                                       const int* row_off, const int* row_seq, void* dx_bf16, const void* aux_bf16, int ld_aux, int aux_mode) {
+  MMDTI_REQUIRE(dout && dx_bf16 && rows > 0 && B > 0 && S > 0 && S < (1 << 24) && D > 0 && ld >= D, "seq_mean_real_bwd: bad arguments");
+  MMDTI_REQUIRE((mask != nullptr) != (row_off != nullptr), "seq_mean_real_bwd: exactly one of mask (padded rows) / row_off (packed rows) is given");
+  MMDTI_REQUIRE(mask ? (long long)rows == (long long)B * S : row_seq != nullptr,
+                "seq_mean_real_bwd: rows is B * S with a mask; packed rows need row_seq");
+  MMDTI_REQUIRE(aux_mode >= 0 && aux_mode <= 2 && (aux_mode == 0 || aux_bf16), "seq_mean_real_bwd: aux_mode %d needs aux", aux_mode);
+  if (ld % 8 == 0 && aligned16(dx_bf16) && (aux_mode == 0 || (ld_aux % 8 == 0 && ld_aux >= ld && aligned16(aux_bf16)))) {
+    if (mask) {
+      hipLaunchKernelGGL(seq_mean_real_bwd_mask_kernel, dim3(B, cdiv(S, 32)), dim3(256), 0, (hipStream_t)stream, dout, S, D, ld, mask,
+                         (const bf16_t*)aux_bf16, ld_aux, aux_mode, (bf16_t*)dx_bf16);
+    } else {
+      const long long chunks = (long long)rows * (ld / 8);
+      hipLaunchKernelGGL(seq_mean_real_bwd_packed_kernel, dim3((unsigned)cdiv(chunks, 256)), dim3(256), 0, (hipStream_t)stream, dout, D, ld, row_off,
+                         row_seq, (const bf16_t*)aux_bf16, ld_aux, aux_mode, (bf16_t*)dx_bf16, (long long)rows);
+    }
+  } else {
+    MMDTI_REQUIRE(aux_mode == 0, "seq_mean_real_bwd: the aux factor needs 8-column aligned rows");
+    hipLaunchKernelGGL(seq_mean_real_bwd_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dout, S, D, ld, mask, row_off, row_seq, (bf16_t*)dx_bf16);
+  }
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

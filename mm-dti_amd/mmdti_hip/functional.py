@@ -1363,11 +1363,19 @@ class InfoNCEFn(torch.autograd.Function):
     returned is this rank's share of the global loss (the sum over ranks equals the single-process loss)."""
 
     @staticmethod
-    def forward(ctx, query, positive, mod, training, gather, reduce_scatter, row0, packs=None, anchor=None):
+    def forward(ctx, query, positive, mod, training, gather, reduce_scatter, row0, packs=None, anchor=None, masks=None):
         """anchor: freeze.grad_anchor(mod.parameters()) -- the backward runs when the head trains even if neither input needs a gradient.
         packs = (PackedRows of query, PackedRows of positive): [M, D] packed rows; the unmasked mean over the padded positions
-        (infonce.py:32-33) weights each representative pad row by the number of padded positions it stands for."""
-        if packs is not None:
+        (infonce.py:32-33) weights each representative pad row by the number of padded positions it stands for.
+        mod.pool == "real" (InfoNCE(pool="real")): the mean runs over the real positions only, in either order of pooling and
+        projecting -- masks = ([B,Nq], [B,Np]) planes (non-zero = real) for padded inputs, pad-free packs for packed rows."""
+        real = getattr(mod, "pool", "all") == "real"
+        if real and (packs is None) == (masks is None):
+            raise ops.MMDTIError("InfoNCEFn(pool='real'): exactly one of masks (padded rows) and packs (pad-free packed rows) is given")
+        if packs is not None and real:
+            B, D = packs[0].B, query.shape[-1]
+            Nq, Np = packs[0].S, packs[1].S
+        elif packs is not None:
             B, D = packs[0].B, query.shape[-1]
             Nq, Np = packs[0].M, packs[1].M           # (rows of the whole side, not per sequence)
             if not (POOL_THEN_PROJECT and mod.info_proj_query[0].weight.shape[0] % 8 == 0 and mod.info_proj_positive[0].weight.shape[0] % 8 == 0):
@@ -1381,6 +1389,25 @@ class InfoNCEFn(torch.autograd.Function):
         p = mod.embed_dropout if training else 0.0
         st = SimpleNamespace(B=B, Nq=Nq, Np=Np, D=D, d=d, ldp=ldp, seed=seed, p=p)
         dev = query.device
+
+        def proj_real(x, seq, n, dropout_p, site, pack, mask):
+            """proj() with the mean over the real rows (ops.seq_mean_real_fwd): mask plane over [B*n] padded rows, or a pad-free pack."""
+            L = SimpleNamespace()
+            rows = B * n if pack is None else pack.M
+            L.x16 = ops.cast_act16(x.contiguous().view(rows, D), dropout_p, seed, site)
+            L.u = torch.empty(rows, seq[0].weight.shape[0], device=dev, dtype=BF16)
+            h = ops.linear_fwd(L.x16, wfwd(seq[0].weight), seq[0].bias, act=ops.ACT_GELU_FWD, aux_out=L.u, out_dtype=BF16)
+            Hd = h.shape[1]
+            if POOL_THEN_PROJECT and Hd % 8 == 0:
+                L.hbar = ops.seq_mean_real_fwd(h, B, n, Hd, Hd, mask=mask, pack=pack)
+                L.mean = ops.linear_f32_fwd(L.hbar, seq[2].weight.detach(), seq[2].bias.detach())
+                L.h = None
+                return L
+            L.h = h
+            pr = torch.zeros(rows, ldp, device=dev, dtype=BF16)
+            ops.gemm(L.h, wbf16(seq[2].weight), M=rows, N=d, K=Hd, lda=Hd, ldb=seq[2].weight.shape[1], out=pr, ldc=ldp, bias=seq[2].bias)
+            L.mean = ops.seq_mean_real_fwd(pr, B, n, d, ldp, mask=mask, pack=pack)
+            return L
 
         def proj(x, seq, n, dropout_p, site, pack=None):
             L = SimpleNamespace()
@@ -1410,9 +1437,13 @@ class InfoNCEFn(torch.autograd.Function):
             L.mean = ops.seq_mean_fwd(pr, B, n, d, ldp)
             return L
 
-        st.packs = packs
-        st.Lq = proj(query, mod.info_proj_query, Nq, p, 1, None if packs is None else packs[0])
-        st.Lp = proj(positive, mod.info_proj_positive, Np, 0.0, 2, None if packs is None else packs[1])
+        st.packs, st.masks, st.real = packs, masks, real
+        if real:
+            st.Lq = proj_real(query, mod.info_proj_query, Nq, p, 1, None if packs is None else packs[0], None if masks is None else masks[0])
+            st.Lp = proj_real(positive, mod.info_proj_positive, Np, 0.0, 2, None if packs is None else packs[1], None if masks is None else masks[1])
+        else:
+            st.Lq = proj(query, mod.info_proj_query, Nq, p, 1, None if packs is None else packs[0])
+            st.Lp = proj(positive, mod.info_proj_positive, Np, 0.0, 2, None if packs is None else packs[1])
         both = torch.cat((st.Lq.mean, st.Lp.mean), dim=1)            # [B, 2d] (tiny; one message under DDP)
         both_all = gather(both) if gather is not None else both
         Bg = both_all.shape[0]
@@ -1438,7 +1469,32 @@ class InfoNCEFn(torch.autograd.Function):
             dboth = ctx.rs(dboth)                                   # sum over ranks, keep own rows
         dboth = (dboth * dloss).contiguous()
 
-        def proj_bwd(L, dmean, seq, n, dropout_p, site, want_dx, pack=None):
+        def proj_bwd(L, dmean, seq, n, dropout_p, site, want_dx, pack=None, mask=None):
+            if st.real:
+                # (masked rows of du / dpr are exact zeros: padded rows enter no weight gradient and receive a zero input gradient)
+                rows = B * n if pack is None else pack.M
+                if L.h is None:
+                    gw, gb = gbuf(seq[2].weight), gbuf(seq[2].bias)
+                    dhbar = ops.linear_f32_bwd(L.hbar, seq[2].weight.detach(), None, dmean.contiguous(), gw, gb)
+                    Hd = L.hbar.shape[1]
+                    du = ops.seq_mean_real_bwd(dhbar, B, n, Hd, Hd, mask=mask, pack=pack, aux=L.u, aux_mode=1 if ops.GELU_SAVE_GRAD else 2)
+                else:
+                    dpr = ops.seq_mean_real_bwd(dmean.contiguous(), B, n, d, ldp, mask=mask, pack=pack)
+                    gw = gbuf(seq[2].weight)
+                    if gw is not None:
+                        ops.linear_bwd_weight(dpr, L.h, gw)
+                    gb = gbuf(seq[2].bias)
+                    if gb is not None:
+                        ops.colsum(dpr, gb, cols=d)
+                    du = ops.gemm(dpr, wbf16(seq[2].weight), M=rows, N=L.h.shape[1], K=d, lda=ldp, ldb=seq[2].weight.shape[1], transB=True,
+                                  act=ops.ACT_GELU_DX, aux_in=L.u)
+                _lin_bwd_params(du, L.x16, seq[0].weight, seq[0].bias)
+                if not want_dx:
+                    return None
+                dx = ops.linear_bwd_input(du, wbf16(seq[0].weight), out_dtype=F32)
+                if dropout_p > 0:
+                    dx = ops.dropout_f32(dx, dropout_p, st.seed, site)
+                return dx
             if L.h is None:                                                                  # pooled first (see forward)
                 gw, gb = gbuf(seq[2].weight), gbuf(seq[2].bias)
                 dhbar = ops.linear_f32_bwd(L.hbar, seq[2].weight.detach(), None, dmean.contiguous(), gw, gb)
@@ -1471,14 +1527,16 @@ class InfoNCEFn(torch.autograd.Function):
                 dx = ops.dropout_f32(dx, dropout_p, st.seed, site)
             return dx
 
-        pk = st.packs
-        dxq = proj_bwd(st.Lq, dboth[:, :d], mod.info_proj_query, st.Nq, st.p, 1, ctx.needs_input_grad[0], None if pk is None else pk[0])
-        dxp = proj_bwd(st.Lp, dboth[:, d:], mod.info_proj_positive, st.Np, 0.0, 2, ctx.needs_input_grad[1], None if pk is None else pk[1])
+        pk, mk = st.packs, st.masks
+        dxq = proj_bwd(st.Lq, dboth[:, :d], mod.info_proj_query, st.Nq, st.p, 1, ctx.needs_input_grad[0], None if pk is None else pk[0],
+                       None if mk is None else mk[0])
+        dxp = proj_bwd(st.Lp, dboth[:, d:], mod.info_proj_positive, st.Np, 0.0, 2, ctx.needs_input_grad[1], None if pk is None else pk[1],
+                       None if mk is None else mk[1])
         notify_grads_ready(mod.parameters())
         if pk is not None:
-            return dxq, dxp, None, None, None, None, None, None, None
+            return dxq, dxp, None, None, None, None, None, None, None, None
         return (None if dxq is None else dxq.view(B, st.Nq, st.D), None if dxp is None else dxp.view(B, st.Np, st.D), None, None, None, None, None, None,
-                None)
+                None, None)
 
 
 class InfoNCELossFn(torch.autograd.Function):

@@ -8,6 +8,11 @@ non-square logits) -- here they raise ``ValueError`` up front.
 
 Extension for data parallelism (absent from the reference): ``set_global_negatives(gather, reduce_scatter, rank_row0)``
 makes the B x B logits use every rank's keys.
+
+Second extension, opt-in: ``InfoNCE(..., pool="real")`` averages the per-token projections over the REAL positions only (the
+reference's :32-33 averages over padding too; ``pool="all"``, the default, keeps that).  The head is random-initialised at
+fine-tune time, so no checkpoint carries the difference; with it no padded row is read by anything in the model, the embedding
+of a molecule no longer depends on how far its batch is padded, and packed token rows need no pad row (packing.py).
 """
 import torch
 from torch import nn
@@ -16,9 +21,26 @@ from ..functional import InfoNCEFn, InfoNCELossFn
 from ..freeze import grad_anchor
 
 
+POOLS = ("all", "real")
+
+
+def pool_from_env(value=None):
+    """The pooling MM_Model(infonce_pool=None) takes: MMDTI_INFONCE_POOL = all | real, unset = "all" (the reference)."""
+    import os
+    v = os.environ.get("MMDTI_INFONCE_POOL") if value is None else value
+    if v is None or v == "":
+        return "all"
+    if v not in POOLS:
+        raise ValueError(f"MMDTI_INFONCE_POOL / infonce_pool must be one of {POOLS} (got {v!r})")
+    return v
+
+
 class InfoNCE(nn.Module):
-    def __init__(self, bert_output_size, graph_ouput_size, temperature=0.1, reduction='mean', negative_mode='unpaired'):
+    def __init__(self, bert_output_size, graph_ouput_size, temperature=0.1, reduction='mean', negative_mode='unpaired', pool="all"):
         super().__init__()
+        if pool not in POOLS:
+            raise ValueError(f"InfoNCE: pool must be one of {POOLS} (got {pool!r})")
+        self.pool = pool
         self.temperature = temperature
         self.reduction = reduction
         self.negative_mode = negative_mode
@@ -36,14 +58,30 @@ class InfoNCE(nn.Module):
     def set_global_negatives(self, gather, reduce_scatter, row0):
         self._gather, self._reduce_scatter, self._row0 = gather, reduce_scatter, int(row0)
 
-    def forward(self, query, positive_key, negative_keys=None, packs=None):
+    def forward(self, query, positive_key, negative_keys=None, packs=None, query_mask=None, key_mask=None):
         """packs = (PackedRows of query, PackedRows of positive_key): the inputs are packed rows [M, D] (packing.py); the
-        unmasked mean of infonce.py:32-33 weights each representative pad row by the padded positions it stands for."""
+        unmasked mean of infonce.py:32-33 weights each representative pad row by the padded positions it stands for.
+        pool="real": padded inputs need query_mask / key_mask ([B,S] bool / uint8, non-zero = real); packed rows need pad-free packs
+        (PackedRows(pad_row=False)).  pool="all" reads no mask and refuses a pad-free pack: it has no pad row to weight."""
+        masks = None
+        if self.pool == "real":
+            if packs is not None:
+                if any(getattr(pk, "pad_row", True) and pk.n_pad_rows for pk in packs):
+                    raise ValueError("InfoNCE(pool='real'): packed rows must be pad-free (PackedRows(pad_row=False))")
+            else:
+                if query_mask is None or key_mask is None:
+                    raise ValueError("InfoNCE(pool='real'): padded inputs need query_mask and key_mask ([B,S], non-zero = real)")
+                for m, x in ((query_mask, query), (key_mask, positive_key)):
+                    if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != tuple(x.shape[:2]):
+                        raise ValueError("InfoNCE(pool='real'): a mask must be [batch, seq] bool / uint8 over its input")
+                masks = (query_mask, key_mask)
+        elif packs is not None and any(not getattr(pk, "pad_row", True) and int(pk.counts_host.min()) < pk.S for pk in packs):
+            raise ValueError("InfoNCE(pool='all'): a pad-free pack has no pad row for the mean over all positions (infonce.py:32-33)")
         if packs is not None:
             if negative_keys is not None or self.reduction != 'mean' or query.dim() != 2 or positive_key.dim() != 2 or packs[0].B != packs[1].B:
                 raise ValueError('packed rows: <query> / <positive_key> must be [rows, dim] with one packing each, implicit negatives.')
             return InfoNCEFn.apply(query.float(), positive_key.float(), self, self.training, self._gather, self._reduce_scatter, self._row0, packs,
-                                   grad_anchor(self.parameters()))
+                                   grad_anchor(self.parameters()), masks)
         if negative_keys is not None:
             raise ValueError("explicit negative_keys are unreachable in the reference (infonce.py:98 raises); not supported")
         if self.reduction != 'mean':
@@ -55,7 +93,7 @@ class InfoNCE(nn.Module):
         if len(query) != len(positive_key):
             raise ValueError('<query> and <positive_key> must must have the same number of samples.')
         return InfoNCEFn.apply(query.float(), positive_key.float(), self, self.training, self._gather, self._reduce_scatter, self._row0, None,
-                               grad_anchor(self.parameters()))
+                               grad_anchor(self.parameters()), masks)
 
 
 def info_nce(query, positive_key, negative_keys=None, temperature=0.1, reduction='mean', negative_mode='unpaired'):

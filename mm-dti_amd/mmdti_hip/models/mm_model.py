@@ -37,7 +37,7 @@ from ..packing import PackedRows
 PAIR_RAGGED = os.environ.get("MMDTI_PAIR_RAGGED", "1") != "0"
 from .transformers import TransformerEncoderWithPair
 from .bert_layers import BertCrossEncoder, RobertaTower
-from .infonce import InfoNCE
+from .infonce import InfoNCE, pool_from_env
 from .fds import FDS
 
 BACKBONE = {'transformer': TransformerEncoderWithPair}
@@ -274,7 +274,11 @@ class MM_Model(nn.Module):
             raise ValueError(f"task={self.task!r}: only classification, multilabel_classification and regression are "
                              "constructible in the reference (mm_model.py:481-491)")
         self.CT = CT
-        self.infonce = InfoNCE(self.cross_cfg.hidden_size, self.cross_cfg.hidden_size)
+        # infonce_pool: "all" (the reference: the InfoNCE head averages over every position, padding included, infonce.py:32-33) or
+        # "real" (over the real tokens only -- then NOTHING reads a padded row: packed rows carry no pad row, the packed step is the
+        # padded step under dropout too, and the auto layout below packs in training).  None: MMDTI_INFONCE_POOL, unset = "all".
+        self.infonce_pool = pool_from_env(params.get('infonce_pool'))
+        self.infonce = InfoNCE(self.cross_cfg.hidden_size, self.cross_cfg.hidden_size, pool=self.infonce_pool)
         if self.use_fds and self.task == 'regression':
             raw = params.get('_fds_raw_values', self.fds_raw_path)
             self.FDS = FDS(raw_data=raw, using_scale=self.using_scale, col_data=self.fds_col_data,
@@ -325,7 +329,7 @@ class MM_Model(nn.Module):
         """True iff a padded row meets a live dropout site on its way to the only thing that reads it, the unmasked InfoNCE mean
         (infonce.py:32-33): tower 1 (embedding / residual / attention dropout), tower 2 (hidden / attention dropout), the InfoNCE
         head's query dropout.  (The fusion block and the pool never read padded rows.)"""
-        if not self.training:
+        if not self.training or self.infonce_pool == "real":     # ("real": the mean skips padded rows -- nothing reads them)
             return False
         ps = [self.encoder.emb_dropout, self.encoder.dropout, self.encoder.attention_dropout, self.bert.cfg.hidden_dropout, self.bert.cfg.attn_dropout,
               getattr(self.infonce, "embed_dropout", 0.0)]
@@ -362,14 +366,15 @@ class MM_Model(nn.Module):
         if not (ops.PAIR_COMPACT and ops.pair_tiled_ok(N)):
             return None                                   # (the packed pair kernels exist for the compact tiled planes)
         c = self._pack_cache
-        if c is not None and c[0] is atom_counts and c[1] is token_counts and c[2] == (B, N, L, src_tokens.device):
+        if c is not None and c[0] is atom_counts and c[1] is token_counts and c[2] == (B, N, L, src_tokens.device, self.infonce_pool):
             return c[3]
         ac, tc = torch.as_tensor(atom_counts, device="cpu"), torch.as_tensor(token_counts, device="cpu")
         if ac.numel() != B or tc.numel() != B or int(ac.max()) > N or int(tc.max()) > L or int(ac.min()) < 1 or int(tc.min()) < 1:
             return None
         packs = None
         if int(ac.min()) < N or int(tc.min()) < L:         # (nothing padded: the padded layout IS the packed one)
-            pk1, pk2 = PackedRows(ac, N), PackedRows(tc, L)
+            pad_row = self.infonce_pool != "real"        # ("real": no consumer of a padded row is left -- pad-free packs)
+            pk1, pk2 = PackedRows(ac, N, pad_row=pad_row), PackedRows(tc, L, pad_row=pad_row)
             D2, D1 = self.bert.cfg.dim, self.args.encoder_embed_dim
             hd_ok = all(ops.attn_eligible(pk1.max_rows, pk2.max_rows, D // h, D) for D, h in
                         ((D2, self.bert.cfg.heads), (self.cross_cfg.hidden_size, self.cross_cfg.num_attention_heads)))
@@ -378,7 +383,7 @@ class MM_Model(nn.Module):
             #  kernels are bounded by pair_tiled_ok(N) above)
             if hd_ok and D1 == self.cross_cfg.hidden_size:
                 packs = (pk1.to(src_tokens.device), pk2.to(src_tokens.device))
-        self._pack_cache = (atom_counts, token_counts, (B, N, L, src_tokens.device), packs)
+        self._pack_cache = (atom_counts, token_counts, (B, N, L, src_tokens.device, self.infonce_pool), packs)
         return packs
 
     def forward(self, src_tokens, src_distance=None, src_edge_type=None, input_ids=None, attention_mask=None, weights=None,
@@ -455,15 +460,17 @@ class MM_Model(nn.Module):
             # The InfoNCE head and the cross-modal block both start from (encoder_rep, out_bert) and meet only in the loss: the
             # head -- two token-level GEMMs and a dozen latency-bound B x B kernels -- runs on the side stream under the
             # block's GEMMs (and its backward under the block's backward: autograd replays on the forward's stream).
+            # (pool="real" on padded rows: the head's mean runs over the device masks -- no host value, so it captures into a graph)
+            imasks = dict(query_mask=img_mask, key_mask=attention_mask) if self.infonce_pool == "real" and packs is None else {}
             if side is not None and self.infonce_on_side_stream:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    ct_loss = self.infonce(encoder_rep, out_bert, packs=packs)
+                    ct_loss = self.infonce(encoder_rep, out_bert, packs=packs, **imasks)
                 encoder_rep.record_stream(side)
                 out_bert.record_stream(side)
                 infonce_side = True
             else:
-                ct_loss = self.infonce(encoder_rep, out_bert, packs=packs)
+                ct_loss = self.infonce(encoder_rep, out_bert, packs=packs, **imasks)
 
         cross_txt_output_layer, cross_output_layer = self.cross_modal_module(encoder_rep, out_bert, img_mask, attention_mask, packs=packs)
         # mm_model.py:572-576 (zero padded rows, concat, masked mean) in one kernel

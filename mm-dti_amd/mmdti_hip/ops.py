@@ -1098,6 +1098,7 @@ def seq_mean_packed_fwd(x, pack, D, ld):
     """x [pack.M, ld] bf16 -> [B, D] fp32: the unmasked mean over the S padded positions, the representative pad row weighted by
     the number of padded positions it stands for (mmdti_seq_mean_packed_fwd)."""
     _chk(x, BF16, "seq_mean_packed.x", contiguous=False)
+    _needs_pad_row(pack, "seq_mean_packed_fwd")
     if x.shape[0] != pack.M:
         raise MMDTIError("seq_mean_packed_fwd: x does not have the packed row count")
     out = torch.empty(pack.B, D, device=x.device, dtype=F32)
@@ -1106,9 +1107,58 @@ def seq_mean_packed_fwd(x, pack, D, ld):
 
 
 def seq_mean_packed_bwd(dout, pack, D, ld, aux=None, aux_mode=0):
+    _needs_pad_row(pack, "seq_mean_packed_bwd")
     dx = torch.empty(pack.M, ld, device=dout.device, dtype=BF16)
     lib().mmdti_seq_mean_packed_bwd(_stream(), dout.data_ptr(), pack.M, pack.S, D, ld, pack.off.data_ptr(), pack.n_real.data_ptr(),
                                     pack.row_seq.data_ptr(), dx.data_ptr(), _p(aux), 0 if aux is None else aux.stride(0), int(aux_mode))
+    return dx
+
+
+def _needs_pad_row(pack, what):
+    # (the unmasked mean of infonce.py:32-33 needs each short sequence's representative pad row: a pad-free pack has none)
+    if not getattr(pack, "pad_row", True) and int(pack.counts_host.min()) < pack.S:
+        raise MMDTIError(f"{what}: a pad-free packing (PackedRows(pad_row=False)) with a sequence shorter than S = {pack.S} has no pad row "
+                         "to weight -- the mean over all positions cannot be formed; use seq_mean_real_* (InfoNCE(pool='real'))")
+
+
+def _real_layout(mask, pack, B, S, what):
+    """-> (mask pointer, row_off pointer, row_seq pointer, rows, keep-alive) for exactly one of a [B,S] mask plane / a pad-free pack."""
+    if (mask is None) == (pack is None):
+        raise MMDTIError(f"{what}: exactly one of mask ([B,S], non-zero = real) and pack (pad-free PackedRows) is given")
+    if pack is not None:
+        if getattr(pack, "pad_row", True) and pack.n_pad_rows:
+            raise MMDTIError(f"{what}: the pack carries representative pad rows; the mean over real tokens takes PackedRows(pad_row=False)")
+        if pack.off is None or (pack.B, pack.S) != (B, S):
+            raise MMDTIError(f"{what}: the pack is not on the device or is not of {B} sequences padded to {S}")
+        return 0, pack.off.data_ptr(), pack.row_seq.data_ptr(), pack.M, None
+    if not mask.is_cuda or tuple(mask.shape) != (B, S) or mask.dtype not in (torch.bool, torch.uint8):
+        raise MMDTIError(f"{what}: mask must be a [{B},{S}] bool / uint8 device tensor")
+    m = _u8(mask)
+    return m.data_ptr(), 0, 0, B * S, m
+
+
+def seq_mean_real_fwd(x, B, S, D, ld, mask=None, pack=None):
+    """x [B*S, ld] bf16 with mask [B,S] (non-zero = real), or x [pack.M, ld] with a pad-free pack -> [B, D] fp32: the mean over each
+    sequence's real rows (mmdti_seq_mean_real_fwd; InfoNCE(pool="real")).  No padded row is read."""
+    _chk(x, BF16, "seq_mean_real.x", contiguous=False)
+    mp, op, _, rows, keep = _real_layout(mask, pack, B, S, "seq_mean_real_fwd")
+    if x.shape[0] != rows or x.stride(0) != ld:
+        raise MMDTIError(f"seq_mean_real_fwd: x must be [{rows}, ld = {ld}] rows")
+    out = torch.empty(B, D, device=x.device, dtype=F32)
+    lib().mmdti_seq_mean_real_fwd(_stream(), x.data_ptr(), B, S, D, ld, mp, op, out.data_ptr())
+    return out
+
+
+def seq_mean_real_bwd(dout, B, S, D, ld, mask=None, pack=None, aux=None, aux_mode=0):
+    """-> dx [rows, ld] bf16 = dout[b] / count_b (times aux / gelu'(aux), aux_mode 1 / 2) in real rows; exact zeros in masked rows and
+    in the pad columns D..ld (mmdti_seq_mean_real_bwd)."""
+    _chk(dout, F32, "seq_mean_real.dout")
+    mp, op, sp, rows, keep = _real_layout(mask, pack, B, S, "seq_mean_real_bwd")
+    if tuple(dout.shape) != (B, D) or (aux is not None and aux.shape[0] != rows):
+        raise MMDTIError(f"seq_mean_real_bwd: dout must be [{B}, {D}] and aux have {rows} rows")
+    dx = torch.empty(rows, ld, device=dout.device, dtype=BF16)
+    lib().mmdti_seq_mean_real_bwd(_stream(), dout.data_ptr(), rows, B, S, D, ld, mp, op, sp, dx.data_ptr(), _p(aux),
+                                  0 if aux is None else aux.stride(0), int(aux_mode))
     return dx
 
 

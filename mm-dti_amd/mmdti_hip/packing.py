@@ -20,6 +20,10 @@ gathering any per-position input there picks up the pad value).
 
 With dropout ON the reference draws an independent mask for every padded row; one weighted row is then equal in expectation
 only -- ``MM_Model(strict_reference=True)`` keeps the padded computation.
+
+``PackedRows(..., pad_row=False)`` is the layout of a model in which nothing reads a padded row (``InfoNCE(pool="real")``: the head
+averages over the real tokens only): sequence ``b`` owns exactly its ``n_real[b]`` real rows, ``M = sum(counts)``, and the packed step is
+the padded step itself, dropout included.
 """
 from __future__ import annotations
 
@@ -27,14 +31,16 @@ import torch
 
 
 class PackedRows:
-    """counts: [B] integers on the HOST (real length of every sequence, 1 <= counts[b] <= S); S: the padded length."""
+    """counts: [B] integers on the HOST (real length of every sequence, 1 <= counts[b] <= S); S: the padded length.
+    pad_row=False: no representative pad row -- rows = counts (for consumers that read no padded row)."""
 
-    def __init__(self, counts, S: int, device=None):
+    def __init__(self, counts, S: int, device=None, pad_row=True):
         c = torch.as_tensor(counts, device="cpu").to(torch.int64).reshape(-1)
         if c.numel() == 0 or int(c.min()) < 1 or int(c.max()) > S:
             raise ValueError(f"PackedRows: lengths must lie in [1, {S}] (got min {int(c.min()) if c.numel() else None}, max {int(c.max()) if c.numel() else None})")
         B = c.numel()
-        rows = c + (c < S).to(torch.int64)                     # + the representative pad row
+        self.pad_row = bool(pad_row)
+        rows = c + (c < S).to(torch.int64) if self.pad_row else c.clone()          # + the representative pad row
         off = torch.zeros(B + 1, dtype=torch.int64)
         torch.cumsum(rows, 0, out=off[1:])
         M = int(off[-1])
@@ -45,7 +51,7 @@ class PackedRows:
         self.counts_host, self.rows_host, self.off_host = c, rows, off
         self.gather_host = seq * S + local                     # flat index into the padded [B*S] arrays
         self.seq_host, self.local_host = seq, local
-        self.n_pad_rows = int((c < S).sum())
+        self.n_pad_rows = int((c < S).sum()) if self.pad_row else 0
         # device images (filled by to(): ONE int32 upload + one int64 upload)
         self.off = self.n_real = self.row_seq = self.gather = None
         if device is not None:
@@ -66,13 +72,19 @@ class PackedRows:
         return x.reshape(self.B * self.S, *x.shape[2:])[self.gather.to(x.device)]
 
     def unpack(self, xp):
-        """[M, ...] -> [B, S, ...]: every padded position receives its sequence's representative pad row."""
+        """[M, ...] -> [B, S, ...]: every padded position receives its sequence's representative pad row (pad_row=False: zeros)."""
         pos = torch.arange(self.S, dtype=torch.int64).view(1, -1)
+        if not self.pad_row:
+            real = (pos < self.counts_host.view(-1, 1)).reshape(-1)
+            out = xp.new_zeros(self.B * self.S, *xp.shape[1:])
+            out[real.to(xp.device)] = xp
+            return out.view(self.B, self.S, *xp.shape[1:])
         idx = self.off_host[:-1].view(-1, 1) + torch.minimum(pos, self.counts_host.view(-1, 1))
         return xp[idx.reshape(-1).to(xp.device)].view(self.B, self.S, *xp.shape[1:])
 
     def pad_weights(self):
-        """[M] fp32 on the host: 1 for a real row, S - n_real for the representative pad row (the InfoNCE mean's weights x S)."""
+        """[M] fp32 on the host: 1 for a real row, S - n_real for the representative pad row (the InfoNCE mean's weights x S);
+        all ones without pad rows."""
         w = torch.ones(self.M, dtype=torch.float32)
         is_pad = self.local_host >= self.counts_host[self.seq_host]
         w[is_pad] = (self.S - self.counts_host[self.seq_host][is_pad]).to(torch.float32)

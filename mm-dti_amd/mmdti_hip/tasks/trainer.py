@@ -375,6 +375,10 @@ class Trainer(object):
             for name, count, elements, scale, wd in engine.param_group_summary():
                 logger.info('param group {}: {} parameters, {} elements, lr_scale {:g}, weight_decay {:g}{}'.format(
                     name, count, elements, scale, wd, ' (decoupled)' if self.decoupled_weight_decay else ''))
+        pool = getattr(model, "infonce_pool", "all")
+        logger.info('InfoNCE pooling: {}'.format(
+            'real tokens only (packed token rows without pad rows; the auto layout packs in training)' if pool == "real"
+            else 'all positions, padding included (the reference)'))
         engine.warmup = int(num_training_steps * self.warmup_ratio)
         self._engine = engine
         task_loss = self._task_loss(loss_func)
