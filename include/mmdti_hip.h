@@ -703,6 +703,22 @@ int mmdti_ct_loss_fwd(mmdti_stream_t stream, int mode, const float* fhat, int B,
                                        null: fp32 atomics */);
 /* dfhat[i] = (1/t) * sum_j (G[i,j]+G[j,i]) fhat[j] */
 int mmdti_ct_loss_bwd(mmdti_stream_t stream, const float* fhat, const float* G, int B, int D, float t, float* dfhat);
+/* Row-block form (global ConR / SupCon negatives under data parallelism): the ranks' local batches concatenated in rank order are
+ * one batch of Bg rows; this rank's anchors are rows [row0, row0 + rows) and their keys are all Bg rows.  fhat_all [Bg,D],
+ * labels_f_all [Bg] / labels_i_all [Bg,C] / pred_all [Bg] / weights_all [Bg] (nullable) are the GATHERED arrays, indexed by global
+ * row.  Per-anchor terms are those of mmdti_ct_loss_fwd on the Bg-row batch (same kernel body, same summation orders):
+ *   loss   (scalar, overwritten) = (1/Bg) sum over this block's anchors: the block's share, the shares of a partition add up to
+ *          the loss of the whole batch;
+ *   G      [rows, Bg] = d(share)/d prod for the block's anchors; row_ws [rows] (nullable as above): the per-anchor terms / Bg.
+ * row0 = 0, rows = Bg is mmdti_ct_loss_fwd bit for bit.  Purely additive: MMDTI_ABI_VERSION does not move. */
+int mmdti_ct_loss_rows_fwd(mmdti_stream_t stream, int mode, const float* fhat_all, int Bg, int D, int row0, int rows,
+                           const float* labels_f_all, const long long* labels_i_all, int C, const float* pred_all,
+                           const float* weights_all, float w, float t, float e, float coef, float* loss, float* G, float* row_ws);
+/* The block's contribution to EVERY row of the feature gradient (all Bg rows written, one writer per element, no atomics):
+ *   dfhat_all[k] = (1/t) sum_j ([j in block] G[j-row0,k] + [k in block] G[k-row0,j]) fhat_all[j].
+ * Summed over the blocks of a partition it is mmdti_ct_loss_bwd's dfhat; with row0 = 0, rows = Bg it is that, bit for bit. */
+int mmdti_ct_loss_rows_bwd(mmdti_stream_t stream, const float* fhat_all, const float* G, int Bg, int D, int row0, int rows, float t,
+                           float* dfhat_all);
 
 /* ---- FDS (models/fds.py; utils/util.py:159-169) --------------------------------------------- */
 /* bins[i] = int((label_i - min_value)//bin_width) in fp32 floor-division arithmetic (fds.py:125,164), int32;

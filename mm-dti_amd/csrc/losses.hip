@@ -546,16 +546,19 @@ __global__ __launch_bounds__(256) void infonce_cols_mfma_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------- ConR / SupCon
-// block per anchor i.  prod_ij = <f_i,f_j>/t.  See contrastive.py for the masks.
-__global__ __launch_bounds__(256) void ct_fwd_kernel(int mode, const float* __restrict__ fh, int B, int D, const float* __restrict__ lab_f,
-                                                     const long long* __restrict__ lab_i, int C, const float* __restrict__ pred,
-                                                     const float* __restrict__ wts, float w, float invt, float e, float thr,
-                                                     float* __restrict__ loss, float* __restrict__ G, float* __restrict__ row_ws) {
+// block per anchor.  prod_ij = <f_i,f_j>/t.  See contrastive.py for the masks.
+// One body for the square form (every row of the batch is an anchor) and the row-block form (anchors [row0, row0 + gridDim.x) of a
+// B-row batch gathered from all ranks, against all B keys): anchor i = row0 + il, its row of G and its slot of row_ws are il; labels,
+// predictions and weights are indexed by global row.  The square kernel is row0 = 0 with B blocks.
+__device__ __forceinline__ void ct_fwd_body(int mode, const float* __restrict__ fh, int B, int D, int row0, const float* __restrict__ lab_f,
+                                            const long long* __restrict__ lab_i, int C, const float* __restrict__ pred,
+                                            const float* __restrict__ wts, float w, float invt, float e, float thr,
+                                            float* __restrict__ loss, float* __restrict__ G, float* __restrict__ row_ws) {
   extern __shared__ float sm[];  // frow[D] | prod[B] | red[4]
   float* frow = sm;
   float* prod = sm + D;
   float* red = prod + B;
-  const int i = blockIdx.x;
+  const int il = blockIdx.x, i = row0 + il;
   for (int d = threadIdx.x; d < D; d += 256) frow[d] = fh[(long long)i * D + d];
   __syncthreads();
   float e_pos = 0.f, e_neg = 0.f, npos = 0.f, nneg = 0.f, nle = 0.f, spos = 0.f;
@@ -593,7 +596,7 @@ __global__ __launch_bounds__(256) void ct_fwd_kernel(int mode, const float* __re
     nneg += neg ? 1.f : 0.f;
     spos += pos ? s : 0.f;
     // stash the mask class in G for the second pass: 1 = pos, 2 = neg (scaled later)
-    G[(long long)i * B + j] = pos ? 1.f : (neg ? 2.f : 0.f);
+    G[(long long)il * B + j] = pos ? 1.f : (neg ? 2.f : 0.f);
   }
   e_pos = block_sum(e_pos, red);
   e_neg = block_sum(e_neg, red);
@@ -606,12 +609,12 @@ __global__ __launch_bounds__(256) void ct_fwd_kernel(int mode, const float* __re
   const float flag = nneg > 0.f ? 1.f : 0.f;
   const float li = flag * (npos * __logf(Dn) - spos) / denom;
   if (threadIdx.x == 0) {
-    if (row_ws) row_ws[i] = li / (float)B;      // (summed in row order by ordered_sum_kernel: reproducible to the bit)
+    if (row_ws) row_ws[il] = li / (float)B;      // (summed in row order by ordered_sum_kernel: reproducible to the bit)
     else atomicAdd(loss, li / (float)B);
   }
   const float cg = flag / denom / (float)B;
   for (int j = threadIdx.x; j < B; j += 256) {
-    const float cls = G[(long long)i * B + j];
+    const float cls = G[(long long)il * B + j];
     float g = 0.f;
     if (cls == 1.f) {
       g = cg * (npos / Dn * __expf(prod[j]) - 1.f);
@@ -621,8 +624,23 @@ __global__ __launch_bounds__(256) void ct_fwd_kernel(int mode, const float* __re
       else pw = wts ? wts[j] : 1.f;
       g = cg * (npos / Dn * pw * __expf(prod[j]));
     }
-    G[(long long)i * B + j] = g;
+    G[(long long)il * B + j] = g;
   }
+}
+
+__global__ __launch_bounds__(256) void ct_fwd_kernel(int mode, const float* __restrict__ fh, int B, int D, const float* __restrict__ lab_f,
+                                                     const long long* __restrict__ lab_i, int C, const float* __restrict__ pred,
+                                                     const float* __restrict__ wts, float w, float invt, float e, float thr,
+                                                     float* __restrict__ loss, float* __restrict__ G, float* __restrict__ row_ws) {
+  ct_fwd_body(mode, fh, B, D, 0, lab_f, lab_i, C, pred, wts, w, invt, e, thr, loss, G, row_ws);
+}
+// anchors [row0, row0 + gridDim.x) of the gathered batch: G [gridDim.x, Bg], row_ws [gridDim.x] (terms already divided by Bg)
+__global__ __launch_bounds__(256) void ct_rows_fwd_kernel(int mode, const float* __restrict__ fh, int Bg, int D, int row0,
+                                                          const float* __restrict__ lab_f, const long long* __restrict__ lab_i, int C,
+                                                          const float* __restrict__ pred, const float* __restrict__ wts, float w, float invt,
+                                                          float e, float thr, float* __restrict__ loss, float* __restrict__ G,
+                                                          float* __restrict__ row_ws) {
+  ct_fwd_body(mode, fh, Bg, D, row0, lab_f, lab_i, C, pred, wts, w, invt, e, thr, loss, G, row_ws);
 }
 
 // out = x[0] + x[1] + ... in index order (one thread: the n per-row terms of a loss)
@@ -632,17 +650,39 @@ __global__ void ordered_sum_kernel(const float* __restrict__ x, int n, float* __
   *out = t;
 }
 
-__global__ __launch_bounds__(256) void ct_bwd_kernel(const float* __restrict__ fh, const float* __restrict__ G, int B, int D, float invt,
-                                                     float* __restrict__ dfh) {
+// dfh[k] = (1/t) sum_j c_j fh[j], c_j = [j owned] G[j,k] + [k owned] G[k,j], for the owned anchors [row0, row0 + rows) whose G rows
+// are held ([rows, B]).  One workgroup per row k of the batch, one writer per element.  The square form owns every row.  A row k that
+// is not owned has c_j = 0 outside the owned rows, and the j loop runs over those alone (same order, zero terms left out).
+// SQUARE: the ownership tests and loop bounds are compile-time facts (row0 = 0, rows = B).
+template <bool SQUARE>
+__device__ __forceinline__ void ct_bwd_body(const float* __restrict__ fh, const float* __restrict__ G, int B, int D, int row0, int rows, float invt,
+                                            float* __restrict__ dfh) {
   extern __shared__ float gs[];  // [B] combined coefficient
-  const int i = blockIdx.x;
-  for (int j = threadIdx.x; j < B; j += 256) gs[j] = (G[(long long)i * B + j] + G[(long long)j * B + i]) * invt;
+  const int k = blockIdx.x;
+  const bool kown = SQUARE || (k >= row0 && k < row0 + rows);
+  const int jlo = kown ? 0 : row0, jhi = kown ? B : row0 + rows;
+  for (int j = jlo + threadIdx.x; j < jhi; j += 256) {
+    const bool jown = SQUARE || (j >= row0 && j < row0 + rows);
+    const float a = kown ? G[(long long)(k - row0) * B + j] : 0.f;
+    const float b = jown ? G[(long long)(j - row0) * B + k] : 0.f;
+    gs[j] = (a + b) * invt;
+  }
   __syncthreads();
   for (int d = threadIdx.x; d < D; d += 256) {
     float s = 0.f;
-    for (int j = 0; j < B; ++j) s += gs[j] * fh[(long long)j * D + d];
-    dfh[(long long)i * D + d] = s;
+    const float* gj = gs + jlo;
+    const float* fj = fh + (long long)jlo * D + d;
+    for (int j = 0; j < jhi - jlo; ++j) s += gj[j] * fj[(long long)j * D];
+    dfh[(long long)k * D + d] = s;
   }
+}
+__global__ __launch_bounds__(256) void ct_bwd_kernel(const float* __restrict__ fh, const float* __restrict__ G, int B, int D, float invt,
+                                                     float* __restrict__ dfh) {
+  ct_bwd_body<true>(fh, G, B, D, 0, B, invt, dfh);
+}
+__global__ __launch_bounds__(256) void ct_rows_bwd_kernel(const float* __restrict__ fh, const float* __restrict__ G, int Bg, int D, int row0,
+                                                          int rows, float invt, float* __restrict__ dfh) {
+  ct_bwd_body<false>(fh, G, Bg, D, row0, rows, invt, dfh);
 }
 
 // ---------------------------------------------------------------- FDS
@@ -1276,6 +1316,45 @@ extern "C" int mmdti_ct_loss_bwd(mmdti_stream_t stream, const float* fhat, const
   MMDTI_REQUIRE(fhat && G && dfhat && B > 0 && D > 0 && t > 0.f, "ct_loss_bwd: bad arguments");
   MMDTI_REQUIRE((size_t)B * sizeof(float) <= 64 * 1024, "ct_loss_bwd: B too large");
   hipLaunchKernelGGL(ct_bwd_kernel, dim3(B), dim3(256), (size_t)B * sizeof(float), (hipStream_t)stream, fhat, G, B, D, 1.0f / t, dfhat);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+extern "C" int mmdti_ct_loss_rows_fwd(mmdti_stream_t stream, int mode, const float* fhat_all, int Bg, int D, int row0, int rows,
+                                      const float* labels_f_all, const long long* labels_i_all, int C, const float* pred_all,
+                                      const float* weights_all, float w, float t, float e, float coef, float* loss, float* G, float* row_ws) {
+  MMDTI_REQUIRE(mode >= 0 && mode <= 2, "ct_loss_rows_fwd: bad mode %d", mode);
+  MMDTI_REQUIRE(fhat_all, "ct_loss_rows_fwd: fhat_all is null");
+  MMDTI_REQUIRE(loss, "ct_loss_rows_fwd: loss is null");
+  MMDTI_REQUIRE(G, "ct_loss_rows_fwd: G is null");
+  MMDTI_REQUIRE(Bg > 0 && D > 0, "ct_loss_rows_fwd: bad sizes (Bg=%d D=%d)", Bg, D);
+  MMDTI_REQUIRE(row0 >= 0 && rows > 0 && (long long)row0 + rows <= Bg, "ct_loss_rows_fwd: bad row block (row0=%d rows=%d Bg=%d)", row0, rows, Bg);
+  MMDTI_REQUIRE(t > 0.f, "ct_loss_rows_fwd: t must be positive");
+  MMDTI_REQUIRE(mode == MMDTI_CT_MULTI ? (labels_i_all && C > 0) : (labels_f_all != nullptr), "ct_loss_rows_fwd: labels missing");
+  MMDTI_REQUIRE(mode != MMDTI_CT_REGRESS || pred_all, "ct_loss_rows_fwd: regress needs predictions (pred_all)");
+  const size_t smem = ((size_t)D + Bg + 4) * sizeof(float);
+  MMDTI_REQUIRE(smem <= 64 * 1024, "ct_loss_rows_fwd: Bg+D too large for LDS");
+  MMDTI_REQUIRE(row_ws || !det_table().on(), "ct_loss_rows_fwd: deterministic mode needs row_ws (without it the per-row terms meet in an atomic)");
+  hipStream_t s = (hipStream_t)stream;
+  if (!row_ws && hipMemsetAsync(loss, 0, sizeof(float), s) != hipSuccess) { set_error("ct_loss_rows_fwd: memset failed"); return MMDTI_ERR_LAUNCH; }
+  const float thr = mode == MMDTI_CT_MULTI ? (float)((double)coef / (double)C) : 0.f;
+  hipLaunchKernelGGL(ct_rows_fwd_kernel, dim3(rows), dim3(256), smem, s, mode, fhat_all, Bg, D, row0, labels_f_all, labels_i_all, C, pred_all,
+                     weights_all, w, 1.0f / t, e, thr, loss, G, row_ws);
+  if (row_ws) hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(1), 0, s, row_ws, rows, loss);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_ct_loss_rows_bwd(mmdti_stream_t stream, const float* fhat_all, const float* G, int Bg, int D, int row0, int rows, float t,
+                                      float* dfhat_all) {
+  MMDTI_REQUIRE(fhat_all, "ct_loss_rows_bwd: fhat_all is null");
+  MMDTI_REQUIRE(G, "ct_loss_rows_bwd: G is null");
+  MMDTI_REQUIRE(dfhat_all, "ct_loss_rows_bwd: dfhat_all is null");
+  MMDTI_REQUIRE(Bg > 0 && D > 0, "ct_loss_rows_bwd: bad sizes (Bg=%d D=%d)", Bg, D);
+  MMDTI_REQUIRE(row0 >= 0 && rows > 0 && (long long)row0 + rows <= Bg, "ct_loss_rows_bwd: bad row block (row0=%d rows=%d Bg=%d)", row0, rows, Bg);
+  MMDTI_REQUIRE(t > 0.f, "ct_loss_rows_bwd: t must be positive");
+  MMDTI_REQUIRE((size_t)Bg * sizeof(float) <= 64 * 1024, "ct_loss_rows_bwd: Bg too large for LDS");
+  hipLaunchKernelGGL(ct_rows_bwd_kernel, dim3(Bg), dim3(256), (size_t)Bg * sizeof(float), (hipStream_t)stream, fhat_all, G, Bg, D, row0, rows,
+                     1.0f / t, dfhat_all);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

@@ -1563,21 +1563,45 @@ class InfoNCELossFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------- ConR / SupCon
 class CTLossFn(torch.autograd.Function):
     """CT_Regress / CT_Single / CT_Multi (models/contrastive.py).  Only `feature` receives a gradient (the masks built
-    from labels / predictions are not differentiable in the reference either)."""
+    from labels / predictions are not differentiable in the reference either).
+
+    negatives (optional, trailing): global negatives under data parallelism -- anything with ``gather(x [B_loc, C]) -> [B_glob, C]`` in
+    rank order, ``reduce_scatter(g [B_glob, C]) -> [B_loc, C]`` (sum over ranks, own rows) and ``row0`` (this rank's first global row:
+    an int, or a callable of B_loc as parallel.GlobalNegatives.row0).  The local rows are normalised here, the payload is gathered
+    (parallel.CTPayload), this rank's anchors meet every rank's keys, and the value returned is this rank's SHARE of the loss of the
+    union batch: (1/B_glob) sum over own anchors.  The backward produces own anchors' contribution to every row, the adjoint of the
+    gather returns the rows of own molecules, and the normalisation's backward stays local."""
 
     @staticmethod
-    def forward(ctx, feature, mode, labels_f, labels_i, pred, weights, w, t, e, coef):
+    def forward(ctx, feature, mode, labels_f, labels_i, pred, weights, w, t, e, coef, negatives=None):
         f = feature.reshape(feature.shape[0], -1).contiguous()
         fh, inv = ops.l2norm_fwd(f)
+        ctx.negatives = negatives
+        if negatives is not None:
+            from .parallel import CTPayload
+            Bl = fh.shape[0]
+            row0 = negatives.row0
+            row0 = int(row0(Bl) if callable(row0) else row0)
+            fa, la, lia, pa, wa = CTPayload.gather(negatives, fh, labels_f=labels_f, labels_i=labels_i, pred=pred, weights=weights)
+            if fa.shape[0] % Bl != 0 or row0 + Bl > fa.shape[0]:
+                raise ValueError(f"CTLossFn: gathered {fa.shape[0]} rows for {Bl} local ones at row0 = {row0}")
+            loss, G, _ = ops.ct_loss_rows_fwd(mode, fa, row0, Bl, labels_f=la, labels_i=lia, pred=pa, weights=wa, w=w, t=t, e=e, coef=coef)
+            ctx.sv, ctx.t, ctx.shape, ctx.row0 = (fh, inv, G, fa), t, feature.shape, row0
+            return loss.view(())
         loss, G = ops.ct_loss_fwd(mode, fh, labels_f=labels_f, labels_i=labels_i, pred=pred, weights=weights, w=w, t=t, e=e, coef=coef)
         ctx.sv, ctx.t, ctx.shape = (fh, inv, G), t, feature.shape
         return loss.view(())
 
     @staticmethod
     def backward(ctx, dl):
+        if ctx.negatives is not None:
+            fh, inv, G, fa = ctx.sv
+            dfa = ops.ct_loss_rows_bwd(fa, G, ctx.row0, ctx.t)
+            df = ops.l2norm_bwd(ctx.negatives.reduce_scatter(dfa).contiguous(), fh, inv)
+            return (df * dl).view(ctx.shape), None, None, None, None, None, None, None, None, None, None
         fh, inv, G = ctx.sv
         df = ops.l2norm_bwd(ops.ct_loss_bwd(fh, G, ctx.t), fh, inv)
-        return (df * dl).view(ctx.shape), None, None, None, None, None, None, None, None, None
+        return (df * dl).view(ctx.shape), None, None, None, None, None, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------- FDS smooth / pool / head / losses

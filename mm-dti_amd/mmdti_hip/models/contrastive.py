@@ -7,6 +7,11 @@ runs ``for i in range(B): pos_i[i][i] = 0`` and, in CT_Multi, a B^2 Python loop 
 Reference quirks kept: masked-out logits contribute exp(0)=1 to the positive denominator (:35,:52); ConR's ``denom``
 counts the anchor itself (:49); SupCon/Multi weights broadcast along KEYS (:95,:150); ``output`` only shapes ConR's
 hard-negative mask and gets no gradient; ``lamda`` is accepted and ignored.
+
+Extension for data parallelism (absent from the reference): a trailing keyword ``negatives`` (see functional.CTLossFn) makes the keys
+GLOBAL -- this rank's anchors against the molecules of every rank -- and the value this rank's share of the union batch's loss.
+Whether a weight column travels is decided here on the host (``None`` / the host ``tensor([1])`` -> none), never from a device value:
+every rank must take the same decision, which holds because all ranks share ``use_weight``.
 """
 import torch
 
@@ -40,27 +45,27 @@ def _weights(weights, B, per_anchor, device=None):
     return w.contiguous()
 
 
-def CT_Regress(feature, depth, output, weights=None, w=0.2, t=0.07, e=0.01):
+def CT_Regress(feature, depth, output, weights=None, w=0.2, t=0.07, e=0.01, negatives=None):
     B = feature.shape[0]
     lab = _f32(depth).reshape(B, -1).mean(dim=1).contiguous()
     pred = _f32(output).reshape(B, -1).mean(dim=1).contiguous()
     wt = None
     if weights is not None:
         wt = _weights(weights, B, per_anchor=True, device=feature.device)
-    return CTLossFn.apply(feature.float(), ops.CT_REGRESS, lab, None, pred, wt, float(w), float(t), float(e), 1.0)
+    return CTLossFn.apply(feature.float(), ops.CT_REGRESS, lab, None, pred, wt, float(w), float(t), float(e), 1.0, negatives)
 
 
-def CT_Single(feature, depth, output, weights=torch.tensor([1]), w=0.2, t=0.07, e=0.2, lamda=1):
+def CT_Single(feature, depth, output, weights=torch.tensor([1]), w=0.2, t=0.07, e=0.2, lamda=1, negatives=None):
     B = feature.shape[0]
     lab = _f32(depth).reshape(B, -1)
     if lab.shape[1] != 1:
         raise ValueError("CT_Single expects one label per sample")
     wt = _weights(weights, B, per_anchor=False, device=feature.device)
-    return CTLossFn.apply(feature.float(), ops.CT_SINGLE, lab.reshape(B).contiguous(), None, None, wt, float(w), float(t), float(e), 1.0)
+    return CTLossFn.apply(feature.float(), ops.CT_SINGLE, lab.reshape(B).contiguous(), None, None, wt, float(w), float(t), float(e), 1.0, negatives)
 
 
-def CT_Multi(feature, depth, output, weights=None, w=0.2, t=0.07, e=0.2, coef=1):
+def CT_Multi(feature, depth, output, weights=None, w=0.2, t=0.07, e=0.2, coef=1, negatives=None):
     B = feature.shape[0]
     lab = depth.detach().reshape(B, -1).to(torch.int64).contiguous()
     wt = None if weights is None else _weights(weights, B, per_anchor=False, device=feature.device)
-    return CTLossFn.apply(feature.float(), ops.CT_MULTI, None, lab, None, wt, float(w), float(t), float(e), float(coef))
+    return CTLossFn.apply(feature.float(), ops.CT_MULTI, None, lab, None, wt, float(w), float(t), float(e), float(coef), negatives)

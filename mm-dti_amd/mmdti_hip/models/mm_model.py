@@ -274,6 +274,7 @@ class MM_Model(nn.Module):
             raise ValueError(f"task={self.task!r}: only classification, multilabel_classification and regression are "
                              "constructible in the reference (mm_model.py:481-491)")
         self.CT = CT
+        self._ct_negatives = None            # set_global_contrast: global ConR / SupCon keys under data parallelism (None: rank-local)
         # infonce_pool: "all" (the reference: the InfoNCE head averages over every position, padding included, infonce.py:32-33) or
         # "real" (over the real tokens only -- then NOTHING reads a padded row: packed rows carry no pad row, the packed step is the
         # padded step under dropout too, and the auto layout below packs in training).  None: MMDTI_INFONCE_POOL, unset = "all".
@@ -386,6 +387,12 @@ class MM_Model(nn.Module):
         self._pack_cache = (atom_counts, token_counts, (B, N, L, src_tokens.device, self.infonce_pool), packs)
         return packs
 
+    def set_global_contrast(self, gather, reduce_scatter, row0):
+        """Global ConR / SupCon keys under data parallelism (beside InfoNCE.set_global_negatives): ``gather`` / ``reduce_scatter`` are the
+        all-gather of [B_loc, C] rows in rank order and its adjoint, ``row0`` this rank's first row of the global batch.  ``gather=None``
+        returns to rank-local keys.  The CT term is then this rank's share of the union batch's loss (models/contrastive.py)."""
+        self._ct_negatives = None if gather is None else SimpleNamespace(gather=gather, reduce_scatter=reduce_scatter, row0=int(row0))
+
     def forward(self, src_tokens, src_distance=None, src_edge_type=None, input_ids=None, attention_mask=None, weights=None,
                 return_infonce_loss=False, return_ct_loss=False, return_feature=False, net_target=None, use_weight=None,
                 epoch=0, atom_counts=None, token_counts=None, token_pad_id=None, packable=False, src_coord=None, **kwargs):
@@ -492,10 +499,12 @@ class MM_Model(nn.Module):
 
         rnc_loss = None
         if return_ct_loss and net_target is not None:
+            # (rank-local keys: the call is the reference's, no extra argument)
+            gkw = {} if self._ct_negatives is None else dict(negatives=self._ct_negatives)
             if use_weight:
-                rnc_loss = self.CT(classification_feats_pooled, net_target, logits, weights=weights, w=self.ct_w)
+                rnc_loss = self.CT(classification_feats_pooled, net_target, logits, weights=weights, w=self.ct_w, **gkw)
             else:
-                rnc_loss = self.CT(classification_feats_pooled, net_target, logits, w=self.ct_w)
+                rnc_loss = self.CT(classification_feats_pooled, net_target, logits, w=self.ct_w, **gkw)
         if infonce_side:
             main.wait_stream(side)
             ct_loss.record_stream(main)

@@ -1204,6 +1204,36 @@ def ct_loss_bwd(fhat, G, t=0.07):
     return d
 
 
+def ct_loss_rows_fwd(mode, fhat_all, row0, rows, labels_f=None, labels_i=None, pred=None, weights=None, w=0.2, t=0.07, e=0.01, coef=1.0):
+    """Anchors [row0, row0 + rows) of the gathered batch fhat_all [Bg, D] against all Bg keys (global ConR / SupCon negatives); labels,
+    predictions and weights are the gathered [Bg] arrays.  -> (loss_share [1] = (1/Bg) sum of the block's per-anchor terms, G [rows, Bg],
+    row_terms [rows] = the per-anchor terms / Bg, summed in row order into loss_share)."""
+    _chk(fhat_all, F32, "ct_loss_rows.fhat_all")
+    Bg, D = fhat_all.shape
+    for what, v in (("labels_f", labels_f), ("pred", pred), ("weights", weights)):       # (the kernel indexes them by global row)
+        if v is not None and (v.dtype != F32 or tuple(v.shape) != (Bg,) or not v.is_contiguous()):
+            raise MMDTIError(f"ct_loss_rows_fwd: {what} must be a contiguous [{Bg}] fp32 tensor (the gathered batch)")
+    if labels_i is not None and (labels_i.dtype != torch.int64 or labels_i.dim() != 2 or labels_i.shape[0] != Bg or not labels_i.is_contiguous()):
+        raise MMDTIError(f"ct_loss_rows_fwd: labels_i must be a contiguous [{Bg}, C] int64 tensor (the gathered batch)")
+    buf = torch.empty(1 + rows, device=fhat_all.device, dtype=F32)
+    G = torch.empty(rows, Bg, device=fhat_all.device, dtype=F32)
+    C = 0 if labels_i is None else labels_i.shape[1]
+    lib().mmdti_ct_loss_rows_fwd(_stream(), mode, fhat_all.data_ptr(), Bg, D, int(row0), int(rows), _p(labels_f), _p(labels_i), C, _p(pred),
+                                 _p(weights), float(w), float(t), float(e), float(coef), buf.data_ptr(), G.data_ptr(), buf.data_ptr() + 4)
+    return buf[:1], G, buf[1:]
+
+
+def ct_loss_rows_bwd(fhat_all, G, row0, t=0.07):
+    """-> dfhat_all [Bg, D]: the block's contribution to every row's gradient (sum over the blocks of a partition = ct_loss_bwd)."""
+    _chk(fhat_all, F32, "ct_loss_rows.fhat_all")
+    Bg, D = fhat_all.shape
+    if G.dtype != F32 or G.dim() != 2 or G.shape[1] != Bg or not G.is_contiguous():
+        raise MMDTIError(f"ct_loss_rows_bwd: G must be a contiguous [rows, {Bg}] fp32 tensor")
+    d = torch.empty_like(fhat_all)
+    lib().mmdti_ct_loss_rows_bwd(_stream(), fhat_all.data_ptr(), G.data_ptr(), Bg, D, int(row0), G.shape[0], float(t), d.data_ptr())
+    return d
+
+
 # --------------------------------------------------------------------------------------------- FDS
 def fds_bins(labels, min_value, bin_width, bucket_start, bucket_num):
     _chk(labels, F32, "fds_bins.labels")

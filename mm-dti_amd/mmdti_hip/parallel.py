@@ -10,6 +10,10 @@ global batch reproduce the single-process loss and gradients:
   * ConR / SupCon and the task loss stay rank-local means; the step loss is the mean over ranks, so gradients are
     all-reduced with op=AVG, except InfoNCE whose value is already this rank's share of the global loss (hence its
     gradient is pre-multiplied by world_size before the AVG);
+  * opt-in (FineTuner(global_ct=True) / MMDTI_GLOBAL_CT=1): ConR / SupCon keys are GLOBAL too -- each rank contributes
+    [B_loc, D + 3] = f-hat | label | pred | weight through one all-gather (CTPayload; multilabel labels as a second, int64
+    one), its anchors meet every rank's keys, the adjoint is a sum-reduce of the [B_glob, D] gradient from which each rank
+    keeps its rows, and the term is scaled like InfoNCE's;
   * gradients live in ONE flat fp32 arena (runtime.ParamArena): the all-reduce walks it in large buckets on a side HIP
     stream, and is launched bucket by bucket while the backward of earlier layers is still running (a bucket goes out
     as soon as every parameter in it has reported its gradients enqueued -- ArenaReducer.on_grads_ready).  xGMI is point-to-point (7 links x ~153 GB/s per GPU): a
@@ -99,6 +103,51 @@ class GlobalNegatives:
 
     def row0(self, b_loc: int) -> int:
         return self.rank * b_loc
+
+
+class CTPayload:
+    """What a rank contributes to the global ConR / SupCon term, as ONE fp32 message [B_loc, D + 3]:  f̂ | label | pred | weight.
+
+    Columns that a mode does not use travel as zeros, so the message has one width (B_loc (D + 3) 4 bytes) and every rank builds the
+    same layout without exchanging a description: whether weights are used (``use_weight``) is a host-side decision all ranks share.
+    Multilabel labels ([B_loc, C] int64, -1 = missing) do not fit a float column exactly in general and travel as a SECOND message of
+    their own dtype; the fp32 label column is then zero.  Two all-gathers at the most, none of which reads a device value on the host."""
+
+    EXTRA = 3
+
+    @staticmethod
+    def pack(fhat, labels_f=None, pred=None, weights=None):
+        """-> [B_loc, D + 3] fp32 (a fresh tensor; enqueued copies only)"""
+        Bl, D = fhat.shape
+        msg = torch.zeros(Bl, D + CTPayload.EXTRA, device=fhat.device, dtype=torch.float32)
+        msg[:, :D] = fhat
+        for c, v in enumerate((labels_f, pred, weights)):
+            if v is not None:
+                if v.numel() != Bl:
+                    raise ValueError(f"CTPayload.pack: a per-molecule column must have {Bl} elements, got {v.numel()}")
+                msg[:, D + c] = v.reshape(Bl)
+        return msg
+
+    @staticmethod
+    def unpack(msg_all, D, labels_f=False, pred=False, weights=False):
+        """gathered [Bg, D + 3] -> (fhat_all [Bg, D], labels_f_all | None, pred_all | None, weights_all | None), contiguous; the flags
+        say which columns the mode uses (the same host-side facts the sender packed by)."""
+        if msg_all.shape[1] != D + CTPayload.EXTRA:
+            raise ValueError(f"CTPayload.unpack: message width {msg_all.shape[1]} is not D + {CTPayload.EXTRA} = {D + CTPayload.EXTRA}")
+        col = lambda c, on: msg_all[:, D + c].contiguous() if on else None
+        return msg_all[:, :D].contiguous(), col(0, labels_f), col(1, pred), col(2, weights)
+
+    @staticmethod
+    def gather(negatives, fhat, labels_f=None, labels_i=None, pred=None, weights=None):
+        """pack, all-gather (``negatives.gather``: GlobalNegatives' equal-rows check covers it), unpack.
+        -> (fhat_all, labels_f_all, labels_i_all, pred_all, weights_all)"""
+        D = fhat.shape[1]
+        msg_all = negatives.gather(CTPayload.pack(fhat, labels_f, pred, weights))
+        fa, la, pa, wa = CTPayload.unpack(msg_all, D, labels_f is not None, pred is not None, weights is not None)
+        lia = None
+        if labels_i is not None:
+            lia = negatives.gather(labels_i.reshape(labels_i.shape[0], -1).contiguous()).contiguous()
+        return fa, la, lia, pa, wa
 
 
 class ArenaReducer:

@@ -244,6 +244,10 @@ class Trainer(object):
         # validation, the early-stop decision and the checkpoint see the moving average of the parameters, not the last step's weights
         self.ema_decay = check_ema_decay(params.get('ema_decay', None), "Trainer")
         self.ema_warmup = bool(params.get('ema_warmup', True))
+        # global ConR / SupCon negatives under data parallelism (FineTuner(global_ct=...); not a reference parameter): None follows
+        # MMDTI_GLOBAL_CT (unset = off, the rank-local term)
+        gct = params.get('global_ct', None)
+        self.global_ct = None if gct is None else bool(gct)
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
@@ -367,7 +371,9 @@ class Trainer(object):
                            max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite,
                            deterministic=self.deterministic, fds_stats=self.fds_stats, weight_decay=self.weight_decay,
                            decoupled_weight_decay=self.decoupled_weight_decay, param_groups=groups, ema_decay=self.ema_decay,
-                           ema_warmup=self.ema_warmup)
+                           ema_warmup=self.ema_warmup, global_ct=self.global_ct)
+        logger.info('ConR / SupCon keys: {}'.format(
+            'global (every rank\'s molecules; the term is the union batch\'s)' if engine.global_ct else 'rank-local (this process\'s batch)'))
         if self.ema_decay is not None:
             logger.info('weight averaging: EMA decay {:g}{}; validation and checkpoints use the averaged weights'.format(
                 self.ema_decay, ' with warm-up min(decay, (1 + t) / (10 + t))' if self.ema_warmup else ''))

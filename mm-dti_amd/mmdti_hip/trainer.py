@@ -38,7 +38,7 @@ class StepOutput:
     loss: torch.Tensor                      # this rank's step loss (alpha*task + beta*infonce_global + beta*ct)
     task_loss: torch.Tensor
     infonce_loss: Optional[torch.Tensor]    # the GLOBAL InfoNCE value (under DDP: sum of the ranks' shares)
-    ct_loss: Optional[torch.Tensor]
+    ct_loss: Optional[torch.Tensor]         # rank-local; with global_ct under DDP the GLOBAL value (sum of the ranks' shares)
     logits: torch.Tensor
     skipped: Optional[torch.Tensor] = None     # skip_nonfinite: 1.0 if this step's optimizer update was skipped (non-finite gradient)
     grad_norm: Optional[torch.Tensor] = None   # pre-clip global gradient norm (what clip_grad_norm_ returns), when the step computed it
@@ -97,7 +97,7 @@ class FineTuner:
                  max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
                  loss_key: Optional[str] = None, deterministic: Optional[bool] = None, fds_stats: str = "epoch_pass",
                  weight_decay: float = 0.0, decoupled_weight_decay: bool = False, param_groups=None,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, global_ct: Optional[bool] = None):
         """deterministic: True enters the process-wide deterministic mode (ops.set_deterministic: every cross-workgroup sum into a
         parameter gradient in a fixed order, one reduction workspace per launch stream); None follows MMDTI_DETERMINISTIC; False (and
         an unset environment) touches nothing.  Sites that have no fixed-order form yet raise in the mode (DESIGN.md lists them), and so
@@ -123,7 +123,11 @@ class FineTuner:
         ``arena.ema``, updated by one launch right after every applied Adam pass (eager and captured; a step the guard skips leaves it
         alone): ema += (1 - d)(p - ema), d = decay or, with ema_warmup (default), min(decay, (1 + t) / (10 + t)) for the t-th applied
         step (ema_decay_at).  ``with engine.averaged():`` puts the average into the model -- parameters, state dict and both 16-bit
-        shadows -- for validation and checkpoints, and takes it out again to the bit (DESIGN.md "Weight averaging (EMA)")."""
+        shadows -- for validation and checkpoints, and takes it out again to the bit (DESIGN.md "Weight averaging (EMA)").
+        global_ct: global ConR / SupCon negatives under data parallelism -- every rank's anchors meet the molecules of ALL ranks, so N
+        ranks on a global batch optimise the single-process CT loss of that batch (DESIGN.md "Global ConR / SupCon negatives").  None
+        follows MMDTI_GLOBAL_CT (unset / 0 = off).  Effective only with distributed=True and active collectives; otherwise, and when
+        off, the CT term is the rank-local one and nothing about the step changes."""
         self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
         self._averaged = False
         if fds_stats not in FDS_STATS_MODES:
@@ -156,6 +160,7 @@ class FineTuner:
         self._graphs, self._state, self._salt, self._salted = {}, None, None, False
         self.world = 1
         self.reducer = None
+        self.global_ct = False                           # (global ConR / SupCon negatives: only under distributed=True, see below)
         remove_grad_ready_hook(self)
         if distributed:
             self.negs = GlobalNegatives()
@@ -171,6 +176,8 @@ class FineTuner:
                 dropout_state.reseed(dropout_state.base + 0x9E37 * (self.negs.rank + 1))
             self.reducer = ArenaReducer(self.arena, bucket_bytes)
             self._b_loc = None
+            want = os.environ.get("MMDTI_GLOBAL_CT", "0") not in ("", "0") if global_ct is None else bool(global_ct)
+            self.global_ct = bool(want and self.negs.active)
             # gradient buckets leave during backward (MMDTI_NO_REDUCE_OVERLAP=1: all of them after it)
             if os.environ.get("MMDTI_NO_REDUCE_OVERLAP") != "1":
                 add_grad_ready_hook(self, self.reducer.on_grads_ready)
@@ -285,6 +292,8 @@ class FineTuner:
     def _bind_global_negatives(self, b_loc: int):
         if self.negs.active and self._b_loc != b_loc:
             self.model.infonce.set_global_negatives(self.negs.gather, self.negs.reduce_scatter, self.negs.row0(b_loc))
+            if self.global_ct:
+                self.model.set_global_contrast(self.negs.gather, self.negs.reduce_scatter, self.negs.row0(b_loc))
             self._b_loc = b_loc
 
     def forward_backward(self, net_input: dict, net_target: torch.Tensor, epoch: int = 0, use_weight: bool = False,
@@ -321,15 +330,24 @@ class FineTuner:
             # under DDP `infonce` is this rank's share of the GLOBAL loss: x world so that the rank-mean of gradients is exact
             loss = loss + self.beta * (infonce * self.world if self.world > 1 else infonce)
         if ct is not None:
-            loss = loss + self.beta * ct
+            # (global_ct: `ct` is this rank's share of the union batch's loss, scaled like InfoNCE's; else a rank-local mean)
+            loss = loss + self.beta * (ct * self.world if self.global_ct and self.world > 1 else ct)
         loss.backward()
         infonce_global = None if infonce is None else infonce.detach()
+        ct_out = None if ct is None else ct.detach()
         if self.reducer is not None:
-            if infonce is not None and self.negs.active and self.world > 1:
+            if self.global_ct and ct is not None and self.world > 1:
+                # the logged values are the GLOBAL ones: the ranks' shares of both terms summed in one message (8 bytes)
+                shares = torch.stack([ct_out.reshape(())] + ([] if infonce is None else [infonce_global.reshape(())]))
+                torch.distributed.all_reduce(shares, op=torch.distributed.ReduceOp.SUM)
+                ct_out = shares[0]
+                if infonce is not None:
+                    infonce_global = shares[1]
+            elif infonce is not None and self.negs.active and self.world > 1:
                 infonce_global = infonce_global.clone()
                 torch.distributed.all_reduce(infonce_global, op=torch.distributed.ReduceOp.SUM)      # 4 bytes, for logging
             self.reducer.finish()
-        return StepOutput(loss.detach(), tl.detach(), infonce_global, None if ct is None else ct.detach(), logits.detach())
+        return StepOutput(loss.detach(), tl.detach(), infonce_global, ct_out, logits.detach())
 
     def optimizer_step(self):
         """Clip + Adam with this step's learning rate; the schedule advances (also on a step the guard skips).
