@@ -1539,6 +1539,19 @@ class InfoNCEFn(torch.autograd.Function):
                 None, None)
 
 
+def infonce_rows_grad(both_all, d, temperature, row0, B):
+    """What InfoNCEFn's backward hands to ``reduce_scatter`` for the rank whose anchors are rows [row0, row0 + B) of the gathered
+    message ``both_all`` [Bg, 2 d] (query | positive): the gradient of that rank's share with respect to every row of the message,
+    before the factor dloss.  Same launches as the Fn's loss tail and the head of its backward (accumulate.TimeChannel.prepare)."""
+    qh, qinv = ops.l2norm_fwd(both_all[:, :d])
+    kh, kinv = ops.l2norm_fwd(both_all[:, d:])
+    loss = torch.zeros(1, device=both_all.device, dtype=F32)
+    dqh, dkh = torch.zeros_like(qh), torch.zeros_like(kh)
+    ops.infonce_dir(qh, kh, row0, B, temperature, loss, dqh, dkh)
+    ops.infonce_dir(kh, qh, row0, B, temperature, loss, dkh, dqh)
+    return torch.cat((ops.l2norm_bwd(dqh, qh, qinv), ops.l2norm_bwd(dkh, kh, kinv)), dim=1)
+
+
 class InfoNCELossFn(torch.autograd.Function):
     """info_nce(query, positive_key) on already-pooled [B,d] embeddings (models/infonce.py:42-98, implicit negatives)."""
 

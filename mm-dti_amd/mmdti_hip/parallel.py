@@ -183,6 +183,9 @@ class ArenaReducer:
         self._have = [set() for _ in self.buckets]
         self._events = [[] for _ in self.buckets]
         self.overlapped = 0                    # buckets launched from inside backward during the last step (diagnostic)
+        # False: this backward only adds to the rank's sum (an earlier micro-batch of an accumulated step) -- gradient-ready reports
+        # are ignored and nothing is launched; FineTuner.forward_backward(reduce=...) sets it
+        self.armed = True
 
     def reduce_range(self, lo: int, hi: int):
         """Launch the all-reduce of every not-yet-reduced bucket fully inside [lo, hi) -- for callers that know which
@@ -195,7 +198,7 @@ class ArenaReducer:
 
     def on_grads_ready(self, params):
         """runtime.notify_grads_ready hook: `params` have all their gradient kernels enqueued on the current stream."""
-        if not self.active:
+        if not self.active or not self.armed:
             return
         ev = None
         if self.stream is not None:
@@ -360,6 +363,39 @@ def pad_to_global_lengths(batch: dict, group=None, pad_values: Optional[dict] = 
             out[k] = v
             continue
         out[k] = torch.nn.functional.pad(v, grow, value=pv[k]) if any(grow) else v
+    return out
+
+
+def pad_group_to_common_lengths(batches, pool: str = "all", pad_values: Optional[dict] = None):
+    """pad_to_global_lengths for micro-batches laid out in time (FineTuner.step_accumulated): a pure function, no collective.  Each batch
+    dict of the group is right-padded to the group's largest atom / token length with PAD_VALUES, so the unmasked InfoNCE mean
+    (pool="all") sees one padded length, as it would on the concatenated batch.  pool="real": the mean skips padding, the loss does not
+    depend on the padded length, and the very same dicts are returned.  Keys without a padded axis are passed through."""
+    batches = list(batches)
+    if pool == "real" or len(batches) <= 1:
+        return batches
+    pv = dict(PAD_VALUES, **(pad_values or {}))
+    n_max = max(b["src_tokens"].shape[1] for b in batches)
+    l_max = max((b["input_ids"].shape[1] if "input_ids" in b else 0) for b in batches)
+    out = []
+    for batch in batches:
+        dn = n_max - batch["src_tokens"].shape[1]
+        dl = l_max - (batch["input_ids"].shape[1] if "input_ids" in batch else 0)
+        grown = {}
+        for k, v in batch.items():
+            if k == "src_tokens":
+                grow = (0, dn)
+            elif k in ("src_distance", "src_edge_type"):
+                grow = (0, dn, 0, dn)
+            elif k == "src_coord":
+                grow = (0, 0, 0, dn)
+            elif k in ("input_ids", "attention_mask"):
+                grow = (0, dl)
+            else:
+                grown[k] = v
+                continue
+            grown[k] = torch.nn.functional.pad(v, grow, value=pv[k]) if any(grow) else v
+        out.append(grown)
     return out
 
 

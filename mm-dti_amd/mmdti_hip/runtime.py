@@ -8,7 +8,6 @@ instead of ~350 small per-tensor launches.  ``nn.Parameter``s stay what the refe
 """
 from __future__ import annotations
 
-import itertools
 import weakref
 from typing import Dict, Iterable, List, Optional
 
@@ -326,14 +325,26 @@ class DropoutState:
 
     def __init__(self, seed: int = 0x5EED):
         self.base = seed
-        self._calls = itertools.count(1)
+        self._calls = 0                     # forward calls that have drawn a seed since the last reseed
 
     def next_seed(self) -> int:
-        return (self.base * 0x9E3779B97F4A7C15 + next(self._calls) * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+        self._calls += 1
+        return (self.base * 0x9E3779B97F4A7C15 + self._calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
 
     def reseed(self, seed: int):
         self.base = seed
-        self._calls = itertools.count(1)
+        self._calls = 0
+
+    def mark(self) -> int:
+        """The call counter as it stands: hand it to rewind() to draw the seeds that follow once more."""
+        return self._calls
+
+    def rewind(self, mark: int):
+        """Set the call counter to a value mark() returned: the next calls draw the seeds (hence the masks) drawn after that mark.
+        FineTuner.step_accumulated replays a micro-batch's forward with it; moving forwards (past a replay) is allowed as well."""
+        if not (isinstance(mark, int) and mark >= 0):
+            raise ValueError(f"DropoutState.rewind: not a mark() value: {mark!r}")
+        self._calls = mark
 
 
 dropout_state = DropoutState()

@@ -248,6 +248,15 @@ class Trainer(object):
         # MMDTI_GLOBAL_CT (unset = off, the rank-local term)
         gct = params.get('global_ct', None)
         self.global_ct = None if gct is None else bool(gct)
+        # accumulated steps (FineTuner.step_accumulated; not reference parameters): accum_steps consecutive loader batches make ONE
+        # optimizer step; accum_negatives says what the contrastive terms see -- "union": all of them, "micro": each batch itself.
+        # 1 (default): engine.step on every batch, as ever
+        self.accum_steps = int(params.get('accum_steps', 1))
+        self.accum_negatives = params.get('accum_negatives', 'union')
+        from ..accumulate import ACCUM_NEGATIVES, optimizer_steps_per_epoch
+        optimizer_steps_per_epoch(0, self.accum_steps)          # (raises on accum_steps < 1)
+        if self.accum_negatives not in ACCUM_NEGATIVES:
+            raise ValueError(f"Trainer: accum_negatives must be one of {ACCUM_NEGATIVES}, got {self.accum_negatives!r}")
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
@@ -355,13 +364,35 @@ class Trainer(object):
         return NNDataLoader(feature_name=feature_name, dataset=train_dataset, batch_size=self.batch_size, shuffle=True,
                             collate_fn=self._collate_for(model), drop_last=True, **self._loader_kwargs()), None
 
+    def total_optimizer_steps(self, batches_per_epoch):
+        """What the schedule (and with it the warm-up) counts: optimizer steps -- (len(loader) // accum_steps) * max_epochs."""
+        from ..accumulate import optimizer_steps_per_epoch
+        return optimizer_steps_per_epoch(batches_per_epoch, self.accum_steps) * self.max_epochs
+
+    def accumulation_groups(self, batches, pool="all"):
+        """accum_steps consecutive (net_input, net_target) batches per optimizer step, a trailing incomplete group dropped (in the spirit
+        of the loader's drop_last=True).  pool="all": the unmasked InfoNCE mean depends on the padded length, so a group is right-padded
+        to its common atom / token lengths (parallel.pad_group_to_common_lengths); pool="real": batches stay as collated."""
+        from ..accumulate import groups_of
+        from ..parallel import pad_group_to_common_lengths
+        for group in groups_of(batches, self.accum_steps):
+            inputs = pad_group_to_common_lengths([net_input for net_input, _ in group], pool)
+            yield [(net_input, net_target) for net_input, (_, net_target) in zip(inputs, group)]
+
     def fit_predict(self, model, train_dataset, valid_dataset, loss_func, activation_fn, dump_dir, fold, target_scaler, feature_name=None,
                     return_infonce_loss=False, return_ct_loss=False, use_weight=False):
         self._require_device()
         model = model.to(self.device)
         train_dataloader, sampler = self.train_loader(model, train_dataset, feature_name)
         min_val_loss, max_score, wait = float("inf"), float("-inf"), 0
-        num_training_steps = len(train_dataloader) * self.max_epochs
+        num_training_steps = self.total_optimizer_steps(len(train_dataloader))
+        if self.accum_steps > 1:
+            from ..accumulate import check_accumulation
+            world = torch.distributed.get_world_size() if self._ddp() else 1
+            check_accumulation([self.batch_size] * self.accum_steps, self.accum_negatives, world)       # (before anything is built)
+            logger.info('accumulated steps: {} x {} = {} molecules per optimizer step{}; contrastive terms see {}'.format(
+                self.accum_steps, self.batch_size, self.accum_steps * self.batch_size, ' and rank' if world > 1 else '',
+                'the union of the micro-batches' if self.accum_negatives == 'union' else 'each micro-batch on its own'))
         groups = self.param_groups
         if self.layer_decay is not None:
             from ..param_groups import layerwise_decay
@@ -399,9 +430,15 @@ class Trainer(object):
             fds_epoch = self.fds and epoch >= model.fds_cfg.start_update
             if fds_epoch and self.fds_stats == "streaming":
                 engine.fds_epoch_begin(epoch)
-            for net_input, net_target in self.device_batches(train_dataloader, feature_name):
-                out = engine.step(net_input, net_target, epoch=epoch, use_weight=use_weight, return_infonce_loss=return_infonce_loss,
-                                  return_ct_loss=return_ct_loss, loss_func=task_loss)
+            skw = dict(epoch=epoch, use_weight=use_weight, return_infonce_loss=return_infonce_loss, return_ct_loss=return_ct_loss,
+                       loss_func=task_loss)
+            batches = self.device_batches(train_dataloader, feature_name)
+            if self.accum_steps > 1:
+                steps_of = (engine.step_accumulated(group, negatives=self.accum_negatives, **skw)
+                            for group in self.accumulation_groups(batches, pool))
+            else:
+                steps_of = (engine.step(net_input, net_target, **skw) for net_input, net_target in batches)
+            for out in steps_of:
                 row = [out.loss, out.task_loss, out.infonce_loss if out.infonce_loss is not None else out.loss.new_zeros(()),
                        out.ct_loss if out.ct_loss is not None else out.loss.new_zeros(())]
                 if out.skipped is not None:

@@ -130,6 +130,7 @@ class FineTuner:
         off, the CT term is the rank-local one and nothing about the step changes."""
         self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
         self._averaged = False
+        self._time_negatives = None                      # accumulate.TimeNegatives while an accumulated union step runs
         if fds_stats not in FDS_STATS_MODES:
             raise ValueError(f"FineTuner: fds_stats must be one of {FDS_STATS_MODES}, got {fds_stats!r}")
         self.fds_stats = fds_stats
@@ -297,25 +298,27 @@ class FineTuner:
             self._b_loc = b_loc
 
     def forward_backward(self, net_input: dict, net_target: torch.Tensor, epoch: int = 0, use_weight: bool = False,
-                         return_infonce_loss: bool = True, return_ct_loss: bool = True, loss_func=None) -> StepOutput:
+                         return_infonce_loss: bool = True, return_ct_loss: bool = True, loss_func=None, *, zero_grad: bool = True,
+                         reduce: bool = True, task_scale: Optional[float] = None, contrast_scale: Optional[float] = None) -> StepOutput:
         """optimizer.zero_grad(); model(...); loss; loss.backward()  (+ gradient all-reduce under DDP).  The two flags
         select the reference's four call forms (tasks/trainer.py:184-212); ``loss_func`` replaces the built-in task-loss
-        kernel with any callable on (logits, target)."""
+        kernel with any callable on (logits, target).
+        Keyword-only, for accumulated steps (defaults: today's step): zero_grad=False adds this backward's gradients to what the arena
+        holds; reduce=False keeps the gradient all-reduce from launching (the arena then holds this rank's sum; the call with
+        reduce=True reduces every bucket once); task_scale / contrast_scale multiply the task term and the two contrastive terms
+        (None: no multiplication is enqueued)."""
         model = self.model
         if not torch.cuda.is_current_stream_capturing():
             self._sync_trainable()
-        self.arena.zero_grad()
+        if zero_grad:
+            self.arena.zero_grad()
         if self.reducer is not None:
-            self._bind_global_negatives(net_target.shape[0])
-            self.reducer.begin_step()
-        kw = dict(epoch=epoch)
-        if return_infonce_loss:
-            kw["return_infonce_loss"] = True
-        if return_ct_loss:
-            kw.update(return_ct_loss=True, use_weight=use_weight)
-        if return_ct_loss or return_infonce_loss or getattr(model, "fds_streaming", False):
-            kw["net_target"] = net_target
-        out = model(**net_input, **kw)
+            if self._time_negatives is None:             # (an accumulated union step has bound its own provider)
+                self._bind_global_negatives(net_target.shape[0])
+            self.reducer.armed = bool(reduce)
+            if reduce:
+                self.reducer.begin_step()
+        out = model(**net_input, **self._model_kwargs(net_target, epoch, use_weight, return_infonce_loss, return_ct_loss))
         out = out if isinstance(out, tuple) else (out,)
         logits = out[0]
         infonce = out[1] if return_infonce_loss else None
@@ -325,6 +328,12 @@ class FineTuner:
             raise ValueError(f"FineTuner: task {self.task!r} has no built-in loss kernel -- pass the task loss as `loss_func` "
                              "(any callable on (logits, target), e.g. the reference's LOSS_RREGISTER entry, models/nnmodel.py:24-34)")
         tl = lf(logits, net_target)
+        # (accumulated steps: a micro-batch's terms enter the step's loss with their weights; the values returned are the weighted ones)
+        if task_scale is not None:
+            tl = tl * task_scale
+        if contrast_scale is not None:
+            infonce = None if infonce is None else infonce * contrast_scale
+            ct = None if ct is None else ct * contrast_scale
         loss = self.alpha * tl
         if infonce is not None:
             # under DDP `infonce` is this rank's share of the GLOBAL loss: x world so that the rank-mean of gradients is exact
@@ -346,8 +355,138 @@ class FineTuner:
             elif infonce is not None and self.negs.active and self.world > 1:
                 infonce_global = infonce_global.clone()
                 torch.distributed.all_reduce(infonce_global, op=torch.distributed.ReduceOp.SUM)      # 4 bytes, for logging
-            self.reducer.finish()
+            if reduce:
+                self.reducer.finish()
+            self.reducer.armed = True
         return StepOutput(loss.detach(), tl.detach(), infonce_global, ct_out, logits.detach())
+
+    def _model_kwargs(self, net_target, epoch, use_weight, return_infonce_loss, return_ct_loss):
+        """the model call's keywords for the reference's four call forms (tasks/trainer.py:184-212)"""
+        kw = dict(epoch=epoch)
+        if return_infonce_loss:
+            kw["return_infonce_loss"] = True
+        if return_ct_loss:
+            kw.update(return_ct_loss=True, use_weight=use_weight)
+        if return_ct_loss or return_infonce_loss or getattr(self.model, "fds_streaming", False):
+            kw["net_target"] = net_target
+        return kw
+
+    # ------------------------------------------------------------------ accumulated steps (DESIGN.md "Accumulated steps")
+    def forward_backward_accumulated(self, micro_batches, epoch: int = 0, use_weight: bool = False, negatives: str = "union",
+                                     return_infonce_loss: bool = True, return_ct_loss: bool = True, loss_func=None) -> StepOutput:
+        """forward_backward over k micro-batches ``[(net_input, net_target), ...]``: the arena ends with the gradient of
+
+            alpha * sum_i (b_i / B) task_loss(micro-batch i) + beta * (InfoNCE + ConR / SupCon),        B = sum_i b_i
+
+        zeroed once before the first backward and, under data parallelism, all-reduced once, during and after the last.
+        negatives="micro": each micro-batch's contrastive terms see its own rows (its micro-step's global rows under data parallelism),
+        weighted b_i / B -- one forward + backward each, any sizes.  negatives="union": the contrastive terms are those of the
+        concatenated batch (equal b_i, one rank) -- accumulate.TimeNegatives plays the other micro-batches' part as the other ranks
+        play it under data parallelism: a no_grad forward of every micro-batch records the messages of the two loss functions, the
+        row-block kernels turn the cached union into each virtual rank's contribution to every row, and the second pass runs forward +
+        backward against the union with its own rows live.  Dropout: pass 2 draws pass 1's masks (DropoutState.mark / rewind), the
+        counter ends advanced by k forwards.  k = 1 is forward_backward itself, launch for launch.
+        -> StepOutput of the whole step: the four scalars summed with their weights, the logits concatenated."""
+        from .accumulate import check_accumulation
+        self._not_averaged("forward_backward_accumulated")
+        micro_batches = list(micro_batches)
+        k, B = check_accumulation([t.shape[0] for _, t in micro_batches], negatives, self.world)
+        fkw = dict(epoch=epoch, use_weight=use_weight, return_infonce_loss=return_infonce_loss, return_ct_loss=return_ct_loss,
+                   loss_func=loss_func)
+        if k == 1:
+            return self.forward_backward(*micro_batches[0], **fkw)
+        union = negatives == "union" and (return_infonce_loss or return_ct_loss)
+        outs = []
+        if not union:
+            for i, (net_input, net_target) in enumerate(micro_batches):
+                w = net_target.shape[0] / B
+                # (negatives="union" without a contrastive term: only the task term is left, weighted like micro's)
+                outs.append(self.forward_backward(net_input, net_target, zero_grad=i == 0, reduce=i == k - 1, task_scale=w,
+                                                  contrast_scale=w, **fkw))
+        else:
+            marks, end = self._record_union(micro_batches, epoch, use_weight, return_infonce_loss, return_ct_loss)
+            try:
+                for i, (net_input, net_target) in enumerate(micro_batches):
+                    self._bind_time_negatives(i)
+                    dropout_state.rewind(marks[i])
+                    outs.append(self.forward_backward(net_input, net_target, zero_grad=i == 0, reduce=i == k - 1,
+                                                      task_scale=net_target.shape[0] / B, **fkw))
+            finally:
+                dropout_state.rewind(end)
+                self._release_time_negatives()
+        total = lambda name: None if getattr(outs[0], name) is None else torch.stack([getattr(o, name).reshape(()) for o in outs]).sum()
+        return StepOutput(total("loss"), total("task_loss"), total("infonce_loss"), total("ct_loss"), torch.cat([o.logits for o in outs], dim=0))
+
+    def _bind_time_negatives(self, i: int):
+        """micro-batch i's view of the two channels (both setters read row0 when they are called: bound anew for every micro-batch)"""
+        tn = self._time_negatives
+        c = tn.infonce.at(i)
+        self.model.infonce.set_global_negatives(c.gather, c.reduce_scatter, c.row0)
+        c = tn.ct.at(i)
+        self.model.set_global_contrast(c.gather, c.reduce_scatter, c.row0)
+
+    def _release_time_negatives(self):
+        """The providers the model had before the accumulated step: none, or -- under distributed=True -- GlobalNegatives, which the
+        next forward_backward binds again."""
+        self._time_negatives = None
+        self.model.infonce.set_global_negatives(None, None, 0)
+        self.model.set_global_contrast(None, None, 0)
+        if self.reducer is not None:
+            self._b_loc = None
+
+    def _record_union(self, micro_batches, epoch, use_weight, return_infonce_loss, return_ct_loss):
+        """Pass 1 and the work between the passes.  -> (dropout marks before each micro-batch's forward, the mark after the last)."""
+        from .accumulate import TimeNegatives, UnionProbe
+        from .functional import infonce_rows_grad
+        model = self.model
+        tn = self._time_negatives = TimeNegatives(len(micro_batches))
+        marks, logits = [], []
+        streaming, model.fds_streaming = getattr(model, "fds_streaming", False), False      # (pass 2's forwards feed the FDS statistics)
+        try:
+            with torch.no_grad():
+                for i, (net_input, net_target) in enumerate(micro_batches):
+                    self._bind_time_negatives(i)
+                    marks.append(dropout_state.mark())
+                    out = model(**net_input, **self._model_kwargs(net_target, epoch, use_weight, return_infonce_loss, return_ct_loss))
+                    logits.append((out[0] if isinstance(out, tuple) else out).detach())
+            end = dropout_state.mark()
+            tn.seal()
+            if tn.infonce.used:
+                head = model.infonce
+                tn.infonce.prepare(lambda c, j: infonce_rows_grad(c.union["f"], head.d_l, head.temperature, j * c.b, c.b))
+            if tn.ct.used:
+                def ct_sent(c, j):
+                    # models.contrastive itself, with its own mode and constants, on the cached union: the probe's gather returns the
+                    # union whatever it is handed, its reduce_scatter keeps rank j's contribution to every row
+                    probe = UnionProbe(c, j)
+                    net_input, net_target = micro_batches[j]
+                    f = c.union["f"][j * c.b:(j + 1) * c.b, :c.union["f"].shape[1] - 3].clone().requires_grad_()
+                    wkw = dict(weights=net_input.get("weights")) if use_weight else {}
+                    with torch.enable_grad():
+                        share = model.CT(f, net_target, logits[j], w=model.ct_w, negatives=probe, **wkw)
+                    torch.autograd.grad(share, f)
+                    return probe.sent
+                tn.ct.prepare(ct_sent)
+        except BaseException:
+            self._release_time_negatives()
+            raise
+        finally:
+            model.fds_streaming = streaming
+        return marks, end
+
+    def step_accumulated(self, micro_batches, epoch: int = 0, use_weight: bool = False, negatives: str = "union", **kw) -> StepOutput:
+        """ONE optimizer step over k micro-batches (forward_backward_accumulated, then optimizer_step): the arena is zeroed once, the
+        clip norm, the skip_nonfinite decision, Adam, the EMA update and the schedule see the summed gradients once."""
+        self._not_averaged("step_accumulated")
+        if getattr(self, "_salted", False):
+            from . import ops
+            ops.seed_salt_reset(sync=False)
+            self._salted = False
+        out = self.forward_backward_accumulated(micro_batches, epoch, use_weight, negatives, **kw)
+        self.last_optimizer_outputs = (None, None)
+        self.optimizer_step()
+        out.skipped, out.grad_norm = self.last_optimizer_outputs
+        return out
 
     def optimizer_step(self):
         """Clip + Adam with this step's learning rate; the schedule advances (also on a step the guard skips).
