@@ -243,6 +243,77 @@ class ParamArena:
         if self.shadow16 is not None:
             self._epoch16 = self._epoch
 
+    # ------------------------------------------------------------------ checkpoints (DESIGN.md "Resuming a run")
+    _STATE_BUFFERS = (("exp_avg", "adam_m"), ("exp_avg_sq", "adam_v"), ("ema", "ema"))
+
+    def _state_names(self, names):
+        names = [str(i) for i in range(len(self.params))] if names is None else [str(n) for n in names]
+        if len(names) != len(self.params) or len(set(names)) != len(names):
+            raise ValueError(f"ParamArena: {len(self.params)} distinct parameter names expected, got {len(names)} ({len(set(names))} distinct)")
+        return names
+
+    def state_dict(self, names=None, sync=True):
+        """The optimizer's side of the arena, keyed by parameter name (``names``: one per parameter in arena order; None: the positions),
+        not a flat dump -- another layout of the same parameters reads it too.  Per parameter ``exp_avg``, ``exp_avg_sq`` and ``ema``
+        where the buffer exists (moments never allocated are absent), each an fp32 host copy of the parameter's slice in its shape; and
+        ``step_count`` and the trainable ``flags``.  The values themselves are the model's (``model.state_dict()``).  sync=False: the
+        copies are only enqueued into pinned memory -- synchronise the stream before reading them."""
+        names = self._state_names(names)
+        host = {k: host_copy(getattr(self, a)) for k, a in self._STATE_BUFFERS if getattr(self, a) is not None}
+        if sync:
+            torch.cuda.current_stream().synchronize()
+        params = {}
+        for name, p in zip(names, self.params):
+            o, n = self.offsets[id(p)], p.numel()
+            params[name] = {k: h[o:o + n].view(p.shape) for k, h in host.items()}
+        return {"step_count": int(self.step_count), "flags": tuple(bool(f) for f in self._flags), "params": params}
+
+    def check_state_dict(self, sd, names):
+        """What load_state_dict would refuse, without writing anything: ValueError."""
+        names = self._state_names(names)
+        params = sd["params"]
+        if set(params) != set(names):
+            odd = sorted(set(params) ^ set(names))
+            raise ValueError(f"ParamArena.load_state_dict: the state and the arena hold different parameters: {odd[:5]}")
+        for k, a in self._STATE_BUFFERS:
+            have = [name for name in names if params[name].get(k) is not None]
+            if have and len(have) != len(names):
+                raise ValueError(f"ParamArena.load_state_dict: {k} is there for {len(have)} of {len(names)} parameters")
+            if k == "ema" and bool(have) != (self.ema is not None):
+                raise ValueError("ParamArena.load_state_dict: the state " + ("holds" if have else "has no") + " parameter average (ema), "
+                                 "this arena " + ("has none" if have else "holds one"))
+            for name, p in zip(names, self.params):
+                t = params[name].get(k)
+                if t is not None and t.numel() != p.numel():
+                    raise ValueError(f"ParamArena.load_state_dict: {k} of {name} has {t.numel()} elements, the parameter {p.numel()}")
+        return names
+
+    def load_state_dict(self, sd, names=None):
+        """Copy a state_dict() into the buffers this arena already has (no address moves: captured graphs stay valid); the moments are
+        allocated first if no step has been taken yet, and zeroed if the state has none.  Then the bf16 shadow is re-cast from the
+        fp32 data as it stands (load the model's values BEFORE this) and the fp16 one is rebuilt at its next use.  The trainable flags
+        are the owner's to apply (requires_grad, then sync_trainable)."""
+        names = self.check_state_dict(sd, names)
+        params = sd["params"]
+        for k, a in self._STATE_BUFFERS:
+            saved = params[names[0]].get(k) is not None
+            if not saved:
+                if k != "ema" and getattr(self, a) is not None:
+                    getattr(self, a).zero_()
+                continue
+            if getattr(self, a) is None:
+                setattr(self, a, torch.zeros_like(self.data))
+            flat = torch.zeros(self.numel, dtype=torch.float32, pin_memory=True)
+            for name, p in zip(names, self.params):
+                o, n = self.offsets[id(p)], p.numel()
+                flat[o:o + n].copy_(params[name][k].reshape(-1))
+            getattr(self, a).copy_(flat, non_blocking=True)
+        self.step_count = int(sd["step_count"])
+        self.refresh_shadow()           # (advances _epoch: the fp16 shadow, if there is one, is stale until _fresh16 re-casts it)
+        tab = getattr(self, "_bias_tab", None)
+        if tab is not None and tab[1].shape[0] < self.step_count:
+            del self._bias_tab
+
     def _bias_table(self, betas):
         """Device table of the host's bias corrections for t = 1 .. >= step_count (the guard's t never exceeds the steps enqueued):
         rebuilt, at twice the length, when the step count outgrows it -- enqueued, no synchronisation."""
@@ -252,6 +323,16 @@ class ParamArena:
             tab = (tuple(betas), ops.adam_bias_table(betas[0], betas[1], steps, self.data.device))
             self._bias_tab = tab
         return tab[1]
+
+
+def host_copy(t: torch.Tensor) -> torch.Tensor:
+    """A device tensor's copy in pinned host memory, ENQUEUED on the current stream: valid once that stream has been synchronised (a
+    checkpoint enqueues all its copies and synchronises once).  A host tensor is cloned."""
+    if not t.is_cuda:
+        return t.detach().clone()
+    out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    out.copy_(t.detach(), non_blocking=True)
+    return out
 
 
 def new_nonfinite_guard(device) -> torch.Tensor:
@@ -345,6 +426,17 @@ class DropoutState:
         if not (isinstance(mark, int) and mark >= 0):
             raise ValueError(f"DropoutState.rewind: not a mark() value: {mark!r}")
         self._calls = mark
+
+    def state(self) -> dict:
+        """{base, calls}: where the stream stands (checkpoints: FineTuner.state_dict)."""
+        return {"base": int(self.base), "calls": int(self._calls)}
+
+    def load_state(self, base: int, calls: int):
+        """Continue the stream of ``base`` after ``calls`` forward calls: the next seeds are those that followed state()."""
+        if not (isinstance(calls, int) and calls >= 0):
+            raise ValueError(f"DropoutState.load_state: calls must be a count >= 0, got {calls!r}")
+        self.base = int(base)
+        self._calls = calls
 
 
 dropout_state = DropoutState()

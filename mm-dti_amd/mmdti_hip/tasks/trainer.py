@@ -268,7 +268,15 @@ class Trainer(object):
         if self.pair_inputs not in PAIR_INPUT_MODES:
             raise ValueError(f"Trainer: pair_inputs must be one of {PAIR_INPUT_MODES}, got {self.pair_inputs!r}")
         self.rank = torch.distributed.get_rank() if (self.distributed and torch.distributed.is_initialized()) else 0
+        if self.distributed and torch.distributed.is_initialized():
+            from ..parallel import host_group
+            host_group()            # (the gloo side group of _checkpoint_barrier / _agree: created here, where every rank is)
         self._loss_cache = {}       # id(loss_func) -> (loss_func, its kernel-backed loss): see _task_loss
+        # resuming (not reference parameters, both off by default: nothing is written and no launch changes).  save_train_state: after
+        # every epoch rank 0 writes train_state_{fold}.pth into dump_dir -- the engine's whole state, the epoch loop's bookkeeping and the
+        # host RNG streams; resume: fit_predict continues from that file when it is there (and keeps writing it)
+        self.resume = bool(params.get('resume', False))
+        self.save_train_state = bool(params.get('save_train_state', False)) or self.resume
 
     # -------------------------------------------------------------- batches
     def decorate_batch(self, batch, feature_name=None):
@@ -420,8 +428,13 @@ class Trainer(object):
         self._engine = engine
         task_loss = self._task_loss(loss_func)
         self.history = []
-        epoch = 0
-        for epoch in range(self.max_epochs):
+        epoch, start_epoch = 0, 0
+        if self.resume:
+            ts = self._load_train_state(engine, task_loss, dump_dir, fold)
+            if ts is not None:
+                epoch, min_val_loss, max_score, wait = ts["epoch"], ts["min_val_loss"], ts["max_score"], ts["wait"]
+                start_epoch = self.max_epochs if ts["finished"] else epoch + 1
+        for epoch in range(start_epoch, self.max_epochs):
             model = model.train()
             if sampler is not None:
                 sampler.set_epoch(epoch)
@@ -466,6 +479,10 @@ class Trainer(object):
                                 + (', skipped steps: {}'.format(skipped) if self.skip_nonfinite else ''))
                 is_early_stop, min_val_loss, wait, max_score = self._early_stop_choice(
                     wait, total_val_loss, min_val_loss, metric_score, max_score, model, dump_dir, fold, self.patience, epoch)
+            if self.save_train_state:
+                # (outside averaged(): the engine's state holds the raw weights and the average each in its own place)
+                self._save_train_state(engine, task_loss, dump_dir, fold, epoch, min_val_loss, max_score, wait,
+                                       finished=is_early_stop or epoch == self.max_epochs - 1)
             if is_early_stop:
                 break
         self._checkpoint_barrier()          # rank 0's last write is complete before any rank reads the file
@@ -484,6 +501,49 @@ class Trainer(object):
         tmp = path + f'.tmp{os.getpid()}'
         torch.save({'model_state_dict': model.state_dict()}, tmp)
         os.replace(tmp, path)
+
+    # -------------------------------------------------------------- resuming (DESIGN.md "Resuming a run")
+    def _train_state_path(self, dump_dir, fold):
+        return os.path.join(dump_dir, f'train_state_{fold}.pth')
+
+    def _train_settings(self):
+        """what decides the number of optimizer steps and the order of the batches: a resumed run must have been started alike"""
+        return dict(batch_size=int(self.batch_size), accum_steps=int(self.accum_steps), epochs=int(self.max_epochs), seed=int(self.seed))
+
+    def _save_train_state(self, engine, task_loss, dump_dir, fold, epoch, min_val_loss, max_score, wait, finished):
+        """After an epoch's early-stop decision: everything the next epoch needs, written atomically by rank 0 (model_{fold}.pth stays
+        what it is: the best epoch's weights under the reference's keys)."""
+        if self.rank == 0:
+            from ..checkpoint import atomic_save, pack_rng
+            history = [dict(h, steps=torch.from_numpy(np.ascontiguousarray(h["steps"])), val_loss=float(h["val_loss"]), score=float(h["score"]),
+                            metric=str(h["metric"])) for h in self.history]
+            atomic_save({"engine": engine.state_dict(), "epoch": int(epoch), "min_val_loss": float(min_val_loss), "max_score": float(max_score),
+                         "wait": int(wait), "history": history, "rng": pack_rng(), "finished": bool(finished),
+                         "task_loss": task_loss.state_dict() if hasattr(task_loss, "state_dict") else None,
+                         "settings": self._train_settings()}, self._train_state_path(dump_dir, fold))
+        self._checkpoint_barrier()
+
+    def _load_train_state(self, engine, task_loss, dump_dir, fold):
+        """-> the file's bookkeeping after the engine, the loss, ``history`` and the RNG streams have been restored; None when there is
+        no file (a run from epoch 0).  ValueError when the file was written under other settings."""
+        path = self._train_state_path(dump_dir, fold)
+        if not os.path.exists(path):
+            logger.info('resume: no {} -- training starts at epoch 1'.format(path))
+            return None
+        from ..checkpoint import load, unpack_rng
+        ts = load(path, map_location="cpu")
+        own = self._train_settings()
+        differ = ['{}: {!r} in the file, {!r} here'.format(k, ts["settings"].get(k), v) for k, v in own.items() if ts["settings"].get(k) != v]
+        if differ:
+            raise ValueError('Trainer: {} was written by a run with other settings ({})'.format(path, '; '.join(differ)))
+        engine.load_state_dict(ts["engine"])
+        if ts.get("task_loss") is not None and hasattr(task_loss, "load_state_dict"):
+            task_loss.load_state_dict(ts["task_loss"])
+        self.history = [dict(h, steps=h["steps"].numpy()) for h in ts["history"]]
+        unpack_rng(ts["rng"])
+        logger.info('resume: {} -- epoch {} of {} done{}'.format(path, ts["epoch"] + 1, self.max_epochs,
+                                                                ', the run had finished' if ts["finished"] else ''))
+        return ts
 
     def _checkpoint_barrier(self):
         if self._ddp():

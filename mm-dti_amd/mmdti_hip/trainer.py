@@ -161,6 +161,7 @@ class FineTuner:
         self._graphs, self._state, self._salt, self._salted = {}, None, None, False
         self.world = 1
         self.reducer = None
+        self._dropout_rank = None                        # the rank whose offset the dropout base carries (None: no offset, checkpoint.py)
         self.global_ct = False                           # (global ConR / SupCon negatives: only under distributed=True, see below)
         remove_grad_ready_hook(self)
         if distributed:
@@ -174,7 +175,9 @@ class FineTuner:
                 torch.distributed.broadcast(self.arena.data, src=0)
                 self.arena.refresh_shadow()
                 # ... while dropout masks must DIFFER across ranks (each rank holds different molecules)
-                dropout_state.reseed(dropout_state.base + 0x9E37 * (self.negs.rank + 1))
+                from .checkpoint import dropout_base_for_rank
+                self._dropout_rank = self.negs.rank
+                dropout_state.reseed(dropout_base_for_rank(dropout_state.base, None, self._dropout_rank))
             self.reducer = ArenaReducer(self.arena, bucket_bytes)
             self._b_loc = None
             want = os.environ.get("MMDTI_GLOBAL_CT", "0") not in ("", "0") if global_ct is None else bool(global_ct)
@@ -275,6 +278,128 @@ class FineTuner:
         if self._averaged:
             raise RuntimeError(f"FineTuner.{what}: not inside averaged() -- the model holds the averaged weights, the raw ones sit in the "
                                "average's buffer until the block ends")
+
+    # ------------------------------------------------------------------ resuming a run (DESIGN.md "Resuming a run")
+    def _arena_names(self):
+        """the arena's parameters by their names in the model, in arena order"""
+        of = {id(p): n for n, p in self.model.named_parameters()}
+        return [of[id(p)] for p in self.arena.params]
+
+    def state_dict(self):
+        """Everything that defines where this engine stands between two optimizer steps (not in the middle of step_accumulated), as
+        tensors on the host, numbers, strings, None, lists, tuples and dicts: ``torch.save`` it, ``checkpoint.load`` reads it back with
+        weights_only=True.  The model's raw weights and buffers, the optimizer's moments and the parameter average by parameter name,
+        the trainable flags, the schedule, the guard's and the graph's device counters, the group table, the dropout stream, the task
+        loss's own state (GHM's bin history) and the streaming FDS accumulator.  Every copy is enqueued into pinned memory and the
+        stream is synchronised once (a loss with state of its own reads its few words after that).  Raises inside averaged(): the
+        model would hand out the averaged weights as the raw ones."""
+        self._not_averaged("state_dict")
+        from .checkpoint import STATE_VERSION
+        from .runtime import host_copy
+        names = self._arena_names()
+        model_sd = {k: host_copy(v) for k, v in self.model.state_dict().items()}
+        fds = getattr(self.model, "FDS", None)
+        fds_acc = getattr(fds, "_stream_acc", None) if self.fds_stats == "streaming" else None
+        sd = {
+            "version": STATE_VERSION,
+            "model": model_sd,
+            "layout": [(n, p.numel()) for n, p in zip(names, self.arena.params)],
+            "optimizer": self.arena.state_dict(names, sync=False),
+            "trainable": {n: bool(p.requires_grad) for n, p in zip(names, self.arena.params)},
+            "schedule": {"sched_step": int(self.sched_step), "total_steps": int(self.total_steps), "warmup": int(self.warmup), "lr": float(self.lr)},
+            "guard": None if self.guard is None else host_copy(self.guard),
+            "graph": None if self._state is None else {"state": host_copy(self._state), "salt": host_copy(self._salt), "salted": bool(self._salted)},
+            "groups": None if self.param_groups is None else {"names": list(self._group_names), "table": [[float(x) for x in row] for row in self._group_table]},
+            "ema": None if self.ema_decay is None else {"decay": float(self.ema_decay), "warmup": bool(self.ema_warmup)},
+            "dropout": dict(dropout_state.state(), rank=self._dropout_rank),
+            "task_loss": None,
+            "fds_stream": None if fds_acc is None else {"acc": host_copy(fds_acc), "active": bool(getattr(self.model, "fds_streaming", False))},
+            "deterministic": bool(self.deterministic),
+        }
+        torch.cuda.current_stream().synchronize()
+        if hasattr(self.task_loss, "state_dict"):
+            sd["task_loss"] = self.task_loss.state_dict()
+        return sd
+
+    def _check_state_dict(self, sd):
+        """Everything load_state_dict refuses, before it writes anything.  -> the arena's names"""
+        from .checkpoint import check_layout, check_version
+        check_version(sd)
+        names = self._arena_names()
+        check_layout(sd["layout"], [(n, p.numel()) for n, p in zip(names, self.arena.params)])
+        for what, saved, own in (("weight averaging (ema)", sd["ema"], self.ema_decay), ("parameter groups", sd["groups"], self.param_groups),
+                                 ("the non-finite guard (skip_nonfinite)", sd["guard"], self.guard)):
+            if (saved is None) != (own is None):
+                raise ValueError(f"FineTuner.load_state_dict: the state was written {'without' if saved is None else 'with'} {what}, this "
+                                 f"engine was built {'without' if own is None else 'with'} it")
+        if sd["groups"] is not None and list(sd["groups"]["names"]) != list(self._group_names):
+            raise ValueError(f"FineTuner.load_state_dict: the state's parameter groups are {list(sd['groups']['names'])}, this engine's "
+                             f"{list(self._group_names)}")
+        own = self.model.state_dict()
+        odd = sorted(set(own) ^ set(sd["model"]))
+        odd += [k for k, v in own.items() if k in sd["model"] and tuple(sd["model"][k].shape) != tuple(v.shape)]
+        if odd:
+            raise ValueError(f"FineTuner.load_state_dict: the model's state differs from the file's (missing, unexpected or of another shape): {odd[:5]}")
+        self.arena.check_state_dict(sd["optimizer"], names)
+        if set(sd["trainable"]) != set(names):
+            raise ValueError("FineTuner.load_state_dict: the trainable flags do not name the optimizer's parameters")
+        loss_sd = sd.get("task_loss")
+        if loss_sd is not None and hasattr(self.task_loss, "bins") and int(loss_sd.get("bins", self.task_loss.bins)) != self.task_loss.bins:
+            raise ValueError(f"FineTuner.load_state_dict: the task loss has {loss_sd['bins']} bins in the state, {self.task_loss.bins} here")
+        fs = sd.get("fds_stream")
+        if fs is not None:
+            fds = getattr(self.model, "FDS", None)
+            if self.fds_stats != "streaming" or fds is None or tuple(fs["acc"].shape) != tuple(fds.stream_state().shape):
+                raise ValueError("FineTuner.load_state_dict: the state holds a streaming FDS accumulator this engine has no place for "
+                                 "(fds_stats='streaming' and the same bucket range and feature width)")
+        return names
+
+    def load_state_dict(self, sd):
+        """Put a state_dict() back: copies into the buffers this engine already has, so no address moves and graphs captured before
+        stay valid (they are dropped only if the trainable set changed, as ever).  Raises ValueError, before anything is written, when
+        the version, the optimizer's parameters (names, sizes, order), the presence of weight averaging, of parameter groups (or their
+        names) or of the guard differ.  total_steps, warmup and lr stay the constructor's (one warning if the file's differ); the
+        schedule continues at the saved step.  The process-wide dropout stream continues where the state left it, from this rank's
+        base.  Under distributed=True every rank loads the same file: the replicas are bit-identical by construction.  Raises inside
+        averaged()."""
+        self._not_averaged("load_state_dict")
+        from . import ops
+        from .checkpoint import dropout_base_for_rank
+        names = self._check_state_dict(sd)
+        sch = sd["schedule"]
+        differ = [f"{k}: {sch[k]!r} in the file, {own!r} here" for k, own in (("total_steps", self.total_steps), ("warmup", self.warmup), ("lr", self.lr))
+                  if sch[k] != own]
+        if differ:
+            logger.warning("FineTuner.load_state_dict: the schedule differs (%s); this engine's values are kept, the step count is restored", "; ".join(differ))
+        dev = self.arena.data.device
+        put = lambda dst, src: dst.copy_(ops.upload(src.to(dst.dtype), dev), non_blocking=True)
+        self.model.load_state_dict(sd["model"])             # (in-place copies: the arena-bound parameters keep their storage)
+        self.arena.load_state_dict(sd["optimizer"], names)
+        for n, p in zip(names, self.arena.params):
+            p.requires_grad_(bool(sd["trainable"][n]))
+        self._sync_trainable()
+        self.sched_step = int(sch["sched_step"])
+        if self.guard is not None:
+            put(self.guard, sd["guard"])
+        g = sd["graph"]
+        if g is not None:
+            if self._state is None:
+                self._state = torch.zeros(4, device=dev, dtype=torch.float32)
+                self._salt = torch.zeros(2, device=dev, dtype=torch.int64)
+            put(self._state, g["state"])
+            put(self._salt, g["salt"])
+            self._salted = bool(g["salted"]) or self._salted    # (the next eager step resets the libraries' salt, as after a replay)
+        if self.param_groups is not None:
+            self._group_table = [[float(x) for x in row] for row in sd["groups"]["table"]]
+            put(self.arena.group_table, torch.tensor(self._group_table, dtype=torch.float32))
+        if sd.get("task_loss") is not None and hasattr(self.task_loss, "load_state_dict"):
+            self.task_loss.load_state_dict(sd["task_loss"])
+        fs = sd.get("fds_stream")
+        if fs is not None:
+            put(self.model.FDS.stream_state(), fs["acc"])
+            self.model.fds_streaming = bool(fs["active"])
+        d = sd["dropout"]
+        dropout_state.load_state(dropout_base_for_rank(d["base"], d["rank"], self._dropout_rank), int(d["calls"]))
 
     # ------------------------------------------------------------------
     def _sync_trainable(self):
