@@ -74,6 +74,7 @@ int mmdti_abi_version(void);
 #define MMDTI_PLAN_PAIR_ATTN_BWD_ELEM 5  /* pair_attn_bwd_kernel */
 #define MMDTI_PLAN_ROW 6                 /* LayerNorm and row softmax (mmdti_row_plan): 26 rows */
 #define MMDTI_PLAN_STREAM 7              /* casts, dropout, axpy, GELU, column sum, sum of squares, Adam, EMA, step state (mmdti_stream_plan): 29 rows */
+#define MMDTI_PLAN_MAPS 8                /* attention maps (mmdti_maps_plan): 12 rows -- attn_map_kernel<16 | 32 | 64>, the pair map by plane layout and tile bucket */
 int mmdti_plan_table_size(int family, int* size_out);
 const char* mmdti_plan_kernel_name(int family, int index);
 /* Run-time tuning switches (A/B measurements inside one process; defaults come from the environment variable of the same
@@ -638,6 +639,45 @@ int mmdti_attn_plan(int backward, int long_entry, const void* q_bf16, const void
                     const void* ctx_or_dctx_bf16, const float* stats, const float* drow, const void* dq_bf16, const void* dk_bf16,
                     const void* dv_bf16, int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int ldo, int lddq, int lddk,
                     float drop_p, const int* q_off, const int* k_off, const int* k_cnt, int q_rows, int* plan_out);
+
+/* ---- Attention maps: the probabilities of an attention, reduced over heads, as [B, Lq, Lk] fp32 -- without the [B, heads, Lq, Lk]
+ * tensor (BertCoAttention's attention_probs mm_module.py:497-514; HF eager_attention_forward's attn_weights
+ * modeling_roberta.py:158-183; the pair attention's softmax, transformers.py:137-139).  Read-outs: nothing in a training step calls them.
+ * Every element of `out` is written exactly once (pass uninitialised memory), each from a sum in a fixed order: no atomics, two calls
+ * give the same bits.  Purely additive: MMDTI_ABI_VERSION does not move.
+ *
+ * mmdti_attn_map: the map of ONE fused attention, from what mmdti_attn_fwd / mmdti_attn_long_fwd read (q, k, key_add, scale, the packed
+ * arguments -- same meaning, same layouts) and wrote: stats, required, [B,heads,Lq,2] dense or [heads,q_rows,2] packed (q_rows = 0: dense).
+ * p_ij = exp2(s2_ij - m_i) * inv_i with s2 = fma(q.k, scale * log2 e, max(key_add * log2 e, -FLT_MAX)): the expression the backward
+ * kernels recompute.  head = -1: the mean over heads (summed in ascending head order, then times fp32(1 / heads)); head = h: that head.
+ * out: [B, Lq_out, ld_out] fp32, POSITIONAL -- query position i of sequence b is row q_off[b] + i of the packed side -- with
+ * Lq_out >= Lq, ld_out >= Lk; 1 <= Lq, Lk <= 512; head_dim 16, 32 or 64.  q_cnt: nullable [B] int32, the REAL queries of each sequence
+ * (dense or packed; null: every row of the sequence -- under packing that includes its representative pad row).  Zeros are written
+ * wherever the query position is not a real query or the key not a real key (packed: >= k_cnt[b]; dense keys are masked by key_add
+ * alone); such rows of q, k and stats are never read. */
+int mmdti_attn_map(mmdti_stream_t stream, const void* q_bf16, const void* k_bf16, const float* key_add, const float* stats, float* out,
+                   int B, int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int Lq_out, int ld_out, float scale, int head,
+                   const int* q_off, const int* k_off, const int* k_cnt, int q_rows, const int* q_cnt);
+/* mmdti_pair_attn_map: the same from ONE layer's stored pair logits s (mmdti_pair_attn_fwd's s_out; the -inf of padded keys is in it):
+ * fp32 softmax over the stored value, widened exactly.  layout 0 (row-major fp32, stride ld, N <= 320), 1 (tiled fp32) or 3 (compact
+ * fp16), the tiled ones N <= 272 (ld is not read).  out: [B, N, ld_out] fp32, ld_out >= N.  head as above; the mean adds the heads of
+ * each of four runs of ceil(H / 4) consecutive heads in ascending order and the four runs in order (layout 0: all heads in order).
+ * Two rules keep it off memory the forward never stored -- key_tiles: nullable [B] int32, layout 3 (as mmdti_pair_attn_fwd): the key
+ * tiles past the covered count of molecule b are never loaded and count as probability 0; n_real: nullable [B] int32, mandatory with
+ * key_tiles: query rows i >= n_real[b] are written as zeros without reading s (under packed rows the rows past the representative pad
+ * row are never stored). */
+int mmdti_pair_attn_map(mmdti_stream_t stream, const void* s, float* out, int B, int N, int H, int ld, int ld_out, int head, int layout,
+                        const int* key_tiles, const int* n_real);
+/* What mmdti_attn_map (pair 0) or mmdti_pair_attn_map (pair != 0) would launch for the same arguments, without launching: the same
+ * validation, message for message, and the same plan (csrc/maps_plan.h).  Pointers are tested for null and alignment only -- it runs on
+ * a machine without a GPU.  pair != 0 reads q_or_s as s, heads as H, Lq as N, ldq as ld, and out, B, ld_out, head, layout, key_tiles,
+ * n_real; pair 0 reads everything but the last three.  plan_out receives 6 ints: the kernel's row in the MMDTI_PLAN_MAPS table
+ * (mmdti_plan_kernel_name), grid x, workgroup size, dynamic LDS bytes, what the instance is keyed by (head_dim; the 5, 9, 13 or 17 tiles a
+ * tiled pair map is unrolled for -- N <= 80, 144, 208, 272; 0 for row-major planes) and the 16-key tiles a workgroup walks. */
+int mmdti_maps_plan(int pair, const void* q_or_s, const void* k_bf16, const float* key_add, const float* stats, const float* out, int B,
+                    int heads, int Lq, int Lk, int head_dim, int ldq, int ldk, int Lq_out, int ld_out, int head, const int* q_off,
+                    const int* k_off, const int* k_cnt, int q_rows, const int* q_cnt, int layout, const int* key_tiles,
+                    const int* n_real, int* plan_out);
 
 /* ---- GELU on bf16 (kept for un-fused call sites) ------------------------------------------- */
 int mmdti_gelu_fwd_bf16(mmdti_stream_t stream, const void* u_bf16, void* y_bf16, long long n);

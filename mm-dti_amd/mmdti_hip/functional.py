@@ -11,6 +11,7 @@ stream / LayerNorm statistics / softmax / pair-bias chain S fp32, q|k|v and atte
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import weakref
@@ -155,6 +156,118 @@ class _Sites:
 
 
 # ------------------------------------------------------------------------------------------------- Uni-Mol pair encoder
+# ------------------------------------------------------------------------------------------------- attention maps (read-out)
+class AttentionRecorder:
+    """What `with record_attention(spec) as rec:` yields.  While it is live, every attention of a requested kind and layer is followed by
+    ONE map kernel (ops.pair_attn_map on the layer's stored logits L.s; ops.attn_map on L.q / L.k / L.stats) that writes the
+    probabilities, reduced over heads, as [B, Lq, Lk] fp32 -- positional, zeros on padding -- into `maps`:
+        maps["unimol"][l] [B,N,N]    maps["bert"][l] [B,L,L]    maps["text_to_graph"][l] [B,L,N]    maps["graph_to_text"][l] [B,N,L]
+    spec: which (subset of {"cross", "unimol", "bert"}), layers ("last" | "all" | [ints]), head ("mean" | int).
+    counts: {"unimol": [B] int32, "bert": [B] int32} device tensors -- the real atoms / tokens of every sequence of a right-padded batch
+    (MM_Model.attention_maps sets them): query rows from there on come out as zeros.  Without them every row of the padded layout is a
+    query (packed rows carry their own counts).  cross_layers: {id(layer module): (direction, index, count)}.
+    A forward that keeps activations for a backward, or runs a live dropout, is refused before its first launch: the maps describe an
+    inference pass (and the small-batch stack path, which only a kept forward takes, is never met)."""
+    KINDS = ("cross", "unimol", "bert")
+
+    def __init__(self, which=("cross",), layers="last", head="mean"):
+        which = (which,) if isinstance(which, str) else tuple(which)
+        bad = [w for w in which if w not in self.KINDS]
+        if bad or not which:
+            raise ValueError(f"record_attention: which must be a non-empty subset of {self.KINDS} (got {which})")
+        if not (layers in ("last", "all") or (isinstance(layers, (list, tuple)) and all(isinstance(i, int) and i >= 0 for i in layers))):
+            raise ValueError(f"record_attention: layers must be 'last', 'all' or a list of layer indices (got {layers!r})")
+        if not (head == "mean" or (isinstance(head, int) and not isinstance(head, bool) and head >= 0)):
+            raise ValueError(f"record_attention: head must be 'mean' or a head index (got {head!r})")
+        self.which, self.layers, self.head = which, layers if isinstance(layers, str) else tuple(layers), -1 if head == "mean" else int(head)
+        self.maps = {"unimol": {}, "bert": {}, "text_to_graph": {}, "graph_to_text": {}}
+        self.counts = {}
+        self.cross_layers = {}
+        self.keep_operands = False        # tests: also keep what each map kernel read, under operands[name][layer]
+        self.operands = {"unimol": {}, "bert": {}, "text_to_graph": {}, "graph_to_text": {}}
+
+    def wants(self, kind, li, n):
+        if kind not in self.which:
+            return False
+        return li == n - 1 if self.layers == "last" else (True if self.layers == "all" else li in self.layers)
+
+    def check(self, where, keep, *drop_ps):
+        if keep:
+            raise ops.MMDTIError(f"{where}: the attention recorder is live and this forward keeps activations for a backward -- record under "
+                                 "torch.no_grad() (MM_Model.attention_maps does)")
+        if any(p > 0.0 for p in drop_ps):
+            raise ops.MMDTIError(f"{where}: the attention recorder is live under a live dropout -- record in eval mode")
+
+    def _head(self, heads, where):
+        if self.head >= heads:
+            raise ops.MMDTIError(f"{where}: head {self.head} asked of an attention with {heads} heads")
+        return self.head
+
+    def pair(self, li, n, s, B, N, H, ld, key_tiles, pack, padding_mask):
+        """tower 1, layer li of n: s is the layer's stored logits.  The two stale-memory rules: a ragged batch's key tiles past a
+        molecule's covered count are never read (key_tiles), nor are the query rows from n_real on (packed rows: never stored)."""
+        if not self.wants("unimol", li, n):
+            return
+        n_real = pack.n_real if pack is not None else self.counts.get("unimol")
+        if n_real is None and key_tiles is not None:
+            n_real = (N - padding_mask.sum(1)).to(torch.int32) if padding_mask is not None else torch.full((B,), N, dtype=torch.int32, device=s.device)
+        self.maps["unimol"][li] = ops.pair_attn_map(s, B, N, H, ld, self._head(H, "PairEncoderFn"), key_tiles=key_tiles, n_real=n_real)
+        if self.keep_operands:
+            self.operands["unimol"][li] = SimpleNamespace(s=s, B=B, N=N, H=H, ld=ld, key_tiles=key_tiles, n_real=n_real)
+
+    def bert(self, st, L):
+        """a BERT-style layer whose forward just ran (tower 2 or one direction of the cross block): st.rec_tag names it"""
+        tag = st.__dict__.get("rec_tag")
+        if tag is None:
+            return
+        name, li, q_cnt, Lq_out, ld_out = tag
+        head = self._head(L.heads, name)
+        B, Lq, Lk, D = st.B, st.Lq, st.Lk, st.D
+        if L.fused:
+            m = ops.attn_map(L.q, L.k, L.key_add, L.stats, B, L.heads, Lq, Lk, 1.0 / math.sqrt(D // L.heads), head, vl=st.vl, q_cnt=q_cnt,
+                             Lq_out=Lq_out, ld_out=ld_out)
+        else:
+            # materialised scores (sequences past the fused kernels' 512 tokens): L.p [B, heads, Lq, ld] bf16, reduced by the same head rule
+            # -- heads added in ascending order, times fp32(1 / heads); padded rows only (packed sequences need the fused kernels)
+            p = L.p[..., :Lk]
+            if head < 0:
+                m = p[:, 0].float()
+                for h in range(1, L.heads):
+                    m = m + p[:, h].float()
+                m = m * (1.0 / L.heads)
+            else:
+                m = p[:, head].float()
+            if q_cnt is not None:
+                m = m * (torch.arange(Lq, device=m.device).view(1, Lq, 1) < q_cnt.view(B, 1, 1)).to(F32)
+            m = m.contiguous()
+        self.maps[name][li] = m
+        if self.keep_operands:
+            self.operands[name][li] = SimpleNamespace(q=L.q, k=L.k, key_add=L.key_add, stats=L.stats if L.fused else None, p=None if L.fused else L.p,
+                                                      B=B, heads=L.heads, Lq=Lq, Lk=Lk, vl=st.vl, q_cnt=q_cnt, Lq_out=Lq_out, ld_out=ld_out)
+
+
+_recorder: Optional[AttentionRecorder] = None
+
+
+def attention_recorder() -> Optional[AttentionRecorder]:
+    """the live recorder, None outside `with record_attention(...)` (a module-level context, like ops.kernel_timer)"""
+    return _recorder
+
+
+@contextlib.contextmanager
+def record_attention(spec=None, **kw):
+    """`with record_attention(dict(which=("cross",), layers="last", head="mean")) as rec:` -- see AttentionRecorder.  Not re-entrant."""
+    global _recorder
+    if _recorder is not None:
+        raise ops.MMDTIError("record_attention: a recorder is already live")
+    rec = spec if isinstance(spec, AttentionRecorder) else AttentionRecorder(**dict(spec or {}, **kw))
+    _recorder = rec
+    try:
+        yield rec
+    finally:
+        _recorder = None
+
+
 class PairEncoderFn(torch.autograd.Function):
     """TransformerEncoderWithPair.forward (models/transformers.py:96-183) minus the discarded aux outputs:
     emb-LN -> dropout -> zero padded rows -> L x [pre-LN pair-bias attention + FFN, S chained] -> final LN.
@@ -208,6 +321,9 @@ class PairEncoderFn(torch.autograd.Function):
                              row_off=row_off, packed=pack is not None)
         keep = any(ctx.needs_input_grad)      # inference (torch.no_grad / frozen tower and inputs): nothing is kept for a backward --
                                               # the 15 per-layer logit tensors are freed as the stack advances
+        rec = _recorder
+        if rec is not None:
+            rec.check("PairEncoderFn", keep, p_emb, p_res, p_att)
         if keep:
             # the backward follows the trainable set (freeze.plan_tower): it stops at the lowest layer that trains unless the embedding
             # LayerNorm or emb needs the stream gradient; the pair-gradient chain leaves layer 0 only when the bias needs a gradient
@@ -258,6 +374,8 @@ class PairEncoderFn(torch.autograd.Function):
                 x, ln_out, mn, rn = _unimol_layer_fwd_seq(st, layer, L, s_prev, kp0 if li == 0 else None, last and pack is None, scale, nl,
                                                           0 if nl is None else (2 if last else 1))
                 s_prev = L.s
+                if rec is not None:
+                    rec.pair(li, nlayers, L.s, B, N, H, ld, key_tiles, pack, padding_mask)
                 if not last:
                     nxt = (ln_out, mn, rn)
                 elif nl is not None:
@@ -271,6 +389,8 @@ class PairEncoderFn(torch.autograd.Function):
             L.s, L.o = ops.pair_attn_fwd(L.qkv, s_prev, padding_mask if li == 0 else None, B, N, H, ld, scale, p_att, seed, L.site_att,
                                          key_tiles=key_tiles, rag_store=(li == nlayers - 1) and pack is None, row_off=row_off)
             s_prev = L.s
+            if rec is not None:
+                rec.pair(li, nlayers, L.s, B, N, H, ld, key_tiles, pack, padding_mask)
             L.site_o = sites.next()
             L.x1, _, L.h2, L.m2, L.r2 = ops.linear_ln_fwd(L.o, wfwd(att.out_proj.weight), att.out_proj.bias, ln2.weight, ln2.bias, ln2.eps,
                                                           residual=x, drop_p=p_res, seed=seed, site=L.site_o)
@@ -949,7 +1069,10 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
     L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq)
     if L.path == paths.LAYER:
         # the layer's six launches from ONE library call (csrc/layers.hip: the same kernels, arguments and order as below)
-        return (_bert_layer_fwd_seq if self_attn else _bert_cross_layer_fwd_seq)(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
+        ret = (_bert_layer_fwd_seq if self_attn else _bert_cross_layer_fwd_seq)(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
+        if _recorder is not None:
+            _recorder.bert(st, L)
+        return ret
     if L.fw is not None:
         if self_attn:
             # (L.fw[3]: the forward-GEMM shadow of the fused weights; q, k, v are stored bf16 in every mode -- the attention kernels'
@@ -978,6 +1101,8 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
         L.ctx = torch.empty(B * Lq, D, device=s1_32.device, dtype=ops.act16())
         ops.gemm(L.pd, L.v, M=Lq, N=hd, K=Lk, lda=ld, ldb=D, transB=True, out=L.ctx, ldc=D, batch=(B, heads),
                  sA=(heads * Lq * ld, Lq * ld), sB=(Lk * D, hd), sC=(Lq * D, hd))
+    if _recorder is not None:
+        _recorder.bert(st, L)
     L.site_o = sites.next()
     # (each closing Linear of a residual branch runs fused with the post-LN LayerNorm behind it: ops.linear_ln_fwd)
     L.y, L.a32, L.a16, L.am, L.ar = ops.linear_ln_fwd(L.ctx, wfwd(W.o_w), W.o_b, W.ln1_w, W.ln1_b, eps, residual=s1_32, drop_p=p_hid, seed=seed,
@@ -1218,6 +1343,10 @@ class RobertaEncoderFn(torch.autograd.Function):
         sites = _Sites()
         p_hid = cfg.hidden_dropout if training else 0.0
         p_att = cfg.attn_dropout if training else 0.0
+        rec = _recorder
+        if rec is not None:
+            rec.check("RobertaEncoderFn", any(ctx.needs_input_grad), p_hid, p_att)
+        S_pad = Lq
         ids = input_ids.contiguous()
         pos = ops.roberta_position_ids(ids, cfg.pad_idx)
         vl, Mq = None, B * Lq
@@ -1245,6 +1374,9 @@ class RobertaEncoderFn(torch.autograd.Function):
         if T is not None:
             x32 = _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites)
         for li, layer in enumerate(mod.layers if T is None else ()):
+            if rec is not None:
+                st.rec_tag = ("bert", li, pack.n_real if pack is not None else rec.counts.get("bert"), S_pad, S_pad) \
+                    if rec.wants("bert", li, len(mod.layers)) else None
             L, x32, x16 = _bert_layer_fwd(st, x32, x16, x16, key_add, bert_weights(layer), cfg.heads, p_hid, p_att, cfg.ln_eps, seed, sites, True)
             if keep:
                 st.layers.append(_kept(L, li, st.plan))
@@ -1311,6 +1443,13 @@ class CrossLayerFn(torch.autograd.Function):
             B, Lq, D = s1.shape
             Lk = s2.shape[1]
             st = SimpleNamespace(B=B, Lq=Lq, Lk=Lk, D=D, seed=seed, Mq=B * Lq, Mk=B * Lk, vl=None)
+        rec = _recorder
+        if rec is not None:
+            rec.check("CrossLayerFn", any(ctx.needs_input_grad), p_hid, p_att)
+            name, li, n = rec.cross_layers.get(id(layer), ("text_to_graph", 0, 1))
+            if rec.wants("cross", li, n):
+                q_cnt = packs[0].n_real if packs is not None else rec.counts.get("bert" if name == "text_to_graph" else "unimol")
+                st.rec_tag = (name, li, q_cnt, st.Lq if packs is None else packs[0].S, st.Lk if packs is None else packs[1].S)
         s1c = s1.contiguous().view(st.Mq, D)
         s1_16 = ops.cast_act16(s1c)
         s2_16 = ops.cast_act16(s2.contiguous().view(st.Mk, D))

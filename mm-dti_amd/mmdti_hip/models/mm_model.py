@@ -20,6 +20,7 @@ Differences by design, all opt-in or inert for the reference's own usage:
 from __future__ import annotations
 
 import argparse
+import inspect
 import itertools
 import os
 from types import SimpleNamespace
@@ -182,6 +183,40 @@ class CrossAttentionModel(nn.Module):
         graph_to_text = self.graph_attention(graph_embeddings, text_embeddings, extended_txt_mask)[-1]
         text_to_graph = self.text_attention(text_embeddings, graph_embeddings, extended_img_mask)[-1]
         return text_to_graph, graph_to_text
+
+
+class AttentionMaps:
+    """What MM_Model.attention_maps returns: the prediction of the recorded pass and the attention weights it used, reduced over heads
+    (or of one head), as fp32 [B, queries, keys] tensors in the batch's padded positions -- zero wherever the query or the key is padding.
+        outputs                  what model(**net_input) returns for the same inputs (that very pass)
+        text_to_graph[l]         [B, L, N]   SMILES tokens (queries) over atoms (keys), cross layer l       (mm_module.py:497-514)
+        graph_to_text[l]         [B, N, L]   atoms over SMILES tokens
+        unimol[l]                [B, N, N]   Uni-Mol layer l, atoms over atoms                              (transformers.py:137-139)
+        bert[l]                  [B, L, L]   ChemBERTa layer l                                              (modeling_roberta.py:158-183)
+        atom_mask [B, N], token_mask [B, L]  bool, True = real"""
+
+    def __init__(self, outputs, maps, atom_mask, token_mask):
+        self.outputs = outputs
+        self.text_to_graph, self.graph_to_text = dict(maps.get("text_to_graph", {})), dict(maps.get("graph_to_text", {}))
+        self.unimol, self.bert = dict(maps.get("unimol", {})), dict(maps.get("bert", {}))
+        self.atom_mask, self.token_mask = atom_mask.bool(), token_mask.bool()
+
+    @staticmethod
+    def _relevance(maps, query_mask, what):
+        if not maps:
+            raise ValueError(f"AttentionMaps: no {what} map was recorded (ask attention_maps for which=('cross', ...))")
+        m = maps[max(maps)]
+        w = query_mask.to(m.dtype)
+        return (m * w.unsqueeze(-1)).sum(1) / w.sum(1, keepdim=True).clamp_min(1.0)
+
+    def atom_relevance(self):
+        """[B, N]: the mean over a molecule's real SMILES tokens of the last text_to_graph map -- how much of the text's attention each atom
+        receives.  Sums to 1 per molecule, zero on padded atoms."""
+        return self._relevance(self.text_to_graph, self.token_mask, "text_to_graph")
+
+    def token_relevance(self):
+        """[B, L]: the mean over a molecule's real atoms of the last graph_to_text map.  Sums to 1 per molecule, zero on padded tokens."""
+        return self._relevance(self.graph_to_text, self.atom_mask, "graph_to_text")
 
 
 def pair_records_of(model, src_coord, src_tokens):
@@ -516,6 +551,54 @@ class MM_Model(nn.Module):
         if rnc_loss is not None:
             out.append(rnc_loss)
         return out[0] if len(out) == 1 else tuple(out)
+
+    # ------------------------------------------------------------------ attention maps (read-out)
+    def attention_maps(self, *args, which=("cross",), layers="last", head="mean", **net_input):
+        """The attention weights of ONE eval-mode, no_grad forward over the forward's own inputs -> AttentionMaps (its `outputs` are the
+        prediction of that very pass).  which: subset of {"cross", "unimol", "bert"}; layers: "last" | "all" | [layer indices]; head:
+        "mean" (over heads) | a head index.  The pass runs in whatever layout the forward takes for these inputs -- packed rows and
+        pair_inputs="coords" included -- and each requested attention is followed by one map kernel (functional.record_attention): no
+        [B, heads, Lq, Lk] tensor exists.  self.training is restored, module by module."""
+        from ..functional import AttentionRecorder, record_attention
+        from ..packing import right_padded_lengths
+        rec = which if isinstance(which, AttentionRecorder) else AttentionRecorder(which, layers, head)
+        bound = inspect.signature(self.forward).bind(*args, **net_input)
+        src_tokens, attention_mask = bound.arguments["src_tokens"], bound.arguments.get("attention_mask")
+        if attention_mask is None:
+            raise TypeError("MM_Model.attention_maps: input_ids and attention_mask are required")
+        atom_mask = ~src_tokens.eq(self.padding_idx)
+        token_mask = attention_mask.bool().to(src_tokens.device)
+        cm = self.cross_modal_module
+        # (the maps are named by what they hold.  forward() hands the block (encoder_rep, out_bert) as the reference does, mm_model.py:568,
+        #  so the block's `text_attention` has the ATOMS as queries and the SMILES tokens as keys: that is graph_to_text [B, N, L])
+        for name, enc in (("graph_to_text", cm.text_attention), ("text_to_graph", cm.graph_attention)):
+            for li, layer in enumerate(enc.layer):
+                rec.cross_layers[id(layer)] = (name, li, len(enc.layer))
+        # Right-padded masks (what the collate produces): the kernels zero the padded query rows themselves, from the per-sequence counts.
+        # Any other mask: every row is computed and the padded ones are zeroed below.
+        am_h, tm_h = atom_mask.cpu(), token_mask.cpu()
+        right = right_padded_lengths(am_h) is not None and right_padded_lengths(tm_h) is not None
+        if right:
+            rec.counts = {"unimol": atom_mask.sum(1).to(torch.int32), "bert": token_mask.sum(1).to(torch.int32)}
+        from ..runtime import dropout_state
+        was = [(m, m.training) for m in self.modules()]
+        mark = dropout_state.mark()
+        self.eval()
+        try:
+            with torch.no_grad(), record_attention(rec):
+                outputs = self(*args, **net_input)
+        finally:
+            for m, t in was:
+                m.training = t
+            dropout_state.rewind(mark)         # (the seeds this pass drew are drawn again: a training step after it is the step without it)
+        if src_tokens.is_cuda:
+            torch.cuda.synchronize(src_tokens.device)      # (the cross block records one direction on its own stream)
+        if not right and self.last_layout != "packed":
+            qm = {"unimol": atom_mask, "graph_to_text": atom_mask, "bert": token_mask, "text_to_graph": token_mask}
+            for name, d in rec.maps.items():
+                for li in d:
+                    d[li] = d[li] * qm[name].to(d[li].dtype).unsqueeze(-1)
+        return AttentionMaps(outputs, rec.maps, atom_mask, token_mask)
 
     # ------------------------------------------------------------------ collate (semantics of :645-682, pinned by G9)
     def batch_collate_fn(self, samples):

@@ -1080,6 +1080,66 @@ def attn_dispatch(Lq, Lk):
     return (attn_long_fwd, attn_long_bwd) if attn_is_long(Lq, Lk) else (attn_fwd, attn_bwd)
 
 
+# --------------------------------------------------------------------------------------------- attention maps (read-outs)
+def attn_map(q, k, key_add, stats, B, heads, Lq, Lk, scale, head=-1, vl=None, q_cnt=None, Lq_out=None, ld_out=None):
+    """The probabilities of one fused attention, reduced over heads (head = -1: the mean; head = h: that head), recomputed from what its
+    forward read and saved: q [B*Lq, D], k [B*Lk, D] bf16 (vl: packed rows, as _attn_fwd), key_add, stats (as _attn_fwd returned
+    them: [B,heads,Lq,2], or [heads,q_rows,2] with vl).  -> [B, Lq_out, ld_out] fp32, positional, zeros wherever the query is not
+    one of the sequence's q_cnt[b] real queries ([B] int32; None: every row) or the key not a real key."""
+    for t_, n_ in ((q, "attn_map.q"), (k, "attn_map.k")):
+        _chk(t_, BF16, n_, contiguous=False)
+        if t_.stride(1) != 1:
+            raise MMDTIError(f"{n_}: unit column stride required")
+    _chk(stats, F32, "attn_map.stats")
+    D = q.shape[1]
+    hd = D // heads
+    rows_q = B * Lq if vl is None else vl.q_rows
+    if q.shape[0] != rows_q or k.shape[0] != (B * Lk if vl is None else vl.k_rows) or (vl is not None and key_add is not None):
+        raise MMDTIError("attn_map: row counts do not match the layout (packed sequences take no key_add)")
+    if stats.numel() != 2 * heads * rows_q:
+        raise MMDTIError(f"attn_map: stats holds {stats.numel()} values, the forward of this attention saved {2 * heads * rows_q}")
+    if key_add is not None:
+        _chk(key_add, F32, "attn_map.key_add")
+        if key_add.numel() != B * Lk:
+            raise MMDTIError("attn_map: key_add must be [B, Lk]")
+    if q_cnt is not None:
+        _chk(q_cnt, torch.int32, "attn_map.q_cnt")
+        if q_cnt.numel() != B:
+            raise MMDTIError("attn_map: q_cnt must be [B]")
+    Lq_out = Lq if Lq_out is None else int(Lq_out)
+    ld_out = Lk if ld_out is None else int(ld_out)
+    out = torch.empty(B, Lq_out, ld_out, device=q.device, dtype=F32)
+    t0 = kernel_timer.begin("attn_map")
+    lib().mmdti_attn_map(_stream(), q.data_ptr(), k.data_ptr(), _p(key_add), stats.data_ptr(), out.data_ptr(), B, heads, Lq, Lk, hd, q.stride(0),
+                         k.stride(0), Lq_out, ld_out, float(scale), int(head), *(_NO_VARLEN if vl is None else vl.args()), _p(q_cnt))
+    kernel_timer.end("attn_map", t0, 2.0 * (heads if head < 0 else 1) * hd * (B * Lq * Lk if vl is None else vl.pairs))     # flops: q.k^T
+    return out
+
+
+def pair_attn_map(s, B, N, H, ld, head=-1, key_tiles=None, n_real=None, ld_out=None):
+    """The probabilities of one Uni-Mol layer, reduced over heads, from its stored logits s (pair_attn_fwd's s_out, any of its layouts)
+    -> [B, N, ld_out] fp32.  key_tiles / n_real ([B] int32): a ragged batch -- the key tiles past a molecule's covered count and the query
+    rows from n_real[b] on were never stored; they are not read and come out as zeros."""
+    layout = _pair_layout_s(s, "pair_attn_map.s")
+    if not s.is_cuda or not s.is_contiguous():
+        raise MMDTIError("pair_attn_map.s: expected a contiguous device tensor")
+    tiled = pair_is_tiled(s)
+    if not _pair_numel_ok(s, B, N, H, ld, tiled):
+        raise MMDTIError(f"pair_attn_map: s holds {s.numel()} elements, the planes of B={B}, H={H}, N={N}, ld={ld} need {_pair_numel(B, N, H, ld, tiled)}")
+    for t_, n_ in ((key_tiles, "pair_attn_map.key_tiles"), (n_real, "pair_attn_map.n_real")):
+        if t_ is not None:
+            _chk(t_, torch.int32, n_)
+            if t_.numel() != B:
+                raise MMDTIError(f"{n_}: expected [B]")
+    ld_out = N if ld_out is None else int(ld_out)
+    out = torch.empty(B, N, ld_out, device=s.device, dtype=F32)
+    t0 = kernel_timer.begin("pair_attn_map")
+    lib().mmdti_pair_attn_map(_stream(), s.data_ptr(), out.data_ptr(), B, N, H, ld, ld_out, int(head), layout, _p(key_tiles), _p(n_real))
+    kept = _pair_kept if key_tiles is not None else 1.0
+    kernel_timer.end("pair_attn_map", t0, float(H if head < 0 else 1) * B * N * N * kept * s.element_size() + 4.0 * B * N * ld_out)
+    return out
+
+
 # --------------------------------------------------------------------------------------------- InfoNCE pieces
 def seq_mean_fwd(x, B, S, D, ld):
     out = torch.empty(B, D, device=x.device, dtype=F32)

@@ -7,6 +7,10 @@
 This module is the one place that chooses.  Pure Python on plain values (sizes, flags, the switch values of the moment), no device
 work, no library: functional.py gathers the values, asks here and follows the answer.  A function that decides for a whole tower
 answers STACK or LAYER, "not the stack": each layer then gets its own decision.  A stack answer also needs stack_call and stack_model.
+
+The attention recorder (functional.record_attention) needs no flag here: it refuses a forward that keeps activations for a backward
+before the first launch, and STACK is only ever answered for such a forward (keep) -- a recorded pass runs LAYER or OPS, where every
+layer's logits (tower 1) or q, k and row statistics (tower 2, cross block) exist when the layer returns.
 """
 from typing import NamedTuple, Sequence
 

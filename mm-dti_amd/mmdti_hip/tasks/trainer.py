@@ -620,6 +620,24 @@ class Trainer(object):
             metric_score = {"ct_loss": float(np.mean(val_loss)) if val_loss else float("nan")}
         return y_preds, val_loss, metric_score
 
+    # -------------------------------------------------------------- attention maps
+    def attention_maps(self, model, dataset, dump_dir, fold, feature_name=None, load_model=True, **kw):
+        """Iterates ``dataset`` as ``predict`` does (same loader, same batches, eval mode, no_grad) and yields, per molecule, a dict of numpy
+        arrays trimmed to the molecule's real lengths: ``prediction`` (the model's raw output row), ``atoms`` / ``tokens`` (the counts),
+        ``text_to_graph`` {layer: [tokens, atoms]}, ``graph_to_text`` {layer: [atoms, tokens]}, ``unimol`` {layer: [atoms, atoms]},
+        ``bert`` {layer: [tokens, tokens]} -- whichever ``which`` asks for (``**kw``: MM_Model.attention_maps' which / layers / head) --
+        and, when the cross maps are there, ``atom_relevance`` [atoms] and ``token_relevance`` [tokens].  A generator: one batch's maps
+        are alive at a time.  ``predict`` keeps the reference's signature; this is the read-out beside it."""
+        self._require_device()
+        model = model.to(self.device)
+        if load_model == True:      # noqa: E712  (predict's spelling)
+            sd = torch.load(os.path.join(dump_dir, f'model_{fold}.pth'), map_location=self.device, weights_only=True)["model_state_dict"]
+            model.load_state_dict(sd)
+        dataloader = NNDataLoader(feature_name=feature_name, dataset=dataset, batch_size=self.batch_size, shuffle=False,
+                                  collate_fn=self._collate_for(model), **self._loader_kwargs())
+        for net_input, _ in self.device_batches(dataloader, feature_name):
+            yield from trim_attention_maps(model.attention_maps(**net_input, **kw))
+
     def _task_loss(self, loss_func):
         """What the step applies for ``loss_func``: None -- the engine's own kernel for the task (MSE / cross-entropy / BCE-with-
         logits); a kernel-backed object of ``mmdti_hip.losses`` for the reference's focal and GHM entries (one per Trainer and loss
@@ -637,6 +655,26 @@ class Trainer(object):
         if torch.cuda.is_available():
             torch.cuda.manual_seed_all(seed)
         np.random.seed(seed)
+
+
+def trim_attention_maps(am):
+    """models.mm_model.AttentionMaps of one batch -> one dict of numpy arrays per molecule, every map cut to the molecule's real atoms /
+    tokens (right-padded batches: the real positions are the first ones)."""
+    out0 = am.outputs[0] if isinstance(am.outputs, (tuple, list)) else am.outputs
+    pred = out0.detach().float().cpu().numpy()
+    na, nt = am.atom_mask.sum(1).cpu().tolist(), am.token_mask.sum(1).cpu().tolist()
+    host = {k: {l: m.detach().cpu().numpy() for l, m in getattr(am, k).items()} for k in ("text_to_graph", "graph_to_text", "unimol", "bert")}
+    rel = (am.atom_relevance().cpu().numpy(), am.token_relevance().cpu().numpy()) if (am.text_to_graph and am.graph_to_text) else None
+    cut = {"text_to_graph": lambda m, a, t: m[:t, :a], "graph_to_text": lambda m, a, t: m[:a, :t], "unimol": lambda m, a, t: m[:a, :a],
+           "bert": lambda m, a, t: m[:t, :t]}
+    for b, (a, t) in enumerate(zip(na, nt)):
+        rec = {"prediction": pred[b], "atoms": int(a), "tokens": int(t)}
+        for k, maps in host.items():
+            if maps:
+                rec[k] = {l: cut[k](m[b], a, t).copy() for l, m in maps.items()}
+        if rel is not None:
+            rec["atom_relevance"], rec["token_relevance"] = rel[0][b, :a].copy(), rel[1][b, :t].copy()
+        yield rec
 
 
 def _builtin_loss(task, loss_func=None):
