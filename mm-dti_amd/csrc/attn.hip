@@ -24,11 +24,10 @@
 // Dropout: per-element hash of (seed, site, head, query, key) -- the same function in all three kernels.
 #include "common.h"
 #include "attn_plan.h"
+#include "attn_shared.h"   // the pieces attn_maps.hip shares: typedefs, ATTN_LOG2E, attn_mask2, attn_frag_global, attn_prob
 
 namespace mmdti {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -54,12 +53,6 @@ __device__ __forceinline__ uint32_t attn_keep4(const AttnRng& k, uint32_t quad, 
   const uint32_t h = rng24_word(k, quad);
   return ((h & 0xffu) >= t8 ? 1u : 0u) | (((h >> 8) & 0xffu) >= t8 ? 2u : 0u) | (((h >> 16) & 0xffu) >= t8 ? 4u : 0u) | ((h >> 24) >= t8 ? 8u : 0u);
 }
-// Logits are carried in base-2 units (scale * log2 e folded into the scale and the additive key mask), so that the softmax
-// exponential is a bare v_exp_f32.  A finite "minus infinity" mask (finfo.min) stays finite: a fully masked row then softmaxes
-// to uniform, as it does in the unfused path.
-constexpr float ATTN_LOG2E = 1.4426950408889634f;
-__device__ __forceinline__ float attn_mask2(float ka) { return fmaxf(ka * ATTN_LOG2E, -3.4028234663852886e38f); }
-
 // Variable-length (packed) sequences.  q_off / k_off: [B+1] int32 row offsets of every sequence in the query-side / key-side row
 // arrays (sequence b owns rows [off[b], off[b+1]) -- its real tokens, then at most one representative pad row); k_cnt: [B]
 // int32, the REAL keys of sequence b (the representative pad row of the key side is no key: the reference masks padded keys,
@@ -119,12 +112,6 @@ __device__ __forceinline__ bf16x8 attn_frag_tr(const bf16_t* lds, int r0, int r1
   const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 }
-template <int HD>
-__device__ __forceinline__ bf16x8 attn_frag_global(const bf16_t* base, bool valid, int c, int lane) {
-  bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (valid && (HD >= 32 || 8 * (lane >> 4) < HD)) z = *reinterpret_cast<const bf16x8*>(base + 32 * c + 8 * (lane >> 4));
-  return z;
-}
 __device__ __forceinline__ bf16x8 attn_pack(const f32x4& a, const f32x4& b) {
   bf16x8 r;
   r[0] = (__bf16)a[0]; r[1] = (__bf16)a[1]; r[2] = (__bf16)a[2]; r[3] = (__bf16)a[3];
@@ -136,11 +123,6 @@ __device__ __forceinline__ void attn_store4(bf16_t* dst, const f32x4& a) {
   pk.x = (uint32_t)f2bf(a[0]) | ((uint32_t)f2bf(a[1]) << 16);
   pk.y = (uint32_t)f2bf(a[2]) | ((uint32_t)f2bf(a[3]) << 16);
   *reinterpret_cast<uint2*>(dst) = pk;
-}
-// One probability from the saved row statistics (max in base-2 units, 1 / sum): THE expression of the dQ kernel's sweeps (both forms)
-// and of the dK/dV kernel -- their bit-identity rests on it being one.
-__device__ __forceinline__ float attn_prob(float s, float scale2, float ka, float m, float inv) {
-  return __builtin_amdgcn_exp2f(s * scale2 + ka - m) * inv;
 }
 #define ATTN_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
 // Images of more than 256 rows (NT > 16) pass the 64 KiB that a ds_read's immediate offset reaches.  Left alone, the compiler gives

@@ -18,22 +18,12 @@
 // past a ragged molecule's covered count and query rows past n_real are never loaded -- their outputs are written as zeros.
 #include "common.h"
 #include "maps_plan.h"
+#include "attn_shared.h"      // the forward's own mask clamp, probability and fragment load (attn.hip)
+#include "pair_attn_plan.h"   // pa_kt_effective: the key tiles a ragged molecule covers
 
 namespace mmdti {
 
-typedef __bf16 am_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float am_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 am_f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr float AM_LOG2E = 1.4426950408889634f;
-// the additive key mask in base-2 units, clamped as attn.hip's attn_mask2 clamps it (finfo.min stays finite: an all-masked row is uniform)
-__device__ __forceinline__ float am_mask2(float ka) { return fmaxf(ka * AM_LOG2E, -3.4028234663852886e38f); }
-// ragged pair batches: the covered key-tile count of a molecule (pair_attn.h, pa_kt_effective: every count up to 9 tiles, every 2nd up
-// to 13, every 4th beyond)
-__device__ __forceinline__ int am_kt_effective(int kt, int nt) {
-  const int s = nt <= 9 ? 1 : (nt <= 13 ? 2 : 4), k = ((kt < 1 ? 1 : kt) + s - 1) / s * s;
-  return k >= nt ? nt : k;
-}
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 struct AttnMapArgs {
   const bf16_t* q;
@@ -49,18 +39,9 @@ struct AttnMapArgs {
   float scale2, inv_heads;
 };
 
-// 16 rows x 8 consecutive k of a [rows, ld] bf16 matrix as an MFMA 16x16x32 operand (lane & 15 = row, lane >> 4 = k group); head_dim 16:
-// the upper two k groups are zeros
-template <int HD>
-__device__ __forceinline__ am_bf16x8 am_frag(const bf16_t* row, bool valid, int c, int lane) {
-  am_bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (valid && (HD >= 32 || 8 * (lane >> 4) < HD)) z = *reinterpret_cast<const am_bf16x8*>(row + 32 * c + 8 * (lane >> 4));
-  return z;
-}
-
-__device__ __forceinline__ void am_store4(float* out_row, int col, int ld_out, bool vec, const am_f32x4& v) {
+__device__ __forceinline__ void am_store4(float* out_row, int col, int ld_out, bool vec, const f32x4& v) {
   if (vec) {
-    if (col < ld_out) *reinterpret_cast<am_f32x4*>(out_row + col) = v;
+    if (col < ld_out) *reinterpret_cast<f32x4*>(out_row + col) = v;
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -75,7 +56,7 @@ __global__ __launch_bounds__(MAPS_BLOCK) void attn_map_kernel(AttnMapArgs a) {
   const int b = blockIdx.x / nqt, qt = blockIdx.x - b * nqt;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int g = lane >> 4, i = lane & 15;
-  int q0, lq, k0, lk;
+  int q0, lq, k0, lk;      // (attn.hip, attn_seq: the same decode; sharing it costs this kernel an instruction, so it stays here)
   if (a.q_off) {
     q0 = __builtin_amdgcn_readfirstlane(a.q_off[b]);
     lq = __builtin_amdgcn_readfirstlane(a.q_off[b + 1]) - q0;
@@ -95,42 +76,42 @@ __global__ __launch_bounds__(MAPS_BLOCK) void attn_map_kernel(AttnMapArgs a) {
   const bf16_t* qrow = a.q + ((long long)q0 + (qv ? qi : 0)) * a.ldq;
   const int nt_out = (a.ld_out + 15) >> 4;
   for (int t = wave; t < nt_out; t += nw) {
-    am_f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
     if (qblock && t * 16 < lk) {                             // (uniform)
       const int key = t * 16 + i;                            // the key row this lane supplies to the product
       const bool kv = key < lk;
       const bf16_t* krow = a.k + ((long long)k0 + (kv ? key : 0)) * a.ldk;
-      am_f32x4 ka;
+      f32x4 ka;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int kr = t * 16 + 4 * g + r;                   // the keys of this lane's accumulator registers
-        ka[r] = kr < lk ? (a.key_add ? am_mask2(a.key_add[(long long)b * a.Lk + kr]) : 0.f) : -INFINITY;
+        ka[r] = kr < lk ? (a.key_add ? attn_mask2(a.key_add[(long long)b * a.Lk + kr]) : 0.f) : -INFINITY;
       }
       // (a head's operands -- K rows, Q rows, the row statistics -- are loaded while the head before it is computed)
-      am_bf16x8 kf[KC], qf[KC], kfn[KC], qfn[KC];
+      bf16x8 kf[KC], qf[KC], kfn[KC], qfn[KC];
       float2 st = make_float2(0.f, 0.f), stn = make_float2(0.f, 0.f);
       const long long srow0 = a.q_off ? (long long)q0 + qi : (long long)b * a.heads * a.Lq + qi;
       const long long sstep = a.q_off ? (long long)a.q_rows : (long long)a.Lq;
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
-        kf[c] = am_frag<HD>(krow + h0 * HD, kv, c, lane);
-        qf[c] = am_frag<HD>(qrow + h0 * HD, qv, c, lane);
+        kf[c] = attn_frag_global<HD>(krow + h0 * HD, kv, c, lane);
+        qf[c] = attn_frag_global<HD>(qrow + h0 * HD, qv, c, lane);
       }
       if (qv) st = *reinterpret_cast<const float2*>(a.stats + (srow0 + h0 * sstep) * 2);
       for (int h = h0; h < h1; ++h) {
         if (h + 1 < h1) {                                    // (uniform)
 #pragma unroll
           for (int c = 0; c < KC; ++c) {
-            kfn[c] = am_frag<HD>(krow + (h + 1) * HD, kv, c, lane);
-            qfn[c] = am_frag<HD>(qrow + (h + 1) * HD, qv, c, lane);
+            kfn[c] = attn_frag_global<HD>(krow + (h + 1) * HD, kv, c, lane);
+            qfn[c] = attn_frag_global<HD>(qrow + (h + 1) * HD, qv, c, lane);
           }
           if (qv) stn = *reinterpret_cast<const float2*>(a.stats + (srow0 + (h + 1) * sstep) * 2);
         }
-        am_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < KC; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[c], qf[c], acc, 0, 0, 0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sum[r] += __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], a.scale2, ka[r]) - st.x) * st.y;
+        for (int r = 0; r < 4; ++r) sum[r] += attn_prob(acc[r], a.scale2, ka[r], st.x, st.y);
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
           kf[c] = kfn[c];
@@ -157,10 +138,10 @@ struct PairMapArgs {
   float inv_heads;
 };
 
-__device__ __forceinline__ am_f32x4 am_load4(const float* p) { return *reinterpret_cast<const am_f32x4*>(p); }
-__device__ __forceinline__ am_f32x4 am_load4(const _Float16* p) {
-  const am_f16x4 h = *reinterpret_cast<const am_f16x4*>(p);
-  am_f32x4 v;
+__device__ __forceinline__ f32x4 am_load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 am_load4(const _Float16* p) {
+  const f16x4 h = *reinterpret_cast<const f16x4*>(p);
+  f32x4 v;
 #pragma unroll
   for (int r = 0; r < 4; ++r) v[r] = (float)h[r];            // (exact)
   return v;
@@ -170,10 +151,10 @@ __device__ __forceinline__ am_f32x4 am_load4(const _Float16* p) {
 // the fp32 pair-attention kernels); a row of NT tiles is 4 NT registers per lane, three times (this head, the next head's loads in flight,
 // the sum over heads).  A head's loads are all issued before the first is used, and the next head's before this head's softmax.
 template <typename T, int NT>
-__device__ __forceinline__ void pair_map_load_row(am_f32x4 (&X)[NT], const T* run, int kte, bool qv, int g, int i, int vr, int N4) {
+__device__ __forceinline__ void pair_map_load_row(f32x4 (&X)[NT], const T* run, int kte, bool qv, int g, int i, int vr, int N4) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    X[t] = am_f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    X[t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     const int jg = 4 * t + g;                                // this lane's 4-key group of the row
     if (t < kte && qv && 4 * jg < N4) X[t] = am_load4(run + 4 * (vr * jg + i));
   }
@@ -182,7 +163,7 @@ __device__ __forceinline__ void pair_map_load_row(am_f32x4 (&X)[NT], const T* ru
 template <typename T, int NT>
 __global__ __launch_bounds__(MAPS_BLOCK) void pair_attn_map_tiled_kernel(PairMapArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char am_smem[];
-  am_f32x4* fold = reinterpret_cast<am_f32x4*>(am_smem);     // [3][nt][64]
+  f32x4* fold = reinterpret_cast<f32x4*>(am_smem);     // [3][nt][64]
   const int N = a.N, H = a.H;
   const int nt = (N + 15) >> 4, N4 = pair_n4(N);
   const int b = blockIdx.x / nt, qb = blockIdx.x - b * nt;
@@ -191,19 +172,19 @@ __global__ __launch_bounds__(MAPS_BLOCK) void pair_attn_map_tiled_kernel(PairMap
   const int vr = min(16, N - qb * 16);
   const int qi = qb * 16 + i;
   const int nreal = a.n_real ? min(max(__builtin_amdgcn_readfirstlane(a.n_real[b]), 0), N) : N;
-  const int kte = a.key_tiles ? am_kt_effective(min(__builtin_amdgcn_readfirstlane(a.key_tiles[b]), nt), nt) : nt;
+  const int kte = a.key_tiles ? pa_kt_effective(min(__builtin_amdgcn_readfirstlane(a.key_tiles[b]), nt), nt) : nt;
   const bool qv = i < vr && qi < nreal;                      // a row this molecule stores
   const bool live = qb * 16 < nreal;                         // (uniform)
   const int nheads = a.head < 0 ? H : 1, hbase = a.head < 0 ? 0 : a.head;
   const int chunk = (nheads + 3) >> 2;
   const int hw0 = hbase + min(wave * chunk, nheads), hw1 = hbase + min((wave + 1) * chunk, nheads);
-  am_f32x4 ACC[NT];
+  f32x4 ACC[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) ACC[t] = am_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NT; ++t) ACC[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (live) {
     const long long plane = pair_plane(N);
     const T* run = reinterpret_cast<const T*>(a.s) + ((long long)b * H + hw0) * plane + (long long)qb * 16 * N4;
-    am_f32x4 X[NT], Xn[NT];
+    f32x4 X[NT], Xn[NT];
     if (hw0 < hw1) pair_map_load_row<T, NT>(X, run, kte, qv, g, i, vr, N4);
     for (int h = hw0; h < hw1; ++h) {
       run += plane;
@@ -217,13 +198,13 @@ __global__ __launch_bounds__(MAPS_BLOCK) void pair_attn_map_tiled_kernel(PairMap
       }
       m = fmaxf(m, __shfl_xor(m, 16, 64));
       m = fmaxf(m, __shfl_xor(m, 32, 64));
-      const float mneg = m == -INFINITY ? 0.f : -m * AM_LOG2E;
+      const float mneg = m == -INFINITY ? 0.f : -m * ATTN_LOG2E;
       float lsum = 0.f;
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(X[t][r], AM_LOG2E, mneg));
+          const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(X[t][r], ATTN_LOG2E, mneg));
           X[t][r] = e;
           lsum += e;
         }
@@ -250,19 +231,19 @@ __global__ __launch_bounds__(MAPS_BLOCK) void pair_attn_map_tiled_kernel(PairMap
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     if (t < nt && t < nt_out) {
-      am_f32x4 v = ACC[t];
+      f32x4 v = ACC[t];
       if (live) {
         v += fold[(0 * nt + t) * 64 + lane];
         v += fold[(1 * nt + t) * 64 + lane];
         v += fold[(2 * nt + t) * 64 + lane];
         if (a.head < 0) v = v * a.inv_heads;
       }
-      if (!qv) v = am_f32x4{0.f, 0.f, 0.f, 0.f};
+      if (!qv) v = f32x4{0.f, 0.f, 0.f, 0.f};
       if (i < vr) am_store4(out_row, t * 16 + 4 * g, a.ld_out, a.vec != 0, v);
     }
   }
   for (int t = nt; t < nt_out; ++t)
-    if (i < vr) am_store4(out_row, t * 16 + 4 * g, a.ld_out, a.vec != 0, am_f32x4{0.f, 0.f, 0.f, 0.f});
+    if (i < vr) am_store4(out_row, t * 16 + 4 * g, a.ld_out, a.vec != 0, f32x4{0.f, 0.f, 0.f, 0.f});
 }
 
 // row-major fp32 planes (layout 0), N <= 320: a wave per query row, 64 keys per step
@@ -291,11 +272,11 @@ __global__ __launch_bounds__(MAPS_BLOCK) void pair_attn_map_rows_kernel(PairMapA
           m = fmaxf(m, x[c]);
         }
         m = wave_max(m);
-        const float mneg = m == -INFINITY ? 0.f : -m * AM_LOG2E;
+        const float mneg = m == -INFINITY ? 0.f : -m * ATTN_LOG2E;
         float lsum = 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          x[c] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[c], AM_LOG2E, mneg));
+          x[c] = __builtin_amdgcn_exp2f(__builtin_fmaf(x[c], ATTN_LOG2E, mneg));
           lsum += x[c];
         }
         lsum = wave_sum(lsum);
@@ -393,7 +374,7 @@ extern "C" int mmdti_attn_map(mmdti_stream_t stream, const void* q_bf16, const v
   a.q_off = q_off; a.k_off = k_off; a.k_cnt = k_cnt; a.q_cnt = q_cnt;
   a.heads = heads; a.Lq = Lq; a.Lk = Lk; a.ldq = ldq; a.ldk = ldk; a.Lq_out = Lq_out; a.ld_out = ld_out; a.q_rows = q_rows; a.head = head;
   a.vec = maps_vec_ok(out, ld_out) ? 1 : 0;
-  a.scale2 = scale * AM_LOG2E;
+  a.scale2 = scale * ATTN_LOG2E;
   a.inv_heads = 1.0f / (float)heads;
   void* args[] = {&a};
   (void)hipLaunchKernel(g_maps_kernels[plan.key].fn, dim3(plan.grid), dim3(plan.block), args, (size_t)plan.lds, (hipStream_t)stream);

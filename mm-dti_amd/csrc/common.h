@@ -181,6 +181,21 @@ __device__ __forceinline__ uint4 h2bf8(const uint4& u) {
   for (int e = 0; e < 8; ++e) o[e] = (__bf16)(float)h[e];
   return __builtin_bit_cast(uint4, o);
 }
+// eight bf16 values (one 16-byte chunk) -> fp32 (exact), and eight fp32 values -> one chunk of bf16 (round to nearest even)
+__device__ __forceinline__ void unpack8_bf16(const uint4& u, float (&o)[8]) {
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    o[2 * i] = __uint_as_float(w[i] << 16);
+    o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ void pack8_bf16(const float (&v)[8], uint4& u) {
+  u.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
+  u.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
+  u.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
+  u.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
+}
 
 // ---- wave-level reductions (64 lanes) on the DPP crossbar -------------------------------------------------------
 // v_*_dpp reads a neighbour lane as part of a normal VALU op (~1 issue slot) whereas __shfl_xor lowers to ds_bpermute
@@ -211,6 +226,21 @@ __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, dpp_f32<DPP_ROW_BCAST15, 0xa, 0xf, false>(NI, v));
   v = fmaxf(v, dpp_f32<DPP_ROW_BCAST31, 0xc, 0xf, false>(NI, v));
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+// over a workgroup of 256 threads (red: 4 floats of LDS); the four waves' results meet in wave order
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+__device__ __forceinline__ float block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 // Sum 8 per-lane values over the 64 lanes; every lane ends up holding the total of v[lane & 7].
 // Reduce-scatter: each exchange step halves the number of live values (xor 1, 2 by quad_perm, xor 4 by row_shl/shr:4,

@@ -291,10 +291,7 @@ __device__ __forceinline__ void epilogue_oct(const GemmArgs& a, const float* src
   if (a.act == MMDTI_ACT_GELU) {
     if (a.aux_out) {
       uint4 u;
-      u.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      u.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      u.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-      u.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
+      pack8_bf16(v, u);
       nt_store16(a.aux_out + (long long)row * a.ld_aux + col, u);
     }
 #pragma unroll
@@ -322,10 +319,7 @@ __device__ __forceinline__ void epilogue_oct(const GemmArgs& a, const float* src
       gq[e] = dy[0]; gq[e + 1] = dy[1];
     }
     uint4 u;
-    u.x = (uint32_t)f2bf(gq[0]) | ((uint32_t)f2bf(gq[1]) << 16);
-    u.y = (uint32_t)f2bf(gq[2]) | ((uint32_t)f2bf(gq[3]) << 16);
-    u.z = (uint32_t)f2bf(gq[4]) | ((uint32_t)f2bf(gq[5]) << 16);
-    u.w = (uint32_t)f2bf(gq[6]) | ((uint32_t)f2bf(gq[7]) << 16);
+    pack8_bf16(gq, u);
     nt_store16(a.aux_out + (long long)row * a.ld_aux + col, u);
   } else if (a.act == MMDTI_ACT_MUL_AUX) {
     const uint4 u = *reinterpret_cast<const uint4*>(a.aux_in + (long long)row * a.ld_aux + col);

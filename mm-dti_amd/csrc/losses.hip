@@ -7,21 +7,6 @@
 
 namespace mmdti {
 
-__device__ __forceinline__ float block_sum(float v, float* red) {  // 256 threads
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // ---------------------------------------------------------------- unmasked sequence mean (infonce.py:32-33)
 __global__ __launch_bounds__(256) void seq_mean_fwd_kernel(const bf16_t* __restrict__ x, int S, int D, int ld, float* __restrict__ out) {
   const int b = blockIdx.x;
@@ -38,6 +23,20 @@ __global__ __launch_bounds__(256) void seq_mean_bwd_kernel(const float* __restri
     dx[row * ld + d] = f2bf(d < D ? dout[(long long)b * D + d] / (float)S : 0.f);
 }
 
+// The wide forward kernels' shape: 32 row phases x 8 pieces of 8 columns per (sequence, 64-column slice).  seq_mean_acc8: one row's
+// piece into a thread's eight sums; seq_mean_stage: a thread's sums into its phase's row of the LDS image, which column threads then
+// add in phase order -- a FIXED order.
+template <bool WEIGHTED>
+__device__ __forceinline__ void seq_mean_acc8(float (&acc)[8], const uint4& u, float w) {
+  float v[8];
+  unpack8_bf16(u, v);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] += WEIGHTED ? w * v[e] : v[e];
+}
+__device__ __forceinline__ void seq_mean_stage(float (&red)[32][65], const float (&acc)[8], int phase, int piece) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) red[phase][piece * 8 + e] = acc[e];
+}
 // Wide rows (D % 8 == 0): 16-byte loads -- the InfoNCE head pools the 512-wide GELU outputs of every token (pool first, project
 // after: mean_t(W2 h_t + b2) = W2 mean_t(h_t) + b2).  One workgroup per (sequence, 64-column slice): 32 row phases x 8 pieces, the
 // phases folded through LDS in a FIXED order.  (Rounds 1-3 split a sequence's rows over workgroups that met in fp32 atomics: the
@@ -64,17 +63,11 @@ __global__ __launch_bounds__(256) void seq_mean_fwd_vec_kernel(const bf16_t* __r
   if (col < D) {
     for (int r = phase; r < rows; r += 32) {
       const uint4 u = *reinterpret_cast<const uint4*>(x + (r0 + r) * ld + col);
-      const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
       const float w = r < nr ? 1.f : wpad;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc[2 * e] += w * __uint_as_float(w4[e] << 16);
-        acc[2 * e + 1] += w * __uint_as_float(w4[e] & 0xffff0000u);
-      }
+      seq_mean_acc8<true>(acc, u, w);
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[phase][piece * 8 + e] = acc[e];
+  seq_mean_stage(red, acc, phase, piece);
   __syncthreads();
   if (threadIdx.x < 64 && c0 + threadIdx.x < D) {
     float t = 0.f;
@@ -83,7 +76,30 @@ __global__ __launch_bounds__(256) void seq_mean_fwd_vec_kernel(const bf16_t* __r
     out[(long long)b * D + c0 + threadIdx.x] = t * (1.0f / (float)S);
   }
 }
-// dx[row, d] = bf16(dout[b, d] / S * f(aux[row, d])) with f = 1 (aux_mode 0), aux itself (1: a saved gelu') or gelu'(aux) (2)
+// The 8-column body of the three wide backward kernels: dx[row, c8 .. c8+7] = bf16(dout[b, .] * w * f(aux[row, .])) with f = 1
+// (aux_mode 0), aux itself (1: a saved gelu') or gelu'(aux) (2); columns D..ld get dout = 0.  REAL (the real-positions mean): a row
+// that is not `real` is written as exact zeros without reading its aux, and the aux factor is applied below D only.
+template <bool REAL>
+__device__ __forceinline__ void seq_mean_store8(const float* __restrict__ dout, int b, int D, int ld, int c8, long long row, bool real, float w,
+                                                const bf16_t* __restrict__ aux, int ld_aux, int aux_mode, bf16_t* __restrict__ dx) {
+  uint4 o = make_uint4(0u, 0u, 0u, 0u);
+  if (!REAL || real) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (c8 + e < D) ? dout[(long long)b * D + c8 + e] * w : 0.f;
+    if (aux_mode) {
+      float a[8];
+      unpack8_bf16(*reinterpret_cast<const uint4*>(aux + row * ld_aux + c8), a);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        v[e] = (!REAL || c8 + e < D) ? v[e] * (aux_mode == 1 ? a[e] : gelu_erf_grad(a[e])) : 0.f;
+      }
+    }
+    pack8_bf16(v, o);
+  }
+  *reinterpret_cast<uint4*>(dx + row * ld + c8) = o;
+}
+// dx[row, d] = bf16(dout[b, d] / S * f(aux[row, d])), f as in seq_mean_store8
 __global__ __launch_bounds__(256) void seq_mean_bwd_vec_kernel(const float* __restrict__ dout, int S, int D, int ld, const bf16_t* __restrict__ aux,
                                                                int ld_aux, int aux_mode, bf16_t* __restrict__ dx, long long rows) {
   const int cpr = ld >> 3;
@@ -93,24 +109,7 @@ __global__ __launch_bounds__(256) void seq_mean_bwd_vec_kernel(const float* __re
   const int c8 = (int)(chunk - row * cpr) * 8;
   const int b = (int)(row / S);
   const float inv = 1.0f / (float)S;
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (c8 + e < D) ? dout[(long long)b * D + c8 + e] * inv : 0.f;
-  if (aux_mode) {
-    const uint4 u = *reinterpret_cast<const uint4*>(aux + row * ld_aux + c8);
-    const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float a = __uint_as_float((e & 1) ? (w4[e >> 1] & 0xffff0000u) : (w4[e >> 1] << 16));
-      v[e] *= aux_mode == 1 ? a : gelu_erf_grad(a);
-    }
-  }
-  uint4 o;
-  o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-  o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-  o.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-  o.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-  *reinterpret_cast<uint4*>(dx + row * ld + c8) = o;
+  seq_mean_store8<false>(dout, b, D, ld, c8, row, true, inv, aux, ld_aux, aux_mode, dx);
 }
 
 __global__ __launch_bounds__(256) void seq_mean_packed_bwd_kernel(const float* __restrict__ dout, int S, int D, int ld, const int* __restrict__ row_off,
@@ -125,24 +124,7 @@ __global__ __launch_bounds__(256) void seq_mean_packed_bwd_kernel(const float* _
   const int b = row_seq[row];
   const int nr = n_real[b];
   const float w = ((int)row - row_off[b] < nr ? 1.f : (float)(S - nr)) / (float)S;
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (c8 + e < D) ? dout[(long long)b * D + c8 + e] * w : 0.f;
-  if (aux_mode) {
-    const uint4 u = *reinterpret_cast<const uint4*>(aux + row * ld_aux + c8);
-    const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float a = __uint_as_float((e & 1) ? (w4[e >> 1] & 0xffff0000u) : (w4[e >> 1] << 16));
-      v[e] *= aux_mode == 1 ? a : gelu_erf_grad(a);
-    }
-  }
-  uint4 o;
-  o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-  o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-  o.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-  o.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-  *reinterpret_cast<uint4*>(dx + row * ld + c8) = o;
+  seq_mean_store8<false>(dout, b, D, ld, c8, row, true, w, aux, ld_aux, aux_mode, dx);
 }
 
 // ---------------------------------------------------------------- mean over the real positions (InfoNCE(pool="real"))
@@ -186,17 +168,10 @@ __global__ __launch_bounds__(256) void seq_mean_real_fwd_vec_kernel(const bf16_t
     if (m && !m[r]) continue;
     ++n;
     if (col < D) {
-      const uint4 u = *reinterpret_cast<const uint4*>(x + (r0 + r) * ld + col);
-      const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc[2 * e] += __uint_as_float(w4[e] << 16);
-        acc[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u);
-      }
+      seq_mean_acc8<false>(acc, *reinterpret_cast<const uint4*>(x + (r0 + r) * ld + col), 1.f);
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[phase][piece * 8 + e] = acc[e];
+  seq_mean_stage(red, acc, phase, piece);
   if (piece == 0) cnt[phase] = n;
   __syncthreads();
   if (threadIdx.x < 64 && c0 + threadIdx.x < D) {
@@ -210,31 +185,8 @@ __global__ __launch_bounds__(256) void seq_mean_real_fwd_vec_kernel(const bf16_t
     out[(long long)b * D + c0 + threadIdx.x] = c > 0 ? t / (float)c : 0.f;
   }
 }
-// dx[row, d] = bf16(dout[b, d] / count_b * f(aux[row, d])), f as in seq_mean_bwd_vec_kernel; a masked row and the pad columns D..ld
+// dx[row, d] = bf16(dout[b, d] / count_b * f(aux[row, d])), f as in seq_mean_store8; a masked row and the pad columns D..ld
 // are exact zeros (the row's aux is not read: the zero keeps padded rows out of the weight gradient that consumes dx).
-__device__ __forceinline__ void seq_mean_real_store8(const float* __restrict__ dout, int b, int D, int ld, int c8, long long row, bool real, float inv,
-                                                     const bf16_t* __restrict__ aux, int ld_aux, int aux_mode, bf16_t* __restrict__ dx) {
-  uint4 o = make_uint4(0u, 0u, 0u, 0u);
-  if (real) {
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (c8 + e < D) ? dout[(long long)b * D + c8 + e] * inv : 0.f;
-    if (aux_mode) {
-      const uint4 u = *reinterpret_cast<const uint4*>(aux + row * ld_aux + c8);
-      const uint32_t w4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float a = __uint_as_float((e & 1) ? (w4[e >> 1] & 0xffff0000u) : (w4[e >> 1] << 16));
-        v[e] = (c8 + e < D) ? v[e] * (aux_mode == 1 ? a : gelu_erf_grad(a)) : 0.f;
-      }
-    }
-    o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    o.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-    o.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
-  }
-  *reinterpret_cast<uint4*>(dx + row * ld + c8) = o;
-}
 // padded rows: one workgroup per (sequence, 32-position slab); it counts the sequence's real positions itself (integers below 2^24
 // summed as floats: exact), so nothing is handed over from the forward
 __global__ __launch_bounds__(256) void seq_mean_real_bwd_mask_kernel(const float* __restrict__ dout, int S, int D, int ld,
@@ -252,7 +204,7 @@ __global__ __launch_bounds__(256) void seq_mean_real_bwd_mask_kernel(const float
   for (int t = threadIdx.x; t < nrow * cpr; t += 256) {
     const int rr = t / cpr;
     const int c8 = (t - rr * cpr) * 8;
-    seq_mean_real_store8(dout, b, D, ld, c8, (long long)b * S + s0 + rr, m[s0 + rr] != 0, inv, aux, ld_aux, aux_mode, dx);
+    seq_mean_store8<true>(dout, b, D, ld, c8, (long long)b * S + s0 + rr, m[s0 + rr] != 0, inv, aux, ld_aux, aux_mode, dx);
   }
 }
 // pad-free packed rows: every row is real, its sequence's count is its row range
@@ -266,7 +218,7 @@ __global__ __launch_bounds__(256) void seq_mean_real_bwd_packed_kernel(const flo
   const int c8 = (int)(chunk - row * cpr) * 8;
   const int b = row_seq[row];
   const float inv = 1.0f / (float)(row_off[b + 1] - row_off[b]);
-  seq_mean_real_store8(dout, b, D, ld, c8, row, true, inv, aux, ld_aux, aux_mode, dx);
+  seq_mean_store8<true>(dout, b, D, ld, c8, row, true, inv, aux, ld_aux, aux_mode, dx);
 }
 // rows that are not 8-column aligned (no aux factor): one workgroup per row, either layout
 __global__ __launch_bounds__(256) void seq_mean_real_bwd_kernel(const float* __restrict__ dout, int S, int D, int ld, const unsigned char* __restrict__ mask,
@@ -391,6 +343,9 @@ __device__ __forceinline__ void nce_combine(float& m, float& s, float m2, float 
   m = mn;
 }
 
+// element c of the four waves' [16][64] accumulator images, added in wave order (the rows kernel's dQ, the cols kernel's dK)
+__device__ __forceinline__ float nce_fold(const float* s, int c) { return s[c] + s[16 * 64 + c] + s[2 * 16 * 64 + c] + s[3 * 16 * 64 + c]; }
+
 __global__ __launch_bounds__(256) void infonce_rows_mfma_kernel(const float* __restrict__ q, const float* __restrict__ k, int Bg, int D, int row0,
                                                                 int Bl, float invT, float* __restrict__ loss_sum, float* __restrict__ dq,
                                                                 float* __restrict__ gl_out) {
@@ -499,7 +454,7 @@ __global__ __launch_bounds__(256) void infonce_rows_mfma_kernel(const float* __r
   for (int c = tid; c < 16 * 64; c += 256) {
     const int a = c >> 6, d = c & 63;
     if (il0 + a < Bl && d < D)
-      dq[(long long)(row0 + il0 + a) * D + d] += sDq[c] + sDq[16 * 64 + c] + sDq[2 * 16 * 64 + c] + sDq[3 * 16 * 64 + c];
+      dq[(long long)(row0 + il0 + a) * D + d] += nce_fold(sDq, c);
   }
 }
 
@@ -541,7 +496,7 @@ __global__ __launch_bounds__(256) void infonce_cols_mfma_kernel(const float* __r
   __syncthreads();
   for (int c = tid; c < 16 * 64; c += 256) {
     const int a = c >> 6, d = c & 63;
-    if (j0 + a < Bg && d < D) dk[(long long)(j0 + a) * D + d] += sDk[c] + sDk[16 * 64 + c] + sDk[2 * 16 * 64 + c] + sDk[3 * 16 * 64 + c];
+    if (j0 + a < Bg && d < D) dk[(long long)(j0 + a) * D + d] += nce_fold(sDk, c);
   }
 }
 

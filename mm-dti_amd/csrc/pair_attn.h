@@ -11,21 +11,10 @@ namespace mmdti {
 
 constexpr int HD = 8;
 
-__device__ __forceinline__ void load8_bf16(const bf16_t* p, float (&o)[8]) {
-  uint4 u = *reinterpret_cast<const uint4*>(p);
-  uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    o[2 * i] = __uint_as_float(w[i] << 16);
-    o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
+__device__ __forceinline__ void load8_bf16(const bf16_t* p, float (&o)[8]) { unpack8_bf16(*reinterpret_cast<const uint4*>(p), o); }
 __device__ __forceinline__ void store8_bf16(bf16_t* p, const float (&v)[8]) {
   uint4 u;
-  u.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-  u.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-  u.z = (uint32_t)f2bf(v[4]) | ((uint32_t)f2bf(v[5]) << 16);
-  u.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
+  pack8_bf16(v, u);
   *reinterpret_cast<uint4*>(p) = u;
 }
 
@@ -152,12 +141,7 @@ __device__ __forceinline__ void pa_store4_nt(__bf16* p, const f32x4& v) { __buil
 // from being issued ahead).  Supported counts: every k up to 9 tiles, every 2nd up to 13, every 4th beyond, and NT itself -- a
 // count in between runs as the next supported one (the extra tiles are ordinary all-padding tiles: -inf logits, zero gradient,
 // read and written like any other), identically in every layer and in both directions.
-__host__ __device__ constexpr int pa_kt_step(int nt) { return nt <= 9 ? 1 : (nt <= 13 ? 2 : 4); }
-// smallest supported count >= kt
-__host__ __device__ constexpr int pa_kt_effective(int kt, int nt) {
-  const int s = pa_kt_step(nt), k = ((kt < 1 ? 1 : kt) + s - 1) / s * s;
-  return k >= nt ? nt : k;
-}
+// (pa_kt_step / pa_kt_effective, the supported counts: pair_attn_plan.h -- the attention-map kernels round a count the same way)
 // f(std::integral_constant<int, ke>) for a count ke that pa_kt_effective produced (K walks down the supported counts)
 template <int NT, int K, typename F>
 __device__ __forceinline__ void pa_dispatch_kt(int ke, F&& f) {

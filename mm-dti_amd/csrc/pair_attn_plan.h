@@ -28,6 +28,13 @@ constexpr int pa_fwd_f32_key(int bucket, int tiled, int full) { return 68 + buck
 constexpr int PA_BWD_COMPACT_ROWS = 34;
 constexpr int pa_bwd_compact_key(int g16, int nt, int rag) { return g16 * PA_BWD_COMPACT_ROWS + (nt - 1) * 2 + rag; }
 constexpr int pa_bwd_f32_key(int bucket, int tiled, int full, int nw) { return 68 + bucket * 5 + (full ? 4 : (tiled ? 2 : 0) + (nw == 4)); }
+// ragged batches: the key-tile counts the sweeps are unrolled for (pair_attn.h, "Ragged batches"; attn_maps.hip covers the same tiles)
+__host__ __device__ constexpr int pa_kt_step(int nt) { return nt <= 9 ? 1 : (nt <= 13 ? 2 : 4); }
+// smallest supported count >= kt
+__host__ __device__ constexpr int pa_kt_effective(int kt, int nt) {
+  const int s = pa_kt_step(nt), k = ((kt < 1 ? 1 : kt) + s - 1) / s * s;
+  return k >= nt ? nt : k;
+}
 // per-element kernels: 64-key chunks 1..5; the backward's deterministic form behind the plain one
 constexpr int pa_elem_nch(int N) { return (N + 63) / 64 < 5 ? (N + 63) / 64 : 5; }
 constexpr int pa_fwd_elem_key(int nch) { return nch - 1; }

@@ -1494,6 +1494,18 @@ def _pad8(n):
     return (n + 7) // 8 * 8
 
 
+def _infonce_pool(real, pack, mask):
+    """The pooling of one InfoNCE side as (forward, backward), both called as (x | dout, B, n, D, ld[, aux=, aux_mode=]): the mean over
+    the real positions (mask plane or pad-free pack), over all positions of packed rows (the pad row weighted), or over all positions."""
+    if real:
+        return (lambda x, *a: ops.seq_mean_real_fwd(x, *a, mask=mask, pack=pack),
+                lambda dout, *a, **aux: ops.seq_mean_real_bwd(dout, *a, mask=mask, pack=pack, **aux))
+    if pack is not None:
+        return (lambda x, B, n, D, ld: ops.seq_mean_packed_fwd(x, pack, D, ld),
+                lambda dout, B, n, D, ld, **aux: ops.seq_mean_packed_bwd(dout, pack, D, ld, **aux))
+    return ops.seq_mean_fwd, ops.seq_mean_bwd
+
+
 class InfoNCEFn(torch.autograd.Function):
     """InfoNCE.forward (models/infonce.py:23-38) + info_nce (:42-98) with implicit negatives.
 
@@ -1529,26 +1541,7 @@ class InfoNCEFn(torch.autograd.Function):
         st = SimpleNamespace(B=B, Nq=Nq, Np=Np, D=D, d=d, ldp=ldp, seed=seed, p=p)
         dev = query.device
 
-        def proj_real(x, seq, n, dropout_p, site, pack, mask):
-            """proj() with the mean over the real rows (ops.seq_mean_real_fwd): mask plane over [B*n] padded rows, or a pad-free pack."""
-            L = SimpleNamespace()
-            rows = B * n if pack is None else pack.M
-            L.x16 = ops.cast_act16(x.contiguous().view(rows, D), dropout_p, seed, site)
-            L.u = torch.empty(rows, seq[0].weight.shape[0], device=dev, dtype=BF16)
-            h = ops.linear_fwd(L.x16, wfwd(seq[0].weight), seq[0].bias, act=ops.ACT_GELU_FWD, aux_out=L.u, out_dtype=BF16)
-            Hd = h.shape[1]
-            if POOL_THEN_PROJECT and Hd % 8 == 0:
-                L.hbar = ops.seq_mean_real_fwd(h, B, n, Hd, Hd, mask=mask, pack=pack)
-                L.mean = ops.linear_f32_fwd(L.hbar, seq[2].weight.detach(), seq[2].bias.detach())
-                L.h = None
-                return L
-            L.h = h
-            pr = torch.zeros(rows, ldp, device=dev, dtype=BF16)
-            ops.gemm(L.h, wbf16(seq[2].weight), M=rows, N=d, K=Hd, lda=Hd, ldb=seq[2].weight.shape[1], out=pr, ldc=ldp, bias=seq[2].bias)
-            L.mean = ops.seq_mean_real_fwd(pr, B, n, d, ldp, mask=mask, pack=pack)
-            return L
-
-        def proj(x, seq, n, dropout_p, site, pack=None):
+        def proj(x, seq, n, dropout_p, site, pack, mask):
             L = SimpleNamespace()
             rows = B * n if pack is None else pack.M
             L.x16 = ops.cast_act16(x.contiguous().view(rows, D), dropout_p, seed, site)
@@ -1556,33 +1549,25 @@ class InfoNCEFn(torch.autograd.Function):
             # (h is pooled, not multiplied: bf16 in every mode)
             h = ops.linear_fwd(L.x16, wfwd(seq[0].weight), seq[0].bias, act=ops.ACT_GELU_FWD, aux_out=L.u, out_dtype=BF16)
             Hd = h.shape[1]
-            if pack is not None:
-                L.hbar = ops.seq_mean_packed_fwd(h, pack, Hd, Hd)
-                L.mean = ops.linear_f32_fwd(L.hbar, seq[2].weight.detach(), seq[2].bias.detach())
-                L.h = None
-                return L
-            if POOL_THEN_PROJECT and Hd % 8 == 0:
+            pool = _infonce_pool(real, pack, mask)[0]
+            if POOL_THEN_PROJECT and Hd % 8 == 0:             # (always, for packed rows with a pad row: checked above)
                 # mean_t(W2 h_t + b2) == W2 mean_t(h_t) + b2: pool the GELU outputs (fp32), then ONE [B, Hd] x [d, Hd] fp32 linear
                 # -- instead of a 50-wide bf16 GEMM over every token, its three backward GEMMs and a bf16 round of the
                 # per-token projections.  (The unmasked mean over all positions is the reference's, infonce.py:32-33.)
-                L.hbar = ops.seq_mean_fwd(h, B, n, Hd, Hd)
+                L.hbar = pool(h, B, n, Hd, Hd)
                 L.mean = ops.linear_f32_fwd(L.hbar, seq[2].weight.detach(), seq[2].bias.detach())
                 L.h = None
                 return L
             L.h = h
-            pr = torch.zeros(B * n, ldp, device=dev, dtype=BF16)
-            ops.gemm(L.h, wbf16(seq[2].weight), M=B * n, N=d, K=L.h.shape[1], lda=L.h.shape[1], ldb=seq[2].weight.shape[1], out=pr, ldc=ldp,
-                     bias=seq[2].bias)
-            L.mean = ops.seq_mean_fwd(pr, B, n, d, ldp)
+            pr = torch.zeros(rows, ldp, device=dev, dtype=BF16)
+            ops.gemm(L.h, wbf16(seq[2].weight), M=rows, N=d, K=Hd, lda=Hd, ldb=seq[2].weight.shape[1], out=pr, ldc=ldp, bias=seq[2].bias)
+            L.mean = pool(pr, B, n, d, ldp)
             return L
 
         st.packs, st.masks, st.real = packs, masks, real
-        if real:
-            st.Lq = proj_real(query, mod.info_proj_query, Nq, p, 1, None if packs is None else packs[0], None if masks is None else masks[0])
-            st.Lp = proj_real(positive, mod.info_proj_positive, Np, 0.0, 2, None if packs is None else packs[1], None if masks is None else masks[1])
-        else:
-            st.Lq = proj(query, mod.info_proj_query, Nq, p, 1, None if packs is None else packs[0])
-            st.Lp = proj(positive, mod.info_proj_positive, Np, 0.0, 2, None if packs is None else packs[1])
+        pk, mk = packs or (None, None), masks or (None, None)
+        st.Lq = proj(query, mod.info_proj_query, Nq, p, 1, pk[0], mk[0])
+        st.Lp = proj(positive, mod.info_proj_positive, Np, 0.0, 2, pk[1], mk[1])
         both = torch.cat((st.Lq.mean, st.Lp.mean), dim=1)            # [B, 2d] (tiny; one message under DDP)
         both_all = gather(both) if gather is not None else both
         Bg = both_all.shape[0]
@@ -1608,56 +1593,24 @@ class InfoNCEFn(torch.autograd.Function):
             dboth = ctx.rs(dboth)                                   # sum over ranks, keep own rows
         dboth = (dboth * dloss).contiguous()
 
-        def proj_bwd(L, dmean, seq, n, dropout_p, site, want_dx, pack=None, mask=None):
-            if st.real:
-                # (masked rows of du / dpr are exact zeros: padded rows enter no weight gradient and receive a zero input gradient)
-                rows = B * n if pack is None else pack.M
-                if L.h is None:
-                    gw, gb = gbuf(seq[2].weight), gbuf(seq[2].bias)
-                    dhbar = ops.linear_f32_bwd(L.hbar, seq[2].weight.detach(), None, dmean.contiguous(), gw, gb)
-                    Hd = L.hbar.shape[1]
-                    du = ops.seq_mean_real_bwd(dhbar, B, n, Hd, Hd, mask=mask, pack=pack, aux=L.u, aux_mode=1 if ops.GELU_SAVE_GRAD else 2)
-                else:
-                    dpr = ops.seq_mean_real_bwd(dmean.contiguous(), B, n, d, ldp, mask=mask, pack=pack)
-                    gw = gbuf(seq[2].weight)
-                    if gw is not None:
-                        ops.linear_bwd_weight(dpr, L.h, gw)
-                    gb = gbuf(seq[2].bias)
-                    if gb is not None:
-                        ops.colsum(dpr, gb, cols=d)
-                    du = ops.gemm(dpr, wbf16(seq[2].weight), M=rows, N=L.h.shape[1], K=d, lda=ldp, ldb=seq[2].weight.shape[1], transB=True,
-                                  act=ops.ACT_GELU_DX, aux_in=L.u)
-                _lin_bwd_params(du, L.x16, seq[0].weight, seq[0].bias)
-                if not want_dx:
-                    return None
-                dx = ops.linear_bwd_input(du, wbf16(seq[0].weight), out_dtype=F32)
-                if dropout_p > 0:
-                    dx = ops.dropout_f32(dx, dropout_p, st.seed, site)
-                return dx
+        def proj_bwd(L, dmean, seq, n, dropout_p, site, want_dx, pack, mask):
+            # (pool="real": masked rows of du / dpr are exact zeros -- padded rows enter no weight gradient and receive a zero input gradient)
+            pool_bwd = _infonce_pool(st.real, pack, mask)[1]
             if L.h is None:                                                                  # pooled first (see forward)
                 gw, gb = gbuf(seq[2].weight), gbuf(seq[2].bias)
                 dhbar = ops.linear_f32_bwd(L.hbar, seq[2].weight.detach(), None, dmean.contiguous(), gw, gb)
                 Hd = L.hbar.shape[1]
-                if pack is not None:
-                    du = ops.seq_mean_packed_bwd(dhbar, pack, Hd, Hd, aux=L.u, aux_mode=1 if ops.GELU_SAVE_GRAD else 2)
-                else:
-                    du = ops.seq_mean_bwd(dhbar, B, n, Hd, Hd, aux=L.u, aux_mode=1 if ops.GELU_SAVE_GRAD else 2)
-                _lin_bwd_params(du, L.x16, seq[0].weight, seq[0].bias)
-                if not want_dx:
-                    return None
-                dx = ops.linear_bwd_input(du, wbf16(seq[0].weight), out_dtype=F32)
-                if dropout_p > 0:
-                    dx = ops.dropout_f32(dx, dropout_p, st.seed, site)
-                return dx
-            dpr = ops.seq_mean_bwd(dmean.contiguous(), B, n, d, ldp)                       # [B*n, ldp] bf16, pad cols 0
-            gw = gbuf(seq[2].weight)
-            if gw is not None:
-                ops.linear_bwd_weight(dpr, L.h, gw)
-            gb = gbuf(seq[2].bias)
-            if gb is not None:
-                ops.colsum(dpr, gb, cols=d)
-            du = ops.gemm(dpr, wbf16(seq[2].weight), M=B * n, N=L.h.shape[1], K=d, lda=ldp, ldb=seq[2].weight.shape[1], transB=True,
-                          act=ops.ACT_GELU_DX, aux_in=L.u)
+                du = pool_bwd(dhbar, B, n, Hd, Hd, aux=L.u, aux_mode=1 if ops.GELU_SAVE_GRAD else 2)
+            else:
+                dpr = pool_bwd(dmean.contiguous(), B, n, d, ldp)                             # [rows, ldp] bf16, pad cols 0
+                gw = gbuf(seq[2].weight)
+                if gw is not None:
+                    ops.linear_bwd_weight(dpr, L.h, gw)
+                gb = gbuf(seq[2].bias)
+                if gb is not None:
+                    ops.colsum(dpr, gb, cols=d)
+                du = ops.gemm(dpr, wbf16(seq[2].weight), M=L.h.shape[0], N=L.h.shape[1], K=d, lda=ldp, ldb=seq[2].weight.shape[1], transB=True,
+                              act=ops.ACT_GELU_DX, aux_in=L.u)
             _lin_bwd_params(du, L.x16, seq[0].weight, seq[0].bias)
             if not want_dx:
                 return None
@@ -1666,13 +1619,11 @@ class InfoNCEFn(torch.autograd.Function):
                 dx = ops.dropout_f32(dx, dropout_p, st.seed, site)
             return dx
 
-        pk, mk = st.packs, st.masks
-        dxq = proj_bwd(st.Lq, dboth[:, :d], mod.info_proj_query, st.Nq, st.p, 1, ctx.needs_input_grad[0], None if pk is None else pk[0],
-                       None if mk is None else mk[0])
-        dxp = proj_bwd(st.Lp, dboth[:, d:], mod.info_proj_positive, st.Np, 0.0, 2, ctx.needs_input_grad[1], None if pk is None else pk[1],
-                       None if mk is None else mk[1])
+        pk, mk = st.packs or (None, None), st.masks or (None, None)
+        dxq = proj_bwd(st.Lq, dboth[:, :d], mod.info_proj_query, st.Nq, st.p, 1, ctx.needs_input_grad[0], pk[0], mk[0])
+        dxp = proj_bwd(st.Lp, dboth[:, d:], mod.info_proj_positive, st.Np, 0.0, 2, ctx.needs_input_grad[1], pk[1], mk[1])
         notify_grads_ready(mod.parameters())
-        if pk is not None:
+        if st.packs is not None:
             return dxq, dxp, None, None, None, None, None, None, None, None
         return (None if dxq is None else dxq.view(B, st.Nq, st.D), None if dxp is None else dxp.view(B, st.Np, st.D), None, None, None, None, None, None,
                 None, None)

@@ -72,12 +72,12 @@ LOG2E32 = torch.tensor(1.44269504088896340736, dtype=F32)
 # the device-side rules (pa_kt_effective, the size limit) that instances() and geometry() mirror; what the launchers choose is asked of the
 # library (library_plan)
 SOURCE_LINES = {
-    "pair_attn.h": (
+    "pair_attn_plan.h": (
         "__host__ __device__ constexpr int pa_kt_step(int nt) { return nt <= 9 ? 1 : (nt <= 13 ? 2 : 4); }",
         "const int s = pa_kt_step(nt), k = ((kt < 1 ? 1 : kt) + s - 1) / s * s;",
         "return k >= nt ? nt : k;",
-        "MMDTI_REQUIRE(N <= 320,",
     ),
+    "pair_attn.h": ("MMDTI_REQUIRE(N <= 320,",),
 }
 PTR = 0x10000          # a fake, 16-byte aligned device address: mmdti_pair_attn_plan never dereferences one
 

@@ -66,6 +66,50 @@ def test_infonce_module_pools_over_real_tokens(M, golden, order, monkeypatch):
         M.inf.InfoNCE(64, 64)(pq.pack(xq.detach()), pk.pack(xk.detach()), packs=(pq, pk))      # pool="all" on a pad-free pack
 
 
+@pytest.mark.parametrize("form", ["all_padded", "real_packed"])
+def test_infonce_project_then_pool_forms_no_other_test_reaches(M, form, monkeypatch):
+    """The two forms of InfoNCEFn that no test above and no step test runs forward AND backward, both in the project-then-pool order:
+    the mean over all positions of padded rows, and the mean over the real positions of pad-free packed rows.  3 sequences of 1, 5 and 9
+    tokens in S = 9, width 16, hidden 24, d_l = 10 (ldp = 16); the references and bands of the module tests: O.infonce_forward
+    (test_infonce_module_golden) / R.infonce_forward_real (above), both in the oracle's bf16 mode.  The order is chosen by the switch, as
+    above: a hidden width that is no multiple of 8 (20, say) cannot run it -- mmdti_gemm_bf16 refuses its row stride ("lda/ldb must be
+    multiples of 8 elements"), before and after InfoNCEFn's two projections became one."""
+    from mmdti_hip import functional, ops
+    from mmdti_hip.packing import PackedRows
+    monkeypatch.setattr(functional, "POOL_THEN_PROJECT", False)
+    monkeypatch.setattr(ops, "FWD_F16", False)               # (this order is stated in the oracle's bf16 mode only, see above)
+    O.set_forward_fp16(False)
+    B, S, D, Hd, d = 3, 9, 16, 24, 10
+    mod = M.inf.InfoNCE(D, D, pool="real" if form == "real_packed" else "all")
+    mod.d_l = mod.d_av = d
+    torch.manual_seed(7)
+    for name in ("info_proj_query", "info_proj_positive"):
+        setattr(mod, name, torch.nn.Sequential(torch.nn.Linear(D, Hd), torch.nn.GELU(), torch.nn.Linear(Hd, d)))
+    mod = mod.cuda()
+    mod.train(); mod.embed_dropout = 0.0
+    P = {"infonce." + k: v.detach().cpu().clone().requires_grad_() for k, v in mod.state_dict().items()}
+    x = torch.randn(2, B, S, D)
+    xq, xk = x[0].clone().cuda().requires_grad_(), x[1].clone().cuda().requires_grad_()
+    xqo, xko = x[0].clone().requires_grad_(), x[1].clone().requires_grad_()
+    lens = torch.tensor([1, 5, 9])
+    mask = torch.arange(S).view(1, -1) < lens.view(-1, 1)
+    if form == "real_packed":
+        pq, pk = PackedRows(lens, S, device="cuda", pad_row=False), PackedRows(lens, S, device="cuda", pad_row=False)
+        loss = mod(pq.pack(xq), pk.pack(xk), packs=(pq, pk))
+        lo = R.infonce_forward_real(xqo, xko, mask, mask, P, p=0.0, bf16=True)
+    else:
+        loss = mod(xq, xk)
+        lo = O.infonce_forward(xqo, xko, P, p=0.0, bf16=True)
+    print("loss", form, float(loss.detach()), float(lo.detach()))
+    assert abs(float(loss.detach()) - float(lo.detach())) <= 3e-4 * abs(float(lo.detach())) + 1e-5
+    loss.backward()
+    lo.backward()
+    check(xq.grad, xqo.grad, 5e-2, "dxq"); check(xk.grad, xko.grad, 5e-2, "dxk")
+    compare_param_grads(grads_of(mod, "infonce."), P, 6e-2)
+    if form == "real_packed":
+        assert float(xq.grad[~mask.cuda()].abs().max()) == 0.0 and float(xk.grad[~mask.cuda()].abs().max()) == 0.0
+
+
 # ------------------------------------------------------------------------------------------------ steps
 def _loss_and_grads(model, d, host, tgt, task):
     from mmdti_hip.functional import CELossFn, MSELossFn
