@@ -731,6 +731,31 @@ int mmdti_l2norm_bwd(mmdti_stream_t stream, const float* dxhat, const float* xha
  * (v_mfma_f32_16x16x4_f32 -- fp32 products and accumulation, the loss keeps fp32 precision); wider D takes scalar kernels. */
 int mmdti_infonce_dir(mmdti_stream_t stream, const float* qh_all, const float* kh_all, int Bg, int D, int row0,
                       int Bl, float temperature, float* loss_sum, float* dq_all, float* dk_all, float* scratch);
+/* ---- Memory bank of InfoNCE negatives: a ring of the last `cap` L2-normalised embeddings of one side, used as extra keys that receive
+ * no gradient (XBM, Wang et al. 2020; the MoCo queue).  bank [cap, D] fp32, bank_valid [cap] bytes, bank_ids [cap] int64, head one
+ * device int.  D <= 64.  Purely additive: MMDTI_ABI_VERSION does not move.
+ *
+ * mmdti_infonce_bank_dir: mmdti_infonce_dir with the key set extended -- the Bg live keys followed by the slots whose bank_valid byte is
+ * non-zero; when bank_ids and ids_all ([Bg] int64) are both non-null, slot s is also skipped for anchor i if bank_ids[s] ==
+ * ids_all[row0 + i] (a molecule's own stale embedding is not its negative).  A skipped slot adds nothing to the log-sum-exp and
+ * nothing to dq.  The label of anchor i stays live key row0 + i.  dq_all rows [row0, row0 + Bl) accumulate over live and bank keys,
+ * dk_all over the live keys only (the bank gets no gradient); scale and normalisation as mmdti_infonce_dir (0.5 / Bg; the caller
+ * divides the loss by 2 Bg).  The rows pass spans anchors x key splits; every sum has a fixed order (no atomics): same inputs, same bits.
+ * scratch: plan word 11 floats.  The bank buffers are only read. */
+int mmdti_infonce_bank_dir(mmdti_stream_t stream, const float* qh_all, const float* kh_all, int Bg, int D, int row0, int Bl,
+                           const float* bank, const unsigned char* bank_valid, const long long* bank_ids /* nullable */,
+                           const long long* ids_all /* nullable */, int cap, float temperature, float* loss_sum, float* dq_all,
+                           float* dk_all, float* scratch);
+/* Its launch plan without launching (csrc/nce_bank_plan.h; a function of Bl, Bg and cap only), 12 words: 0 grid and 1 block of the two
+ * rows launches (grid = anchor blocks x splits), 2 splits, 3 key tiles in all, 4 live key tiles, 5 anchor blocks of 16, 6 grid of the dQ
+ * fold (256 threads), 7 grid of the column pass, 8-10 scratch offsets in floats of the loss terms, the (max, sum) pairs and the dQ
+ * slabs (the logit gradients [Bl, Bg] sit at 0), 11 scratch floats in all. */
+int mmdti_infonce_bank_plan(int Bg, int Bl, int cap, int D, long long* plan_out);
+/* rows [n, D] -> slots (head + i) % cap, i < n <= cap; a slot's valid byte is 1 only if every element of its row is finite (a
+ * non-finite row is stored as zeros), its id is ids[i] or -1 when ids is null; then head = (head + n) % cap in a launch of its own.
+ * No host read, no synchronisation: a captured graph replays it. */
+int mmdti_infonce_bank_push(mmdti_stream_t stream, float* bank, unsigned char* bank_valid, long long* bank_ids, int* head,
+                            const float* rows, const long long* ids /* nullable */, int n, int D, int cap);
 
 /* ---- ConR / SupCon (models/contrastive.py:3-59, 62-112, 114-169) --------------------------- */
 /* fhat: L2-normalised features [B,D].  labels_f: [B] fp32 (regress: mean target; single: class id as float);

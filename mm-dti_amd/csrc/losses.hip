@@ -4,6 +4,7 @@
 // latency-bound, so each is a small number of single-pass kernels with the gradient produced in the same pass as
 // the loss (no materialised autograd graph, no host sync, no Python loops over B as in the reference).
 #include "common.h"
+#include "nce_bank_plan.h"
 
 namespace mmdti {
 
@@ -498,6 +499,218 @@ __global__ __launch_bounds__(256) void infonce_cols_mfma_kernel(const float* __r
     const int a = c >> 6, d = c & 63;
     if (j0 + a < Bg && d < D) dk[(long long)(j0 + a) * D + d] += nce_fold(sDk, c);
   }
+}
+
+// ---------------------------------------------------------------- InfoNCE with a memory bank of negatives (feature width <= 64)
+// The key set of one direction is the Bg live keys followed by the valid slots of a [cap, D] ring of past embeddings (no gradient to
+// them).  At B = 32, cap = 4096 the rows kernel above would be 2 workgroups over 258 key tiles each, so this rows pass also spans the
+// keys: a workgroup is ONE wave owning 16 anchors and one split's contiguous range of key tiles (nce_bank_plan.h); no tile mixes live
+// keys and slots.
+//   stats  L^tile = Q_a . K_t^T -> online (max, sum) per anchor over the split's unmasked keys -> stats[split][anchor]
+//   grad   folds the splits' (max, sum) in split order -> lse; L^tile again -> gl = (softmax - onehot) * scale; the live-key part goes to
+//          the [Bl, Bg] matrix the column pass reads (with each anchor's loss term behind it, as the rows kernel above leaves them);
+//          dQ_a += gl . K_t over live and bank keys -> this split's slab
+//   fold   dq += the slabs, in split order
+// then infonce_cols_mfma_kernel as it is (dK over the live keys, the loss terms summed in row order).  No atomics: same bits every run.
+// A slot is skipped when its valid byte is 0, and for anchor i when ids are given and its id equals the anchor's: the lane that owns a
+// key column reads the byte and the id once per tile.  Invalid slots are never multiplied (0 * NaN), their rows are not read.
+struct NceBankArgs {
+  const float* q;
+  const float* k;
+  const float* bank;
+  const unsigned char* valid;
+  const long long* bank_ids;      // null (with ids): no id mask
+  const long long* ids;
+  int Bg, D, row0, Bl, cap, splits, tiles, live_tiles, anchor_blocks;
+  float invT;
+};
+
+// the key column of lane i in tile t: its row (unread when !ok), whether it takes part at all, its id (bank tiles with ids only)
+__device__ __forceinline__ const float* nce_bank_key(const NceBankArgs& a, int t, int i, bool& ok, long long& id) {
+  id = 0;
+  if (t < a.live_tiles) {
+    const int key = 16 * t + i;
+    ok = key < a.Bg;
+    return a.k + (long long)(ok ? key : 0) * a.D;
+  }
+  const int slot = 16 * (t - a.live_tiles) + i;
+  ok = slot < a.cap && a.valid[slot] != 0;
+  if (ok && a.bank_ids) id = a.bank_ids[slot];
+  return a.bank + (long long)(ok ? slot : 0) * a.D;
+}
+
+// rows = anchors 4g + r, column = key i of the tile (unscaled); qa: this lane's A operands, anchor i, features 4 s4 + g
+__device__ __forceinline__ nce_f32x4 nce_bank_logits(const float (&qa)[16], const float* __restrict__ kr, bool ok, int D, int nks, int g) {
+  nce_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s4 = 0; s4 < 16; ++s4) {
+    if (s4 < nks) {
+      const int d = 4 * s4 + g;
+      const float bv = (ok && d < D) ? kr[d] : 0.f;
+      acc = NCE_MFMA(qa[s4], bv, acc);
+    }
+  }
+  return acc;
+}
+
+__device__ __forceinline__ void nce_bank_anchor_regs(const NceBankArgs& a, int il0, int g, int i, float (&qa)[16], long long (&aid)[4]) {
+#pragma unroll
+  for (int s4 = 0; s4 < 16; ++s4) {
+    const int d = 4 * s4 + g;
+    qa[s4] = (il0 + i < a.Bl && d < a.D) ? a.q[(long long)(a.row0 + il0 + i) * a.D + d] : 0.f;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int il = il0 + 4 * g + r;
+    aid[r] = (a.ids && a.bank_ids && il < a.Bl) ? a.ids[a.row0 + il] : 0;
+  }
+}
+
+__global__ __launch_bounds__(64) void infonce_bank_stats_kernel(NceBankArgs a, float* __restrict__ stats) {
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int ab = blockIdx.x / a.splits, sp = blockIdx.x - ab * a.splits, il0 = 16 * ab;
+  const int nks = ((a.D + 3) & ~3) >> 2;
+  const bool use_ids = a.ids && a.bank_ids;
+  float qa[16];
+  long long aid[4];
+  nce_bank_anchor_regs(a, il0, g, i, qa, aid);
+  const int t0 = (int)((long long)sp * a.tiles / a.splits), t1 = (int)((long long)(sp + 1) * a.tiles / a.splits);
+  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, sum[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int t = t0; t < t1; ++t) {
+    bool ok;
+    long long id;
+    const float* kr = nce_bank_key(a, t, i, ok, id);
+    const nce_f32x4 acc = nce_bank_logits(qa, kr, ok, a.D, nks, g);
+    const bool idm = use_ids && t >= a.live_tiles;
+    if (ok) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (!(idm && id == aid[r])) nce_combine(m[r], sum[r], acc[r] * a.invT, 1.0f);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+      const float m2 = __shfl_xor(m[r], o, 64), s2 = __shfl_xor(sum[r], o, 64);
+      nce_combine(m[r], sum[r], m2, s2);
+    }
+    if (i == 0) {
+      float* st = stats + (((long long)sp * a.anchor_blocks + ab) * 16 + 4 * g + r) * 2;
+      st[0] = m[r];
+      st[1] = sum[r];
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void infonce_bank_grad_kernel(NceBankArgs a, const float* __restrict__ stats, float* __restrict__ gl_out,
+                                                               float* __restrict__ slabs) {
+  __shared__ float patch[16 * 17];
+  const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+  const int ab = blockIdx.x / a.splits, sp = blockIdx.x - ab * a.splits, il0 = 16 * ab;
+  const int nks = ((a.D + 3) & ~3) >> 2, NU = (a.D + 15) >> 4;
+  const bool use_ids = a.ids && a.bank_ids;
+  float qa[16];
+  long long aid[4];
+  nce_bank_anchor_regs(a, il0, g, i, qa, aid);
+  // every split's (max, sum) of anchor i, in split order
+  float mm = -INFINITY, ss = 0.f;
+  for (int s = 0; s < a.splits; ++s) {
+    const float* st = stats + (((long long)s * a.anchor_blocks + ab) * 16 + i) * 2;
+    nce_combine(mm, ss, st[0], st[1]);
+  }
+  const float lse_i = mm + __logf(ss);
+  float lse[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lse[r] = __shfl(lse_i, 4 * g + r, 64);
+  const int t0 = (int)((long long)sp * a.tiles / a.splits), t1 = (int)((long long)(sp + 1) * a.tiles / a.splits);
+  const float gscale = 0.5f / (float)a.Bg;     // d[(CE_a + CE_b)/2 mean over Bg]/d CE_i
+  nce_f32x4 dacc[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) dacc[u] = nce_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = t0; t < t1; ++t) {
+    bool ok;
+    long long id;
+    const float* kr = nce_bank_key(a, t, i, ok, id);
+    const nce_f32x4 acc = nce_bank_logits(qa, kr, ok, a.D, nks, g);
+    const bool live = t < a.live_tiles, idm = use_ids && !live;
+    const int key = 16 * t + i;                // (a live key's global index)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int an = 4 * g + r, il = il0 + an;
+      float gl = 0.f;
+      if (ok && il < a.Bl && !(idm && id == aid[r])) {
+        const float l = acc[r] * a.invT;
+        const bool diag = live && key == a.row0 + il;
+        gl = (__expf(l - lse[r]) - (diag ? 1.f : 0.f)) * gscale * a.invT;
+        if (live) {
+          gl_out[(long long)il * a.Bg + key] = gl;
+          if (diag) gl_out[(long long)a.Bl * a.Bg + il] = lse[r] - l;      // (this row's loss term: summed in row order by the column pass)
+        }
+      }
+      patch[an * 17 + i] = gl;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float* base = live ? a.k : a.bank;
+    const int c0 = live ? 16 * t : 16 * (t - a.live_tiles);
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const int c = 4 * s4 + g;
+      const float av = patch[i * 17 + c];                        // A: anchor i, key c of the tile
+      const bool okc = __shfl((int)ok, c, 64) != 0;              // (lane c owns column c)
+      const float* kc = base + (long long)(okc ? c0 + c : 0) * a.D;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (u < NU) {
+          const int d = 16 * u + i;
+          const float bv = (okc && d < a.D) ? kc[d] : 0.f;       // B: key c, feature 16 u + i
+          dacc[u] = NCE_MFMA(av, bv, dacc[u]);
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                              // the next tile overwrites the patch
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  float* slab = slabs + ((long long)sp * a.anchor_blocks + ab) * 16 * 64;
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) slab[(4 * g + r) * 64 + 16 * u + i] = dacc[u][r];
+}
+
+// dq[row0 + il] += the splits' slabs, in split order; thread = (anchor, feature)
+__global__ __launch_bounds__(256) void infonce_bank_fold_kernel(const float* __restrict__ slabs, int splits, int rows16, int Bl, int D, int row0,
+                                                                float* __restrict__ dq) {
+  const int c = blockIdx.x * 256 + threadIdx.x, il = c >> 6, d = c & 63;
+  if (il >= Bl || d >= D) return;
+  float t = 0.f;
+  for (int s = 0; s < splits; ++s) t += slabs[((long long)s * rows16 + il) * 64 + d];
+  dq[(long long)(row0 + il) * D + d] += t;
+}
+
+// ring push: wave per row; row r -> slot (head + r) % cap, valid only if every element is finite (a non-finite row is stored as zeros)
+__global__ __launch_bounds__(64) void infonce_bank_push_kernel(float* __restrict__ bank, unsigned char* __restrict__ valid,
+                                                               long long* __restrict__ bank_ids, const int* __restrict__ head,
+                                                               const float* __restrict__ rows, const long long* __restrict__ ids, int D, int cap) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int h = ((*head % cap) + cap) % cap;
+  const int slot = (int)(((long long)h + r) % cap);
+  float bad = 0.f;
+  for (int d = lane; d < D; d += 64) bad += ((__float_as_uint(rows[(long long)r * D + d]) & 0x7f800000u) == 0x7f800000u) ? 1.f : 0.f;
+  bad = wave_sum(bad);
+  for (int d = lane; d < D; d += 64) bank[(long long)slot * D + d] = bad > 0.f ? 0.f : rows[(long long)r * D + d];
+  if (lane == 0) {
+    valid[slot] = bad > 0.f ? 0 : 1;
+    bank_ids[slot] = ids ? ids[r] : -1LL;
+  }
+}
+// (its own launch: no workgroup of the push reads the new head)
+__global__ void infonce_bank_advance_kernel(int* __restrict__ head, int n, int cap) {
+  const int h = ((*head % cap) + cap) % cap;
+  *head = (int)(((long long)h + n) % cap);
 }
 
 // ---------------------------------------------------------------- ConR / SupCon
@@ -1243,6 +1456,58 @@ extern "C" int mmdti_infonce_dir(mmdti_stream_t stream, const float* qh_all, con
                      1.0f / temperature, loss_sum, dq_all, scratch);
   MMDTI_LAUNCH_CHECK();
   hipLaunchKernelGGL(infonce_cols_kernel, dim3(Bg), dim3(64), 0, (hipStream_t)stream, qh_all, scratch, Bg, D, row0, Bl, dk_all, loss_sum);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+
+static int nce_bank_check(const char* who, int Bg, int D, int row0, int Bl, int cap) {
+  MMDTI_REQUIRE(Bg > 0 && D > 0 && row0 >= 0 && Bl > 0 && row0 + Bl <= Bg, "%s: bad sizes (Bg=%d row0=%d Bl=%d)", who, Bg, row0, Bl);
+  MMDTI_REQUIRE(D <= NCE_MAXD, "%s: feature width %d > %d (the head is 50 wide; the bank has the matrix-pipe kernels only)", who, D, NCE_MAXD);
+  MMDTI_REQUIRE(cap > 0 && cap <= (1 << 24), "%s: bank capacity %d out of range", who, cap);
+  return MMDTI_OK;
+}
+extern "C" int mmdti_infonce_bank_plan(int Bg, int Bl, int cap, int D, long long* plan_out) {
+  MMDTI_REQUIRE(plan_out, "infonce_bank_plan: null plan_out");
+  if (int rc = nce_bank_check("infonce_bank_plan", Bg, D, 0, Bl, cap)) return rc;
+  const mmdti::NceBankPlan p = mmdti::nce_bank_plan(Bg, Bl, cap);
+  const long long w[mmdti::NCE_BANK_PLAN_WORDS] = {p.grid,      p.block,     p.splits,    p.tiles,     p.live_tiles, p.anchor_blocks,
+                                                   p.fold_grid, p.cols_grid, p.off_terms, p.off_stats, p.off_slabs,  p.scratch_floats};
+  for (int i = 0; i < mmdti::NCE_BANK_PLAN_WORDS; ++i) plan_out[i] = w[i];
+  return MMDTI_OK;
+}
+extern "C" int mmdti_infonce_bank_dir(mmdti_stream_t stream, const float* qh_all, const float* kh_all, int Bg, int D, int row0, int Bl,
+                                      const float* bank, const unsigned char* bank_valid, const long long* bank_ids,
+                                      const long long* ids_all, int cap, float temperature, float* loss_sum, float* dq_all, float* dk_all,
+                                      float* scratch) {
+  MMDTI_REQUIRE(qh_all && kh_all && bank && bank_valid && loss_sum && dq_all && dk_all && scratch, "infonce_bank_dir: null pointer");
+  if (int rc = nce_bank_check("infonce_bank_dir", Bg, D, row0, Bl, cap)) return rc;
+  MMDTI_REQUIRE(temperature > 0.f, "infonce_bank_dir: temperature must be positive");
+  const mmdti::NceBankPlan p = mmdti::nce_bank_plan(Bg, Bl, cap);
+  const bool use_ids = bank_ids && ids_all;
+  NceBankArgs a = {qh_all, kh_all,   bank,    bank_valid,   use_ids ? bank_ids : nullptr, use_ids ? ids_all : nullptr, Bg, D, row0, Bl, cap,
+                   p.splits, p.tiles, p.live_tiles, p.anchor_blocks, 1.0f / temperature};
+  float* stats = scratch + p.off_stats;
+  float* slabs = scratch + p.off_slabs;
+  hipLaunchKernelGGL(infonce_bank_stats_kernel, dim3(p.grid), dim3(p.block), 0, (hipStream_t)stream, a, stats);
+  MMDTI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(infonce_bank_grad_kernel, dim3(p.grid), dim3(p.block), 0, (hipStream_t)stream, a, stats, scratch, slabs);
+  MMDTI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(infonce_bank_fold_kernel, dim3(p.fold_grid), dim3(256), 0, (hipStream_t)stream, slabs, p.splits, 16 * p.anchor_blocks, Bl, D,
+                     row0, dq_all);
+  MMDTI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(infonce_cols_mfma_kernel, dim3(p.cols_grid), dim3(256), 0, (hipStream_t)stream, qh_all, scratch, Bg, D, row0, Bl, dk_all,
+                     loss_sum);
+  MMDTI_LAUNCH_CHECK();
+  return MMDTI_OK;
+}
+extern "C" int mmdti_infonce_bank_push(mmdti_stream_t stream, float* bank, unsigned char* bank_valid, long long* bank_ids, int* head,
+                                       const float* rows, const long long* ids, int n, int D, int cap) {
+  MMDTI_REQUIRE(bank && bank_valid && bank_ids && head && rows, "infonce_bank_push: null pointer");
+  MMDTI_REQUIRE(D > 0 && cap > 0 && n >= 0 && n <= cap, "infonce_bank_push: bad sizes (n=%d cap=%d D=%d): a push holds at most cap rows", n, cap, D);
+  if (n == 0) return MMDTI_OK;
+  hipLaunchKernelGGL(infonce_bank_push_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, bank, bank_valid, bank_ids, head, rows, ids, D, cap);
+  MMDTI_LAUNCH_CHECK();
+  hipLaunchKernelGGL(infonce_bank_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, head, n, cap);
   MMDTI_LAUNCH_CHECK();
   return MMDTI_OK;
 }

@@ -129,6 +129,34 @@ def atom_counts(src_tokens, pad_idx=0):
     return (real.to(torch.int64) * pos).amax(dim=1).to(torch.int32)
 
 
+class IndexedDataset:
+    """dataset[i] -> (dataset[i], i): the samples travel with their dataset index (the InfoNCE memory bank's sample ids).  Same length,
+    so a sampler draws the same order; picklable when the dataset is (worker processes)."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, i):
+        return self.dataset[i], int(i)
+
+
+class IndexedCollate:
+    """The collate of an IndexedDataset: the wrapped collate sees the samples alone and in their order, so everything it produces is
+    unchanged; the indices are added to its dict as ``sample_ids`` [B] int64."""
+
+    def __init__(self, collate_fn):
+        self.collate_fn = collate_fn
+
+    def __call__(self, samples):
+        net_input, net_target = self.collate_fn([s for s, _ in samples])
+        if isinstance(net_input, dict):
+            net_input = dict(net_input, sample_ids=torch.tensor([i for _, i in samples], dtype=torch.int64))
+        return net_input, net_target
+
+
 def to_device(net_input, device, non_blocking=True):
     """.to(device) for every field of a collated batch except the host-side ones."""
     return {k: (v if k in HOST_FIELDS else v.to(device, non_blocking=non_blocking)) for k, v in net_input.items()}

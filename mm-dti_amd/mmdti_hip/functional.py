@@ -1514,12 +1514,17 @@ class InfoNCEFn(torch.autograd.Function):
     returned is this rank's share of the global loss (the sum over ranks equals the single-process loss)."""
 
     @staticmethod
-    def forward(ctx, query, positive, mod, training, gather, reduce_scatter, row0, packs=None, anchor=None, masks=None):
+    def forward(ctx, query, positive, mod, training, gather, reduce_scatter, row0, packs=None, anchor=None, masks=None, bank=None):
         """anchor: freeze.grad_anchor(mod.parameters()) -- the backward runs when the head trains even if neither input needs a gradient.
         packs = (PackedRows of query, PackedRows of positive): [M, D] packed rows; the unmasked mean over the padded positions
         (infonce.py:32-33) weights each representative pad row by the number of padded positions it stands for.
         mod.pool == "real" (InfoNCE(pool="real")): the mean runs over the real positions only, in either order of pooling and
-        projecting -- masks = ([B,Nq], [B,Np]) planes (non-zero = real) for padded inputs, pad-free packs for packed rows."""
+        projecting -- masks = ([B,Nq], [B,Np]) planes (non-zero = real) for padded inputs, pad-free packs for packed rows.
+        bank = (ring of past query-side embeddings, ring of past positive-side ones, sample_ids [B] int64 | None), models/infonce.py's
+        MemoryRing: the valid slots are extra keys without a gradient (direction a reads the positive-side ring, direction b the
+        query-side one; a slot holding the anchor's own id is skipped), then all Bg rows of both sides are pushed -- under data
+        parallelism the gathered rows, so every rank holds the same rings (the ids ride a second, int64 all-gather).  None: no bank,
+        the launches below are the bank-less ones."""
         real = getattr(mod, "pool", "all") == "real"
         if real and (packs is None) == (masks is None):
             raise ops.MMDTIError("InfoNCEFn(pool='real'): exactly one of masks (padded rows) and packs (pad-free packed rows) is given")
@@ -1576,8 +1581,20 @@ class InfoNCEFn(torch.autograd.Function):
         loss = torch.zeros(1, device=dev, dtype=F32)
         dqh, dkh = torch.zeros_like(qh), torch.zeros_like(kh)
         T = mod.temperature
-        ops.infonce_dir(qh, kh, row0, B, T, loss, dqh, dkh)
-        ops.infonce_dir(kh, qh, row0, B, T, loss, dkh, dqh)
+        if bank is None:
+            ops.infonce_dir(qh, kh, row0, B, T, loss, dqh, dkh)
+            ops.infonce_dir(kh, qh, row0, B, T, loss, dkh, dqh)
+        else:
+            ring_q, ring_k, ids = bank
+            if Bg > ring_q.rows.shape[0]:
+                raise ValueError(f"InfoNCE: memory_bank={ring_q.rows.shape[0]} is smaller than the global batch ({Bg} rows are pushed per step)")
+            if ids is not None:
+                ids = ids.contiguous()
+                ids = gather(ids.view(-1, 1)).view(-1).contiguous() if gather is not None else ids
+            ops.infonce_bank_dir(qh, kh, row0, B, T, loss, dqh, dkh, ring_k.rows, ring_k.valid, ring_k.ids, ids)
+            ops.infonce_bank_dir(kh, qh, row0, B, T, loss, dkh, dqh, ring_q.rows, ring_q.valid, ring_q.ids, ids)
+            ops.infonce_bank_push(ring_q.rows, ring_q.valid, ring_q.ids, ring_q.head, qh, ids)
+            ops.infonce_bank_push(ring_k.rows, ring_k.valid, ring_k.ids, ring_k.head, kh, ids)
         st.qh, st.kh, st.dqh, st.dkh, st.Bg, st.row0 = qh, kh, dqh, dkh, Bg, row0
         ctx.st, ctx.mod, ctx.rs = st, mod, reduce_scatter
         return (loss / (2.0 * Bg)).view(())
@@ -1624,9 +1641,9 @@ class InfoNCEFn(torch.autograd.Function):
         dxp = proj_bwd(st.Lp, dboth[:, d:], mod.info_proj_positive, st.Np, 0.0, 2, ctx.needs_input_grad[1], pk[1], mk[1])
         notify_grads_ready(mod.parameters())
         if st.packs is not None:
-            return dxq, dxp, None, None, None, None, None, None, None, None
+            return dxq, dxp, None, None, None, None, None, None, None, None, None
         return (None if dxq is None else dxq.view(B, st.Nq, st.D), None if dxp is None else dxp.view(B, st.Np, st.D), None, None, None, None, None, None,
-                None, None)
+                None, None, None)
 
 
 def infonce_rows_grad(both_all, d, temperature, row0, B):

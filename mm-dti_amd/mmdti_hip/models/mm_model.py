@@ -430,7 +430,9 @@ class MM_Model(nn.Module):
 
     def forward(self, src_tokens, src_distance=None, src_edge_type=None, input_ids=None, attention_mask=None, weights=None,
                 return_infonce_loss=False, return_ct_loss=False, return_feature=False, net_target=None, use_weight=None,
-                epoch=0, atom_counts=None, token_counts=None, token_pad_id=None, packable=False, src_coord=None, **kwargs):
+                epoch=0, atom_counts=None, token_counts=None, token_pad_id=None, packable=False, src_coord=None, sample_ids=None, **kwargs):
+        # sample_ids: optional [B] int64, one id per molecule (the Trainer passes dataset indices) -- read only by the InfoNCE memory bank
+        # (InfoNCE(memory_bank=Q)): a stored embedding of the anchor's own molecule is not its negative.
         # Pair inputs: the two [B,N,N] planes when the batch carries them (used exactly as ever, src_coord then stays unread as in the
         # reference, mm_model.py:540); else src_coord [B,N,3], from which the kernels derive every pair (pair_bias).  Neither: an error.
         if src_distance is None or src_edge_type is None:
@@ -504,15 +506,16 @@ class MM_Model(nn.Module):
             # block's GEMMs (and its backward under the block's backward: autograd replays on the forward's stream).
             # (pool="real" on padded rows: the head's mean runs over the device masks -- no host value, so it captures into a graph)
             imasks = dict(query_mask=img_mask, key_mask=attention_mask) if self.infonce_pool == "real" and packs is None else {}
+            ikw = {} if sample_ids is None or self.infonce.memory_bank == 0 else dict(sample_ids=sample_ids)
             if side is not None and self.infonce_on_side_stream:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    ct_loss = self.infonce(encoder_rep, out_bert, packs=packs, **imasks)
+                    ct_loss = self.infonce(encoder_rep, out_bert, packs=packs, **imasks, **ikw)
                 encoder_rep.record_stream(side)
                 out_bert.record_stream(side)
                 infonce_side = True
             else:
-                ct_loss = self.infonce(encoder_rep, out_bert, packs=packs, **imasks)
+                ct_loss = self.infonce(encoder_rep, out_bert, packs=packs, **imasks, **ikw)
 
         cross_txt_output_layer, cross_output_layer = self.cross_modal_module(encoder_rep, out_bert, img_mask, attention_mask, packs=packs)
         # mm_model.py:572-576 (zero padded rows, concat, masked mean) in one kernel

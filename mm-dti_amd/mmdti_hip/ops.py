@@ -1245,6 +1245,48 @@ def infonce_dir(qh_all, kh_all, row0, Bl, temperature, loss_sum, dq_all, dk_all)
                             dq_all.data_ptr(), dk_all.data_ptr(), scratch.data_ptr())
 
 
+INFONCE_BANK_PLAN_FIELDS = ("grid", "block", "splits", "tiles", "live_tiles", "anchor_blocks", "fold_grid", "cols_grid", "off_terms",
+                            "off_stats", "off_slabs", "scratch_floats")
+
+
+def infonce_bank_plan(Bg, Bl, cap, D=50):
+    """The launch plan of infonce_bank_dir (csrc/nce_bank_plan.h) as a dict, without launching: no device is touched."""
+    import ctypes
+    words = (ctypes.c_longlong * len(INFONCE_BANK_PLAN_FIELDS))()
+    lib().mmdti_infonce_bank_plan(int(Bg), int(Bl), int(cap), int(D), ctypes.addressof(words))
+    return dict(zip(INFONCE_BANK_PLAN_FIELDS, (int(w) for w in words)))
+
+
+def infonce_bank_dir(qh_all, kh_all, row0, Bl, temperature, loss_sum, dq_all, dk_all, bank, valid, bank_ids=None, ids_all=None):
+    """infonce_dir with the valid slots of `bank` [cap, D] as further keys (no gradient to them); ids: a slot whose id equals the
+    anchor's is skipped for that anchor."""
+    Bg, D = qh_all.shape
+    cap = bank.shape[0]
+    _chk(bank, F32, "infonce_bank.bank")
+    if bank.shape[1] != D or valid.dtype != torch.uint8 or valid.numel() != cap or not valid.is_contiguous():
+        raise MMDTIError(f"infonce_bank_dir: bank must be [cap, {D}] fp32 with valid [cap] uint8 (got {tuple(bank.shape)}, {valid.dtype})")
+    for t, n in ((bank_ids, cap), (ids_all, Bg)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous()):
+            raise MMDTIError(f"infonce_bank_dir: ids must be contiguous int64 ({n} of them)")
+    scratch = torch.empty(infonce_bank_plan(Bg, Bl, cap, D)["scratch_floats"], device=qh_all.device, dtype=F32)
+    lib().mmdti_infonce_bank_dir(_stream(), qh_all.data_ptr(), kh_all.data_ptr(), Bg, D, row0, Bl, bank.data_ptr(), valid.data_ptr(),
+                                 _p(bank_ids), _p(ids_all), cap, float(temperature), loss_sum.data_ptr(), dq_all.data_ptr(),
+                                 dk_all.data_ptr(), scratch.data_ptr())
+
+
+def infonce_bank_push(bank, valid, bank_ids, head, rows, ids=None):
+    """rows [n, D] -> slots (head + i) % cap; head (one device int32) advances by n on the device (no host read: capturable)."""
+    cap, D = bank.shape
+    _chk(rows, F32, "infonce_bank.rows")
+    n = rows.shape[0]
+    if rows.shape[1] != D or head.dtype != torch.int32 or bank_ids.dtype != torch.int64 or valid.dtype != torch.uint8:
+        raise MMDTIError("infonce_bank_push: rows [n, D] fp32, head int32, bank_ids int64, valid uint8")
+    if ids is not None and (ids.dtype != torch.int64 or ids.numel() != n or not ids.is_contiguous()):
+        raise MMDTIError(f"infonce_bank_push: ids must be {n} contiguous int64")
+    lib().mmdti_infonce_bank_push(_stream(), bank.data_ptr(), valid.data_ptr(), bank_ids.data_ptr(), head.data_ptr(), rows.data_ptr(),
+                                  _p(ids), n, D, cap)
+
+
 # --------------------------------------------------------------------------------------------- ConR / SupCon
 def ct_loss_fwd(mode, fhat, labels_f=None, labels_i=None, pred=None, weights=None, w=0.2, t=0.07, e=0.01, coef=1.0):
     B, D = fhat.shape

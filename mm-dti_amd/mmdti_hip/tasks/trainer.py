@@ -257,6 +257,13 @@ class Trainer(object):
         optimizer_steps_per_epoch(0, self.accum_steps)          # (raises on accum_steps < 1)
         if self.accum_negatives not in ACCUM_NEGATIVES:
             raise ValueError(f"Trainer: accum_negatives must be one of {ACCUM_NEGATIVES}, got {self.accum_negatives!r}")
+        # cross-batch memory of InfoNCE negatives (FineTuner(memory_bank=Q); not a reference parameter, 0 = off): Q slots per side of past
+        # embeddings as extra negatives; every training sample then travels with its dataset index, so that a molecule's own stale
+        # embedding is not its negative
+        from ..models.infonce import check_memory_bank
+        self.memory_bank = check_memory_bank(params.get('memory_bank', 0), "Trainer")
+        if self.memory_bank and self.accum_steps > 1 and self.accum_negatives == 'union':
+            raise ValueError("Trainer: memory_bank is not available with accum_negatives='union' (use accum_negatives='micro')")
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
@@ -364,13 +371,18 @@ class Trainer(object):
         """-> (loader, sampler | None).  Data parallel: each rank draws a disjoint, equally sized shard of every epoch's permutation
         (``DistributedSampler(drop_last=True)``; batch_size is per rank), so every rank takes the same number of steps -- a rank
         with one batch more would wait forever in that step's collectives.  Device-independent (covered by the 2-rank gloo tests)."""
+        collate_fn = self._collate_for(model)
+        if getattr(self, "memory_bank", 0):
+            # (same length, same sampler draws, the same collate over the same samples: only ``sample_ids`` is added to the batch)
+            from ..collate import IndexedCollate, IndexedDataset
+            train_dataset, collate_fn = IndexedDataset(train_dataset), IndexedCollate(collate_fn)
         if self._ddp():
             from torch.utils.data.distributed import DistributedSampler
             sampler = DistributedSampler(train_dataset, shuffle=True, seed=self.seed, drop_last=True)
-            return TorchDataLoader(dataset=train_dataset, batch_size=self.batch_size, sampler=sampler, collate_fn=self._collate_for(model),
+            return TorchDataLoader(dataset=train_dataset, batch_size=self.batch_size, sampler=sampler, collate_fn=collate_fn,
                                    drop_last=True, **self._loader_kwargs()), sampler
         return NNDataLoader(feature_name=feature_name, dataset=train_dataset, batch_size=self.batch_size, shuffle=True,
-                            collate_fn=self._collate_for(model), drop_last=True, **self._loader_kwargs()), None
+                            collate_fn=collate_fn, drop_last=True, **self._loader_kwargs()), None
 
     def total_optimizer_steps(self, batches_per_epoch):
         """What the schedule (and with it the warm-up) counts: optimizer steps -- (len(loader) // accum_steps) * max_epochs."""
@@ -410,7 +422,11 @@ class Trainer(object):
                            max_norm=self.max_norm if self.amp else None, distributed=self.distributed, skip_nonfinite=self.skip_nonfinite,
                            deterministic=self.deterministic, fds_stats=self.fds_stats, weight_decay=self.weight_decay,
                            decoupled_weight_decay=self.decoupled_weight_decay, param_groups=groups, ema_decay=self.ema_decay,
-                           ema_warmup=self.ema_warmup, global_ct=self.global_ct)
+                           ema_warmup=self.ema_warmup, global_ct=self.global_ct, memory_bank=self.memory_bank or None)
+        if engine.memory_bank:
+            model.infonce.reset_memory_bank()            # (every fit starts from an empty bank; a resumed state then fills it)
+            logger.info('InfoNCE memory bank: {} slots per side ({} steps of history)'.format(
+                engine.memory_bank, engine.memory_bank // max(1, self.batch_size)))
         logger.info('ConR / SupCon keys: {}'.format(
             'global (every rank\'s molecules; the term is the union batch\'s)' if engine.global_ct else 'rank-local (this process\'s batch)'))
         if self.ema_decay is not None:

@@ -97,7 +97,8 @@ class FineTuner:
                  max_norm: Optional[float] = 5.0, distributed: bool = False, bucket_bytes: int = 32 << 20, skip_nonfinite: bool = False,
                  loss_key: Optional[str] = None, deterministic: Optional[bool] = None, fds_stats: str = "epoch_pass",
                  weight_decay: float = 0.0, decoupled_weight_decay: bool = False, param_groups=None,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True, global_ct: Optional[bool] = None):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, global_ct: Optional[bool] = None,
+                 memory_bank: Optional[int] = None):
         """deterministic: True enters the process-wide deterministic mode (ops.set_deterministic: every cross-workgroup sum into a
         parameter gradient in a fixed order, one reduction workspace per launch stream); None follows MMDTI_DETERMINISTIC; False (and
         an unset environment) touches nothing.  Sites that have no fixed-order form yet raise in the mode (DESIGN.md lists them), and so
@@ -127,7 +128,12 @@ class FineTuner:
         global_ct: global ConR / SupCon negatives under data parallelism -- every rank's anchors meet the molecules of ALL ranks, so N
         ranks on a global batch optimise the single-process CT loss of that batch (DESIGN.md "Global ConR / SupCon negatives").  None
         follows MMDTI_GLOBAL_CT (unset / 0 = off).  Effective only with distributed=True and active collectives; otherwise, and when
-        off, the CT term is the rank-local one and nothing about the step changes."""
+        off, the CT term is the rank-local one and nothing about the step changes.
+        memory_bank: Q > 0 gives the model's InfoNCE head a cross-batch memory of Q slots per side (InfoNCE.set_memory_bank): the last Q
+        L2-normalised embeddings of each side stay on the device as extra negatives without a gradient, every training step reads them and
+        then pushes its own (global) rows; ``StepOutput.infonce_loss`` is the banked value.  0 removes a bank the model has; None (default)
+        leaves the model as it is.  Without a bank no launch, argument or allocation changes (DESIGN.md "Memory bank of InfoNCE negatives").
+        net_input may carry ``sample_ids`` ([B] int64): a slot that holds the anchor's own molecule is skipped."""
         self.ema_decay, self.ema_warmup = check_ema_decay(ema_decay), bool(ema_warmup)
         self._averaged = False
         self._time_negatives = None                      # accumulate.TimeNegatives while an accumulated union step runs
@@ -135,6 +141,15 @@ class FineTuner:
             raise ValueError(f"FineTuner: fds_stats must be one of {FDS_STATS_MODES}, got {fds_stats!r}")
         self.fds_stats = fds_stats
         self.model, self.task = model, task
+        if memory_bank is not None:
+            from .models.infonce import check_memory_bank
+            Q = check_memory_bank(memory_bank, "FineTuner")
+            head = getattr(model, "infonce", None)
+            if head is None or not hasattr(head, "set_memory_bank"):
+                if Q:
+                    raise ValueError("FineTuner: memory_bank needs a model with an InfoNCE head (model.infonce)")
+            elif head.memory_bank != Q:
+                head.set_memory_bank(Q)
         from . import ops
         self.deterministic = ops.deterministic_default() if deterministic is None else bool(deterministic)
         if self.deterministic:
@@ -280,6 +295,16 @@ class FineTuner:
                                "average's buffer until the block ends")
 
     # ------------------------------------------------------------------ resuming a run (DESIGN.md "Resuming a run")
+    def _bank_state(self):
+        """[(name, tensor)] of the InfoNCE memory bank's rings; [] without one"""
+        head = getattr(self.model, "infonce", None)
+        return head.memory_bank_state() if hasattr(head, "memory_bank_state") else []
+
+    @property
+    def memory_bank(self) -> int:
+        """slots per side of the model's InfoNCE memory bank (0: none)"""
+        return int(getattr(getattr(self.model, "infonce", None), "memory_bank", 0))
+
     def _arena_names(self):
         """the arena's parameters by their names in the model, in arena order"""
         of = {id(p): n for n, p in self.model.named_parameters()}
@@ -316,6 +341,9 @@ class FineTuner:
             "fds_stream": None if fds_acc is None else {"acc": host_copy(fds_acc), "active": bool(getattr(self.model, "fds_streaming", False))},
             "deterministic": bool(self.deterministic),
         }
+        bank = self._bank_state()
+        if bank:                  # (a state written without a bank has no such key: those files stay as they were)
+            sd["memory_bank"] = dict({"slots": self.memory_bank}, **{n: host_copy(t) for n, t in bank})
         torch.cuda.current_stream().synchronize()
         if hasattr(self.task_loss, "state_dict"):
             sd["task_loss"] = self.task_loss.state_dict()
@@ -332,6 +360,16 @@ class FineTuner:
             if (saved is None) != (own is None):
                 raise ValueError(f"FineTuner.load_state_dict: the state was written {'without' if saved is None else 'with'} {what}, this "
                                  f"engine was built {'without' if own is None else 'with'} it")
+        saved_bank = sd.get("memory_bank")
+        if (saved_bank is None) != (self.memory_bank == 0):
+            raise ValueError(f"FineTuner.load_state_dict: the state was written {'without' if saved_bank is None else 'with'} an InfoNCE memory "
+                             f"bank, this engine was built {'without' if self.memory_bank == 0 else 'with'} one")
+        if saved_bank is not None:
+            own = dict(self._bank_state())
+            if int(saved_bank["slots"]) != self.memory_bank or any(n not in saved_bank or tuple(saved_bank[n].shape) != tuple(t.shape)
+                                                                   for n, t in own.items()):
+                raise ValueError(f"FineTuner.load_state_dict: the state's InfoNCE memory bank has {int(saved_bank['slots'])} slots per side, "
+                                 f"this engine's {self.memory_bank}")
         if sd["groups"] is not None and list(sd["groups"]["names"]) != list(self._group_names):
             raise ValueError(f"FineTuner.load_state_dict: the state's parameter groups are {list(sd['groups']['names'])}, this engine's "
                              f"{list(self._group_names)}")
@@ -398,6 +436,8 @@ class FineTuner:
         if fs is not None:
             put(self.model.FDS.stream_state(), fs["acc"])
             self.model.fds_streaming = bool(fs["active"])
+        for n, t in self._bank_state():
+            put(t, sd["memory_bank"][n])
         d = sd["dropout"]
         dropout_state.load_state(dropout_base_for_rank(d["base"], d["rank"], self._dropout_rank), int(d["calls"]))
 
@@ -516,6 +556,10 @@ class FineTuner:
         self._not_averaged("forward_backward_accumulated")
         micro_batches = list(micro_batches)
         k, B = check_accumulation([t.shape[0] for _, t in micro_batches], negatives, self.world)
+        if negatives == "union" and self.memory_bank and return_infonce_loss:
+            # (the union's recorded first pass and the bank would disagree on what "past" means)
+            raise ValueError("step_accumulated: negatives='union' is not available with an InfoNCE memory bank (use negatives='micro': each "
+                             "micro-batch reads the bank, then pushes)")
         fkw = dict(epoch=epoch, use_weight=use_weight, return_infonce_loss=return_infonce_loss, return_ct_loss=return_ct_loss,
                    loss_func=loss_func)
         if k == 1:
@@ -716,6 +760,8 @@ class FineTuner:
         # ... and so is the streaming FDS accumulator the forward feeds (allocated here, before the capture; its address stays put)
         fds_acc = self.model.FDS.stream_state() if getattr(self.model, "fds_streaming", False) else None
         fds_saved = None if fds_acc is None else fds_acc.clone()
+        # ... and the InfoNCE memory bank the warm-up steps push into
+        bank_saved = [(t, t.clone()) for _, t in self._bank_state()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -733,6 +779,8 @@ class FineTuner:
             loss_state.copy_(loss_saved)
         if fds_acc is not None:
             fds_acc.copy_(fds_saved)
+        for t, was in bank_saved:
+            t.copy_(was)
         self.arena.refresh_shadow()
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
