@@ -75,6 +75,7 @@ int mmdti_abi_version(void);
 #define MMDTI_PLAN_ROW 6                 /* LayerNorm and row softmax (mmdti_row_plan): 26 rows */
 #define MMDTI_PLAN_STREAM 7              /* casts, dropout, axpy, GELU, column sum, sum of squares, Adam, EMA, step state (mmdti_stream_plan): 29 rows */
 #define MMDTI_PLAN_MAPS 8                /* attention maps (mmdti_maps_plan): 12 rows -- attn_map_kernel<16 | 32 | 64>, the pair map by plane layout and tile bucket */
+#define MMDTI_PLAN_LORA 9                /* LoRA adapters (mmdti_lora_plan): 27 rows -- lora_fwd_kernel<R, F16, YF16>, lora_bwd_kernel<R, XF16, SLAB>, lora_dx_kernel<R, DXBF16> */
 int mmdti_plan_table_size(int family, int* size_out);
 const char* mmdti_plan_kernel_name(int family, int index);
 /* Run-time tuning switches (A/B measurements inside one process; defaults come from the environment variable of the same
@@ -1020,6 +1021,39 @@ int mmdti_row_plan(int entry, int deterministic, const void* const* ptrs, int ro
 #define MMDTI_STREAM_EMA_SWAP 15
 #define MMDTI_STREAM_STEP_STATE_ADVANCE 16
 int mmdti_stream_plan(int entry, int deterministic, const void* const* ptrs, long long n, int a, int b, int c, float f, long long* plan_out);
+
+/* ---- LoRA adapters on a Linear (csrc/lora.hip; DESIGN.md "LoRA adapters") -----------------------------------------
+ * Not part of any reference interface: the reference has no adapters.  One adapted Linear y = x.W^T (+ bias) trains the rank-r update
+ * W + s.B.A with s = alpha / r: x is [T, in] (row stride ldx), A [r, in], B [out, r], all row-major.  r is 8, 16 or 32; in and out are
+ * multiples of 64 (at most 8192); T >= 1 is arbitrary; row strides are multiples of 8 elements and every 16-bit base is 16-byte
+ * aligned.  Anything else is MMDTI_ERR_INVALID before a launch.  All products are 16-bit MFMAs with fp32 accumulation.
+ *
+ * mmdti_lora_fwd: t = bf16(x.A^T), stored to t_bf16 [T, r] for the backward; then, in place, y <- round16(float(y) + s.t.B^T) where y
+ * [T, out] (row stride ldy; it may be a column slice of a fused q | k | v buffer) is what the base Linear wrote.  x, A and B are
+ * bf16 (f16 = 0) or fp16 (f16 = 1, the fp16 forward-operand mode; t stays bf16 and enters the second product converted to fp16, which
+ * is exact for 2^-14 <= |t| <= 65504); y is bf16 (y_f16 = 0) or, beside fp16 operands only, fp16 (y_f16 = 1; the store saturates).  BOTH roundings -- t to bf16, then y to its 16-bit type -- are part
+ * of the contract.  An element whose update s.(t.B^T) is zero keeps its bits: with B = 0, y is unchanged to the bit.
+ *
+ * mmdti_lora_bwd: u = bf16(s.dy.B), stored to u_bf16 [T, r] for mmdti_lora_dx; dB [out, r] += s.dy^T.t and dA [r, in] += u^T.x, both
+ * fp32 (the arena's gradient buffers).  x is bf16, or (x_f16 = 1) a saved fp16 activation converted to bf16 inside the kernel as the
+ * weight-gradient GEMM does; dy (row stride lddy), t and B are bf16 (A is not an input: no product of the backward reads it).  One
+ * pass over x and dy.  Partial sums of workgroups meet in fp32 atomics; in the deterministic mode they go to per-workgroup slabs of the
+ * stream's reduction workspace, folded in workgroup order -- never atomics, and a missing or too small workspace is MMDTI_ERR_INVALID.
+ *
+ * mmdti_lora_dx: dx [T, in] (row stride lddx) += u.A in place; dx is fp32 (dx_bf16 = 0) or bf16 (1, rounded to nearest even).
+ *
+ * mmdti_lora_plan: what entry 0 (mmdti_lora_fwd), 1 (mmdti_lora_bwd) or 2 (mmdti_lora_dx; n_out is ignored) would launch, without
+ * launching (csrc/lora_plan.h; the same shape validation, message for message); no GPU needed.  flag: x_f16 | dx_bf16 of the
+ * entry; for the forward 0 (bf16), 1 (fp16 operands and y) or 2 (fp16 operands, bf16 y).  plan_out receives 18 long long: the number of launches (1; 3 for the deterministic backward: the slab kernel, then the
+ * fixed-order fold of dB and of dA), three launches of (the kernel's row in the MMDTI_PLAN_LORA table, or -1 for the fold; grid x;
+ * grid y; workgroup size; dynamic LDS bytes), token rows per workgroup (forward, dx) or per chunk (backward), and the floats of one
+ * workgroup's slab (deterministic backward; else 0).  Purely additive: MMDTI_ABI_VERSION does not move. */
+int mmdti_lora_fwd(mmdti_stream_t stream, const void* x, int ldx, const void* A, const void* B, void* y, int ldy, void* t_bf16, int T,
+                   int n_in, int n_out, int r, float scale, int f16, int y_f16);
+int mmdti_lora_bwd(mmdti_stream_t stream, const void* x, int ldx, int x_f16, const void* dy_bf16, int lddy, const void* t_bf16,
+                   const void* B_bf16, void* u_bf16, float* dA, float* dB, int T, int n_in, int n_out, int r, float scale);
+int mmdti_lora_dx(mmdti_stream_t stream, const void* u_bf16, const void* A_bf16, void* dx, int lddx, int dx_bf16, int T, int n_in, int r);
+int mmdti_lora_plan(int entry, int deterministic, int T, int n_in, int n_out, int r, int flag, long long* plan_out);
 
 /* ---- hardware probes used by the test-suite ------------------------------------------------- */
 /* out[64*4] <- what ds_read_b64_tr_b16 returns to each lane for an LDS image holding element index == value */

@@ -115,6 +115,7 @@ const KernelRow* gbf_kernel_table(int* n);    // gbf.hip
 const KernelRow* pair_attn_kernel_row(int family, int key);   // pair_attn_bwd.hip: row `key` of a PairAttnFamily table, null past its end
 const KernelRow* ln_kernel_table(int* n);     // layernorm.hip: rows 0..19 of MMDTI_PLAN_ROW (elementwise.hip holds the softmax rows behind them)
 const KernelRow* maps_kernel_table(int* n);   // attn_maps.hip: MMDTI_PLAN_MAPS
+const KernelRow* lora_kernel_table(int* n);   // lora.hip: MMDTI_PLAN_LORA
 // layernorm.hip: the validation and plan its two launchers and mmdti_row_plan (elementwise.hip) share
 int ln_fwd_prepare(RowPlan& plan, const float* x, const float* gamma, const float* beta, int rows, int D, const float* y_f32,
                    const void* y_bf16, float drop_p);

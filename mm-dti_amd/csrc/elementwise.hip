@@ -880,7 +880,8 @@ static const KernelRow* plan_row(int family, int index) {
   if (family == MMDTI_PLAN_ROW && index >= ROW_LN_KERNELS) return index < ROW_KERNELS ? &g_softmax_kernels[index - ROW_LN_KERNELS] : nullptr;
   int n = 0;
   const KernelRow* t = family == MMDTI_PLAN_ATTN ? attn_kernel_table(&n) : family == MMDTI_PLAN_GBF ? gbf_kernel_table(&n)
-                       : family == MMDTI_PLAN_ROW ? ln_kernel_table(&n) : family == MMDTI_PLAN_MAPS ? maps_kernel_table(&n) : nullptr;
+                       : family == MMDTI_PLAN_ROW ? ln_kernel_table(&n) : family == MMDTI_PLAN_MAPS ? maps_kernel_table(&n)
+                       : family == MMDTI_PLAN_LORA ? lora_kernel_table(&n) : nullptr;
   if (family == MMDTI_PLAN_STREAM) t = g_stream_kernels, n = STREAM_KERNELS;
   return t && index >= 0 && index < n ? &t[index] : nullptr;
 }

@@ -348,7 +348,7 @@ class PairEncoderFn(torch.autograd.Function):
         nxt = None
         out = None
         sw = _switches()
-        path = paths.unimol_layer_fwd(sw, emb.is_cuda, compact, D, H)
+        path = paths.unimol_layer_fwd(sw, emb.is_cuda, compact, D, H, adapters=_has_adapters(mod.layers))
         seq = path == paths.LAYER
         kp0 = ops._u8(padding_mask) if seq else None
         # small batches: ALL layers from one library call (see _unimol_stack_fwd); the per-layer loop below then has nothing left to do
@@ -384,6 +384,8 @@ class PairEncoderFn(torch.autograd.Function):
                     st.layers.append(_kept(L, li, st.plan))
                 continue
             L.qkv = ops.linear_fwd(L.h1, wfwd(att.in_proj.weight), att.in_proj.bias)
+            if getattr(att, "lora_targets", None):         # LoRA: q | k | v += s.bf16(h1.A^T).B^T next to the frozen in_proj (lora.py)
+                L.lt = ops.lora_fwd(L.h1, wfwd(att.lora_A), wfwd(att.lora_B), L.qkv, att.lora_scale)
             L.site_att = sites.next()
             # (ragged batches: all-padding key tiles are skipped; the last layer writes them as -inf because its S is returned)
             L.s, L.o = ops.pair_attn_fwd(L.qkv, s_prev, padding_mask if li == 0 else None, B, N, H, ld, scale, p_att, seed, L.site_att,
@@ -482,7 +484,7 @@ class PairEncoderFn(torch.autograd.Function):
 
             def _wgrad(*args, **kw):
                 pending.append((args, kw))
-            if paths.unimol_layer_bwd(seq_path, dx16 is not None, hold, full[li]) == paths.LAYER:
+            if paths.unimol_layer_bwd(seq_path, dx16 is not None, hold, full[li], adapters=hasattr(L, "lt")) == paths.LAYER:
                 g_zero = G is None
                 if g_zero:
                     G = _pair_grad_chain(L.s, st.kt)
@@ -508,10 +510,13 @@ class PairEncoderFn(torch.autograd.Function):
                 G = _pair_grad_chain(L.s, st.kt)
             dqkv = ops.pair_attn_bwd(L.qkv, L.s, do, G, B, N, H, ld, scale, g_zero, st.p_att, seed, L.site_att, key_tiles=st.kt, row_off=st.row_off)
             _wgrad(dqkv, L.h1, att.in_proj.weight, att.in_proj.bias)
+            lu = _lora_bwd(att, "", L.h1, dqkv, L.lt) if hasattr(L, "lt") else None
             if lowest and not (ln1.weight.requires_grad or ln1.bias.requires_grad):
                 dh1 = None                               # (no dX product: nothing reads it)
             else:
                 dh1 = ops.linear_bwd_input(dqkv, wbf16(att.in_proj.weight))
+                if lu is not None:
+                    ops.lora_dx(lu, wbf16(att.lora_A), dh1)
             if dh1 is None:
                 dx, dx16 = None, None
             elif lowest or li == 0:                      # (no layer under this one reads a bf16 copy)
@@ -569,10 +574,41 @@ def _ptr_table(ptrs):
     return arr, ctypes.addressof(arr)
 
 
+def _has_adapters(layers) -> bool:
+    """Does a layer of the tower carry LoRA adapters (lora.apply_lora)?  Such layers run op by op."""
+    return any(getattr(getattr(l, "self_attn", None), "lora_targets", None) for l in layers)
+
+
+def _has_bert_adapters(layers) -> bool:
+    return any(getattr(l.attention.self, "lora_targets", None) for l in layers)
+
+
+def _lora_pair(att, t):
+    """(A, B) of the adapter of projection `t` ('' -- tower 1's fused in_proj --, 'q', 'k', 'v') on an attention module"""
+    sfx = f"_{t}" if t else ""
+    return getattr(att, "lora_A" + sfx), getattr(att, "lora_B" + sfx)
+
+
+def _lora_fwd(att, t, x16, y):
+    """y (what the frozen projection wrote) += s.bf16(x.A^T).B^T in place -> the saved t"""
+    A, B = _lora_pair(att, t)
+    return ops.lora_fwd(x16, wfwd(A), wfwd(B), y, att.lora_scale)
+
+
+def _lora_bwd(att, t, x16, dy, lt):
+    """The adapter's gradients into its gradient buffers -> u = bf16(s.dy.B) for ops.lora_dx.  A frozen adapter is refused: it has no
+    gradient buffer to write to, and leaving its s.B.A out of the dX product would be wrong -- merge it first."""
+    A, B = _lora_pair(att, t)
+    gA, gB = gbuf(A), gbuf(B)
+    if gA is None or gB is None:
+        raise ops.MMDTIError("LoRA: an adapter pair trains or is frozen as a whole, and a frozen one must be merged (lora.merge_lora)")
+    return ops.lora_bwd(x16, dy, lt, wbf16(B), gA, gB, att.lora_scale)
+
+
 def bert_weights(layer) -> SimpleNamespace:
     """Parameter view of an HF RobertaLayer / mm_module BertCrossAttentionLayer (identical sub-module names)."""
     a, o = layer.attention.self, layer.attention.output
-    return SimpleNamespace(q_w=a.query.weight, q_b=a.query.bias, k_w=a.key.weight, k_b=a.key.bias, v_w=a.value.weight, v_b=a.value.bias,
+    return SimpleNamespace(att=a, lora=getattr(a, "lora_targets", ()), q_w=a.query.weight, q_b=a.query.bias, k_w=a.key.weight, k_b=a.key.bias, v_w=a.value.weight, v_b=a.value.bias,
                            o_w=o.dense.weight, o_b=o.dense.bias, ln1_w=o.LayerNorm.weight, ln1_b=o.LayerNorm.bias,
                            i_w=layer.intermediate.dense.weight, i_b=layer.intermediate.dense.bias,
                            o2_w=layer.output.dense.weight, o2_b=layer.output.dense.bias,
@@ -1066,7 +1102,9 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
         L.fw, L.fb = fused_views(plist_w), fused_views(plist_b)
         if L.fw is None or L.fb is None:
             L.fw = L.fb = None
-    L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq)
+    if W.lora and L.fw is not None:
+        raise ops.MMDTIError("LoRA: an adapted projection must be frozen (lora.apply_lora freezes its tower; merge_lora before unfreezing)")
+    L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq, adapters=bool(W.lora))
     if L.path == paths.LAYER:
         # the layer's six launches from ONE library call (csrc/layers.hip: the same kernels, arguments and order as below)
         ret = (_bert_layer_fwd_seq if self_attn else _bert_cross_layer_fwd_seq)(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
@@ -1087,6 +1125,8 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
         L.q = ops.linear_fwd(s1_16, wfwd(W.q_w), W.q_b, out_dtype=BF16)
         L.k = ops.linear_fwd(s2_16, wfwd(W.k_w), W.k_b, out_dtype=BF16)
         L.v = ops.linear_fwd(s2_16, wfwd(W.v_w), W.v_b, out_dtype=BF16)
+        if W.lora:                                          # LoRA next to the frozen projections (lora.py)
+            L.lt = {t: _lora_fwd(W.att, t, s1_16 if t == "q" else s2_16, {"q": L.q, "k": L.k, "v": L.v}[t]) for t in W.lora}
     if L.fused:
         # scores, softmax, dropout and context in one kernel: the [B,heads,Lq,Lk] tensor never reaches HBM
         L.ctx, L.stats = ops.attn_dispatch(Lq, Lk)[0](L.q, L.k, L.v, key_add, B, heads, Lq, Lk, 1.0 / math.sqrt(hd), p_att, seed, L.site_att, vl=vl)
@@ -1189,19 +1229,32 @@ def _bert_layer_bwd(st, L, dout, seed, want=(True, True)):
     pend.append(((dk, L.s2_16, W.k_w, W.k_b), {}))
     pend.append(((dv, L.s2_16, W.v_w, W.v_b), {}))
     _lin_bwd_params_many(pend, raw)
+    # LoRA: the adapters' gradients from the dq / dk / dv at hand; u = bf16(s.dy.B) then adds u.A to the stream gradient wherever the
+    # base dX GEMM below writes one
+    lt = getattr(L, "lt", None) or {}
+    lu = {t: _lora_bwd(W.att, t, L.s1_16 if t == "q" else L.s2_16, {"q": dq, "k": dk, "v": dv}[t], lt[t]) for t in lt}
+
+    def lora_dx(t, ds):
+        if t in lu:
+            ops.lora_dx(lu[t], wbf16(_lora_pair(W.att, t)[0]), ds)
     # ds1 = dy (residual) + dq.Wq ; ds2 = dk.Wk + dv.Wv     (fp32, accumulated by the GEMM's beta=1 epilogue)
     ds1 = dy if want[0] else None
     if want[0]:
         ops.gemm(dq, wbf16(W.q_w), M=Mq, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+        lora_dx("q", ds1)
     if L.self_attn:
         if want[0]:
             ops.gemm(dk, wbf16(W.k_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
             ops.gemm(dv, wbf16(W.v_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds1, ldc=D, beta=1.0)
+            lora_dx("k", ds1)
+            lora_dx("v", ds1)
         return ds1, None
     if not want[1]:
         return ds1, None
     ds2 = ops.gemm(dk, wbf16(W.k_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out_dtype=F32)
     ops.gemm(dv, wbf16(W.v_w), M=Mk, N=D, K=D, lda=D, ldb=D, transB=True, out=ds2, ldc=D, beta=1.0)
+    lora_dx("k", ds2)
+    lora_dx("v", ds2)
     return ds1, ds2
 
 
@@ -1369,7 +1422,7 @@ class RobertaEncoderFn(torch.autograd.Function):
         st.stack = None
         T = None
         sw = _switches()
-        if paths.bert_tower_fwd(sw, x32.is_cuda, keep, len(mod.layers), Mq) == paths.STACK:
+        if paths.bert_tower_fwd(sw, x32.is_cuda, keep, len(mod.layers), Mq, adapters=_has_bert_adapters(mod.layers)) == paths.STACK:
             T = _stack_tables(_bert_stack_desc, mod, Mq, sw, D % cfg.heads == 0 and ops.attn_eligible(Lq, st.Lk, D // cfg.heads, D))
         if T is not None:
             x32 = _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites)

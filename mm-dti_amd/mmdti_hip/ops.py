@@ -1287,6 +1287,81 @@ def infonce_bank_push(bank, valid, bank_ids, head, rows, ids=None):
                                   _p(ids), n, D, cap)
 
 
+# --------------------------------------------------------------------------------------------- LoRA adapters
+LORA_ENTRIES = {"fwd": 0, "bwd": 1, "dx": 2}
+
+
+def lora_plan(entry, T, n_in, n_out, r, flag=False, deterministic=False):
+    """What lora_fwd / lora_bwd / lora_dx (entry 'fwd' | 'bwd' | 'dx') would launch (csrc/lora_plan.h), without launching: no device is
+    touched.  flag: fp16 x (bwd), bf16 dx (dx); fwd: 0 bf16, 1 fp16 operands and y, 2 fp16 operands beside a bf16 y.  -> {"nlaunch", "launches": [{"key", "gx", "gy", "block", "lds"}],
+    "chunk_rows", "slab_floats"}."""
+    import ctypes
+    words = (ctypes.c_longlong * 18)()
+    lib().mmdti_lora_plan(LORA_ENTRIES[entry], int(bool(deterministic)), int(T), int(n_in), int(n_out), int(r), int(flag),
+                          ctypes.addressof(words))
+    w = [int(v) for v in words]
+    launches = [dict(zip(("key", "gx", "gy", "block", "lds"), w[1 + 5 * i:6 + 5 * i])) for i in range(w[0])]
+    return {"nlaunch": w[0], "launches": launches, "chunk_rows": w[16], "slab_floats": w[17]}
+
+
+def _lora_rows(t, name, cols=None):
+    """a 2-D 16-bit or fp32 matrix whose rows are contiguous (a column slice of a wider buffer is fine) -> its row stride"""
+    if t.dim() != 2 or t.stride(1) != 1 or not t.is_cuda or (cols is not None and t.shape[1] != cols):
+        raise MMDTIError(f"{name}: expected a device matrix with contiguous rows{'' if cols is None else f' of {cols} columns'} "
+                         f"(got shape {tuple(t.shape)}, strides {t.stride()})")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def lora_fwd(x, A, B, y, scale):
+    """y [T, out] (in place; what the base Linear wrote, possibly a column slice) += scale * bf16(x.A^T).B^T, rounded to y's type; returns
+    t = bf16(x.A^T) [T, r] for lora_bwd.  x, A and B share one 16-bit type (bf16, or fp16 in the fp16 forward-operand mode); y has it too,
+    or is bf16 beside fp16 operands (tower 2 and the cross block store q, k, v as bf16 in every mode)."""
+    r, n_in = A.shape
+    n_out = B.shape[0]
+    T = x.shape[0]
+    if not (x.dtype == A.dtype == B.dtype and x.dtype in (BF16, F16) and y.dtype in (x.dtype, BF16)):
+        raise MMDTIError(f"lora_fwd: x, A and B must share bf16 or fp16, y has their type or is bf16 (got {x.dtype}, {A.dtype}, {B.dtype}, {y.dtype})")
+    if B.shape[1] != r or y.shape[0] != T or not A.is_contiguous() or not B.is_contiguous():
+        raise MMDTIError(f"lora_fwd: A [r, in], B [out, r] contiguous and y [T, out] expected (got {tuple(A.shape)}, {tuple(B.shape)}, {tuple(y.shape)})")
+    ldx, ldy = _lora_rows(x, "lora_fwd.x", n_in), _lora_rows(y, "lora_fwd.y", n_out)
+    t = torch.empty(T, r, device=x.device, dtype=BF16)
+    lib().mmdti_lora_fwd(_stream(), x.data_ptr(), ldx, A.data_ptr(), B.data_ptr(), y.data_ptr(), ldy, t.data_ptr(), T, n_in, n_out, r,
+                         float(scale), 1 if x.dtype == F16 else 0, 1 if y.dtype == F16 else 0)
+    return t
+
+
+def lora_bwd(x, dy, t, B, dA, dB, scale):
+    """dB [out, r] += scale * dy^T.t and dA [r, in] += u^T.x (both fp32, in place) with u = bf16(scale * dy.B) [T, r], which is returned
+    for lora_dx.  x: bf16, or a saved fp16 activation (converted in the kernel); dy (possibly a column slice), t and B: bf16."""
+    n_out, r = B.shape
+    T, n_in = x.shape
+    if x.dtype not in (BF16, F16) or dy.dtype != BF16 or t.dtype != BF16 or B.dtype != BF16:
+        raise MMDTIError(f"lora_bwd: x bf16 / fp16 and dy, t, B bf16 expected (got {x.dtype}, {dy.dtype}, {t.dtype}, {B.dtype})")
+    _chk(dA, F32, "lora_bwd.dA"), _chk(dB, F32, "lora_bwd.dB")
+    if (tuple(dA.shape) != (r, n_in) or tuple(dB.shape) != (n_out, r) or tuple(t.shape) != (T, r) or dy.shape[0] != T
+            or not t.is_contiguous() or not B.is_contiguous()):
+        raise MMDTIError(f"lora_bwd: dA [r, in], dB [out, r], t [T, r] and dy [T, out] expected (got {tuple(dA.shape)}, {tuple(dB.shape)}, "
+                         f"{tuple(t.shape)}, {tuple(dy.shape)})")
+    ldx, lddy = _lora_rows(x, "lora_bwd.x"), _lora_rows(dy, "lora_bwd.dy", n_out)
+    u = torch.empty(T, r, device=x.device, dtype=BF16)
+    lib().mmdti_lora_bwd(_stream(), x.data_ptr(), ldx, 1 if x.dtype == F16 else 0, dy.data_ptr(), lddy, t.data_ptr(), B.data_ptr(),
+                         u.data_ptr(), dA.data_ptr(), dB.data_ptr(), T, n_in, n_out, r, float(scale))
+    return u
+
+
+def lora_dx(u, A, dx):
+    """dx [T, in] (fp32 or bf16, in place) += u.A with u [T, r] and A [r, in] bf16"""
+    r, n_in = A.shape
+    T = u.shape[0]
+    if u.dtype != BF16 or A.dtype != BF16 or dx.dtype not in (F32, BF16):
+        raise MMDTIError(f"lora_dx: u and A bf16, dx fp32 or bf16 expected (got {u.dtype}, {A.dtype}, {dx.dtype})")
+    if tuple(u.shape) != (T, r) or dx.shape[0] != T or not u.is_contiguous() or not A.is_contiguous():
+        raise MMDTIError(f"lora_dx: u [T, r] and dx [T, in] expected (got {tuple(u.shape)}, {tuple(dx.shape)})")
+    lddx = _lora_rows(dx, "lora_dx.dx", n_in)
+    lib().mmdti_lora_dx(_stream(), u.data_ptr(), A.data_ptr(), dx.data_ptr(), lddx, 1 if dx.dtype == BF16 else 0, T, n_in, r)
+    return dx
+
+
 # --------------------------------------------------------------------------------------------- ConR / SupCon
 def ct_loss_fwd(mode, fhat, labels_f=None, labels_i=None, pred=None, weights=None, w=0.2, t=0.07, e=0.01, coef=1.0):
     B, D = fhat.shape

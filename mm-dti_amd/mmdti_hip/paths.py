@@ -51,17 +51,18 @@ def head_dim_is_8(D: int, H: int) -> bool:
 
 
 # ------------------------------------------------------------------------------------------------- tower 1 (Uni-Mol pair encoder)
-def unimol_layer_fwd(sw: Switches, on_gpu: bool, compact: bool, D: int, H: int) -> str:
+def unimol_layer_fwd(sw: Switches, on_gpu: bool, compact: bool, D: int, H: int, adapters: bool = False) -> str:
     """The forward of the tower's layers, one answer for all: LAYER or OPS.  (A forward launches no weight gradient: grouped_dw_ok
-    only bears on the backward.)"""
-    ok = sw.layer_seq and on_gpu and f16_operands_covered(sw.fwd_f16, compact) and not sw.timer and head_dim_is_8(D, H)
+    only bears on the backward.)  adapters: a layer of the tower carries LoRA adapters -- no sequencer launches their kernels."""
+    ok = not adapters and sw.layer_seq and on_gpu and f16_operands_covered(sw.fwd_f16, compact) and not sw.timer and head_dim_is_8(D, H)
     return LAYER if ok else OPS
 
 
-def unimol_tower_fwd(sw: Switches, layer_path: str, keep: bool, nlayers: int, rows: int, aux_grads: bool, final_ln: bool) -> str:
+def unimol_tower_fwd(sw: Switches, layer_path: str, keep: bool, nlayers: int, rows: int, aux_grads: bool, final_ln: bool,
+                     adapters: bool = False) -> str:
     """STACK for a small batch that keeps its activations for a backward (keep), else layer_path (unimol_layer_fwd's answer).
     aux_grads: the auxiliary outputs are differentiable; final_ln: the encoder ends in a LayerNorm."""
-    ok = layer_path == LAYER and keep and sw.stack_seq and nlayers > 0 and rows < sw.stack_max_rows and not aux_grads and final_ln
+    ok = not adapters and layer_path == LAYER and keep and sw.stack_seq and nlayers > 0 and rows < sw.stack_max_rows and not aux_grads and final_ln
     return STACK if ok else layer_path
 
 
@@ -74,24 +75,27 @@ def unimol_tower_bwd(sw: Switches, on_gpu: bool, nkept: int, lowest: int, f16_op
     return LAYER if ok else OPS
 
 
-def unimol_layer_bwd(tower_path: str, have_dx16: bool, held: bool, full: bool) -> str:
+def unimol_layer_bwd(tower_path: str, have_dx16: bool, held: bool, full: bool, adapters: bool = False) -> str:
     """One layer of the backward.  have_dx16: the LayerNorm backward above left the bf16 copy of the stream gradient; held: the layer's
     weight gradients wait for the end of the backward (functional.DEFER_WGRAD_LAYERS); full: every parameter of the layer trains -- a
-    frozen or partly frozen layer runs op by op, where its gradient kernels drop out one by one."""
-    return LAYER if (tower_path == LAYER and have_dx16 and not held and full) else OPS
+    frozen or partly frozen layer runs op by op, where its gradient kernels drop out one by one; adapters: the layer's forward ran LoRA
+    adapters, whose gradient kernels only the op-by-op backward launches."""
+    return LAYER if (tower_path == LAYER and have_dx16 and not held and full and not adapters) else OPS
 
 
 # ------------------------------------------------------------------------------------------------- tower 2 (RoBERTa), cross block
-def bert_tower_fwd(sw: Switches, on_gpu: bool, keep: bool, nlayers: int, rows: int) -> str:
-    """STACK for a small batch that keeps its activations for a backward, else LAYER: each layer asks bert_layer_fwd."""
-    ok = sw.layer_seq and sw.stack_seq and keep and on_gpu and rows < sw.stack_max_rows and nlayers > 0 and not sw.timer
+def bert_tower_fwd(sw: Switches, on_gpu: bool, keep: bool, nlayers: int, rows: int, adapters: bool = False) -> str:
+    """STACK for a small batch that keeps its activations for a backward, else LAYER: each layer asks bert_layer_fwd.  adapters: a layer
+    of the tower carries LoRA adapters."""
+    ok = not adapters and sw.layer_seq and sw.stack_seq and keep and on_gpu and rows < sw.stack_max_rows and nlayers > 0 and not sw.timer
     return STACK if ok else LAYER
 
 
-def bert_layer_fwd(sw: Switches, self_attn: bool, fused_proj: bool, on_gpu: bool, D: int, F: int, rows: int) -> str:
+def bert_layer_fwd(sw: Switches, self_attn: bool, fused_proj: bool, on_gpu: bool, D: int, F: int, rows: int, adapters: bool = False) -> str:
     """One BERT-style layer.  fused_proj: query | key | value (cross-attention: key | value) run as one GEMM over parameters that sit
-    back to back in the arena and all train -- which implies the fused attention kernels and projection biases.  rows: query rows."""
-    if not (sw.layer_seq and fused_proj and on_gpu and not sw.timer):
+    back to back in the arena and all train -- which implies the fused attention kernels and projection biases.  rows: query rows.
+    adapters: the layer carries LoRA adapters, which only the op-by-op body launches."""
+    if adapters or not (sw.layer_seq and fused_proj and on_gpu and not sw.timer):
         return OPS
     return LAYER if (grouped_dw_ok(sw, D, F, rows) if self_attn else cross_dims_ok(D, F)) else OPS
 

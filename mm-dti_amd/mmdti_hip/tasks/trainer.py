@@ -264,6 +264,16 @@ class Trainer(object):
         self.memory_bank = check_memory_bank(params.get('memory_bank', 0), "Trainer")
         if self.memory_bank and self.accum_steps > 1 and self.accum_negatives == 'union':
             raise ValueError("Trainer: memory_bank is not available with accum_negatives='union' (use accum_negatives='micro')")
+        # LoRA adapters on the attention projections (lora.apply_lora; not reference parameters, lora_rank = 0: off, nothing changes):
+        # the selected towers are frozen and train rank-r updates of their q / k / v projections; model_{fold}.pth is written MERGED,
+        # under the reference's keys, and train_state_{fold}.pth carries the adapters through the engine's state
+        self.lora_rank = int(params.get('lora_rank', 0))
+        self.lora_config = None
+        if self.lora_rank:
+            from ..lora import LoRAConfig, TOWERS
+            self.lora_config = LoRAConfig(rank=self.lora_rank, alpha=float(params.get('lora_alpha', 16.0)),
+                                          targets=tuple(params.get('lora_targets', ("q", "v"))), towers=tuple(params.get('lora_towers', TOWERS)),
+                                          seed=int(self.seed))
         # input pipeline (not reference parameters, defaults keep the reference's in-process loader):
         #   num_workers > 0 -> collate runs in DataLoader worker processes (HostCollate: no model copy in the workers) into
         #   pinned memory; narrow_inputs -> src_edge_type crosses PCIe as int16 and the never-read src_coord stays on the host
@@ -403,6 +413,12 @@ class Trainer(object):
                     return_infonce_loss=False, return_ct_loss=False, use_weight=False):
         self._require_device()
         model = model.to(self.device)
+        if self.lora_config is not None:
+            from ..lora import apply_lora
+            apply_lora(model, self.lora_config)        # (before the engine: its arena then holds the adapters and the heads only)
+            logger.info('LoRA: rank {}, alpha {:g}, targets {}, towers {} -- {} adapter elements train beside the heads'.format(
+                self.lora_config.rank, self.lora_config.alpha, ','.join(self.lora_config.targets), ','.join(self.lora_config.towers),
+                sum(p.numel() for n, p in model.named_parameters() if '.lora_' in n)))
         train_dataloader, sampler = self.train_loader(model, train_dataset, feature_name)
         min_val_loss, max_score, wait = float("inf"), float("-inf"), 0
         num_training_steps = self.total_optimizer_steps(len(train_dataloader))
@@ -502,6 +518,9 @@ class Trainer(object):
             if is_early_stop:
                 break
         self._checkpoint_barrier()          # rank 0's last write is complete before any rank reads the file
+        if self.lora_config is not None:
+            from ..lora import merge_lora
+            merge_lora(model)               # (the checkpoint is merged: the closing prediction loads it into the reference-shaped model)
         y_preds, _, _ = self.predict(model, valid_dataset, loss_func, activation_fn, dump_dir, fold, target_scaler, epoch, load_model=True,
                                      feature_name=feature_name)
         return y_preds
@@ -515,7 +534,11 @@ class Trainer(object):
         os.makedirs(dump_dir, exist_ok=True)
         path = os.path.join(dump_dir, f'model_{fold}.pth')
         tmp = path + f'.tmp{os.getpid()}'
-        torch.save({'model_state_dict': model.state_dict()}, tmp)
+        sd = model.state_dict()
+        if self.lora_config is not None:
+            from ..lora import merged_state_dict
+            sd = merged_state_dict(model)   # (W + s.B.A under the reference's keys; inside engine.averaged(): of the averaged weights)
+        torch.save({'model_state_dict': sd}, tmp)
         os.replace(tmp, path)
 
     # -------------------------------------------------------------- resuming (DESIGN.md "Resuming a run")
@@ -524,7 +547,11 @@ class Trainer(object):
 
     def _train_settings(self):
         """what decides the number of optimizer steps and the order of the batches: a resumed run must have been started alike"""
-        return dict(batch_size=int(self.batch_size), accum_steps=int(self.accum_steps), epochs=int(self.max_epochs), seed=int(self.seed))
+        s = dict(batch_size=int(self.batch_size), accum_steps=int(self.accum_steps), epochs=int(self.max_epochs), seed=int(self.seed))
+        c = getattr(self, "lora_config", None)
+        if c is not None:       # (absent without adapters: files written before, or without, LoRA compare as ever; alpha is not in the state)
+            s["lora"] = "rank {} alpha {:g} targets {} towers {}".format(c.rank, c.alpha, ",".join(c.targets), ",".join(c.towers))
+        return s
 
     def _save_train_state(self, engine, task_loss, dump_dir, fold, epoch, min_val_loss, max_score, wait, finished):
         """After an epoch's early-stop decision: everything the next epoch needs, written atomically by rank 0 (model_{fold}.pth stays
