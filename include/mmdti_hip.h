@@ -347,6 +347,112 @@ int mmdti_bert_stack_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run, con
                          unsigned int site0, const float* dout, float* ds1_final, const void* s1_16_0, const void* arena,
                          long long arena_bytes, long long stats_bytes, void* ws, long long ws_bytes, long long dw_slab_bytes);
 
+/* ---- Sequenced layers that carry LoRA adapters next to a FROZEN base (csrc/layers.hip; DESIGN.md "LoRA adapters").  What the
+ * op-by-op host path launches for such a layer -- the same kernels, arguments and order, bit-identical results -- behind one call per
+ * layer or per tower: the sequences above with mmdti_lora_fwd / _bwd / _dx in them and without the weight gradients, which a frozen
+ * base has none of.  The gradient fields of the layer blocks (dw_*, db_*, dg_*, dbt_*) may all be null here.  The calls allocate
+ * nothing: the saved t = bf16(x.A^T) of every adapter and the backward's u = bf16(s.dy.B) are the caller's, as rows of
+ * MMDTI_LORA_ROW_BYTES(rows) bytes (room for the widest rank, rounded up to 256 bytes).  Not part of any reference interface.
+ * Purely additive: MMDTI_ABI_VERSION does not move. */
+
+/* One adapter: A [r, in], B [out, r] (mmdti_lora_fwd).  A null block, or r == 0, means "this projection carries no adapter"; any
+ * other rank than 8, 16 or 32 is refused before a launch.  (The two blocks of this section follow the field rules of the sequencers'
+ * blocks above.  They carry a struct tag so that the six blocks above stay what an untagged scan of this header finds -- callers
+ * that enumerate the sequencers' blocks, such as the layout check of tests/test_layer_structs_cpu.py, go on seeing exactly those; a
+ * binding gets all eight with _abi.parse_structs(tagged=True), which is what mmdti_hip loads.) */
+typedef struct mmdti_lora_adapter {
+  const void *A, *B;               /* forward: the 16-bit shadows (bf16, or fp16 under fwd_f16) */
+  const void *A_bf16, *B_bf16;     /* backward: the bf16 shadows */
+  float *dA, *dB;                  /* gradients: fp32, accumulated.  A forward-only caller leaves them null */
+  int r;
+  float scale;                     /* alpha / r */
+} mmdti_lora_adapter_t;
+
+/* The separate query, key and value projections of a BERT-style layer whose base is frozen (a frozen base has no fused [3D, D] view:
+ * w_qkv / w_q of its mmdti_bert_layer_t stay null). */
+typedef struct mmdti_bert_split {
+  const void *w_q, *w_k, *w_v;     /* forward: the 16-bit shadows, each [D, D] */
+  const float *b_q, *b_k, *b_v;    /* (nullable) */
+  const void *wb_q, *wb_k, *wb_v;  /* backward: the bf16 shadows */
+} mmdti_bert_split_t;
+
+#define MMDTI_LORA_MAX_RANK 32
+#define MMDTI_LORA_ROW_BYTES(rows) (((long long)(rows) * MMDTI_LORA_MAX_RANK * 2 + 255) / 256 * 256)
+
+/* Tower 1, one layer.  Forward: mmdti_unimol_layer_fwd's sequence with mmdti_lora_fwd on q | k | v right behind the in_proj GEMM (one
+ * adapter on the fused [3D, D] projection; lora null or r 0: none); t [M, r] bf16 is written for the backward.
+ * Backward: mmdti_unimol_layer_bwd's sequence without the grouped weight gradients, mmdti_lora_bwd on dqkv behind the pair-attention
+ * backward and mmdti_lora_dx on the bf16 dh1 behind the in_proj input gradient.  dx_out null: the lowest layer that runs -- the in_proj
+ * input gradient, the adapter's dx and the LayerNorm-1 backward are skipped (mmdti_lora_bwd still runs).
+ * ws: mmdti_unimol_lora_stack_layout's out[2] bytes, 16-byte aligned. */
+int mmdti_unimol_lora_layer_fwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run_block, const mmdti_unimol_layer_t* layer,
+                                const mmdti_unimol_saved_t* saved, const mmdti_lora_adapter_t* lora, void* t, unsigned int site_att,
+                                unsigned int site_o, unsigned int site_f, const void* s_in, const unsigned char* key_pad, int rag_store,
+                                int next_mode, const float* g_next, const float* bt_next, float eps_next, float* x_out, void* ln_out,
+                                float* mn, float* rn);
+int mmdti_unimol_lora_layer_bwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run_block, const mmdti_unimol_layer_t* layer,
+                                const mmdti_unimol_saved_t* saved, const mmdti_lora_adapter_t* lora, const void* t,
+                                unsigned int site_f_below, unsigned int site_o, unsigned int site_att, const float* dx_in, const void* dy2,
+                                float* dx_out, void* dx16_out, float* db_below, void* G, int g_in_zero, void* ws, long long ws_bytes);
+
+/* ALL nl layers of tower 1: nl x the calls above, as mmdti_unimol_stack_fwd / _bwd.  lora: nl adapter blocks, one per layer (r 0: that
+ * layer has none).  mmdti_unimol_lora_stack_layout (launch-free): out[0] = arena bytes per layer (mmdti_unimol_stack_layout's slice
+ * and the layer's t row behind it), out[1] = the stack backward's workspace bytes (mmdti_unimol_stack_layout's without slabs, and a u
+ * row behind each of its two layer workspaces), out[2] = ONE layer's backward workspace bytes (its temporaries rounded up to 256, and one u row).  dx_final null: nothing under
+ * layer 0 reads its input gradient (see dx_out above). */
+int mmdti_unimol_lora_stack_layout(int M, int D, int F, long long s_bytes, long long* out);
+int mmdti_unimol_lora_stack_fwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run_block, const mmdti_unimol_layer_t* layers,
+                                const mmdti_lora_adapter_t* lora, int nl, unsigned int site0, const float* x0, const void* h1_0,
+                                const void* s_in, const unsigned char* key_pad, int rag_store_last, const float* g_final,
+                                const float* bt_final, float eps_final, void* arena, long long arena_bytes, long long s_bytes,
+                                float* x_last, void* s_last, float* out_final, float* mean_final, float* rstd_final);
+int mmdti_unimol_lora_stack_bwd(mmdti_stream_t stream, const mmdti_unimol_run_t* run_block, const mmdti_unimol_layer_t* layers,
+                                const mmdti_lora_adapter_t* lora, int nl, unsigned int site0, const float* dx_in, const void* dy2_in,
+                                float* dx_final, const float* x0, const void* h1_0, const float* m1_0, const float* r1_0,
+                                const void* s_last, void* G, int g_first_zero, const void* arena, long long arena_bytes,
+                                long long s_bytes, void* ws, long long ws_bytes);
+
+/* Tower 2's self-attention layer and the cross layer.  lora: three adapter blocks -- query, key, value -- of which any subset has r 0
+ * (lora null: none is adapted).  saved->qkv holds q [Mq, D], k [Mk, D] and v [Mk, D] as three planes back to back (saved->q is not
+ * read); t: three rows of MMDTI_LORA_ROW_BYTES(max(Mq, Mk)) bytes -- query, key, value -- each [rows, r] bf16.
+ * Forward: the three projection GEMMs, mmdti_lora_fwd of every adapted one (query, key, value order), then the fused attention and the
+ * rest of mmdti_bert_layer_fwd.
+ * Backward: the six launches the two backwards above share, mmdti_lora_bwd of every adapted projection, then the input gradients:
+ * ds1 += dq . W_q, the query adapter's dx; self-attention: ds1 += dk . W_k, ds1 += dv . W_v, the key and the value adapter's dx; cross:
+ * ds2 = dk . W_k, ds2 += dv . W_v, the two dx into ds2.  want_ds1 / want_ds2 0: that gradient's products are not launched (ds1 is still
+ * written by the LayerNorm-1 backward and must be there; ds2 may then be null).  ws: mmdti_bert_lora_stack_layout's out[2] (cross: out[3]). */
+int mmdti_bert_lora_layer_fwd(mmdti_stream_t stream, const mmdti_bert_run_t* run_block, const mmdti_bert_layer_t* layer,
+                              const mmdti_bert_split_t* split, const mmdti_lora_adapter_t* lora, const mmdti_bert_saved_t* saved, void* t,
+                              unsigned int site_att, unsigned int site_o, unsigned int site_f, float* out32, void* out16);
+int mmdti_bert_lora_cross_layer_fwd(mmdti_stream_t stream, const mmdti_bert_run_t* run_block, const mmdti_bert_layer_t* layer,
+                                    const mmdti_bert_split_t* split, const mmdti_lora_adapter_t* lora, const mmdti_bert_saved_t* saved,
+                                    void* t, unsigned int site_att, unsigned int site_o, unsigned int site_f, float* out32, void* out16);
+int mmdti_bert_lora_layer_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run_block, const mmdti_bert_layer_t* layer,
+                              const mmdti_bert_split_t* split, const mmdti_lora_adapter_t* lora, const mmdti_bert_saved_t* saved,
+                              const void* t, unsigned int site_att, unsigned int site_o, unsigned int site_f, const float* dout, float* ds1,
+                              int want_ds1, void* ws, long long ws_bytes);
+int mmdti_bert_lora_cross_layer_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run_block, const mmdti_bert_layer_t* layer,
+                                    const mmdti_bert_split_t* split, const mmdti_lora_adapter_t* lora, const mmdti_bert_saved_t* saved,
+                                    const void* t, unsigned int site_att, unsigned int site_o, unsigned int site_f, const float* dout,
+                                    float* ds1, int want_ds1, float* ds2, int want_ds2, void* ws, long long ws_bytes);
+
+/* ALL nl layers of tower 2: nl x mmdti_bert_lora_layer_fwd / _bwd, as mmdti_bert_stack_fwd / _bwd (the cross block has no stack).
+ * split: nl blocks; lora: 3 nl adapter blocks (layer l: 3 l + {0: query, 1: key, 2: value}).  mmdti_bert_lora_stack_layout
+ * (launch-free): out[0] = arena bytes per layer (mmdti_bert_stack_layout's slice and three t rows of Mq), out[1] = the stack backward's
+ * workspace bytes (mmdti_bert_stack_layout's without slabs, and three u rows), out[2] / out[3] = ONE self-attention / cross layer's
+ * backward workspace bytes (the temporaries rounded up to 256 -- the cross layer's activation gradients, its caller's in
+ * mmdti_bert_cross_layer_bwd, are temporaries here -- and three u rows of max(Mq, Mk)), out[4] = bytes of one layer call's t (three rows of max(Mq, Mk)).  Self-attention: Mk = Mq.
+ * want_ds1_final 0: nothing reads the gradient of s1_32_0 (ds1_final is still the LayerNorm-1 backward's output buffer). */
+int mmdti_bert_lora_stack_layout(int Mq, int Mk, int D, int F, long long stats_bytes, long long nrow, long long* out);
+int mmdti_bert_lora_stack_fwd(mmdti_stream_t stream, const mmdti_bert_run_t* run_block, const mmdti_bert_layer_t* layers,
+                              const mmdti_bert_split_t* split, const mmdti_lora_adapter_t* lora, int nl, unsigned int site0,
+                              const float* s1_32_0, const void* s1_16_0, void* arena, long long arena_bytes, long long stats_bytes,
+                              float* out32_last);
+int mmdti_bert_lora_stack_bwd(mmdti_stream_t stream, const mmdti_bert_run_t* run_block, const mmdti_bert_layer_t* layers,
+                              const mmdti_bert_split_t* split, const mmdti_lora_adapter_t* lora, int nl, unsigned int site0,
+                              const float* dout, float* ds1_final, int want_ds1_final, const void* s1_16_0, const void* arena,
+                              long long arena_bytes, long long stats_bytes, void* ws, long long ws_bytes);
+
 
 /* ---- LayerNorm (unicore LayerNorm eps 1e-5: transformers.py:69,71,114,161; BertLayerNorm eps 1e-12:
  * mm_module.py:320-333; HF nn.LayerNorm) -------------------------------------------------------

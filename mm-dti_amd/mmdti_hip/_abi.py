@@ -44,11 +44,17 @@ def _source(path):
     return re.sub(r"//[^\n]*", "", src)
 
 
-def parse_structs(path: str = HEADER):
+def parse_structs(path: str = HEADER, tagged: bool = False):
     """-> {name: ctypes.Structure subclass} for every `typedef struct { ... } mmdti_*_t;` of the header, fields in header order.  A
-    declaration is `type a, b;` or -- pointers -- `type *a, *b;` / `type* a;`; no arrays, bitfields or nested structs."""
+    declaration is `type a, b;` or -- pointers -- `type *a, *b;` / `type* a;`; no arrays, bitfields or nested structs.
+    tagged: also the blocks declared with a struct tag, `typedef struct mmdti_x { ... } mmdti_x_t;` (the adapted sequencers').  The
+    default leaves them out for one reason only: callers that enumerate the six blocks of the plain sequencers -- the layout and
+    null-pointer checks of tests/test_layer_structs_cpu.py pin that set -- keep their answer.  lib().struct(name) knows all of them;
+    tests/test_lora_seq_cpu.py holds the tagged ones to the C compiler's layout."""
     structs = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\{([^{}]*)\}\s*(mmdti_[a-z0-9_]+_t)\s*;", _source(path)):
+    for tag, body, name in re.findall(r"typedef\s+struct\s*(mmdti_[a-z0-9_]+)?\s*\{([^{}]*)\}\s*(mmdti_[a-z0-9_]+_t)\s*;", _source(path)):
+        if tag and not tagged:
+            continue
         fields = []
         for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
             first, *more = [d.strip() for d in decl.split(",")]
@@ -95,7 +101,7 @@ class _Lib:
                 f"(make -C mm-dti_amd/csrc).  There is no CPU fallback for the product path.")
         self._dll = ctypes.CDLL(LIB_PATH)
         self.protos = parse_header()
-        self.structs = parse_structs()
+        self.structs = parse_structs(tagged=True)
         self.const = header_constants()
         try:
             version = self._dll.mmdti_abi_version()

@@ -71,6 +71,9 @@ def _lin_bwd_params_many(calls, raw_items=()):
 # kernels and arguments of the op-by-op path below, minus ~140 us of Python per layer -- what paces a step of 16-32 molecules
 # (which path a layer takes -- this call, the stack call further down, or op by op -- is decided in paths.py)
 LAYER_SEQ = os.environ.get("MMDTI_LAYER_SEQ", "1") != "0"
+# layers that carry LoRA adapters next to a frozen base take the library's adapted sequencers (mmdti_*_lora_*: the launches of the op-by-op
+# bodies below, bit for bit); 0: they run op by op, the path the tests compare against
+LORA_SEQ = os.environ.get("MMDTI_LORA_SEQ", "1") != "0"
 POOL_THEN_PROJECT = os.environ.get("MMDTI_INFONCE_POOL_FIRST", "1") != "0"      # InfoNCE head: pool the GELU outputs, then project
 
 
@@ -348,14 +351,17 @@ class PairEncoderFn(torch.autograd.Function):
         nxt = None
         out = None
         sw = _switches()
-        path = paths.unimol_layer_fwd(sw, emb.is_cuda, compact, D, H, adapters=_has_adapters(mod.layers))
+        adapters = _has_adapters(mod.layers)
+        st.aseq = adapters and _adapter_seq(mod.layers, _self_attn_of)
+        path = paths.unimol_layer_fwd(sw, emb.is_cuda, compact, D, H, adapters=adapters, adapter_seq=st.aseq)
         seq = path == paths.LAYER
         kp0 = ops._u8(padding_mask) if seq else None
         # small batches: ALL layers from one library call (see _unimol_stack_fwd); the per-layer loop below then has nothing left to do
         st.stack = None
         T = None
-        if paths.unimol_tower_fwd(sw, path, keep, nlayers, M, aux_grads, mod.final_layer_norm is not None) == paths.STACK:
-            T = _stack_tables(_unimol_stack_desc, mod, M, sw)
+        if paths.unimol_tower_fwd(sw, path, keep, nlayers, M, aux_grads, mod.final_layer_norm is not None, adapters=adapters,
+                                  adapter_seq=st.aseq) == paths.STACK:
+            T = _lora_stack_tables(False, mod, M, sw) if adapters else _stack_tables(_unimol_stack_desc, mod, M, sw)
         if T is not None:
             x, out, s_prev = _unimol_stack_fwd(st, T, mod, x, s_prev, kp0, pack is None, scale, sites, tiled)
         for li, layer in enumerate(mod.layers if T is None else ()):
@@ -472,7 +478,8 @@ class PairEncoderFn(torch.autograd.Function):
         n_defer = DEFER_WGRAD_LAYERS if (dout.is_cuda and M >= 8192) else 0
         plan = st.plan
         full = [all(p.requires_grad for p in l.parameters()) for l in mod.layers] if st.layers else []
-        seq_path, seq_ws = _unimol_seq_workspace(st, mod, full, dout.is_cuda)
+        aseq = bool(st.layers) and st.aseq and _adapter_seq(mod.layers, _self_attn_of)      # (asked again: flags may have changed since the forward)
+        seq_path, seq_ws = _unimol_seq_workspace(st, mod, full, dout.is_cuda, aseq)
         for li, layer, L in zip(range(len(st.layers) - 1, -1, -1), reversed(mod.layers), reversed(st.layers)):
             if li < plan.lowest:                         # nothing at or under this layer trains: the backward stops above it
                 L.__dict__.clear()
@@ -484,12 +491,12 @@ class PairEncoderFn(torch.autograd.Function):
 
             def _wgrad(*args, **kw):
                 pending.append((args, kw))
-            if paths.unimol_layer_bwd(seq_path, dx16 is not None, hold, full[li], adapters=hasattr(L, "lt")) == paths.LAYER:
+            if paths.unimol_layer_bwd(seq_path, dx16 is not None, hold, full[li], adapters=hasattr(L, "lt"), adapter_seq=aseq) == paths.LAYER:
                 g_zero = G is None
                 if g_zero:
                     G = _pair_grad_chain(L.s, st.kt)
                 dx, dx16 = _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, seq_ws,
-                                                 None if (li == 0 or lowest) else (below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)))
+                                                 None if (li == 0 or lowest) else (below[li - 1], gbuf(mod.layers[li - 1].fc2.bias)), lowest)
                 L.__dict__.clear()
                 notify_grads_ready(layer.parameters())
                 continue
@@ -575,12 +582,42 @@ def _ptr_table(ptrs):
 
 
 def _has_adapters(layers) -> bool:
-    """Does a layer of the tower carry LoRA adapters (lora.apply_lora)?  Such layers run op by op."""
+    """Does a layer of the tower carry LoRA adapters (lora.apply_lora)?  Such layers take the adapted sequencers or run op by op."""
     return any(getattr(getattr(l, "self_attn", None), "lora_targets", None) for l in layers)
 
 
 def _has_bert_adapters(layers) -> bool:
     return any(getattr(l.attention.self, "lora_targets", None) for l in layers)
+
+
+_adapter_params = weakref.WeakKeyDictionary()
+_adapter_params_gen = [0]          # counts rebuilt entries: the cached tables of the adapted stacks (_lora_stack_tables) are built for one value
+
+
+def _adapter_seq(layers, att_of, fused_attn=True) -> bool:
+    """paths.adapter_seq_ok over `layers` (att_of: a layer's attention module): every one carries adapters, every adapter trains, every
+    other parameter is frozen."""
+    base, adp = [], []
+    for l in layers:
+        att = att_of(l)
+        tg = getattr(att, "lora_targets", None)
+        if not tg:
+            return False
+        # (a layer's parameters are kept as (owning module's table, name, parameter, is an adapter): walking the modules costs more than the
+        #  library call at small batches.  Every call checks that each table still holds that very object under that name -- a parameter
+        #  replaced by assignment or load_state_dict(assign=True) builds the entry again -- and new adapters change lora_targets)
+        ent = _adapter_params.get(l)
+        if ent is None or ent[0] is not tg or any(tab.get(n) is not q for tab, n, q, _ in ent[1]):
+            ent = _adapter_params[l] = (tg, [(m._parameters, n, q, n.startswith("lora_")) for m in l.modules() for n, q in m._parameters.items()
+                                             if q is not None])
+            _adapter_params_gen[0] += 1
+        for _, _, q, is_adapter in ent[1]:
+            (adp if is_adapter else base).append(q.requires_grad)
+    return paths.adapter_seq_ok(LORA_SEQ, base, adp, fused_attn)
+
+
+_self_attn_of = lambda l: l.self_attn                 # noqa: E731
+_bert_attn_of = lambda l: l.attention.self            # noqa: E731
 
 
 def _lora_pair(att, t):
@@ -605,10 +642,50 @@ def _lora_bwd(att, t, x16, dy, lt):
     return ops.lora_bwd(x16, dy, lt, wbf16(B), gA, gB, att.lora_scale)
 
 
+def _lora_blocks(att, targets, w16=None, wb=None, g=None):
+    """The adapter blocks (mmdti_lora_adapter_t, one per entry of `targets`: ('',) tower 1, ('q', 'k', 'v') otherwise) of an attention
+    module as one array; a projection without an adapter keeps r 0.  w16 / wb / g: as _layer_block."""
+    S = ops.lib().struct("mmdti_lora_adapter_t")
+    blocks = []
+    for t in targets:
+        f = {}
+        if t in att.lora_targets:
+            A, B = _lora_pair(att, t)
+            f = dict(r=A.shape[0], scale=float(att.lora_scale))
+            if w16 is not None:
+                f.update(A=w16(A), B=w16(B))
+            if g is not None:
+                f.update(A_bf16=wb(A), B_bf16=wb(B), dA=g(A), dB=g(B))
+        blocks.append(S(**f))
+    return blocks
+
+
+def _block_array(blocks):
+    """-> (array, its address) of same-typed blocks"""
+    arr = (type(blocks[0]) * len(blocks))(*blocks)
+    return arr, ctypes.addressof(arr)
+
+
+def _split_block(W, w16=None, wb=None):
+    """The three separate projections of a BERT-style layer with a frozen base (mmdti_bert_split_t)."""
+    f = {}
+    for k, w, b in (("q", W.q_w, W.q_b), ("k", W.k_w, W.k_b), ("v", W.v_w, W.v_b)):
+        if w16 is not None:
+            f["w_" + k], f["b_" + k] = w16(w), ops._p(b)
+        if wb is not None:
+            f["wb_" + k] = wb(w)
+    return ops.lib().struct("mmdti_bert_split_t")(**f)
+
+
+def _lora_rows(buf, row_bytes, shapes):
+    """[rows, r] bf16 views of the rows of a t buffer (uint8; row j at j * row_bytes), one per (rows, r) of `shapes` (None: no adapter)"""
+    return [None if sh is None else buf[j * row_bytes:j * row_bytes + sh[0] * sh[1] * 2].view(BF16).view(sh) for j, sh in enumerate(shapes)]
+
+
 def bert_weights(layer) -> SimpleNamespace:
     """Parameter view of an HF RobertaLayer / mm_module BertCrossAttentionLayer (identical sub-module names)."""
     a, o = layer.attention.self, layer.attention.output
-    return SimpleNamespace(att=a, lora=getattr(a, "lora_targets", ()), q_w=a.query.weight, q_b=a.query.bias, k_w=a.key.weight, k_b=a.key.bias, v_w=a.value.weight, v_b=a.value.bias,
+    return SimpleNamespace(layer=layer, att=a, lora=getattr(a, "lora_targets", ()), q_w=a.query.weight, q_b=a.query.bias, k_w=a.key.weight, k_b=a.key.bias, v_w=a.value.weight, v_b=a.value.bias,
                            o_w=o.dense.weight, o_b=o.dense.bias, ln1_w=o.LayerNorm.weight, ln1_b=o.LayerNorm.bias,
                            i_w=layer.intermediate.dense.weight, i_b=layer.intermediate.dense.bias,
                            o2_w=layer.output.dense.weight, o2_b=layer.output.dense.bias,
@@ -755,6 +832,101 @@ def _stack_tables(desc, mod, rows, sw, attn_ok=True):
     return T
 
 
+def _bert_lora_desc(l):
+    """An adapted BERT-style layer's description for _layer_block: the Linears behind the attention (the three projections go in by
+    _split_block, the adapters by _lora_blocks)."""
+    W = bert_weights(l)
+    return SimpleNamespace(struct="mmdti_bert_layer_t", lin={"o": (W.o_w, W.o_b), "i": (W.i_w, W.i_b), "o2": (W.o2_w, W.o2_b)},
+                           ln={"ln1": (W.ln1_w, W.ln1_b), "ln2": (W.ln2_w, W.ln2_b)}, extra={}, probe=W.i_w, eps=(), W=W)
+
+
+def _lora_stack_tables(bert, mod, rows, sw, attn_ok=True):
+    """_stack_tables for a tower whose layers all carry adapters next to a frozen base (the caller has asked paths.adapter_seq_ok): the
+    layer blocks, the adapter blocks and -- tower 2 (`bert`) -- the split-projection blocks of the adapted stack calls, cached on the
+    adapters' arena; None when the stack calls do not cover this model or call.  The adapters are addressed as offsets into their arena,
+    like the parameters of _stack_tables.  The frozen base is not: its 16-bit shadows are tensors of their own (runtime.wfwd / wbf16),
+    kept alive by the table and re-cast into NEW storage after an in-place write (merge_lora, a checkpoint load), so every call
+    compares each base weight's version and address with what the table was built from and builds it again on a difference."""
+    layers = list(mod.layers)
+    att_of, targets = (_bert_attn_of, ("q", "k", "v")) if bert else (_self_attn_of, ("",))
+    att0 = att_of(layers[0])
+    probe0 = (_bert_stack_desc if bert else _unimol_stack_desc).probe(layers[0])
+    arena = getattr(_lora_pair(att0, att0.lora_targets[0])[0], "_mmdti_arena", None)
+    F, D = probe0.shape
+    if paths.stack_call(sw, arena is not None, D, F, rows, attn_ok, adapter_seq=True) != paths.STACK:
+        return None
+    cache = arena.__dict__.setdefault("_lora_stack_tables", {})
+    key = (weakref.ref(mod), ops.FWD_F16, bert)
+    T = cache.get(key)
+    # (the caller's _adapter_seq has just checked every parameter's identity: a replaced one moved the generation)
+    if T is not None and T is not False and (T.gen != _adapter_params_gen[0] or any(w._version != v or w.data_ptr() != dp for w, v, dp in T.base)):
+        T = None
+    if T is None:
+        ds = [(_bert_lora_desc if bert else _unimol_stack_desc)(l) for l in layers]
+        pairs = [q for l in layers for t in att_of(l).lora_targets for q in _lora_pair(att_of(l), t)]
+        off = arena.offsets
+        same_arena = all(getattr(q, "_mmdti_arena", None) is arena for q in pairs)
+        uniform = all(tuple(d.probe.shape) == (F, D) and all(e == ds[0].eps[0] for e in d.eps) for d in ds)
+        if paths.stack_model(trainable_flags(pairs), same_arena, uniform) != paths.STACK:
+            cache[key] = False
+            return None
+        if ops.FWD_F16:
+            arena._fresh16()
+        sh16 = (arena.shadow16 if ops.FWD_F16 else arena.shadow).data_ptr()
+        shb, gr = arena.shadow.data_ptr(), arena.grad.data_ptr()
+        keep, base = [], []
+
+        def shadow(cast, record=False):          # a frozen weight's shadow: kept alive; record: the weight's state, once per weight
+            def ptr(w):
+                t = cast(w)
+                keep.append(t)
+                if record:
+                    base.append((w, w._version, w.data_ptr()))
+                return t.data_ptr()
+            return ptr
+        blocks = [_layer_block(d, w16=shadow(wfwd, True), wb=shadow(wbf16), g=lambda q: 0) for d in ds]
+        lora = [b for l in layers for b in _lora_blocks(att_of(l), targets, w16=lambda q: sh16 + 2 * off[id(q)], wb=lambda q: shb + 2 * off[id(q)],
+                                                        g=lambda q: gr + 4 * off[id(q)])]
+        split = _block_array([_split_block(d.W, w16=shadow(wfwd, True), wb=shadow(wbf16)) for d in ds]) if bert else None
+        # (biases and LayerNorm parameters go in by their own fp32 address: watched like the weights)
+        for d in ds:
+            raw = [b for _, b in d.lin.values()] + [q for pair in d.ln.values() for q in pair] + ([d.W.q_b, d.W.k_b, d.W.v_b] if bert else [])
+            base += [(q, q._version, q.data_ptr()) for q in raw if q is not None]
+        T = cache[key] = SimpleNamespace(gen=_adapter_params_gen[0], nl=len(layers), D=D, F=F, layers=_block_array(blocks), lora=_block_array(lora), split=split, base=base, keep=keep,
+                                         weights=[(q, id(q)) for q in pairs], params=[q for l in layers for q in l.parameters()], f16=ops.FWD_F16,
+                                         probes=[(q, q.data_ptr(), gr + 4 * off[id(q)]) for q in pairs])
+    if T is False:
+        return None
+    ver = arena._version
+    for q, i in T.weights:                       # an adapter written in place since the last cast (load_lora_state_dict): re-cast
+        if q._version != ver[i]:
+            arena._fresh(q)
+    if T.f16:
+        arena._fresh16()
+    for q, dptr, gptr in T.probes:               # storage or gradient views re-bound behind our back: the per-layer path looks them up
+        g = q.grad
+        if g is None or g.data_ptr() != gptr or q.data_ptr() != dptr:
+            return None
+    return T
+
+
+_lora_layouts = {}
+
+
+def _lora_layout(query, *args):
+    """The byte counts of the adapted sequencers (mmdti_unimol_lora_stack_layout -> 3, mmdti_bert_lora_stack_layout -> 5: the header says
+    which), asked of the library once per shape."""
+    key = (query,) + args
+    r = _lora_layouts.get(key)
+    if r is None:
+        out = (ctypes.c_longlong * 5)()
+        getattr(ops.lib(), query)(*args, ctypes.addressof(out))
+        if len(_lora_layouts) > 4096:
+            _lora_layouts.clear()
+        r = _lora_layouts[key] = tuple(int(v) for v in out)
+    return r
+
+
 # Byte counts come from the library's own arithmetic (csrc/layers.hip), asked once per shape.  A Uni-Mol layer and a BERT self-attention
 # layer hand the grouped weight-gradient launch the same set of matrices -- four of [D, D] (in_proj's three and out_proj; query, key, value
 # and the output dense) and two of [F, D] -- whose split-K partial sums take one fp32 slab per split.
@@ -823,7 +995,11 @@ def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, rag_store_last, scale, sit
     e = torch.empty
     s_last = torch.empty_like(s_prev) if tiled else e(B, H, N, ld, device=dev, dtype=F32)
     s_bytes = s_last.numel() * s_last.element_size()
-    stride, ws_bytes, slab = _stack_layout("mmdti_unimol_stack_layout", M, D, F, s_bytes)[:3]
+    lora = getattr(T, "lora", None)              # (_lora_stack_tables: adapted layers on a frozen base)
+    if lora is not None:
+        stride, ws_bytes, slab = _lora_layout("mmdti_unimol_lora_stack_layout", M, D, F, s_bytes)[:2] + (0,)
+    else:
+        stride, ws_bytes, slab = _stack_layout("mmdti_unimol_stack_layout", M, D, F, s_bytes)[:3]
     arena = e(stride * T.nl, device=dev, dtype=torch.uint8)
     x_last, out = e(M, D, device=dev, dtype=F32), e(M, D, device=dev, dtype=F32)
     st.f_mean, st.f_rstd = e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
@@ -831,10 +1007,13 @@ def _unimol_stack_fwd(st, T, mod, x, s_prev, key_pad, rag_store_last, scale, sit
     sites.n += 3 * T.nl
     f16 = h1.dtype == torch.float16
     run = _unimol_run(st, F, ops._pair_layout_s(s_prev, "pair_attn.bias"), scale, f16)
-    ops.lib().mmdti_unimol_stack_fwd(
-        ops._stream(), ctypes.addressof(run), T.layers[1], T.nl, site0, x.data_ptr(), h1.data_ptr(), s_prev.data_ptr(), ops._p(key_pad), int(rag_store_last),
-        fl.weight.data_ptr(), fl.bias.data_ptr(), float(fl.eps), arena.data_ptr(), arena.numel(), s_bytes, x_last.data_ptr(), s_last.data_ptr(),
-        out.data_ptr(), st.f_mean.data_ptr(), st.f_rstd.data_ptr())
+    rest = (T.nl, site0, x.data_ptr(), h1.data_ptr(), s_prev.data_ptr(), ops._p(key_pad), int(rag_store_last), fl.weight.data_ptr(), fl.bias.data_ptr(),
+            float(fl.eps), arena.data_ptr(), arena.numel(), s_bytes, x_last.data_ptr(), s_last.data_ptr(), out.data_ptr(), st.f_mean.data_ptr(),
+            st.f_rstd.data_ptr())
+    if lora is not None:
+        ops.lib().mmdti_unimol_lora_stack_fwd(ops._stream(), ctypes.addressof(run), T.layers[1], lora[1], *rest)
+    else:
+        ops.lib().mmdti_unimol_stack_fwd(ops._stream(), ctypes.addressof(run), T.layers[1], *rest)
     st.stack = SimpleNamespace(T=T, arena=arena, s_bytes=s_bytes, ws_bytes=ws_bytes, slab=slab, site0=site0, x0=x, h1=h1, m1=m1, r1=r1, s_last=s_last, f16=f16)
     return x_last, out, s_last
 
@@ -845,13 +1024,17 @@ def _unimol_stack_bwd(st, dx, dx16, scale):
     T = S.T
     G = _pair_grad_chain(S.s_last, st.kt)
     run = _unimol_run(st, T.F, ops._pair_layout_s(S.s_last, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0), scale, S.f16)
-    dx_final = torch.empty_like(dx)
+    lora = getattr(T, "lora", None)
+    # (adapted layers: nothing under layer 0 may read its input gradient -- the lowest layer's dX products are then not launched)
+    dx_final = torch.empty_like(dx) if (lora is None or st.plan.needs_dx(0)) else None
     ws = torch.empty(S.ws_bytes, device=dx.device, dtype=torch.uint8)
-    side, events = _stack_side()
-    ops.lib().mmdti_unimol_stack_bwd(
-        ops._stream(), ctypes.addressof(run), T.layers[1], T.nl, S.site0, dx.data_ptr(), dx16.data_ptr(), dx_final.data_ptr(), S.x0.data_ptr(),
-        S.h1.data_ptr(), S.m1.data_ptr(), S.r1.data_ptr(), S.s_last.data_ptr(), G.data_ptr(), 1, S.arena.data_ptr(), S.arena.numel(), S.s_bytes,
-        ws.data_ptr(), ws.numel(), S.slab, side, events)
+    rest = (T.nl, S.site0, dx.data_ptr(), dx16.data_ptr(), ops._p(dx_final), S.x0.data_ptr(), S.h1.data_ptr(), S.m1.data_ptr(), S.r1.data_ptr(),
+            S.s_last.data_ptr(), G.data_ptr(), 1, S.arena.data_ptr(), S.arena.numel(), S.s_bytes, ws.data_ptr(), ws.numel())
+    if lora is not None:
+        ops.lib().mmdti_unimol_lora_stack_bwd(ops._stream(), ctypes.addressof(run), T.layers[1], lora[1], *rest)
+    else:
+        side, events = _stack_side()
+        ops.lib().mmdti_unimol_stack_bwd(ops._stream(), ctypes.addressof(run), T.layers[1], *rest, S.slab, side, events)
     return dx_final, G
 
 
@@ -874,41 +1057,56 @@ def _unimol_layer_fwd_seq(st, layer, L, s_prev, key_pad, rag_store, scale, nl, n
         ln_out = e(M, D, device=dev, dtype=a16 if next_mode == 1 else F32)
         mn, rn = e(M, device=dev, dtype=F32), e(M, device=dev, dtype=F32)
     p = ops._p
-    ops.lib().mmdti_unimol_layer_fwd(
-        ops._stream(), ctypes.addressof(st.run), ctypes.addressof(P), ctypes.addressof(saved), int(L.site_att), int(L.site_o), int(L.site_f),
-        s_prev.data_ptr(), p(key_pad), int(rag_store), next_mode, p(nl.weight) if nl is not None else 0, p(nl.bias) if nl is not None else 0,
-        float(nl.eps) if nl is not None else 0.0, x_out.data_ptr(), p(ln_out), p(mn), p(rn))
+    head = (ops._stream(), ctypes.addressof(st.run), ctypes.addressof(P), ctypes.addressof(saved))
+    rest = (int(L.site_att), int(L.site_o), int(L.site_f), s_prev.data_ptr(), p(key_pad), int(rag_store), next_mode, p(nl.weight) if nl is not None else 0,
+            p(nl.bias) if nl is not None else 0, float(nl.eps) if nl is not None else 0.0, x_out.data_ptr(), p(ln_out), p(mn), p(rn))
+    att = layer.self_attn
+    if getattr(att, "lora_targets", None):       # an adapted layer on a frozen base (paths.adapter_seq_ok): L.lt is the adapter's saved t
+        L.lt = e(M, att.lora_A.shape[0], device=dev, dtype=BF16)
+        ad = _block_array(_lora_blocks(att, ("",), w16=_w16_ptr))
+        ops.lib().mmdti_unimol_lora_layer_fwd(*head, ad[1], L.lt.data_ptr(), *rest)
+    else:
+        ops.lib().mmdti_unimol_layer_fwd(*head, *rest)
     return x_out, ln_out, mn, rn
 
 
-def _unimol_seq_workspace(st, mod, full, on_gpu):
+def _unimol_seq_workspace(st, mod, full, on_gpu, adapter_seq=False):
     """-> (paths.LAYER, workspace) when layers of this backward may take mmdti_unimol_layer_bwd (paths.unimol_tower_bwd; full: per layer,
-    every parameter trains), else (paths.OPS, None).  The workspace holds one layer's temporaries and is shared by all layers."""
+    every parameter trains; adapter_seq: adapted layers on a frozen base -- mmdti_unimol_lora_layer_bwd), else (paths.OPS, None).  The
+    workspace holds one layer's temporaries and is shared by all layers."""
     nkept, lowest = len(st.layers), st.plan.lowest
     D, F, M = st.D, (mod.layers[0].fc1.weight.shape[0] if nkept else 0), st.M
     L0 = st.layers[lowest] if lowest < nkept else None          # (the lowest layer that runs: what the forward kept of it)
     path = paths.unimol_tower_bwd(_switches(), on_gpu, nkept, lowest, L0 is not None and L0.h1.dtype == torch.float16,
-                                  L0 is not None and L0.s.dtype == torch.float16, D, F, M, full)
+                                  L0 is not None and L0.s.dtype == torch.float16, D, F, M, full, adapter_seq=adapter_seq)
     if path != paths.LAYER:
         return path, None
+    if adapter_seq:
+        return path, _layer_workspace(_lora_layout("mmdti_unimol_lora_stack_layout", M, D, F, 0)[2], st.emb.device)
     return path, _layer_workspace(_stack_layout("mmdti_unimol_stack_layout", M, D, F, 0)[3], st.emb.device)
 
 
-def _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, ws, below):
+def _unimol_layer_bwd_seq(st, layer, L, dx, dx16, G, g_zero, scale, ws, below, lowest=False):
     """One Uni-Mol layer's backward as ONE library call (csrc/layers.hip): -> (dx, dx16) for the layer below (dx16 None at the
-    lowest layer).  Same launches, arguments and order as the op-by-op body of PairEncoderFn.backward."""
+    lowest layer).  Same launches, arguments and order as the op-by-op body of PairEncoderFn.backward.  An adapted layer (L.lt) takes
+    mmdti_unimol_lora_layer_bwd; lowest: nothing reads its input gradient -> (None, None)."""
     M, D, F = st.M, st.D, layer.fc1.weight.shape[0]
-    dx_out = torch.empty_like(dx)
+    adapted = hasattr(L, "lt")
+    dx_out = None if (adapted and lowest) else torch.empty_like(dx)
     dx16_out = torch.empty(M, D, device=dx.device, dtype=BF16) if below is not None else None
     if st.__dict__.get("run_bwd") is None:    # (one run block serves every layer of this backward: G's type is known from the first on)
         st.run_bwd = _unimol_run(st, F, ops._pair_layout_s(L.s, "pair_attn_bwd.s") | (4 if G.dtype == BF16 else 0), scale, L.h1.dtype == torch.float16)
     saved = _saved_block("mmdti_unimol_saved_t", L)
     P = _layer_block(_layer_desc(_unimol_stack_desc, layer), wb=_wb_ptr, g=_grad_ptr)
     p = ops._p
-    ops.lib().mmdti_unimol_layer_bwd(
-        ops._stream(), ctypes.addressof(st.run_bwd), ctypes.addressof(P), ctypes.addressof(saved), int(below[0]) if below is not None else 0, int(L.site_o),
-        int(L.site_att), dx.data_ptr(), dx16.data_ptr(), dx_out.data_ptr(), p(dx16_out), p(below[1]) if below is not None else 0, G.data_ptr(), int(g_zero),
-        ws[1], ws[2])
+    head = (ops._stream(), ctypes.addressof(st.run_bwd), ctypes.addressof(P), ctypes.addressof(saved))
+    rest = (int(below[0]) if below is not None else 0, int(L.site_o), int(L.site_att), dx.data_ptr(), dx16.data_ptr(), p(dx_out), p(dx16_out),
+            p(below[1]) if below is not None else 0, G.data_ptr(), int(g_zero), ws[1], ws[2])
+    if adapted:
+        ad = _block_array(_lora_blocks(layer.self_attn, ("",), wb=_wb_ptr, g=_grad_ptr))
+        ops.lib().mmdti_unimol_lora_layer_bwd(*head, ad[1], L.lt.data_ptr(), *rest)
+    else:
+        ops.lib().mmdti_unimol_layer_bwd(*head, *rest)
     return dx_out, dx16_out
 
 
@@ -1104,7 +1302,8 @@ def _bert_layer_fwd(st, s1_32, s1_16, s2_16, key_add, W, heads, p_hid, p_att, ep
             L.fw = L.fb = None
     if W.lora and L.fw is not None:
         raise ops.MMDTIError("LoRA: an adapted projection must be frozen (lora.apply_lora freezes its tower; merge_lora before unfreezing)")
-    L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq, adapters=bool(W.lora))
+    aseq = bool(W.lora) and _adapter_seq((W.layer,), _bert_attn_of, L.fused and W.q_b is not None)
+    L.path = paths.bert_layer_fwd(_switches(), self_attn, L.fw is not None, s1_32.is_cuda, D, W.i_w.shape[0], Mq, adapters=bool(W.lora), adapter_seq=aseq)
     if L.path == paths.LAYER:
         # the layer's six launches from ONE library call (csrc/layers.hip: the same kernels, arguments and order as below)
         ret = (_bert_layer_fwd_seq if self_attn else _bert_cross_layer_fwd_seq)(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, seed, sites)
@@ -1160,7 +1359,10 @@ def _grad_buffers_live(W, self_attn):
     """The re-check of a sequenced layer's backward: every gradient buffer that the library call writes through itself still exists (a
     parameter frozen between forward and backward has none).  The fused q | k | v buffers were taken as views in the forward; the
     cross-attention call leaves the weight gradients to the host, which looks each one up."""
-    ps = (W.o_w, W.o_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b) if self_attn else (W.o_b, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b)
+    if W.lora:                             # (an adapted layer on a frozen base: the call writes the adapters' gradients and no other)
+        ps = [q for t in W.lora for q in _lora_pair(W.att, t)]
+    else:
+        ps = (W.o_w, W.o_b, W.i_w, W.i_b, W.o2_w, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b) if self_attn else (W.o_b, W.o2_b, W.ln1_w, W.ln1_b, W.ln2_w, W.ln2_b)
     return all(gbuf(p) is not None for p in ps)
 
 
@@ -1287,12 +1489,15 @@ def _bert_seq_fwd(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, see
     L.site_o, L.site_f = sites.next(), sites.next()          # (L.site_att was drawn by the caller: the same numbering as the op-by-op path)
     a16 = s1_16.dtype                         # bf16, or fp16 (fp16 forward operands); q | k | v and the saved gelu' stay bf16 in every mode
     rows, f32 = ((Mq, D), F32), ((Mq,), F32)
-    alloc = dict(qkv=((Mk, 2 * D) if cross else (Mq, 3 * D), BF16), ctx=((Mq, D), a16), stats=((B, heads, Lq, 2) if vl is None else (heads, Mq, 2), F32),
+    adapted = bool(W.lora)                    # a frozen base: q, k, v as three planes of one buffer, the adapters' t rows in another
+    alloc = dict(qkv=(((Mq + 2 * Mk) * D,) if adapted else (Mk, 2 * D) if cross else (Mq, 3 * D), BF16), ctx=((Mq, D), a16), stats=((B, heads, Lq, 2) if vl is None else (heads, Mq, 2), F32),
                  y=rows, a32=rows, a16=((Mq, D), a16), am=f32, ar=f32, u=((Mq, F), BF16), i=((Mq, F), a16), z=rows, zm=f32, zr=f32)
-    if cross:
+    if cross and not adapted:
         alloc["q"] = ((Mq, D), BF16)
     saved = _saved_block("mmdti_bert_saved_t", L, alloc, dev, s1_32=s1_32)
-    if cross:
+    if adapted:
+        L.q, L.k, L.v = L.qkv[:Mq * D].view(Mq, D), L.qkv[Mq * D:(Mq + Mk) * D].view(Mk, D), L.qkv[(Mq + Mk) * D:].view(Mk, D)
+    elif cross:
         L.k, L.v = L.qkv[:, :D], L.qkv[:, D:]
     else:
         L.q, L.k, L.v = L.qkv[:, :D], L.qkv[:, D:2 * D], L.qkv[:, 2 * D:]
@@ -1301,10 +1506,20 @@ def _bert_seq_fwd(st, L, s1_32, s1_16, key_add, W, heads, p_hid, p_att, eps, see
     if st.__dict__.get("run") is None:        # (one run block serves every layer of a tower's forward -- and the backward)
         st.run = _bert_run(st, heads, F, key_add, p_hid, p_att, eps, seed, a16 == torch.float16)
     L.run = st.run
+    rest = (int(L.site_att), int(L.site_o), int(L.site_f), out32.data_ptr(), out16.data_ptr())
+    if adapted:
+        row3 = _lora_layout("mmdti_bert_lora_stack_layout", Mq, Mk, D, F, 0, 0)[4]
+        L.lt_buf = torch.empty(row3, device=dev, dtype=torch.uint8)
+        shapes = [((Mk if t != "q" else Mq), _lora_pair(W.att, t)[0].shape[0]) if t in W.lora else None for t in ("q", "k", "v")]
+        L.lt = {t: v for t, v in zip(("q", "k", "v"), _lora_rows(L.lt_buf, row3 // 3, shapes)) if v is not None}
+        P = _layer_block(_bert_layer_desc(W, False), w16=_w16_ptr)
+        split, ad = _split_block(W, w16=_w16_ptr), _block_array(_lora_blocks(W.att, ("q", "k", "v"), w16=_w16_ptr))
+        (ops.lib().mmdti_bert_lora_cross_layer_fwd if cross else ops.lib().mmdti_bert_lora_layer_fwd)(
+            ops._stream(), ctypes.addressof(L.run), ctypes.addressof(P), ctypes.addressof(split), ad[1], ctypes.addressof(saved), L.lt_buf.data_ptr(), *rest)
+        return L, out32, out16
     P = _layer_block(_bert_layer_desc(W, cross), w16=_w16_ptr, w_qkv=L.fw[3].data_ptr(), b_qkv=L.fb[1].data_ptr())
     (ops.lib().mmdti_bert_cross_layer_fwd if cross else ops.lib().mmdti_bert_layer_fwd)(
-        ops._stream(), ctypes.addressof(L.run), ctypes.addressof(P), ctypes.addressof(saved), int(L.site_att), int(L.site_o), int(L.site_f),
-        out32.data_ptr(), out16.data_ptr())
+        ops._stream(), ctypes.addressof(L.run), ctypes.addressof(P), ctypes.addressof(saved), *rest)
     return L, out32, out16
 
 
@@ -1321,6 +1536,20 @@ def _bert_seq_bwd(st, L, dout, want=(True, True)):
     e = torch.empty
     ds1 = e(Mq, D, device=dev, dtype=F32)
     nrow = _attn_stat_rows(st, heads)
+    if W.lora:
+        # an adapted layer on a frozen base: the whole backward is the call's -- no weight gradient is left for the host
+        _, ws, ws_bytes = _layer_workspace(_lora_layout("mmdti_bert_lora_stack_layout", Mq, Mk, D, F, nrow * 8, nrow)[3 if cross else 2], dev)
+        saved = _saved_block("mmdti_bert_saved_t", L)
+        P = _layer_block(_bert_layer_desc(W, False), wb=_wb_ptr, g=_grad_ptr)
+        split, ad = _split_block(W, wb=_wb_ptr), _block_array(_lora_blocks(W.att, ("q", "k", "v"), wb=_wb_ptr, g=_grad_ptr))
+        head = (ops._stream(), ctypes.addressof(L.run), ctypes.addressof(P), ctypes.addressof(split), ad[1], ctypes.addressof(saved), L.lt_buf.data_ptr(),
+                int(L.site_att), int(L.site_o), int(L.site_f), dout.data_ptr(), ds1.data_ptr(), int(bool(want[0])))
+        if not cross:
+            ops.lib().mmdti_bert_lora_layer_bwd(*head, ws, ws_bytes)
+            return (ds1 if want[0] else None), None
+        ds2 = e(Mk, D, device=dev, dtype=F32) if want[1] else None
+        ops.lib().mmdti_bert_lora_cross_layer_bwd(*head, ops._p(ds2), int(ds2 is not None), ws, ws_bytes)
+        return (ds1 if want[0] else None), ds2
     _, ws, ws_bytes = _layer_workspace(_stack_layout("mmdti_bert_stack_layout", Mq, D, F, nrow * 8, nrow)[4 if cross else 3], dev)
     saved = _saved_block("mmdti_bert_saved_t", L)
     P = _layer_block(_bert_layer_desc(W, cross), wb=_wb_ptr, g=_grad_ptr, wb_qkv=L.fw[0].data_ptr(), dw_qkv=L.fw[2].data_ptr(), lddw_qkv=L.fw[2].stride(0),
@@ -1352,15 +1581,22 @@ def _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites):
     """All layers of tower 2 as ONE library call -> the tower's fp32 output [Mq, D]."""
     nrow = _attn_stat_rows(st, st.heads)
     stats_bytes = nrow * 8
-    stride, ws_bytes, slab = _stack_layout("mmdti_bert_stack_layout", st.Mq, T.D, T.F, stats_bytes, nrow)[:3]
+    lora = getattr(T, "lora", None)              # (_lora_stack_tables: adapted layers on a frozen base)
+    if lora is not None:
+        stride, ws_bytes, slab = _lora_layout("mmdti_bert_lora_stack_layout", st.Mq, st.Mq, T.D, T.F, stats_bytes, nrow)[:2] + (0,)
+    else:
+        stride, ws_bytes, slab = _stack_layout("mmdti_bert_stack_layout", st.Mq, T.D, T.F, stats_bytes, nrow)[:3]
     dev = x32.device
     arena = torch.empty(stride * T.nl, device=dev, dtype=torch.uint8)
     out32 = torch.empty(st.Mq, T.D, device=dev, dtype=F32)
     site0 = sites.n + 1
     sites.n += 3 * T.nl
     run = _bert_run(st, st.heads, T.F, key_add, p_hid, p_att, cfg.ln_eps, seed, x16.dtype == torch.float16)
-    ops.lib().mmdti_bert_stack_fwd(ops._stream(), ctypes.addressof(run), T.layers[1], T.nl, site0, x32.data_ptr(), x16.data_ptr(), arena.data_ptr(),
-                                   arena.numel(), stats_bytes, out32.data_ptr())
+    rest = (T.nl, site0, x32.data_ptr(), x16.data_ptr(), arena.data_ptr(), arena.numel(), stats_bytes, out32.data_ptr())
+    if lora is not None:
+        ops.lib().mmdti_bert_lora_stack_fwd(ops._stream(), ctypes.addressof(run), T.layers[1], T.split[1], lora[1], *rest)
+    else:
+        ops.lib().mmdti_bert_stack_fwd(ops._stream(), ctypes.addressof(run), T.layers[1], *rest)
     # (x16, key_add: the run block and the backward read them -- kept alive here)
     st.stack = SimpleNamespace(T=T, arena=arena, ws_bytes=ws_bytes, slab=slab, stats_bytes=stats_bytes, site0=site0, x16=x16, key_add=key_add, run=run)
     return out32
@@ -1373,8 +1609,12 @@ def _bert_stack_bwd(st, dout):
     dev = dout.device
     ds1 = torch.empty(st.Mq, T.D, device=dev, dtype=F32)
     ws = torch.empty(S.ws_bytes, device=dev, dtype=torch.uint8)
-    ops.lib().mmdti_bert_stack_bwd(ops._stream(), ctypes.addressof(S.run), T.layers[1], T.nl, S.site0, dout.data_ptr(), ds1.data_ptr(), S.x16.data_ptr(),
-                                   S.arena.data_ptr(), S.arena.numel(), S.stats_bytes, ws.data_ptr(), ws.numel(), S.slab)
+    tail = (S.x16.data_ptr(), S.arena.data_ptr(), S.arena.numel(), S.stats_bytes, ws.data_ptr(), ws.numel())
+    if getattr(T, "lora", None) is not None:
+        ops.lib().mmdti_bert_lora_stack_bwd(ops._stream(), ctypes.addressof(S.run), T.layers[1], T.split[1], T.lora[1], T.nl, S.site0, dout.data_ptr(),
+                                            ds1.data_ptr(), int(st.plan.needs_dx(0)), *tail)
+    else:
+        ops.lib().mmdti_bert_stack_bwd(ops._stream(), ctypes.addressof(S.run), T.layers[1], T.nl, S.site0, dout.data_ptr(), ds1.data_ptr(), *tail, S.slab)
     return ds1
 
 
@@ -1422,8 +1662,11 @@ class RobertaEncoderFn(torch.autograd.Function):
         st.stack = None
         T = None
         sw = _switches()
-        if paths.bert_tower_fwd(sw, x32.is_cuda, keep, len(mod.layers), Mq, adapters=_has_bert_adapters(mod.layers)) == paths.STACK:
-            T = _stack_tables(_bert_stack_desc, mod, Mq, sw, D % cfg.heads == 0 and ops.attn_eligible(Lq, st.Lk, D // cfg.heads, D))
+        adapters = _has_bert_adapters(mod.layers)
+        attn_ok = D % cfg.heads == 0 and ops.attn_eligible(Lq, st.Lk, D // cfg.heads, D)
+        aseq = adapters and _adapter_seq(mod.layers, _bert_attn_of, attn_ok and all(l.attention.self.query.bias is not None for l in mod.layers))
+        if paths.bert_tower_fwd(sw, x32.is_cuda, keep, len(mod.layers), Mq, adapters=adapters, adapter_seq=aseq) == paths.STACK:
+            T = _lora_stack_tables(True, mod, Mq, sw, attn_ok) if adapters else _stack_tables(_bert_stack_desc, mod, Mq, sw, attn_ok)
         if T is not None:
             x32 = _bert_stack_fwd(st, T, x32, x16, key_add, cfg, p_hid, p_att, seed, sites)
         for li, layer in enumerate(mod.layers if T is None else ()):

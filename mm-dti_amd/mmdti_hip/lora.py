@@ -6,7 +6,7 @@ pair per adapted projection ``W``: ``A`` [r, in] (seeded Kaiming-uniform) and ``
 ``in_proj`` [3D, D] is adapted as a whole; ``lora_A_q`` / ``lora_B_q`` ... on ``attention.self`` of tower 2 and the cross block): the
 parameter arena, parameter groups (``ParamGroup(match="lora_")``), EMA, resume and the gradient reducer see them by name.  Call it
 before building the FineTuner.  functional.py runs the base projection exactly as before and ops.lora_fwd / lora_bwd / lora_dx next to
-it (csrc/lora.hip); adapted layers run op by op (paths.py).
+it (csrc/lora.hip); adapted layers on a frozen base leave from the library's adapted sequencers (paths.py; ``MMDTI_LORA_SEQ=0``: op by op).
 
 ``merge_lora(model)`` folds ``s.B.A`` into the fp32 base weights and removes the adapters: the state dict then has the reference's keys.
 """

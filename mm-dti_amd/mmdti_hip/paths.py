@@ -2,6 +2,7 @@
 
   STACK  all layers of a tower behind one library call per direction (mmdti_unimol_stack_*, mmdti_bert_stack_*);
   LAYER  one library call per layer and direction (mmdti_unimol_layer_*, mmdti_bert_layer_*, mmdti_bert_cross_layer_*);
+         layers that carry LoRA adapters next to a frozen base have their own STACK and LAYER calls (mmdti_*_lora_*: adapter_seq);
   OPS    the op-by-op Python body of functional.py: the general path, which the tests hold the other two bit-identical to.
 
 This module is the one place that chooses.  Pure Python on plain values (sizes, flags, the switch values of the moment), no device
@@ -50,52 +51,73 @@ def head_dim_is_8(D: int, H: int) -> bool:
     return D == H * 8
 
 
+def adapter_seq_ok(switch: bool, base_trainable: Sequence[bool], adapters_trainable: Sequence[bool], fused_attn: bool = True) -> bool:
+    """The `adapter_seq` of the functions below: layers that carry LoRA adapters may take the library's adapted sequencers
+    (mmdti_*_lora_*).  switch: functional.LORA_SEQ; base_trainable / adapters_trainable: requires_grad of every base parameter and of
+    every adapter parameter of the layers in question -- the adapted calls launch no weight gradient and every adapter's gradient
+    kernel, so every base parameter is frozen and every adapter pair trains; fused_attn (tower 2, cross block): the fused attention
+    kernels take the layer's lengths and head size, and its projections have biases."""
+    return bool(switch and fused_attn and not any(base_trainable) and len(adapters_trainable) > 0 and all(adapters_trainable))
+
+
 # ------------------------------------------------------------------------------------------------- tower 1 (Uni-Mol pair encoder)
-def unimol_layer_fwd(sw: Switches, on_gpu: bool, compact: bool, D: int, H: int, adapters: bool = False) -> str:
+def unimol_layer_fwd(sw: Switches, on_gpu: bool, compact: bool, D: int, H: int, adapters: bool = False, adapter_seq: bool = False) -> str:
     """The forward of the tower's layers, one answer for all: LAYER or OPS.  (A forward launches no weight gradient: grouped_dw_ok
-    only bears on the backward.)  adapters: a layer of the tower carries LoRA adapters -- no sequencer launches their kernels."""
-    ok = not adapters and sw.layer_seq and on_gpu and f16_operands_covered(sw.fwd_f16, compact) and not sw.timer and head_dim_is_8(D, H)
+    only bears on the backward.)  adapters: a layer of the tower carries LoRA adapters -- only the adapted sequencers launch their
+    kernels, and only where adapter_seq (adapter_seq_ok over the tower's layers) holds."""
+    ok = ((not adapters or adapter_seq) and sw.layer_seq and on_gpu and f16_operands_covered(sw.fwd_f16, compact) and not sw.timer
+          and head_dim_is_8(D, H))
     return LAYER if ok else OPS
 
 
 def unimol_tower_fwd(sw: Switches, layer_path: str, keep: bool, nlayers: int, rows: int, aux_grads: bool, final_ln: bool,
-                     adapters: bool = False) -> str:
+                     adapters: bool = False, adapter_seq: bool = False) -> str:
     """STACK for a small batch that keeps its activations for a backward (keep), else layer_path (unimol_layer_fwd's answer).
     aux_grads: the auxiliary outputs are differentiable; final_ln: the encoder ends in a LayerNorm."""
-    ok = not adapters and layer_path == LAYER and keep and sw.stack_seq and nlayers > 0 and rows < sw.stack_max_rows and not aux_grads and final_ln
+    ok = ((not adapters or adapter_seq) and layer_path == LAYER and keep and sw.stack_seq and nlayers > 0 and rows < sw.stack_max_rows
+          and not aux_grads and final_ln)
     return STACK if ok else layer_path
 
 
 def unimol_tower_bwd(sw: Switches, on_gpu: bool, nkept: int, lowest: int, f16_operands: bool, compact: bool, D: int, F: int, rows: int,
-                     full: Sequence[bool]) -> str:
+                     full: Sequence[bool], adapter_seq: bool = False) -> str:
     """LAYER: layers of this backward may take the library call (its workspace is allocated); OPS: none does.  nkept: layers the forward
-    kept (0 after a stack forward); lowest: freeze.TowerPlan.lowest; f16_operands / compact: as the forward ran; full: see below."""
+    kept (0 after a stack forward); lowest: freeze.TowerPlan.lowest; f16_operands / compact: as the forward ran; full: see below.
+    adapter_seq: the layers are adapted ones on a frozen base (adapter_seq_ok) -- no grouped weight gradient, and `full` is moot."""
     ok = (sw.layer_seq and on_gpu and lowest < nkept and f16_operands_covered(f16_operands, compact) and not sw.timer
-          and grouped_dw_ok(sw, D, F, rows) and any(full[lowest:]))
+          and (adapter_seq or (grouped_dw_ok(sw, D, F, rows) and any(full[lowest:]))))
     return LAYER if ok else OPS
 
 
-def unimol_layer_bwd(tower_path: str, have_dx16: bool, held: bool, full: bool, adapters: bool = False) -> str:
+def unimol_layer_bwd(tower_path: str, have_dx16: bool, held: bool, full: bool, adapters: bool = False, adapter_seq: bool = False) -> str:
     """One layer of the backward.  have_dx16: the LayerNorm backward above left the bf16 copy of the stream gradient; held: the layer's
     weight gradients wait for the end of the backward (functional.DEFER_WGRAD_LAYERS); full: every parameter of the layer trains -- a
     frozen or partly frozen layer runs op by op, where its gradient kernels drop out one by one; adapters: the layer's forward ran LoRA
-    adapters, whose gradient kernels only the op-by-op backward launches."""
-    return LAYER if (tower_path == LAYER and have_dx16 and not held and full and not adapters) else OPS
+    adapters, whose gradient kernels the op-by-op backward launches -- or, adapter_seq, the adapted library call, which has no weight
+    gradient to hold back."""
+    if adapters:
+        return LAYER if (tower_path == LAYER and have_dx16 and adapter_seq) else OPS
+    return LAYER if (tower_path == LAYER and have_dx16 and not held and full) else OPS
 
 
 # ------------------------------------------------------------------------------------------------- tower 2 (RoBERTa), cross block
-def bert_tower_fwd(sw: Switches, on_gpu: bool, keep: bool, nlayers: int, rows: int, adapters: bool = False) -> str:
+def bert_tower_fwd(sw: Switches, on_gpu: bool, keep: bool, nlayers: int, rows: int, adapters: bool = False, adapter_seq: bool = False) -> str:
     """STACK for a small batch that keeps its activations for a backward, else LAYER: each layer asks bert_layer_fwd.  adapters: a layer
-    of the tower carries LoRA adapters."""
-    ok = not adapters and sw.layer_seq and sw.stack_seq and keep and on_gpu and rows < sw.stack_max_rows and nlayers > 0 and not sw.timer
+    of the tower carries LoRA adapters; adapter_seq: adapter_seq_ok over all of the tower's layers."""
+    ok = (not adapters or adapter_seq) and sw.layer_seq and sw.stack_seq and keep and on_gpu and rows < sw.stack_max_rows and nlayers > 0 and not sw.timer
     return STACK if ok else LAYER
 
 
-def bert_layer_fwd(sw: Switches, self_attn: bool, fused_proj: bool, on_gpu: bool, D: int, F: int, rows: int, adapters: bool = False) -> str:
+def bert_layer_fwd(sw: Switches, self_attn: bool, fused_proj: bool, on_gpu: bool, D: int, F: int, rows: int, adapters: bool = False,
+                   adapter_seq: bool = False) -> str:
     """One BERT-style layer.  fused_proj: query | key | value (cross-attention: key | value) run as one GEMM over parameters that sit
     back to back in the arena and all train -- which implies the fused attention kernels and projection biases.  rows: query rows.
-    adapters: the layer carries LoRA adapters, which only the op-by-op body launches."""
-    if adapters or not (sw.layer_seq and fused_proj and on_gpu and not sw.timer):
+    adapters: the layer carries LoRA adapters, which the op-by-op body launches -- or, adapter_seq (adapter_seq_ok over this layer), the
+    adapted library call: three separate projections of a frozen base and no grouped weight gradient, so neither fused_proj nor
+    grouped_dw_ok applies, only rows of whole 16-byte vectors."""
+    if adapters:
+        return LAYER if (adapter_seq and sw.layer_seq and on_gpu and not sw.timer and cross_dims_ok(D, F)) else OPS
+    if not (sw.layer_seq and fused_proj and on_gpu and not sw.timer):
         return OPS
     return LAYER if (grouped_dw_ok(sw, D, F, rows) if self_attn else cross_dims_ok(D, F)) else OPS
 
@@ -107,10 +129,11 @@ def bert_layer_bwd(fwd_path: str, timer: bool, buffers_live: bool) -> str:
 
 
 # ------------------------------------------------------------------------------------------------- the stack calls' own conditions
-def stack_call(sw: Switches, in_arena: bool, D: int, F: int, rows: int, attn_ok: bool = True) -> str:
+def stack_call(sw: Switches, in_arena: bool, D: int, F: int, rows: int, attn_ok: bool = True, adapter_seq: bool = False) -> str:
     """Per call.  in_arena: the tower's parameters live in a trainer arena (the pointer tables are offsets into it); attn_ok (tower 2):
-    the fused attention kernels take the sequence lengths and head size."""
-    return STACK if (in_arena and grouped_dw_ok(sw, D, F, rows) and attn_ok) else LAYER
+    the fused attention kernels take the sequence lengths and head size.  adapter_seq: the adapted stack calls -- in_arena speaks of the
+    adapters (the frozen base is addressed through its shadows), and no grouped weight gradient is launched."""
+    return STACK if (in_arena and (cross_dims_ok(D, F) if adapter_seq else grouped_dw_ok(sw, D, F, rows)) and attn_ok) else LAYER
 
 
 def stack_model(trainable: Sequence[bool], same_arena: bool, uniform: bool, adjacent: bool = True) -> str:

@@ -4,6 +4,10 @@
         every arm, 2 rounds alternating, written to OUT (default profiles/lora.txt).  --parent DIR: a directory holding the PARENT
         commit's ``include/`` and ``mm-dti_amd/mmdti_hip`` package with its built library -- the full fine-tune of the headline step then
         also runs from it (the default path must not have moved).
+    python scratch/lora_measure.py seq [OUT] --parent DIR [--shape small|head]
+        the measurements behind profiles/lora_seq.txt (adapted layers issued from the library's sequencers): per shape the full fine-tune
+        and the LoRA step of this tree and of the parent commit's package, and this tree's LoRA step with MMDTI_LORA_SEQ=0 (op by op);
+        2 rounds alternating, written to OUT (default profiles/lora_seq.txt; with --shape the other shape's lines in OUT are kept).
     python scratch/lora_measure.py arm NAME
         one arm in this process: kernels | {head,small}_{full,frozen,lora}
 """
@@ -91,12 +95,49 @@ def step(name, warmup=5, steps=30):
     t0 = time.perf_counter()
     for _ in range(steps):
         tuner.step(b, y, epoch=0)
+    host = (time.perf_counter() - t0) / steps * 1e3          # the host's share: all steps enqueued, the device not yet waited for
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / steps * 1e3
     what = "32 mixed-length molecules" if small else "headline, 256 molecules"
     label = {"full": "full fine-tune", "frozen": "both towers frozen", "lora": "both towers LoRA r=16 q,v"}[mode]
     print(f"{name:12s} {what:26s} {label:26s}: {ms:8.3f} ms / step over {steps} steps, peak {torch.cuda.max_memory_allocated() / 2 ** 30:6.2f} GiB, "
-          f"{tuner.arena.numel} trainable elements", flush=True)
+          f"{tuner.arena.numel} trainable elements, host enqueue {host:.3f} ms / step", flush=True)
+
+
+def _arm(name, pkg=None, env_extra=None):
+    """one arm in a fresh process -> its result lines (nothing more is started on the device after a failure)"""
+    env = dict(os.environ, **(env_extra or {}))
+    if pkg:
+        env["LORA_MEASURE_PACKAGE"] = pkg
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "arm", name], capture_output=True, text=True, timeout=300, env=env)
+    if r.returncode != 0:
+        raise SystemExit(f"arm {name} failed ({r.returncode}): {r.stderr[-1500:]}")
+    return [l for l in r.stdout.strip().splitlines() if " us " in l or " ms " in l]
+
+
+SEQ_HEAD = ["Adapted layers from the library's sequencers (reference architecture, 128 atoms x 256 tokens, train mode, one MI355X); one fresh",
+            "process per arm, arms alternating over 2 rounds; host clock round a synchronised loop of engine.step on a resident batch (5",
+            "warm-up steps).  LoRA: r = 16 on q and v of tower 1 and tower 2, both towers frozen; the cross block and the heads train in every",
+            "arm.  'parent commit': the package of the commit before this change; 'op by op': this tree with MMDTI_LORA_SEQ=0.", ""]
+
+
+def run_seq(out_path, parent, shapes):
+    assert parent, "seq needs --parent DIR"
+    kept = []
+    if os.path.exists(out_path):                # (a run of one shape keeps the other shape's lines)
+        kept = [l for l in open(out_path).read().splitlines() if l.startswith("round ") and not any(f" {s}_" in l for s in shapes)]
+    lines = []
+    for rnd in range(2):
+        for shape in shapes:
+            for tag, name, pkg, env in (("this tree      ", f"{shape}_full", None, None), ("parent commit  ", f"{shape}_full", parent, None),
+                                        ("this tree      ", f"{shape}_lora", None, None), ("parent commit  ", f"{shape}_lora", parent, None),
+                                        ("this, op by op ", f"{shape}_lora", None, {"MMDTI_LORA_SEQ": "0"})):
+                for ln in _arm(name, pkg, env):
+                    line = f"round {rnd}  {tag} {ln}"
+                    print(line, flush=True)
+                    lines.append(line)
+                with open(out_path, "w") as f:
+                    f.write("\n".join(SEQ_HEAD + kept + lines) + "\n")
 
 
 def run_all(out_path, parent):
@@ -114,14 +155,8 @@ def run_all(out_path, parent):
         for name, pkg in arms:
             if name == "kernels" and rnd:
                 continue
-            env = dict(os.environ)
-            if pkg:
-                env["LORA_MEASURE_PACKAGE"] = pkg
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "arm", name], capture_output=True, text=True, timeout=300, env=env)
-            if r.returncode != 0:          # (nothing more is started on the device after a failure)
-                raise SystemExit(f"arm {name} failed ({r.returncode}): {r.stderr[-1500:]}")
             tag = "parent commit  " if pkg else "this tree      "
-            for ln in [l for l in r.stdout.strip().splitlines() if " us " in l or " ms " in l]:
+            for ln in _arm(name, pkg):
                 line = f"round {rnd}  {tag} {ln}"
                 print(line, flush=True)
                 lines.append(line)
@@ -135,13 +170,21 @@ if __name__ == "__main__":
         kernels()
     elif what == "arm" and len(sys.argv) > 2 and sys.argv[2] in STEP_ARMS:
         step(sys.argv[2])
-    elif what == "all":
+    elif what in ("all", "seq"):
         rest = sys.argv[2:]
         parent = None
+        shapes = ("small", "head")
+        if "--shape" in rest:
+            i = rest.index("--shape")
+            shapes = (rest[i + 1],)
+            del rest[i:i + 2]
         if "--parent" in rest:
             i = rest.index("--parent")
             parent = os.path.join(os.path.abspath(rest[i + 1]), "mm-dti_amd")
             del rest[i:i + 2]
-        run_all(rest[0] if rest else os.path.join(ROOT, "profiles", "lora.txt"), parent)
+        if what == "seq":
+            run_seq(rest[0] if rest else os.path.join(ROOT, "profiles", "lora_seq.txt"), parent, shapes)
+        else:
+            run_all(rest[0] if rest else os.path.join(ROOT, "profiles", "lora.txt"), parent)
     else:
         raise SystemExit(__doc__)
